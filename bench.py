@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched random-agent rollout (BASELINE.json metric) + the evidence around it.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 HEADLINE (the contract line).  One "step" = one env-step of EVERY game of the batch (Tron: all live players move).
@@ -43,6 +43,11 @@ script (and gpurun_out/bench_detail.json when that directory exists) and, as one
                 its thread count), nproc stated, plus the reference's own Python+Cython path as timed in the build
                 container (it cannot run here)
   gather        (--gather-probe) the cost of the end-of-rollout collective in a one-rank RCCL group
+
+--dump-outputs DIR (rank 0): what the timed region handed its caller after its last step -- the gathered result rows of
+every game and this rank's game state -- as DIR/<name>.npy in float32 / float64 (`timed_outputs`), written at the end.
+The inputs are fixed by the arguments (reset states, counter-based RNG keyed by --seed and the game id), so two builds
+run with the same arguments can be compared file by file.
 """
 import argparse
 import gc
@@ -98,6 +103,13 @@ HEADLINE = "tron_p4_n20_b65536"
 # "all_gather" (every rank gets everything: a ring).  CRL_BENCH_COLLECTIVE overrides; both are timed in every N > 1 record
 # (`collective` section) and in a one-rank RCCL group by --gather-probe (profiles/r5_gather_probe.json).
 COLLECTIVE = os.environ.get("CRL_BENCH_COLLECTIVE", "gather")
+# --dump-outputs: the state a caller of the timed rollout holds afterwards (stepper attribute -> the axis that indexes games)
+STATE_OUTPUTS = {
+    "tron": {"board": 0, "heads": 1, "dirs": 1, "deaths": 1},
+    "ttt": {"occ": 1, "winner": 0, "to_move": 0},
+    "blokus": {"occ": 0, "inv": 0, "score": 0, "round": 0, "to_move": 0},
+}
+DUMP_BYTES = 64 * 1000 * 1000 - (1 << 16)        # all the files of one dump, less room for their .npy headers
 
 
 def reference_python(workload):
@@ -552,6 +564,35 @@ def launch_time_pass(torch, sr, steps, seed, chunk, events):
 def mean_episode_len(gathered):
     n_ep = int(gathered[..., 0].sum().item())
     return int(gathered[..., 1].sum().item()) / max(n_ep, 1), n_ep
+
+
+def timed_outputs(game, stepper, rows, budget=DUMP_BYTES):
+    """--dump-outputs: {name: numpy array} of what the timed region left its caller -- `rows`, the gathered result rows of
+    every game, and this rank's state tensors (STATE_OUTPUTS).  Integers of up to 16 bits become float32, wider ones
+    float64, both exactly.  When the whole would exceed `budget` bytes, every array keeps a sample of at most the same
+    number of games, drawn by np.random.default_rng(0) and kept in ascending order, so runs with the same arguments
+    write the same games."""
+    import numpy as np
+    import torch
+    arrays = {"rows": (rows, 0)}
+    arrays.update((name, (getattr(stepper, name), axis)) for name, axis in STATE_OUTPUTS[game].items())
+    dtype = {name: np.dtype(np.float32 if t.element_size() <= 2 else np.float64) for name, (t, _) in arrays.items()}
+    per_game = sum(t.numel() // t.shape[axis] * dtype[name].itemsize for name, (t, axis) in arrays.items())
+    keep = max(1, budget // per_game)
+    out = {}
+    for name, (t, axis) in arrays.items():
+        if t.shape[axis] > keep:
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[axis], keep, replace=False))
+            t = t.index_select(axis, torch.from_numpy(idx).to(t.device))
+        out[name] = t.cpu().numpy().astype(dtype[name])
+    return out
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def contract_record(workload, batch, world, steps, warmup, chunk, meas, launch_s, launch_source, copy_gbs, gather_desc):
@@ -1159,6 +1200,8 @@ def parse_args(argv=None):
     ap.add_argument("--only-dropin", action="store_true", help="run just the single-state drop-in latency section")
     ap.add_argument("--only-out-of-cache", action="store_true",
                     help="run just the out-of-Infinity-Cache section (Tron 20x20, 1,048,576 games: 20-step rollout, step_observe, step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed region computed (result rows, game state) to DIR/<name>.npy, at most 64 MB")
     return ap.parse_args(argv)
 
 
@@ -1254,6 +1297,15 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
     under_launcher, world, rank, local_rank = launcher_env()
+    bad = None
+    if args.steps < 1 or args.warmup < 0:
+        bad = "--steps must be >= 1 and --warmup >= 0 (got %d, %d)" % (args.steps, args.warmup)
+    elif args.dump_outputs and (args.only_dropin or args.only_out_of_cache or args.only_step_api):
+        bad = "--dump-outputs writes the timed rollout's outputs; --only-dropin / --only-out-of-cache / --only-step-api run none"
+    if bad:
+        if rank == 0:
+            fail(bad)
+        sys.exit(2)
     if under_launcher and args.gpus != world:
         if rank == 0:
             fail("--gpus %d but the launcher started WORLD_SIZE=%d ranks" % (args.gpus, world))
@@ -1315,6 +1367,7 @@ def main(argv=None):
 
     # ---- THE measurement: the first W + K region of the process.  Everything below it is evidence around it.
     meas = contract_region(pl, sr, args.steps, args.warmup, args.seed, args.chunk, region_events)
+    dumped = timed_outputs(game, sr.stepper, meas["rows"]) if args.dump_outputs and rank == 0 else None
     kernel_s = meas["marker_s"]
     if kernel_s is None:
         kernel_s = launch_time_pass(torch, sr, args.steps, args.seed, args.chunk, events)
@@ -1424,6 +1477,8 @@ def main(argv=None):
                 out["gather"] = {"error": repr(exc)[:300]}
         # the full single-process run owns bench_detail.json; --only-headline and launcher runs write their own file
         emit(out, name="bench_detail.json" if full_run else "bench_detail_n%d%s.json" % (world, "_rccl" if pl.use_dist else "_headline"))
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
     if pl.use_dist and dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -250,3 +250,44 @@ def test_contract_region_and_line_in_a_world_of_two(tmp_path):
     assert c["row_bytes"] == 16 and c["rows_bytes_into_rank0"] == 16 * batch and len(c["elapsed_ranks_us"]) == 2
     assert c["rank_spread_us"] == pytest.approx(max(c["elapsed_ranks_us"]) - min(c["elapsed_ranks_us"]), abs=0.02 + 2e-4 * max(c["elapsed_ranks_us"]))
     assert rec["config"]["completion"] == "none (cpu)"
+
+
+class StateStepper:
+    """Tron-shaped state tensors whose every entry names its game, as a TronBatch holds them after a rollout."""
+
+    def __init__(self, batch, P=4, NN=400):
+        g = torch.arange(batch, dtype=torch.int32)
+        self.board = (g % 100).to(torch.int8)[:, None].repeat(1, NN)
+        self.heads = g.to(torch.int16)[None, :].repeat(P, 1)
+        self.dirs = (g % 4).to(torch.int8)[None, :].repeat(P, 1)
+        self.deaths = (g % 3).to(torch.int8)[None, :].repeat(P, 1)
+
+
+def test_timed_outputs_are_exact_floats_of_one_fixed_sample_of_games():
+    B = 3000
+    st = StateStepper(B)
+    rows = torch.stack([torch.arange(B, dtype=torch.int32) * 7, torch.full((B,), 2 ** 30, dtype=torch.int32)], dim=1)
+    whole = bench.timed_outputs("tron", st, rows)
+    assert sorted(whole) == ["board", "deaths", "dirs", "heads", "rows"]
+    assert whole["board"].dtype == np.float32 and whole["heads"].dtype == np.float32 and whole["rows"].dtype == np.float64
+    assert np.array_equal(whole["heads"], st.heads.numpy()) and np.array_equal(whole["board"], st.board.numpy())
+    assert np.array_equal(whole["rows"], rows.numpy()) and whole["rows"][0, 1] == 2 ** 30
+    per_game = 400 * 4 + 3 * 4 * 4 + 2 * 8
+    budget = 1000 * per_game + 17
+    part = bench.timed_outputs("tron", st, rows, budget=budget)
+    assert sum(a.nbytes for a in part.values()) <= budget
+    games = part["heads"][0].astype(np.int64)
+    assert len(games) == 1000 and np.all(np.diff(games) > 0)                 # ascending, no game twice
+    assert np.array_equal(games, np.sort(np.random.default_rng(0).choice(B, 1000, replace=False)))
+    assert np.array_equal(part["rows"][:, 0], games * 7) and np.array_equal(part["board"][:, 5], games % 100)
+    assert np.array_equal(part["dirs"], np.tile(games % 4, (4, 1))) and np.array_equal(part["deaths"][3], games % 3)
+    again = bench.timed_outputs("tron", StateStepper(B), rows.clone(), budget=budget)
+    assert all(np.array_equal(part[k], again[k]) for k in part)
+
+
+def test_bench_refuses_meaningless_step_counts_and_dumps(no_gpu_context, tmp_path):
+    for argv, what in ((["--steps", "0"], "--steps"), (["--warmup", "-1"], "--warmup"),
+                       (["--dump-outputs", str(tmp_path), "--only-dropin"], "--dump-outputs")):
+        rc, out, _ = _run_bench(argv)
+        assert rc != 0 and what in json.loads(out.strip())["error"], (argv, out)
+    assert os.listdir(tmp_path) == []

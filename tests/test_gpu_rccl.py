@@ -159,3 +159,32 @@ def test_bench_gpus_2_on_a_one_gpu_box_fails(run_fresh):
     assert rc != 0
     rec = _one_json_line(out)
     assert "value" not in rec and "--gpus 2" in rec["error"]
+
+
+def test_bench_dump_outputs_are_what_the_timed_steps_computed(run_fresh, tmp_path):
+    """`bench.py --dump-outputs DIR` writes the state and result rows the timed region left behind -- exactly W + K steps
+    from reset, nothing of the timing passes after it -- as float arrays of at most 64 MB: the CPU oracle run for
+    W + K = 25 steps on the same games gives the same numbers."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_parallel_gloo import OracleTronStepper
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--only-headline",
+           "--no-cpu-baseline", "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "LOCAL_RANK")}
+    rc, out, err = run_fresh(cmd, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"), cwd=ROOT, timeout=600, split=True)
+    assert rc == 0, err[-3000:]
+    assert _one_json_line(out)["steps"] == 20
+    names = sorted(os.listdir(tmp_path))
+    assert names == ["board.npy", "deaths.npy", "dirs.npy", "heads.npy", "rows.npy"]
+    assert sum(os.path.getsize(os.path.join(tmp_path, n)) for n in names) <= 64 * 1000 * 1000
+    got = {n[:-4]: np.load(os.path.join(tmp_path, n)) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    B = 65536
+    games = np.sort(np.random.default_rng(0).choice(B, got["rows"].shape[0], replace=False))
+    ref = OracleTronStepper(B, 0, N=20, P=4)
+    ref.rollout(5, 0)
+    ref.rollout(20, 0)
+    s = ref.st
+    assert np.array_equal(got["rows"], ref.results_packed().numpy()[games])
+    assert np.array_equal(got["board"], s.board[games]) and np.array_equal(got["heads"], s.heads[:, games])
+    assert np.array_equal(got["dirs"], s.dirs[:, games]) and np.array_equal(got["deaths"], s.deaths[:, games])

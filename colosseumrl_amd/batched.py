@@ -256,6 +256,47 @@ class TronBatch(_Waitable):
                                             _ptr(self.tcount), int(advance), _ptr(act), _stream()), "crl_tron_sample")
         return act
 
+    # -- the reference's scripted opponent (SimpleAvoidAgent) for one step: int8 [P][B] actions in the step() encoding
+    def sample_avoid(self, seed: int = 0, noise: float = 0.1, players=None, out: Optional[torch.Tensor] = None,
+                     advance: bool = True):
+        """Actions of the reference's ``SimpleAvoidAgent(noise)`` (envs/tron/rllib.py:68-95) at each game's step counter
+        (``tcount``), under the Philox contract of ``crl_tron_sample_avoid`` (include/colosseum_hip.h), decided on the
+        current (pre-step) boards.  ``players``: the player ids to fill (default: all); only their rows of ``out``
+        (int8 [P, B]; a new zeroed tensor when None) are written, so a caller writes its learner's row and lets this fill
+        in the opponents.  With ``advance`` the counter moves on, so ``step(sample_avoid(seed, noise), auto_reset=True)``
+        T times == ``rollout_avoid(T, seed, noise)``."""
+        P, B = self.P, self.B
+        if out is None:
+            out = torch.zeros((P, B), dtype=torch.int8, device=self.device)
+        else:
+            _want(out, torch.int8, (P, B), self.device, "out")
+        mask = (1 << P) - 1
+        if players is not None:
+            mask = 0
+            for p in players:
+                if not 0 <= int(p) < P:
+                    raise ValueError("sample_avoid: player %d out of range 0..%d" % (int(p), P - 1))
+                mask |= 1 << int(p)
+        with _DevGuard(self.device):
+            check(self._lib.crl_tron_sample_avoid(self._ctx.handle, B, seed & (2 ** 64 - 1), self.first_env_id, _ptr(self.tcount),
+                                                  int(advance), float(noise), mask, _ptr(self.board), _ptr(self.heads),
+                                                  _ptr(self.dirs), _ptr(self.deaths), _ptr(out), _stream()),
+                  "crl_tron_sample_avoid")
+        return out
+
+    # -- T fused steps with every player on the avoid agent, auto-reset
+    def rollout_avoid(self, steps: int, seed: int = 0, noise: float = 0.1):
+        """``rollout`` with every player on the reference's ``SimpleAvoidAgent(noise)`` instead of the random agent
+        (``crl_tron_rollout_avoid``): the same statistics tensors, ``results()`` rows and step counter."""
+        if self._rollout_args is None:
+            self._rollout_args = (_ptr(self.board), _ptr(self.heads), _ptr(self.dirs), _ptr(self.deaths), self._stats())
+        with _DevGuard(self.device):
+            rc = self._lib.crl_tron_rollout_avoid(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id, int(steps),
+                                                  float(noise), *self._rollout_args, 0, _stream())
+        if rc:
+            check(rc, "crl_tron_rollout_avoid")
+        self._stat_steps += int(steps)
+
     # -- state_to_observation for all games; player int8 [B]
     def observe(self, player: torch.Tensor):
         _want(player, torch.int8, (self.B,), self.device, "player")

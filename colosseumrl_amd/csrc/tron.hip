@@ -4494,6 +4494,418 @@ inline TronPad pad_of(const crl_tron_cfg &cfg, const int RS)
 constexpr int kLdsDynamic = 160 * 1024 - 1024;  // dynamic part; the kernels also hold small static tables (actions, wall pattern)
 
 
+// ---- the scripted opponent: reference SimpleAvoidAgent (envs/tron/rllib.py:68-95) ------------------------------------
+// Contract: include/colosseum_hip.h, crl_tron_sample_avoid.  The agent reads the STATE board (0 is "free" there as in every
+// relabelled observation) around its own head: ahead, right and left, each cell CLAMPED onto the board as the reference's
+// next_cell(..., board_size) does (TronGridEnvironment.py:467-481; at a wall the clamped cell is the head itself, which is
+// occupied).  All three cells are probed at once -- the step's own target is one of them whenever it lies on the board, so
+// the agent costs two byte probes beyond the step's one, issued together with it.
+
+// the cell next to (hx, hy) in direction dir, clamped onto the board
+__device__ __forceinline__ int tron_avoid_cell(const int N, const int hx, const int hy, const int dir)
+{
+    // (plain compares, not the step's byte tables: the clamp needs the signed unit step itself, which the step only ever
+    //  tests through an unsigned range check)
+    const int dd = dir & 3;
+    const int nx = min(max(hx + (dd == 1) - (dd == 3), 0), N - 1);
+    const int ny = min(max(hy + (dd == 2) - (dd == 0), 0), N - 1);
+    return ny * N + nx;
+}
+
+// the decision of player p of global game gid at step counter c, from the raw cells ahead / right / left (0 = free):
+// 0 forward, 1 right, 3 left (= -1 mod 4, the step's encoding)
+__device__ __forceinline__ int tron_avoid_code(const uint32_t gid, const uint32_t c, const int p, const uint32_t k0,
+                                               const uint32_t k1, const uint64_t thr, const int r_fwd, const int r_right,
+                                               const int r_left)
+{
+    const philox_out w = philox4x32_10(gid, c, (uint32_t)p, CRL_TAG_TRON_AVOID, k0, k1);
+    const uint32_t a3 = __umulhi(w.w[1], 3u);                  // noisy: random.choice(['forward', 'right', 'left'])
+    const bool left_first = (w.w[2] >> 31) != 0u;               // random.choice([(1, right, left), (-1, left, right)])
+    const bool first_free = (left_first ? r_left : r_right) == 0;
+    const int side = (left_first == first_free) ? 3 : 1;        // the first side if free, else the backup
+    return ((uint64_t)w.w[0] < thr) ? (int)(a3 + (a3 >> 1)) : (r_fwd == 0 ? 0 : side);
+}
+
+// one lane per (player, game): the lanes of a game are 1 << kSh consecutive lanes of one wave, so the step counter every
+// one of them reads is advanced (by the game's player-0 lane) only after all have read it
+template <int P>
+__global__ void __launch_bounds__(256)
+tron_sample_avoid_kernel(const TronGeom g, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
+                         const uint64_t first_env_id, uint32_t *__restrict__ tcount, const int advance, const uint64_t thr,
+                         const uint32_t pmask, const int8_t *__restrict__ board, const int16_t *__restrict__ heads,
+                         const int8_t *__restrict__ dirs, const int8_t *__restrict__ deaths, int8_t *__restrict__ actions)
+{
+    constexpr int kSh = P <= 1 ? 0 : P <= 2 ? 1 : P <= 4 ? 2 : 3;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t b = i >> kSh;
+    const int p = (int)(i & ((1 << kSh) - 1));
+    if (b >= B) return;                                         // (whole games: a game's lanes leave together)
+    const uint32_t c = tcount[b];
+    if (p < P && ((pmask >> p) & 1u)) {
+        const int64_t pb = (int64_t)p * B + b;
+        int code = 0;                                           // dead players' rows: 0
+        if (deaths[pb] == 0) {
+            const int N = g.N, NN = g.NN;
+            const int h = min(max((int)heads[pb], 0), NN - 1);
+            const int hy = (int)__umulhi((uint32_t)h, g.inv_n), hx = h - hy * N;
+            const int d = dirs[pb] & 3;
+            const int c_f = tron_avoid_cell(N, hx, hy, d), c_r = tron_avoid_cell(N, hx, hy, d + 1), c_l = tron_avoid_cell(N, hx, hy, d + 3);
+            CRL_BOUNDS_LT(c_f, NN, 150);
+            CRL_BOUNDS_LT(c_r, NN, 151);
+            CRL_BOUNDS_LT(c_l, NN, 152);
+            const int8_t *gb = board + b * NN;
+            code = tron_avoid_code((uint32_t)(first_env_id + (uint64_t)b), c, p, seed_lo, seed_hi, thr, gb[c_f], gb[c_r], gb[c_l]);
+        }
+        actions[pb] = (int8_t)(code == 3 ? -1 : code);
+    }
+    if (advance && p == 0) tcount[b] = c + 1u;
+}
+
+// wave-cooperative new_state of the games whose quad / lane leader is set in `ending` (a ballot over the wave; game of
+// lane l = env0 + (l >> shift)): 16-byte stores between the board's unaligned ends (as tron_rollout_gquad_kernel)
+template <int P>
+__device__ __forceinline__ void tron_avoid_rewrite(const crl_tron_cfg &cfg, int8_t *board, const int64_t env0, const int NN,
+                                                   const int shift, const int lane, uint64_t ending)
+{
+    while (ending) {
+        const int l = (int)__builtin_ctzll(ending);
+        ending &= ending - 1;
+        uint8_t *eb = reinterpret_cast<uint8_t *>(board) + (env0 + (l >> shift)) * NN;
+        const int lead = min((int)((16u - (uint32_t)((uintptr_t)eb & 15u)) & 15u), NN);
+        const int chunks = (NN - lead) >> 4, tail0 = lead + (chunks << 4);
+        for (int c = lane; c < chunks; c += CRL_WAVE)
+            *reinterpret_cast<uint4 *>(eb + lead + (c << 4)) = tron_fresh_chunk16<P>(cfg, lead + (c << 4));
+        const int odd = lane < lead ? lane : (lane - lead < NN - tail0 ? tail0 + lane - lead : -1);   // (lead + tail < 31 bytes)
+        if (odd >= 0) {
+            int v = 0;
+#pragma unroll
+            for (int q = 0; q < P; ++q) v = (cfg.start_heads[q] == odd) ? q + 1 : v;
+            eb[odd] = (uint8_t)v;
+        }
+    }
+}
+
+// T fused steps with every player on the avoid agent: tron_rollout_gquad_kernel with the agent in place of the random
+// stream -- one lane per player on boards in GLOBAL memory (any board size, at most 4 players), the quad sharing the alive
+// count and the reset, the reference's sequential order resolved on DPP-gathered copies only in wave-steps where players
+// interact.  A step is  decide (three clamped probes of the pre-step board + one Philox call)  ->  fence  ->  step (the
+// target's cell is the probe of the chosen direction; trail store, reset).  Cells cross lanes of a wave through memory (a
+// trail one lane stamps is probed by another lane in a later step; a reset's stores come from the whole wave), so the
+// order is made explicit with wavefront-scope fences: after the probes (no store of the step may move above them) and
+// at the end of the step (no probe of the next step may move above its stores).  They emit no instruction on gfx950:
+// one wave's vector memory operations reach its CU's cache in program order; the fences pin the program order.
+template <int P>
+__global__ void __launch_bounds__(256)
+tron_rollout_avoid_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_t B,
+                          const uint32_t seed_lo, const uint32_t seed_hi, const uint64_t first_env_id, const int T,
+                          const uint64_t thr, int8_t *__restrict__ board, int16_t *__restrict__ heads,
+                          int8_t *__restrict__ dirs, int8_t *__restrict__ deaths, const crl_tron_stats st)
+{
+    static_assert(P <= 4, "one lane per player, four lanes per game");
+    constexpr int kGames = 64, kWaveGames = 16;
+    const int N = g.N, NN = g.NN;
+    const int lane = threadIdx.x & (CRL_WAVE - 1);
+    const int wave = threadIdx.x >> 6;
+    const int p = lane & 3;                                     // my player
+    const int slot = threadIdx.x >> 2;
+    const int64_t b = (int64_t)blockIdx.x * kGames + slot;
+    const bool gvalid = b < B;
+    const bool seat = p < P;                                    // this lane has a player at all
+    const bool pvalid = gvalid && seat;
+    const int64_t bb = gvalid ? b : 0;
+    const int64_t env0 = (int64_t)blockIdx.x * kGames + wave * kWaveGames;   // first game of this wave
+    const uint8_t *gb = reinterpret_cast<const uint8_t *>(board) + bb * NN;  // my game's board
+    uint8_t *gbw = reinterpret_cast<uint8_t *>(board) + bb * NN;
+    const int64_t pb = (int64_t)(seat ? p : 0) * B + bb;
+    const int h_in = heads[pb];
+    const int d_in = dirs[pb];
+    int k = deaths[pb];
+    const int old_ret = st.ret_sum[pb];
+    const uint32_t old_wins = st.win_count[pb];
+    uint32_t tc = st.tcount[bb], ts = st.tstep[bb];
+    const uint32_t old_n_ep = st.n_episodes[bb], old_len_sum = st.len_sum[bb];
+    const uint32_t old_last_w = st.last_winners[bb];
+    k = pvalid ? k : 1;                                         // a seat without a player counts as dead for good
+    int fh = cfg.start_heads[0], fd = cfg.start_dirs[0];
+    fh = (p == 1) ? cfg.start_heads[1] : fh; fd = (p == 1) ? cfg.start_dirs[1] : fd;
+    fh = (p == 2) ? cfg.start_heads[2] : fh; fd = (p == 2) ? cfg.start_dirs[2] : fd;
+    fh = (p == 3) ? cfg.start_heads[3] : fh; fd = (p == 3) ? cfg.start_dirs[3] : fd;
+    fh = seat ? fh : 0;
+    const int fy = (int)__umulhi((uint32_t)fh, g.inv_n), fx = fh - fy * N;
+    const int fresh_a = pvalid ? 1 : 0;
+    // a head that is not a cell of the board never equals a target: seats without a player carry one of their own
+    const int no_head = -6 - p, no_tgt = -2 - p;
+    int h = seat ? min(max(h_in, 0), NN - 1) : no_head;
+    int hy = seat ? (int)__umulhi((uint32_t)h, g.inv_n) : 0, hx = seat ? h - hy * N : 0;
+    int d = d_in & 3;
+    // alive_steps: steps after which my player was alive; wn: episodes finished (high 16 bits) and my wins (low 16);
+    // marks: (steps into the launch << 1 | my player alive) at the last two terminal steps (low / high 16 bits)
+    uint32_t alive_steps = 0, wn = 0, marks = 0;
+    const uint32_t gid = (uint32_t)(first_env_id + (uint64_t)bb);
+    const uint32_t tc_in = tc;
+    int a = (k == 0) ? 1 : 0;
+    for (int t = 0; t < T; ++t) {
+        const bool run = a != 0;
+        // ---- decide, on the pre-step board
+        const int c_f = run ? tron_avoid_cell(N, hx, hy, d) : 0;
+        const int c_r = run ? tron_avoid_cell(N, hx, hy, d + 1) : 0;
+        const int c_l = run ? tron_avoid_cell(N, hx, hy, d + 3) : 0;
+        CRL_BOUNDS_LT(c_f, NN, 153);                            // the agent's probes stay on my game's board
+        CRL_BOUNDS_LT(c_r, NN, 154);
+        CRL_BOUNDS_LT(c_l, NN, 155);
+        const int r_f = gb[c_f], r_r = gb[c_r], r_l = gb[c_l];
+        const int code = tron_avoid_code(gid, tc_in + (uint32_t)t, p, seed_lo, seed_hi, thr, r_f, r_r, r_l);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // every probe of this step before any store of it
+        // ---- step (CyTronGrid.pyx:15-62)
+        const int dir = (d + code) & 3;
+        const int sh8 = dir << 3;
+        const int nx = hx + __builtin_amdgcn_sbfe((int)0xff000100u, sh8, 8);
+        const int ny = hy + __builtin_amdgcn_sbfe((int)0x000100ffu, sh8, 8);
+        const bool oob = ((unsigned)nx >= (unsigned)N) | ((unsigned)ny >= (unsigned)N);
+        const int tgt = (int)(__umul24((unsigned)ny, (unsigned)N) + (unsigned)nx);
+        const bool look = run & !oob;
+        const int raw = code == 0 ? r_f : (code == 1 ? r_r : r_l);   // = board[tgt] wherever the target is on the board
+        // does anything in this wave need the reference's sequential order?  (as tron_rollout_gquad_kernel)
+        const int tq = look ? tgt : no_tgt;
+        const int x1 = tq ^ tron_quad<0x39>(h), x2 = tq ^ tron_quad<0x4E>(h), x3 = tq ^ tron_quad<0x93>(h);
+        const int y1 = tq ^ tron_quad<0x39>(tq), y2 = tq ^ tron_quad<0x4E>(tq);
+        const uint32_t near = min(min(min(min((uint32_t)x1, (uint32_t)x2), (uint32_t)x3), (uint32_t)y1), (uint32_t)y2);
+        const int h0 = h, hx0 = hx, hy0 = hy, d0 = d, k0 = k;     // (k == 0 exactly while my player is alive)
+        bool dead = run & (oob | (raw != 0));                   // :47-57
+        bool moved = run ^ dead;                                // :60-62
+        k = dead ? (oob ? p + 1 : raw) : k;
+        d = run ? dir : d;                                      // :44
+        h = moved ? tgt : h; hx = moved ? nx : hx; hy = moved ? ny : hy;
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(near == 0u) != 0ull, 0)) {
+            // rare: the quad's four players in the reference's order from the pre-step state, redundantly in its four lanes
+            TronRegs<4> s;
+            TronProbe<4> pr;
+            const int oobi = oob ? 1 : 0;
+            s.h[0] = tron_quad<0x00>(h0); s.h[1] = tron_quad<0x55>(h0); s.h[2] = tron_quad<0xAA>(h0); s.h[3] = tron_quad<0xFF>(h0);
+            s.x[0] = tron_quad<0x00>(hx0); s.x[1] = tron_quad<0x55>(hx0); s.x[2] = tron_quad<0xAA>(hx0); s.x[3] = tron_quad<0xFF>(hx0);
+            s.y[0] = tron_quad<0x00>(hy0); s.y[1] = tron_quad<0x55>(hy0); s.y[2] = tron_quad<0xAA>(hy0); s.y[3] = tron_quad<0xFF>(hy0);
+            s.d[0] = tron_quad<0x00>(d0); s.d[1] = tron_quad<0x55>(d0); s.d[2] = tron_quad<0xAA>(d0); s.d[3] = tron_quad<0xFF>(d0);
+            s.k[0] = tron_quad<0x00>(k0); s.k[1] = tron_quad<0x55>(k0); s.k[2] = tron_quad<0xAA>(k0); s.k[3] = tron_quad<0xFF>(k0);
+            pr.tgt[0] = tron_quad<0x00>(tgt); pr.tgt[1] = tron_quad<0x55>(tgt); pr.tgt[2] = tron_quad<0xAA>(tgt); pr.tgt[3] = tron_quad<0xFF>(tgt);
+            pr.raw[0] = tron_quad<0x00>(raw); pr.raw[1] = tron_quad<0x55>(raw); pr.raw[2] = tron_quad<0xAA>(raw); pr.raw[3] = tron_quad<0xFF>(raw);
+            pr.ndir[0] = tron_quad<0x00>(dir); pr.ndir[1] = tron_quad<0x55>(dir); pr.ndir[2] = tron_quad<0xAA>(dir); pr.ndir[3] = tron_quad<0xFF>(dir);
+            pr.nx[0] = tron_quad<0x00>(nx); pr.nx[1] = tron_quad<0x55>(nx); pr.nx[2] = tron_quad<0xAA>(nx); pr.nx[3] = tron_quad<0xFF>(nx);
+            pr.ny[0] = tron_quad<0x00>(ny); pr.ny[1] = tron_quad<0x55>(ny); pr.ny[2] = tron_quad<0xAA>(ny); pr.ny[3] = tron_quad<0xFF>(ny);
+            const int o0 = tron_quad<0x00>(oobi), o1 = tron_quad<0x55>(oobi), o2 = tron_quad<0xAA>(oobi), o3 = tron_quad<0xFF>(oobi);
+            pr.oob[0] = o0 != 0; pr.oob[1] = o1 != 0; pr.oob[2] = o2 != 0; pr.oob[3] = o3 != 0;
+            int rew4[4], term4, wm4;
+            const PlainBoard nowhere{nullptr CRL_CELLS_INIT(NN)};
+            tron_resolve<4>(nowhere, false, s, pr, rew4, term4, wm4);   // valid = false: no stores here (below, with everybody's)
+            int hS = s.h[0], xS = s.x[0], yS = s.y[0], dS = s.d[0], kS = s.k[0];
+            hS = (p == 1) ? s.h[1] : hS; xS = (p == 1) ? s.x[1] : xS; yS = (p == 1) ? s.y[1] : yS; dS = (p == 1) ? s.d[1] : dS; kS = (p == 1) ? s.k[1] : kS;
+            hS = (p == 2) ? s.h[2] : hS; xS = (p == 2) ? s.x[2] : xS; yS = (p == 2) ? s.y[2] : yS; dS = (p == 2) ? s.d[2] : dS; kS = (p == 2) ? s.k[2] : kS;
+            hS = (p == 3) ? s.h[3] : hS; xS = (p == 3) ? s.x[3] : xS; yS = (p == 3) ? s.y[3] : yS; dS = (p == 3) ? s.d[3] : dS; kS = (p == 3) ? s.k[3] : kS;
+            moved = hS != h0;                                   // (a head is never its owner's own target)
+            h = hS; hx = xS; hy = yS; d = dS;
+            k = kS;                                             // (also a dead player's entry, overwritten by a head-on killer: :56-57)
+        }
+        // TronGridEnvironment.py:309-321 for the game: alive players over the quad
+        a = (run && k == 0) ? 1 : 0;
+        int alive = a + tron_quad<0xB1>(a);
+        alive += tron_quad<0x4E>(alive);
+        alive_steps += (uint32_t)a;
+        const bool over = alive <= 1;                           // (a game beyond the batch is "over" at every step)
+        // the trail -- unless the game ends with this step: its board is about to be rewritten as a whole
+        if (moved && !over && gvalid) {
+            CRL_BOUNDS_LT(h, NN, 156);
+            gbw[h] = (uint8_t)(p + 1);
+        }
+        if (over) {
+            wn += 0x10000u + (uint32_t)a;
+            marks = (marks << 16) + 2u * (uint32_t)(t + 1) + (uint32_t)a;
+            h = seat ? fh : no_head; hx = fx; hy = fy; d = fd;
+            k = pvalid ? 0 : 1;
+            a = fresh_a;
+        }
+        // new_state for the games of this wave that ended: the whole wave writes each one's start board
+        tron_avoid_rewrite<P>(cfg, board, env0, NN, 2, lane, __builtin_amdgcn_ballot_w64(over && gvalid && p == 0));
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // this step's stores before the next step's probes
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    // ---- per-player state and statistics (my columns), per-game statistics (lane 0 of the quad); as tron_rollout_gquad_kernel
+    const uint32_t n_ep = wn >> 16, wins = wn & 0xffffu;
+    const int done_last = (int)((marks & 0xffffu) >> 1), done_prev = (int)(marks >> 17), last_alive = (int)(marks & 1u);
+    tc = tc_in + (uint32_t)T;
+    const uint32_t ts_at_entry = ts;
+    ts = n_ep ? (uint32_t)(T - done_last) : ts_at_entry + (uint32_t)T;
+    const int last_len = (n_ep > 1u) ? done_last - done_prev : (int)ts_at_entry + done_last;
+    int lw = (last_alive & 1) << p;
+    lw |= tron_quad<0xB1>(lw);
+    lw |= tron_quad<0x4E>(lw);
+    const int ret = 2 * (int)alive_steps - T + 9 * (int)wins;   // alive +1, dead -1, alive at a terminal step +10
+    int32_t *row = st.results ? st.results + b * (3 + 2 * P) : nullptr;
+    uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow<P> : nullptr;
+    if (pvalid) {
+        heads[p * B + b] = (int16_t)h;
+        dirs[p * B + b] = (int8_t)d;
+        deaths[p * B + b] = (int8_t)k;
+        const int rs = old_ret + ret;
+        const uint32_t wc = old_wins + wins;
+        st.ret_sum[p * B + b] = rs;
+        st.win_count[p * B + b] = wc;
+        if (row) { row[3 + p] = (int32_t)wc; row[3 + P + p] = rs; }
+        if (pk) pk[4 + p] = (uint16_t)rs;
+    }
+    if (gvalid && p == 0) {
+        const uint32_t ne = old_n_ep + n_ep, ls = old_len_sum + (ts_at_entry + (uint32_t)T - ts);
+        st.tcount[b] = tc;
+        st.tstep[b] = ts;
+        st.n_episodes[b] = ne;
+        st.len_sum[b] = ls;
+        if (n_ep > 0) {
+            st.last_winners[b] = (uint8_t)lw;
+            st.last_len[b] = (uint16_t)last_len;
+        }
+        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = n_ep > 0 ? lw : (int32_t)old_last_w; }
+        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(n_ep > 0 ? (uint32_t)lw : old_last_w); pk[3] = (uint16_t)ts; }
+    }
+}
+
+// The same for 5..8 players, one lane per game on boards in global memory: the agent's 3P clamped probes of the pre-step
+// board, fence, then the reference's sequential step on registers (tron_resolve, trail stores), TronAcc bookkeeping, and
+// the wave-cooperative rewrite of the boards that ended.  Same fences as above.
+template <int P>
+__global__ void __launch_bounds__(256)
+tron_rollout_avoid_game_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_t B,
+                               const uint32_t seed_lo, const uint32_t seed_hi, const uint64_t first_env_id, const int T,
+                               const uint64_t thr, int8_t *__restrict__ board, int16_t *__restrict__ heads,
+                               int8_t *__restrict__ dirs, int8_t *__restrict__ deaths, const crl_tron_stats st)
+{
+    const int N = g.N, NN = g.NN;
+    const int lane = threadIdx.x & (CRL_WAVE - 1);
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = b < B;
+    const int64_t bb = valid ? b : 0;
+    const int64_t env0 = b - lane;
+    TronRegs<P> s, fresh;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        s.h[p] = valid ? min(max((int)heads[p * B + bb], 0), NN - 1) : 0;
+        s.d[p] = valid ? (dirs[p * B + bb] & 3) : 0;
+        s.k[p] = valid ? deaths[p * B + bb] : 1;
+    }
+    tron_split_heads<P>(g, s);
+    tron_regs_to_start<P>(cfg, g, fresh);
+    TronAcc<P> acc;
+    acc.load(st, valid, bb, B);
+    const uint32_t gid = (uint32_t)(first_env_id + (uint64_t)bb);
+    const PlainBoard bd{board + bb * NN CRL_CELLS_INIT(NN)};
+    for (int t = 0; t < T; ++t) {
+        int cf[P], cr[P], cl[P], rf[P], rr[P], rl[P];
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            const bool run = s.k[i] == 0;
+            cf[i] = run ? tron_avoid_cell(N, s.x[i], s.y[i], s.d[i]) : 0;
+            cr[i] = run ? tron_avoid_cell(N, s.x[i], s.y[i], s.d[i] + 1) : 0;
+            cl[i] = run ? tron_avoid_cell(N, s.x[i], s.y[i], s.d[i] + 3) : 0;
+        }
+#pragma unroll
+        for (int i = 0; i < P; ++i) { rf[i] = bd.raw(cf[i]); rr[i] = bd.raw(cr[i]); rl[i] = bd.raw(cl[i]); }
+        int act[P];
+#pragma unroll
+        for (int i = 0; i < P; ++i) act[i] = tron_avoid_code(gid, acc.tc, i, seed_lo, seed_hi, thr, rf[i], rr[i], rl[i]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // every probe of this step before any store of it
+        TronProbe<P> pr;
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            const int dir = (s.d[i] + act[i]) & 3;
+            const int sh8 = dir << 3;
+            pr.ndir[i] = dir;
+            pr.nx[i] = s.x[i] + __builtin_amdgcn_sbfe((int)0xff000100u, sh8, 8);
+            pr.ny[i] = s.y[i] + __builtin_amdgcn_sbfe((int)0x000100ffu, sh8, 8);
+            pr.oob[i] = ((unsigned)pr.nx[i] >= (unsigned)N) | ((unsigned)pr.ny[i] >= (unsigned)N);
+            pr.tgt[i] = pr.oob[i] ? 0 : (int)(__umul24((unsigned)pr.ny[i], (unsigned)N) + (unsigned)pr.nx[i]);
+            pr.raw[i] = act[i] == 0 ? rf[i] : (act[i] == 1 ? rr[i] : rl[i]);
+        }
+        int rew[P], term, wm;
+        tron_resolve<P>(bd, valid, s, pr, rew, term, wm);
+        acc.tc += 1;
+        acc.ts += 1;
+#pragma unroll
+        for (int p = 0; p < P; ++p) acc.ret[p] += rew[p];
+        const bool ends = valid && term;
+        if (ends) {
+            acc.finish_episode(wm);
+            s = fresh;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the trails before the rewrite of a board that ended
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        tron_avoid_rewrite<P>(cfg, board, env0, NN, 0, lane, __builtin_amdgcn_ballot_w64(ends));
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // this step's stores before the next step's probes
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (valid) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            heads[p * B + b] = (int16_t)s.h[p];
+            dirs[p * B + b] = (int8_t)s.d[p];
+            deaths[p * B + b] = (int8_t)s.k[p];
+        }
+        acc.store(st, B, b);
+    }
+}
+
+// One step of a learner-vs-scripted-opponents batch (TronSinglePlayerVectorEnv; reference TronRaySinglePlayerEnvironment.step,
+// envs/tron/rllib.py:131-153): the learner's action index {0 forward, 1 right, 2 left} for player 0, the opponents' rows of
+// `actions` for the others, the step of tron_step_kernel, then done = learner dead or game terminal and new_state for the
+// games that are done (each lane rewrites its OWN board, as tron_step_kernel's auto-reset does).
+template <int P>
+__global__ void __launch_bounds__(256)
+tron_step_single_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_t B,
+                        int8_t *__restrict__ board, int16_t *__restrict__ heads, int8_t *__restrict__ dirs,
+                        int8_t *__restrict__ deaths, const int8_t *__restrict__ actions, const int64_t *__restrict__ learner,
+                        int8_t *__restrict__ reward, uint8_t *__restrict__ done, uint8_t *__restrict__ terminal)
+{
+    const int NN = g.NN;
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = b < B;
+    const int64_t bb = valid ? b : 0;
+    TronRegs<P> s;
+    int act[P], rew[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        s.h[p] = valid ? heads[p * B + bb] : 0;
+        s.d[p] = valid ? dirs[p * B + bb] : 0;
+        s.k[p] = valid ? deaths[p * B + bb] : 1;
+        act[p] = (valid && p > 0) ? actions[p * B + bb] : 0;
+    }
+    const int la = valid ? (int)(((learner[bb] % 3) + 3) % 3) : 0;   // 0, 1, 2 -> 0, +1, -1
+    act[0] = la == 2 ? -1 : la;
+    tron_split_heads<P>(g, s);
+    int term, wm;
+    const PlainBoard bd{board + bb * NN CRL_CELLS_INIT(NN)};
+    tron_step_core<P>(g, bd, valid, s, act, rew, term, wm);
+    const bool dn = term || s.k[0] != 0;
+    if (valid) {
+        reward[b] = (int8_t)rew[0];
+        done[b] = (uint8_t)dn;
+        terminal[b] = (uint8_t)term;
+    }
+    if (valid && dn) {
+        int8_t *own = board + b * NN;
+        if ((NN & 15) == 0 && (((uintptr_t)own & 15) == 0))
+            for (int off = 0; off < NN; off += 16) *reinterpret_cast<uint4 *>(own + off) = make_uint4(0, 0, 0, 0);
+        else
+            for (int off = 0; off < NN; ++off) own[off] = 0;
+        tron_regs_to_start<P>(cfg, g, s);
+#pragma unroll
+        for (int p = 0; p < P; ++p) own[s.h[p]] = (int8_t)(p + 1);
+    }
+    if (valid) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            heads[p * B + b] = (int16_t)s.h[p];
+            dirs[p * B + b] = (int8_t)s.d[p];
+            deaths[p * B + b] = (int8_t)s.k[p];
+        }
+    }
+}
+
 } // namespace
 
 #define TRON_DISPATCH_P(P_, CALL)          \
@@ -4868,6 +5280,87 @@ int crl_tron_sample(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first
     TRON_DISPATCH_P(ctx->tron.P, {
         hipLaunchKernelGGL((tron_sample_kernel<PP>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, B,
                            (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, tcount, advance, actions);
+    });
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+// the avoid agent's noise threshold: W[0] < thr is "noisy", thr = min(2^32, ceil(noise * 2^32)) in 64 bits
+static uint64_t tron_avoid_threshold(const double noise)
+{
+    const double x = ceil(noise * 4294967296.0);
+    return x >= 4294967296.0 ? ((uint64_t)1 << 32) : (uint64_t)x;
+}
+
+int crl_tron_sample_avoid(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *tcount, int advance,
+                          double noise, uint32_t player_mask, const int8_t *board, const int16_t *heads, const int8_t *dirs,
+                          const int8_t *deaths, int8_t *actions, void *stream)
+{
+    TRON_CTX_CHECK("crl_tron_sample_avoid");
+    CRL_REQUIRE(tcount && actions, "crl_tron_sample_avoid: NULL tcount / actions pointer");
+    CRL_REQUIRE(board && heads && dirs && deaths, "crl_tron_sample_avoid: NULL state pointer");
+    CRL_REQUIRE(noise >= 0.0 && noise <= 1.0, "crl_tron_sample_avoid: noise=%g not in [0, 1]", noise);
+    const crl_tron_cfg &cfg = ctx->tron;
+    CRL_REQUIRE((player_mask >> cfg.P) == 0u, "crl_tron_sample_avoid: player_mask 0x%x names players beyond P=%d", player_mask, cfg.P);
+    const TronGeom g = geom_of(cfg);
+    const uint64_t thr = tron_avoid_threshold(noise);
+    const int lanes = cfg.P <= 1 ? 1 : cfg.P <= 2 ? 2 : cfg.P <= 4 ? 4 : 8;     // per game (tron_sample_avoid_kernel)
+    TRON_DISPATCH_P(cfg.P, {
+        hipLaunchKernelGGL((tron_sample_avoid_kernel<PP>), dim3(blocks_for(B * lanes, 256)), dim3(256), 0, (hipStream_t)stream,
+                           g, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, tcount, advance, thr, player_mask,
+                           board, heads, dirs, deaths, actions);
+    });
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_tron_rollout_avoid(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, double noise,
+                           int8_t *board, int16_t *heads, int8_t *dirs, int8_t *deaths, crl_tron_stats st, uint32_t flags,
+                           void *stream)
+{
+    TRON_CTX_CHECK("crl_tron_rollout_avoid");
+    CRL_REQUIRE(board && heads && dirs && deaths, "crl_tron_rollout_avoid: NULL state pointer");
+    CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.len_sum && st.ret_sum &&
+                st.last_winners && st.last_len, "crl_tron_rollout_avoid: NULL stats pointer");
+    CRL_REQUIRE(T >= 0 && T <= (1 << 24), "crl_tron_rollout_avoid: T=%d out of range", T);
+    CRL_REQUIRE(noise >= 0.0 && noise <= 1.0, "crl_tron_rollout_avoid: noise=%g not in [0, 1]", noise);
+    CRL_REQUIRE(flags == 0u, "crl_tron_rollout_avoid: unknown flags 0x%x", flags);
+    const crl_tron_cfg &cfg = ctx->tron;
+    if (T == 0) return CRL_OK;
+    const TronGeom g = geom_of(cfg);
+    const uint64_t thr = tron_avoid_threshold(noise);
+    hipStream_t s = (hipStream_t)stream;
+    constexpr int kMaxT = 16383;                                // (16-bit episode / win / step counts per launch)
+    for (int t0 = 0; t0 < T; t0 += kMaxT) {
+        const int Tl = std::min(kMaxT, T - t0);
+        if (cfg.P <= 4) {
+            TRON_DISPATCH_P4(cfg.P, {
+                hipLaunchKernelGGL((tron_rollout_avoid_kernel<PP>), dim3(blocks_for(B, 64)), dim3(256), 0, s, cfg, g, B,
+                                   (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, Tl, thr, board, heads, dirs, deaths, st);
+            });
+        } else {
+            TRON_DISPATCH_P(cfg.P, {
+                hipLaunchKernelGGL((tron_rollout_avoid_game_kernel<PP>), dim3(blocks_for(B, 256)), dim3(256), 0, s, cfg, g, B,
+                                   (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, Tl, thr, board, heads, dirs, deaths, st);
+            });
+        }
+        CRL_LAUNCH_CHECK();
+    }
+    return CRL_OK;
+}
+
+int crl_tron_step_single(const crl_ctx *ctx, int64_t B, int8_t *board, int16_t *heads, int8_t *dirs, int8_t *deaths,
+                         const int8_t *actions, const int64_t *learner_action, int8_t *reward, uint8_t *done, uint8_t *terminal,
+                         void *stream)
+{
+    TRON_CTX_CHECK("crl_tron_step_single");
+    CRL_REQUIRE(board && heads && dirs && deaths, "crl_tron_step_single: NULL state pointer");
+    CRL_REQUIRE(actions && learner_action && reward && done && terminal, "crl_tron_step_single: NULL action / output pointer");
+    const crl_tron_cfg &cfg = ctx->tron;
+    const TronGeom g = geom_of(cfg);
+    TRON_DISPATCH_P(cfg.P, {
+        hipLaunchKernelGGL((tron_step_single_kernel<PP>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, cfg, g, B,
+                           board, heads, dirs, deaths, actions, learner_action, reward, done, terminal);
     });
     CRL_LAUNCH_CHECK();
     return CRL_OK;

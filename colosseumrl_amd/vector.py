@@ -10,7 +10,8 @@ from typing import Dict, Tuple
 
 import torch
 
-from .batched import BlokusBatch, TronBatch, TTTBatch
+from ._native import check
+from .batched import BlokusBatch, TronBatch, TTTBatch, _DevGuard, _ptr, _stream
 
 
 class TronVectorEnv:
@@ -35,6 +36,58 @@ class TronVectorEnv:
         obs = {p: {"board": o["board"][p], "heads": o["heads"][p], "directions": o["directions"][p], "deaths": o["deaths"][p]}
                for p in range(self.num_players)}
         return obs, o["rewards"].clone(), o["terminal"].clone(), {"winners": o["winners"].clone()}
+
+
+class TronSinglePlayerVectorEnv:
+    """B games of one learner (player 0) against P - 1 scripted opponents: the batched counterpart of the reference's
+    ``TronRaySinglePlayerEnvironment`` (envs/tron/rllib.py:98-157) with its default opponent ``SimpleAvoidAgent(noise)``.
+
+    ``reset() -> obs`` and ``step(action) -> obs, reward, done, info`` with ``action`` int64 [B] in {0 forward, 1 right,
+    2 left} (the reference's ``action_to_string`` order).  ``obs`` is player 0's relative observation, which for player 0 is
+    the state itself: {'board' int8 [B, N, N], 'heads' int16 [P, B], 'directions' int8 [P, B], 'deaths' int8 [P, B]} --
+    views of the live state, valid until the next ``step`` / ``reset`` (clone what you keep).  ``reward`` int8 [B] is the
+    learner's reward, ``done`` uint8 [B] is "learner dead or game over"; done games restart in the same step and ``obs`` is
+    of the state after that restart.  ``info['terminal']`` uint8 [B]: the game itself ended.  ``reward`` / ``done`` /
+    ``info`` are buffers rewritten by every step as well.
+    A step is two launches (opponents' actions, then step + done + reset) with no host synchronisation, and can be
+    captured into a HIP graph (``torch.cuda.graph``).  The opponents' draws follow ``crl_tron_sample_avoid``'s contract
+    at each game's step counter, keyed by ``seed``."""
+
+    def __init__(self, board_size: int = 15, num_players: int = 4, batch: int = 1024, noise: float = 0.1, seed: int = 0,
+                 spawn_offset: int = 2, device="cuda"):
+        if num_players < 1:
+            raise ValueError("num_players must be at least 1")
+        self.batch = TronBatch(board_size, num_players, batch, device=device, spawn_offset=spawn_offset)
+        self.num_players, self.num_envs = num_players, batch
+        self.noise, self.seed = float(noise), int(seed)
+        if not 0.0 <= self.noise <= 1.0:
+            raise ValueError("noise=%r not in [0, 1]" % (noise,))
+        dev = self.batch.device
+        self._actions = torch.zeros((num_players, batch), dtype=torch.int8, device=dev)
+        self._opponents = list(range(1, num_players))
+        self.reward = torch.zeros((batch,), dtype=torch.int8, device=dev)
+        self.done = torch.zeros((batch,), dtype=torch.uint8, device=dev)
+        self.terminal = torch.zeros((batch,), dtype=torch.uint8, device=dev)
+
+    def observation(self) -> Dict[str, torch.Tensor]:
+        b = self.batch
+        return {"board": b.board.view(b.B, b.N, b.N), "heads": b.heads, "directions": b.dirs, "deaths": b.deaths}
+
+    def reset(self) -> Dict[str, torch.Tensor]:
+        self.batch.reset()
+        return self.observation()
+
+    def step(self, action: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict]:
+        b = self.batch
+        if action.dtype != torch.int64 or tuple(action.shape) != (b.B,) or action.device != b.device or not action.is_contiguous():
+            raise ValueError("action must be a contiguous int64 tensor of shape (%d,) on %s" % (b.B, b.device))
+        if self._opponents:
+            b.sample_avoid(self.seed, self.noise, players=self._opponents, out=self._actions)
+        with _DevGuard(b.device):
+            check(b._lib.crl_tron_step_single(b._ctx.handle, b.B, _ptr(b.board), _ptr(b.heads), _ptr(b.dirs), _ptr(b.deaths),
+                                              _ptr(self._actions), _ptr(action), _ptr(self.reward), _ptr(self.done),
+                                              _ptr(self.terminal), _stream()), "crl_tron_step_single")
+        return self.observation(), self.reward, self.done, {"terminal": self.terminal}
 
 
 class TicTacToeVectorEnv:

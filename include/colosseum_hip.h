@@ -76,8 +76,9 @@ const char *crl_last_error(void);
  * 100: round 1.  101: crl_tron_stats gained `packed`.  102: TicTacToe sampled agent draws 8 plies per Philox block.
  * 104: round 4.  105: crl_stream_wait_mapped.  106: crl_diag_issue_probe.  107: crl_blokus_fits.  108: crl_diag_bounds.
  * 109: crl_blokus_step / _step_observe place ANY action as the reference's next_state does (numpy index rules, extended ids,
- *      CRL_BLOKUS_*_ERROR codes in the reward slot).  110: crl_tron_next_state_inplace64 (+ _host) / _relative_player_inplace64.  111: crl_ttt_step_board_host. */
-#define CRL_ABI_VERSION 111
+ *      CRL_BLOKUS_*_ERROR codes in the reward slot).  110: crl_tron_next_state_inplace64 (+ _host) / _relative_player_inplace64.  111: crl_ttt_step_board_host.
+ * 112: crl_tron_sample_avoid / crl_tron_rollout_avoid (the scripted avoid agent), crl_tron_step_single. */
+#define CRL_ABI_VERSION 112
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
 int crl_device_count(void);
@@ -226,6 +227,53 @@ int crl_tron_check_state(const crl_ctx *ctx, int64_t B, const int8_t *board, con
  * crl_tron_rollout(T); callers overwrite the rows of the players they control.  No reference counterpart. */
 int crl_tron_sample(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *tcount, int advance,
                     int8_t *actions, void *stream);
+
+/* The reference's scripted opponent, SimpleAvoidAgent.__call__ (colosseumrl/envs/tron/rllib.py:68-95; the default opponent of
+ * TronRaySinglePlayerEnvironment), for player p of global game g = first_env_id + b at step counter c = tcount[b].
+ * Contract -- one Philox call per (game, step, player) under its own domain tag (the random agent's above is untouched):
+ *   W = Philox4x32-10(ctr = {g, c, p, 0x54410000}, key = {seed lo, seed hi})
+ *   noisy  iff  W[0] < thr,  thr = min(2^32, ceil(noise * 2^32)) computed on the host in 64 bits: noise = 0 is never noisy,
+ *          noise = 1 always.  (The reference tests random.random() <= noise; the tie is an event of measure zero and is
+ *          the one place where the two differ.)
+ *   noisy:  a = mulhi32(W[1], 3): 0 forward, 1 right, 2 left  (the order of random.choice(['forward', 'right', 'left'])).
+ *   else:   with `cell(dir)` = next_cell(x, y, dir, N) WITH clamping (TronGridEnvironment.py:467-481: a move off the board is
+ *           clamped back onto it, so at a wall the cell ahead is the head itself, which is occupied):
+ *           board[cell(d)] == 0                       -> forward;
+ *           else side = W[2] >> 31: 0 = (+1, right, left), 1 = (-1, left, right); board[cell((d + offset) mod 4)] == 0 ->
+ *           the first action of the pair, else the second.
+ *   0 is "free" in the state and in every relabelled observation alike, so the agent reads the STATE board (no observation
+ *   needed).  All players decide on the pre-step board (the reference computes every action before next_state).
+ * crl_tron_sample_avoid writes actions[p*B+b] (0 forward, +1 right, -1 left, the crl_tron_step encoding; dead players: 0)
+ * ONLY for the players whose bit is set in player_mask: the other rows are left untouched, so a caller writes its learner's
+ * row and one launch fills in the opponents.  advance != 0 increments tcount, as crl_tron_sample does.  One lane per
+ * (player, game): one Philox call and three byte probes (ahead, right, left) of the board.
+ * Errors (CRL_EINVAL): noise outside [0, 1] or NaN, player_mask bits >= P, NULL pointers.  No reference counterpart
+ * as a batched call. */
+int crl_tron_sample_avoid(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *tcount, int advance,
+                          double noise, uint32_t player_mask, const int8_t *board, const int16_t *heads, const int8_t *dirs,
+                          const int8_t *deaths, int8_t *actions, void *stream);
+
+/* T fused steps with EVERY player on the avoid agent, auto-reset, and the crl_tron_stats bookkeeping of crl_tron_rollout.
+ * Bit-exact equivalent of
+ *   T x (crl_tron_sample_avoid(all players, advance = 1); crl_tron_step(CRL_STEP_AUTO_RESET))
+ * plus the statistics that loop implies (as crl_tron_rollout keeps them).  One launch (per 16,383 steps): with P <= 4 one lane
+ * per player on boards in global memory (any board size; the quad shares the alive count and the reset), with P = 5..8 one
+ * lane per game (same results).  Every step decides on the pre-step board before any lane of the game stores.  flags must
+ * be 0 (reserved).  Argument checks as crl_tron_sample_avoid and crl_tron_rollout. */
+int crl_tron_rollout_avoid(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, double noise,
+                           int8_t *board, int16_t *heads, int8_t *dirs, int8_t *deaths, crl_tron_stats stats, uint32_t flags,
+                           void *stream);
+
+/* One step of B "learner against scripted opponents" games (reference TronRaySinglePlayerEnvironment.step,
+ * colosseumrl/envs/tron/rllib.py:131-153, batched): player 0 plays learner_action[b] (int64: 0 forward, 1 right, 2 left;
+ * other values are taken mod 3), players 1..P-1 play rows 1..P-1 of actions (int8 [P][B], the crl_tron_step encoding; row 0
+ * is not read -- fill the others with crl_tron_sample_avoid).  Outputs: reward int8 [B] = the learner's crl_tron_step reward,
+ * terminal uint8 [B] = the game ended, done uint8 [B] = the learner died or the game ended; the done games are reset to the
+ * start layout in the same launch (the state then is new_state's, as after CRL_STEP_AUTO_RESET).  Player 0's relative
+ * observation IS the state (relabelling for player 0 is the identity).  One launch, one lane per game. */
+int crl_tron_step_single(const crl_ctx *ctx, int64_t B, int8_t *board, int16_t *heads, int8_t *dirs, int8_t *deaths,
+                         const int8_t *actions, const int64_t *learner_action, int8_t *reward, uint8_t *done, uint8_t *terminal,
+                         void *stream);
 
 /* replaces CyTronGrid.relative_player_inplace (CyTronGrid.pyx:65-71) + the rolls of
  * TronGridEnvironment.state_to_observation (TronGridEnvironment.py:385-405), fully observable branch.

@@ -15,10 +15,11 @@ LIB_PATH = os.environ.get("CRL_LIB_PATH") or os.path.join(PKG_DIR, "libcolosseum
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")
 
 # the revision of include/colosseum_hip.h this binding (struct layouts, argument lists, RNG contract) was written against
-CRL_ABI_VERSION = 112
+CRL_ABI_VERSION = 113
 CRL_STEP_AUTO_RESET = 1
 CRL_STEP_BYTES = 2
 CRL_STEP_STAGED = 4
+CRL_STEP_RANK_ACTION = 8
 CRL_ROLLOUT_NO_LDS = 2
 CRL_ROLLOUT_BYTES = 4
 CRL_ROLLOUT_BITS = 8
@@ -108,6 +109,7 @@ PROTOTYPES = {
     "crl_ttt_rollout": (_I, [_VP, _I64, _U64, _U64, _I, _VP, _VP, _VP, TTTStats, _VP]),
     "crl_ttt_sample": (_I, [_VP, _I64, _U64, _U64, _VP, _VP, _I, _VP, _VP]),
     "crl_ttt_step_observe": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 10 + [_I, _U32, _VP]),
+    "crl_ttt_step_single": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 11 + [_I, _U32, _VP]),
     "crl_blokus_create": (_I, [C.POINTER(_VP)]),
     "crl_blokus_placement": (_I, [_I, _I, _I, _VP]),
     "crl_blokus_stamps": (_I, [_VP, _I]),
@@ -124,6 +126,7 @@ PROTOTYPES = {
     "crl_blokus_rollout": (_I, [_VP, _I64, _U64, _U64, _I, _VP, _VP, _VP, _VP, _VP, BlokusStats, _VP]),
     "crl_blokus_sample": (_I, [_VP, _I64, _U64, _U64, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     "crl_blokus_step_observe": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 15 + [_U32, _VP]),
+    "crl_blokus_step_single": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 15 + [_U32, _VP]),
 }
 
 

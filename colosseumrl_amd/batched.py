@@ -15,7 +15,7 @@ import ctypes as C
 import torch
 
 from . import _native
-from ._native import CRL_STEP_AUTO_RESET, TronStats, TTTStats, check
+from ._native import CRL_STEP_AUTO_RESET, CRL_STEP_RANK_ACTION, TronStats, TTTStats, check
 from .envs.tron import layout as tron_layout
 
 
@@ -512,6 +512,31 @@ class TTTBatch(_Waitable):
         out["mover"], out["reward"], out["terminal"], out["winners"] = self.to_move, self.reward, self.terminal, self.winners
         return out
 
+    def step_single(self, seat: torch.Tensor, learner_action: Optional[torch.Tensor] = None, seed: int = 0,
+                    rel_mod: Optional[int] = None, out: Optional[dict] = None):
+        """One step of "learner at seat[b] against the random agent" in every game, ONE launch (``crl_ttt_step_single``):
+        the learner plays ``learner_action`` (int64 [B]: a cell in [-1, cells), anything else passes) when it is its turn,
+        the random agent plays every other seat until it is the learner's turn again, finished games restart on the way.
+        ``learner_action=None`` only advances to the learner's turn.  seat int8 [B].  Returns
+        {'board' int8 [B, cells] relative to the learner, 'valid' int32 [B] empties mask, 'reward' int8 [B] (+1 the learner
+        won, -1 another player, 0 draw or not over), 'done' uint8 [B], 'winners' int8 [B]}; every ply, the learner's
+        included, advances ``tcount`` (the draws are ``sample``'s)."""
+        _want(seat, torch.int8, (self.B,), self.device, "seat")
+        if learner_action is not None:
+            _want(learner_action, torch.int64, (self.B,), self.device, "learner_action")
+        if out is None:
+            out = {"board": torch.empty((self.B, self.n_cells), dtype=torch.int8, device=self.device),
+                   "valid": torch.empty((self.B,), dtype=torch.int32, device=self.device),
+                   "done": torch.empty((self.B,), dtype=torch.uint8, device=self.device)}
+        with _DevGuard(self.device):
+            check(self._lib.crl_ttt_step_single(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
+                                                _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move), _ptr(seat),
+                                                _ptr(learner_action), _ptr(self.tcount), _ptr(self.reward), _ptr(out["done"]),
+                                                _ptr(self.winners), _ptr(out["board"]), _ptr(out["valid"]),
+                                                int(rel_mod if rel_mod else self.P), 0, _stream()), "crl_ttt_step_single")
+        out["reward"], out["winners"] = self.reward, self.winners
+        return out
+
     def _stats(self):
         return TTTStats(*[t.data_ptr() for t in (self.tcount, self.tstep, self.n_episodes, self.win_count,
                                                   self.draw_count, self.len_sum, self._results)])
@@ -763,6 +788,35 @@ class BlokusBatch(_Waitable):
                 ids = torch.empty((self.B, int(list_cap)), dtype=torch.int32, device=self.device)
             ids.fill_(-1)
             out["ids"] = self.valid_list(int(list_cap), out=ids)[1]
+        return out
+
+    def step_single(self, seat: torch.Tensor, learner_action: Optional[torch.Tensor] = None, seed: int = 0,
+                    rank: bool = False, out: Optional[dict] = None):
+        """One step of "learner at seat[b] against the random agent" in every game, ONE launch (``crl_blokus_step_single``):
+        the learner plays ``learner_action`` (int64 [B]: a dense or extended id, < 0 = pass; with ``rank=True`` the index
+        into its ordered legal list, outside [0, count) = pass) when it is its turn, the random agent plays the other
+        seats until it is the learner's turn again, finished games restart on the way.  ``learner_action=None`` only
+        advances to the learner's turn.  seat int8 [B].  Returns {'board', 'pieces', 'score' (the learner's observation),
+        'n_valid' int32 [B] (its number of legal actions), 'reward' int8 [B] (its final rank when a game ended, else 0, or
+        a ``CRL_BLOKUS_*_ERROR`` code for an action the reference's next_state raises on -- that game then stays as it
+        was), 'done' uint8 [B], 'winners' uint8 [B]}; every ply, the learner's included, advances ``tcount``."""
+        _want(seat, torch.int8, (self.B,), self.device, "seat")
+        if learner_action is not None:
+            _want(learner_action, torch.int64, (self.B,), self.device, "learner_action")
+        if out is None:
+            out = {"board": torch.empty((self.B, 20, 20), dtype=torch.int8, device=self.device),
+                   "pieces": torch.empty((self.B, 4, 21), dtype=torch.uint8, device=self.device),
+                   "score": torch.empty((self.B, 4), dtype=torch.int32, device=self.device),
+                   "n_valid": torch.empty((self.B,), dtype=torch.int32, device=self.device),
+                   "done": torch.empty((self.B,), dtype=torch.uint8, device=self.device)}
+        with _DevGuard(self.device):
+            check(self._lib.crl_blokus_step_single(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
+                                                   *self._state(), _ptr(seat), _ptr(learner_action), _ptr(self.tcount),
+                                                   _ptr(self.reward), _ptr(out["done"]), _ptr(self.winners),
+                                                   _ptr(out["n_valid"]), _ptr(out["board"]), _ptr(out["pieces"]),
+                                                   _ptr(out["score"]), CRL_STEP_RANK_ACTION if rank else 0, _stream()),
+                  "crl_blokus_step_single")
+        out["reward"], out["winners"] = self.reward, self.winners
         return out
 
     def board(self):

@@ -1106,6 +1106,101 @@ blokus_step_observe_kernel(const BlkTables *__restrict__ tables, const int64_t B
     blk_write_observation(L.occ, inv, score, pl, b, lane, obs_board, obs_pieces, obs_score);
 }
 
+// ---- one learner against the random agent (crl_blokus_step_single; the contract is in include/colosseum_hip.h): per game
+// an optional learner ply, then the random agent for every other seat until it is the learner's turn again -- across the
+// end of a game and its restart -- and the learner's count and observation of what that leaves.  The wave that owns the
+// game plays every ply (at most 1 + 6) on its LDS copy of the board: one load and one store of the state per call, where
+// a chain of step_observe calls reloads the board and rebuilds the allowed / corner rows per ply.  Each ply is that of
+// blokus_step_observe_kernel (the draw of blokus_sample_kernel, blk_play, the terminal test on the pre-move board); the
+// loop runs on wave-uniform values (mover, seat, step counter), so it costs no divergence.
+__global__ void __launch_bounds__(256, BLK_WAVES_PER_SIMD)
+blokus_step_single_kernel(const BlkTables *__restrict__ tables, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
+                          const uint64_t first_env_id, uint32_t *__restrict__ occ, uint32_t *__restrict__ inv_g,
+                          int32_t *__restrict__ score_g, int32_t *__restrict__ round_g, int32_t *__restrict__ to_move_g,
+                          const int8_t *__restrict__ seat, const int64_t *__restrict__ learner_action,
+                          uint32_t *__restrict__ tcount, int8_t *__restrict__ reward, uint8_t *__restrict__ done,
+                          uint8_t *__restrict__ winners, int32_t *__restrict__ n_valid, int8_t *__restrict__ obs_board,
+                          uint8_t *__restrict__ obs_pieces, int32_t *__restrict__ obs_score, const uint32_t flags)
+{
+    BLK_SHARED_SETUP();
+    uint32_t inv[4];
+    int score[4];
+    blk_load_state(L, b, lane, occ, inv_g, score_g, inv, score);
+    int round = __builtin_amdgcn_readfirstlane(round_g[b]), pl = __builtin_amdgcn_readfirstlane(to_move_g[b]) & 3;
+    const int s = __builtin_amdgcn_readfirstlane((int)seat[b]) & 3;
+    uint32_t tc = (uint32_t)__builtin_amdgcn_readfirstlane((int)tcount[b]);
+    int rew = 0, dn_wn = 0;                                      // dn_wn: done | winners << 1
+    // plies: bit 3 = the next ply is the learner's, bits 0..2 = opponent plies played
+    int plies = (learner_action != nullptr && pl == s) ? 8 : 0;
+    for (; plies >= 8 || (pl != s && plies < 6); ) {
+        const bool learner = plies >= 8;
+        blk_prep(L, lane, round);                                // allowed / corner rows of the PRE-move board (:424)
+        uint32_t ip = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ip = (c == pl) ? inv[c] : ip;
+        int id = -1;
+        if (learner && !(flags & CRL_STEP_RANK_ACTION)) {                             // crl_blokus_step's int32 action; v < -1 is the pass
+            const int64_t v = learner_action[b];
+            const int64_t top = (int64_t)CRL_BLOKUS_EXT_BASE + CRL_BLOKUS_EXT_IDS;
+            id = __builtin_amdgcn_readfirstlane(v < 0 ? -1 : (int)(v < top ? v : top));
+        } else {                                                 // a rank into the mover's ordered legal list
+            const uint32_t total = blk_count(T, L, pl, ip, lane);
+            int64_t r;
+            if (learner) {
+                r = learner_action[b];
+            } else {                                             // the random agent at this game's step counter
+                const philox_out rnd = philox4x32_10((uint32_t)(first_env_id + (uint64_t)b), tc >> 2, 0u, CRL_TAG_BLOKUS, seed_lo, seed_hi);
+                const uint32_t sel = tc & 3u;
+                const uint32_t word = sel == 0 ? rnd.w[0] : sel == 1 ? rnd.w[1] : sel == 2 ? rnd.w[2] : rnd.w[3];
+                r = __umulhi(word, total);
+            }
+            const int ri = __builtin_amdgcn_readfirstlane(r >= 0 && r < (int64_t)total ? (int)r : -1);
+            if (ri >= 0) {
+                const BlkMove mv = blk_select(T, L, pl, ip, (uint32_t)ri, lane);
+                id = ((mv.piece * 400 + mv.y * BN + mv.x) * 8 + mv.orient) * 5 + mv.shift;
+            }
+        }
+        plies = learner ? 0 : plies + 1;
+        const int status = id >= 0 ? blk_play(T, L, pl, id, inv, score, lane) : 0;   // '' (pass) below 0 (:418)
+        if (status != 0) { rew = status; break; }                // (the learner's ply only: a drawn action is legal)
+        tc += 1u;
+        bool any_move = false;
+        for (int q = 0; q < 4 && !any_move; ++q) {               // old board, old round, NEW inventories (:424)
+            uint32_t iq = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) iq = (c == q) ? inv[c] : iq;
+            any_move = blk_exists(T, L, q, iq, lane);
+        }
+        const BlkOutcome out = blk_outcome(any_move, pl, score);
+        round += (pl == 3) ? 1 : 0;                              // :446-447
+        pl = (pl + 1) & 3;
+        if (out.terminal) {                                      // the learner's rank (:424-440 with the mover = s), restart
+            dn_wn = 1 | out.winners << 1;
+            rew = blk_outcome(false, s, score).reward;
+            blk_fresh(L, lane, inv, score);
+            round = 0;
+            pl = 0;
+        }
+    }
+    blk_store_state(L, b, lane, occ, inv_g, score_g, inv, score);
+    if (lane == 0) {
+        round_g[b] = round;
+        to_move_g[b] = pl;
+        tcount[b] = tc;
+        reward[b] = (int8_t)rew;
+        done[b] = (uint8_t)(dn_wn & 1);
+        winners[b] = (uint8_t)(dn_wn >> 1);
+    }
+    // ---- what the learner needs: its number of legal actions and its observation (:453-500, :752-768)
+    blk_prep(L, lane, round);
+    uint32_t is = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) is = (c == s) ? inv[c] : is;
+    const uint32_t total = blk_count(T, L, s, is, lane);
+    if (lane == 0) n_valid[b] = (int32_t)total;
+    blk_write_observation(L.occ, inv, score, s, b, lane, obs_board, obs_pieces, obs_score);
+}
+
 __global__ void __launch_bounds__(256, BLK_WAVES_PER_SIMD)
 blokus_rollout_kernel(const BlkTables *__restrict__ tables, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
                       const uint64_t first_env_id, const int T_steps, uint32_t *__restrict__ occ, uint32_t *__restrict__ inv_g,
@@ -1864,6 +1959,28 @@ int crl_blokus_step_observe(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64
                        (const BlkTables *)ctx->blokus, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
                        occ, inv, score, round, to_move, action, tcount, reward, terminal, winners, n_valid,
                        obs_board, obs_pieces, obs_score, obs_player, flags);
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_blokus_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                           uint32_t *occ, uint32_t *inv, int32_t *score, int32_t *round, int32_t *to_move,
+                           const int8_t *seat, const int64_t *learner_action, uint32_t *tcount,
+                           int8_t *reward, uint8_t *done, uint8_t *winners, int32_t *n_valid,
+                           int8_t *obs_board, uint8_t *obs_pieces, int32_t *obs_score, uint32_t flags, void *stream)
+{
+    // (the pointer and flag checks come before the context's: they need no device)
+    CRL_REQUIRE(occ && inv && score && round && to_move, "crl_blokus_step_single: NULL state pointer");
+    CRL_REQUIRE(seat && tcount, "crl_blokus_step_single: NULL seat / tcount pointer");
+    CRL_REQUIRE(reward && done && winners && n_valid && obs_board && obs_pieces && obs_score,
+                "crl_blokus_step_single: NULL output pointer");
+    CRL_REQUIRE((flags & ~CRL_STEP_RANK_ACTION) == 0, "crl_blokus_step_single: unknown flags 0x%x", flags);
+    CRL_REQUIRE((((uintptr_t)obs_board) & 3) == 0, "crl_blokus_step_single: obs_board must be 4-byte aligned");
+    BLK_CTX_CHECK("crl_blokus_step_single");
+    hipLaunchKernelGGL(blokus_step_single_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const BlkTables *)ctx->blokus, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
+                       occ, inv, score, round, to_move, seat, learner_action, tcount, reward, done, winners, n_valid,
+                       obs_board, obs_pieces, obs_score, flags);
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }

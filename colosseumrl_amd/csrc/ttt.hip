@@ -69,9 +69,11 @@ __device__ __forceinline__ bool ttt_has_line(const ttt_dirs &dd, const uint32_t 
     return hit != 0;
 }
 
-template <int P, int ND>
+// WT: test for a line by the win-mask table win_bits of a board of at most 16 cells (in LDS; crl_ttt_create builds it)
+template <int P, int ND, bool WT = false>
 __device__ __forceinline__ void ttt_step_core(const ttt_dirs &dd, uint32_t (&o)[P], int &winner, int &to_move,
-                                              const int action, int &reward, int &term, int &winners)
+                                              const int action, int &reward, int &term, int &winners,
+                                              const uint32_t *win_bits = nullptr)
 {
     const int pl = to_move;
     uint32_t all = 0, mine = 0;
@@ -86,7 +88,13 @@ __device__ __forceinline__ void ttt_step_core(const ttt_dirs &dd, uint32_t (&o)[
         all |= bit;
 #pragma unroll
         for (int p = 0; p < P; ++p) o[p] = (p == pl) ? mine : o[p];
-        if (ttt_has_line<ND>(dd, mine)) winner = pl;   // :296-300
+        bool won;                                      // :296-300
+        if constexpr (WT) {
+            CRL_BOUNDS_LT(mine >> 5, 2048u, 203);
+            won = ((win_bits[mine >> 5] >> (mine & 31u)) & 1u) != 0u;
+        }
+        else won = ttt_has_line<ND>(dd, mine);
+        if (won) winner = pl;
     }
     reward = 0; term = 0; winners = -1;
     if (winner >= 0) {                                 // :302-308
@@ -525,6 +533,93 @@ ttt_step_observe_kernel(const ttt_dirs dd, const uint32_t inv_cells, const int64
     ttt_write_boards<P>(s_occ, s_mover, dd.n_cells, inv_cells, rel_mod, g0, B, obs);
 }
 
+// ---- one learner against the random agent (crl_ttt_step_single; the contract is in include/colosseum_hip.h): per game
+// an optional learner ply, then the random agent for every other seat until it is the learner's turn again -- across the
+// end of a game and its restart -- and the learner's valid mask and observation of what that leaves.  One lane per game,
+// the plies a per-lane loop of at most 1 + 2 (P - 1) trips over ttt_step_core (the same ply as crl_ttt_step); the draws are
+// crl_ttt_sample's.  Boards of at most 16 cells take the win test out of the win-mask table (WT), staged into LDS as the
+// rollout does.  The observation goes through LDS as in ttt_step_observe_kernel.
+template <int P, int ND, bool WT>
+__global__ void __launch_bounds__(256)
+ttt_step_single_kernel(const ttt_dirs dd, const uint32_t inv_cells, const int64_t B, const uint32_t seed_lo,
+                       const uint32_t seed_hi, const uint64_t first_env_id, uint32_t *__restrict__ occ,
+                       int8_t *__restrict__ winner, int8_t *__restrict__ to_move, const int8_t *__restrict__ seat,
+                       const int64_t *__restrict__ learner_action, uint32_t *__restrict__ tcount,
+                       int8_t *__restrict__ reward, uint8_t *__restrict__ done, int8_t *__restrict__ winners,
+                       int8_t *__restrict__ obs, uint32_t *__restrict__ valid, const int rel_mod,
+                       const uint32_t *__restrict__ win_tab)
+{
+    __shared__ uint32_t s_occ[P][256];
+    __shared__ int s_seat[256];
+    __shared__ uint32_t win_bits[WT ? 2048 : 1];
+    if (WT) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(win_tab);
+        uint4 *dst = reinterpret_cast<uint4 *>(win_bits);
+        dst[threadIdx.x] = src[threadIdx.x];
+        dst[threadIdx.x + 256] = src[threadIdx.x + 256];
+        __syncthreads();
+    }
+    const int64_t g0 = (int64_t)blockIdx.x * 256;
+    const int64_t b = g0 + threadIdx.x;
+    uint32_t o[P];
+    int s = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) o[p] = 0u;
+    if (b < B) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) o[p] = occ[p * B + b];
+        int w = winner[b], tm = to_move[b];
+        s = (int)seat[b] % P;
+        s += s < 0 ? P : 0;
+        uint32_t c = tcount[b];
+        const uint32_t g = (uint32_t)(first_env_id + (uint64_t)b);
+        int rew = 0, dn = 0, wout = -1;
+        bool learner = learner_action != nullptr && tm == s;
+        for (int opp = 0; learner || (tm != s && opp < 2 * (P - 1)); ) {
+            int act;
+            if (learner) {                          // crl_ttt_step's int8 action for v in [-1, cells), else the pass
+                const int64_t v = learner_action[b];
+                act = (v >= -1 && v < dd.n_cells) ? (int)v : -1;
+            } else {                                // crl_ttt_sample at this game's step counter
+                uint32_t all = 0;
+#pragma unroll
+                for (int p = 0; p < P; ++p) all |= o[p];
+                const uint32_t empty = dd.full & ~all;
+                const int n_empty = __popc(empty);
+                act = n_empty ? nth_set_bit(empty, (int)__umulhi(ttt_agent_word(g, c, n_empty, seed_lo, seed_hi), (uint32_t)n_empty)) : -1;
+                ++opp;
+            }
+            c += 1u;
+            learner = false;
+            int r, t, ws;
+            ttt_step_core<P, ND, WT>(dd, o, w, tm, act, r, t, ws, win_bits);
+            if (t) {                                // the learner's outcome (current_rewards, tictactoe_2p_env.py:233-236), restart
+                dn = 1;
+                wout = ws;
+                rew = ws < 0 ? 0 : (ws == s ? 1 : -1);
+#pragma unroll
+                for (int p = 0; p < P; ++p) o[p] = 0;
+                w = -1; tm = 0;
+            }
+        }
+        uint32_t all = 0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) { occ[p * B + b] = o[p]; all |= o[p]; }
+        winner[b] = (int8_t)w;
+        to_move[b] = (int8_t)tm;
+        tcount[b] = c;
+        reward[b] = (int8_t)rew;
+        done[b] = (uint8_t)dn;
+        winners[b] = (int8_t)wout;
+        valid[b] = dd.full & ~all;
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) s_occ[p][threadIdx.x] = o[p];
+    s_seat[threadIdx.x] = s;
+    __syncthreads();
+    ttt_write_boards<P>(s_occ, s_seat, dd.n_cells, inv_cells, rel_mod, g0, B, obs);
+}
+
 // the rollout's random agent for one step
 __global__ void __launch_bounds__(256)
 ttt_sample_kernel(const int P, const uint32_t full, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
@@ -898,6 +993,42 @@ int crl_ttt_step_observe(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t 
                                inv_cells, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, action,
                                tcount, reward, terminal, winners, obs_board, valid, rel_mod, flags);
     });
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_ttt_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                        uint32_t *occ, int8_t *winner, int8_t *to_move, const int8_t *seat,
+                        const int64_t *learner_action, uint32_t *tcount,
+                        int8_t *reward, uint8_t *done, int8_t *winners,
+                        int8_t *obs_board, uint32_t *valid, int rel_mod, uint32_t flags, void *stream)
+{
+    TTT_CTX_CHECK("crl_ttt_step_single");
+    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_step_single: NULL state pointer");
+    CRL_REQUIRE(seat && tcount, "crl_ttt_step_single: NULL seat / tcount pointer");
+    CRL_REQUIRE(reward && done && winners && obs_board && valid, "crl_ttt_step_single: NULL output pointer");
+    CRL_REQUIRE(rel_mod >= 1, "crl_ttt_step_single: rel_mod must be >= 1");
+    CRL_REQUIRE(flags == 0, "crl_ttt_step_single: unknown flags 0x%x", flags);
+    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "crl_ttt_step_single: a board of %d cells for %d players (a fresh game could end "
+                "before the learner's turn)", ctx->ttt.n_cells, ctx->ttt.P);
+    CRL_REQUIRE((((uintptr_t)obs_board) & 3) == 0, "crl_ttt_step_single: obs_board must be 4-byte aligned");
+    const ttt_dirs dd = dirs_of(ctx);
+    const uint32_t inv_cells = dd.n_cells == 1 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint64_t)dd.n_cells) + 1u;
+    const uint32_t *win_tab = nullptr;                      // the <= 16-cell win table, when it lives on this device
+    if (ctx->ttt_win_dev) {
+        int dev = -1;
+        if (hipGetDevice(&dev) == hipSuccess && dev == ctx->ttt_win_device) win_tab = ctx->ttt_win_dev;
+    }
+#define TTT_SINGLE_LAUNCH(ND_, WT_)                                                                                       \
+    hipLaunchKernelGGL((ttt_step_single_kernel<PP, ND_, WT_>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd, \
+                       inv_cells, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, seat,   \
+                       learner_action, tcount, reward, done, winners, obs_board, valid, rel_mod, win_tab)
+    TTT_DISPATCH_P(ctx->ttt.P, {
+        if (dd.n_dirs <= 4 && dd.n_cells <= 16 && win_tab != nullptr) TTT_SINGLE_LAUNCH(4, true);
+        else if (dd.n_dirs <= 4) TTT_SINGLE_LAUNCH(4, false);
+        else TTT_SINGLE_LAUNCH(13, false);
+    });
+#undef TTT_SINGLE_LAUNCH
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }

@@ -162,3 +162,110 @@ class BlokusVectorEnv:
         if list_cap > 0:
             info["ids"] = o["ids"]
         return obs, o["player"].view(-1), o["n_valid"], o["reward"].clone(), o["terminal"].clone(), info
+
+
+def _seat_tensor(seat, P: int, B: int, device) -> torch.Tensor:
+    """int or int8 [B] tensor of seats in [0, P) -> a device int8 [B] tensor the env owns (checked once, here)."""
+    if isinstance(seat, torch.Tensor):
+        if seat.dtype != torch.int8 or tuple(seat.shape) != (B,):
+            raise ValueError("seat must be an int or an int8 tensor of shape (%d,)" % B)
+        out = seat.to(device).clone()
+        if bool(((out < 0) | (out >= P)).any()):
+            raise ValueError("seat values must lie in [0, %d)" % P)
+        return out
+    if not 0 <= int(seat) < P:
+        raise ValueError("seat=%r not in [0, %d)" % (seat, P))
+    return torch.full((B,), int(seat), dtype=torch.int8, device=device)
+
+
+def _check_action(action: torch.Tensor, B: int, device):
+    if action.dtype != torch.int64 or tuple(action.shape) != (B,) or action.device != device or not action.is_contiguous():
+        raise ValueError("action must be a contiguous int64 tensor of shape (%d,) on %s" % (B, device))
+
+
+class TicTacToeSinglePlayerVectorEnv:
+    """B TicTacToe games of one learner against the random agent in every other seat: the turn-based counterpart of
+    ``TronSinglePlayerVectorEnv``.  ``seat`` (an int, or an int8 [B] tensor: a seat per game, so that one learner trains on
+    every position) is the learner's player id.
+
+    ``reset() -> obs`` and ``step(action) -> obs, reward, done, info`` with ``action`` int64 [B] a flat cell index (-1 or
+    any value outside [0, cells) passes; an occupied cell passes too, as the reference's next_state has it).  Each step
+    plays the learner's move and then the random agent until it is the learner's turn again; a game that ends restarts
+    in the same step and the opponents before the learner play their first moves of the new game.  ``obs`` = {'board'
+    int8 [B, cells]} relative to the learner (reference state_to_observation), ``reward`` int8 [B] is +1 when the learner
+    won, -1 when another player won, 0 for a draw or a running game, ``done`` uint8 [B] the game ended in this step,
+    ``info`` = {'valid' int32 [B] empties mask of the new state, 'winners' int8 [B]}.  All of them are buffers that the next
+    ``step`` / ``reset`` rewrites (clone what you keep).
+    A step is ONE launch (``crl_ttt_step_single``) with no host synchronisation, and can be captured into a HIP graph
+    (``torch.cuda.graph``).  The opponents' draws are ``crl_ttt_sample``'s at each game's step counter, keyed by ``seed``;
+    the learner's ply advances the counter as well."""
+
+    def __init__(self, dims=(3, 3), k: int = 3, num_players: int = 2, batch: int = 1024, seat=0, seed: int = 0,
+                 device="cuda"):
+        self.batch = TTTBatch(dims, k, num_players, batch, device=device)
+        self.num_players, self.num_envs, self.seed = num_players, batch, int(seed)
+        self.seat = _seat_tensor(seat, num_players, batch, self.batch.device)
+        self._out = None
+
+    def _step(self, action):
+        self._out = self.batch.step_single(self.seat, action, self.seed, out=self._out)
+        o = self._out
+        return {"board": o["board"]}, o["reward"], o["done"], {"valid": o["valid"], "winners": o["winners"]}
+
+    def reset(self) -> Dict[str, torch.Tensor]:
+        self.batch.reset()
+        return self._step(None)[0]
+
+    def step(self, action: torch.Tensor):
+        _check_action(action, self.num_envs, self.batch.device)
+        return self._step(action)
+
+
+class BlokusSinglePlayerVectorEnv:
+    """B Blokus games of one learner against the random agent in the other three seats: the turn-based counterpart of
+    ``TronSinglePlayerVectorEnv``.  ``seat`` (an int, or an int8 [B] tensor: a seat per game) is the learner's colour - 1.
+
+    ``reset() -> obs`` and ``step(action) -> obs, reward, done, info`` with ``action`` int64 [B]: with ``action="id"`` a
+    dense action id (``envs.blokus.actions``; < 0 passes), placed as the reference's next_state places any action -- pick
+    ids from ``info['ids']`` (``list_cap`` > 0) to stay legal; with ``action="rank"`` the index into the learner's ordered
+    legal list (``info['n_valid']`` long; outside it = pass), which needs no list at all.  Each step plays the learner's
+    move and then the random agent until it is the learner's turn again; a game that ends restarts in the same step.
+    ``obs`` = {'board' int8 [B, 20, 20], 'pieces' uint8 [B, 4, 21], 'score' int32 [B, 4]}: the learner's observation
+    (reference state_to_observation).  ``reward`` int8 [B] = the learner's rank in the final scores (0 = last, 3 = best:
+    the reference's reward at the end of a game) when the game ended, else 0 -- or a ``CRL_BLOKUS_*_ERROR`` code (< 0) for
+    an action the reference's next_state raises on, which leaves that game as it was; ``done`` uint8 [B] the game ended;
+    ``info`` = {'n_valid' int32 [B] the learner's number of legal actions, 'winners' uint8 [B] bitmask} and, with
+    ``list_cap`` > 0, 'ids' int32 [B, list_cap]: the learner's legal ids in the reference's order (only
+    ``ids[b, :n_valid[b]]`` is written).  All of them are buffers that the next ``step`` / ``reset`` rewrites.
+    A step is ONE launch (``crl_blokus_step_single``; a second, ``crl_blokus_valid_list``, with ``list_cap`` > 0), has no
+    host synchronisation and can be captured into a HIP graph.  The opponents' draws are ``crl_blokus_sample``'s at each
+    game's step counter, keyed by ``seed``; the learner's ply advances the counter as well."""
+
+    def __init__(self, batch: int = 1024, seat=0, seed: int = 0, list_cap: int = 0, action: str = "id", device="cuda"):
+        if action not in ("id", "rank"):
+            raise ValueError("action must be 'id' or 'rank', not %r" % (action,))
+        if list_cap < 0:
+            raise ValueError("list_cap must be >= 0")
+        self.batch = BlokusBatch(batch, device=device)
+        self.num_players, self.num_envs, self.seed = 4, batch, int(seed)
+        self.list_cap, self.rank = int(list_cap), action == "rank"
+        self.seat = _seat_tensor(seat, 4, batch, self.batch.device)
+        self._out = None
+        self._ids = (torch.full((batch, self.list_cap), -1, dtype=torch.int32, device=self.batch.device)
+                     if self.list_cap > 0 else None)
+
+    def _step(self, action):
+        self._out = self.batch.step_single(self.seat, action, self.seed, rank=self.rank, out=self._out)
+        o = self._out
+        info = {"n_valid": o["n_valid"], "winners": o["winners"]}
+        if self._ids is not None:
+            info["ids"] = self.batch.valid_list(self.list_cap, player=self.seat, out=self._ids)[1]
+        return {"board": o["board"], "pieces": o["pieces"], "score": o["score"]}, o["reward"], o["done"], info
+
+    def reset(self) -> Dict[str, torch.Tensor]:
+        self.batch.reset()
+        return self._step(None)[0]
+
+    def step(self, action: torch.Tensor):
+        _check_action(action, self.num_envs, self.batch.device)
+        return self._step(action)

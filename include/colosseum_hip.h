@@ -51,6 +51,8 @@ extern "C" {
 /* crl_tron_step only: pin one of its two interchangeable kernels (identical results; the default is the faster one) */
 #define CRL_STEP_BYTES      2u  /* byte probes in HBM, one lane per game, nothing staged */
 #define CRL_STEP_STAGED     4u  /* boards read once, coalesced, into LDS (boards of whole 16-byte chunks that fit; else ignored) */
+/* crl_blokus_step_single only: the learner's action is a RANK into its ordered legal list (as crl_blokus_select) */
+#define CRL_STEP_RANK_ACTION 8u
 /* flags for crl_tron_rollout */
 #define CRL_ROLLOUT_NO_LDS  2u  /* force the lane-per-game global-memory kernel even when the boards would fit in LDS */
 #define CRL_ROLLOUT_BYTES   4u  /* force the lane-per-game byte-per-cell LDS kernel */
@@ -77,8 +79,9 @@ const char *crl_last_error(void);
  * 104: round 4.  105: crl_stream_wait_mapped.  106: crl_diag_issue_probe.  107: crl_blokus_fits.  108: crl_diag_bounds.
  * 109: crl_blokus_step / _step_observe place ANY action as the reference's next_state does (numpy index rules, extended ids,
  *      CRL_BLOKUS_*_ERROR codes in the reward slot).  110: crl_tron_next_state_inplace64 (+ _host) / _relative_player_inplace64.  111: crl_ttt_step_board_host.
- * 112: crl_tron_sample_avoid / crl_tron_rollout_avoid (the scripted avoid agent), crl_tron_step_single. */
-#define CRL_ABI_VERSION 112
+ * 112: crl_tron_sample_avoid / crl_tron_rollout_avoid (the scripted avoid agent), crl_tron_step_single.
+ * 113: crl_ttt_step_single / crl_blokus_step_single (one learner against the random agent), CRL_STEP_RANK_ACTION. */
+#define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
 int crl_device_count(void);
@@ -426,6 +429,39 @@ typedef struct {
 int crl_ttt_rollout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T,
                     uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats stats, void *stream);
 
+/* ------------------------------------------------------------------ one learner against the random agent (turn-based games)
+ * crl_ttt_step_single / crl_blokus_step_single: one step of B games in which ONE seat is a learner and every other seat
+ * plays the random agent of crl_*_rollout -- the reference's random opponent, random.choice(valid_actions)
+ * (examples/blokus_client.py:22-23), under this header's Philox contract.  State layouts are those of the game's other
+ * entries; seat int8 [B] is the learner's player id in game b (read modulo P; & 3 for Blokus); tcount uint32 [B] is the
+ * step counter of the RNG contract.  With s = seat[b], per game, in one launch:
+ *   1. Learner ply: only if learner_action != NULL and to_move[b] == s.  learner_action int64 [B] is applied as the
+ *      game's step entry would apply it (the per-game encodings are given below); the ply consumes one value of tcount[b],
+ *      exactly as a sampled ply does, so a learner that plays the random agent's own draw reproduces crl_*_rollout.
+ *   2. Opponent plies: while to_move[b] != s, the random agent's action at tcount[b] -- what crl_*_sample(advance = 1)
+ *      returns on that state -- is applied as crl_*_step applies it.
+ *   3. If the game ended in 1. or 2.: done[b] = 1, winners[b] as crl_*_step sets it for the ending ply, reward[b] = the
+ *      learner's outcome (below); the game is reset (to_move 0) and 2. goes on until it is the learner's turn.  A fresh game
+ *      cannot end within P - 1 plies (TicTacToe: no line in fewer than P + 1 plies as K >= 2, and crl_ttt_step_single
+ *      requires cells >= P; Blokus: no player is out of moves in round 0), so one call ends a game at most once.
+ *   4. Otherwise reward[b] = 0, done[b] = 0 and winners[b] the step's "no winner" (-1 TicTacToe, 0 Blokus).
+ *   5. Always written, of the state the call leaves: the learner's legal moves and its observation (below).
+ * learner_action == NULL plays no learner ply: the call that advances a freshly reset batch to the learner's turn.  At most
+ * 2 (P - 1) opponent plies are played per call, which no state of the game (to_move in [0, P)) reaches.
+ * Argument checks (CRL_EINVAL) before any device work: NULL pointers, unknown flag bits, B out of range, and per game below.
+ *
+ * TicTacToe: learner_action v in [-1, cells) is played as crl_ttt_step's int8 action v, every other value as -1 (pass:
+ * an occupied cell or a pass leaves the board and passes the turn, as there).  reward int8 [B] = +1 if the winner is s,
+ * -1 if another player won, 0 for a draw (current_rewards, tictactoe_2p_env.py:233-236); winners int8 [B] as crl_ttt_step.
+ * valid uint32 [B] = empties mask; obs_board int8 [B][cells] (4-byte aligned) = crl_ttt_board(player = s, rel_mod).
+ * flags must be 0; rel_mod >= 1 (as crl_ttt_step_observe); the context must have cells >= P.  One lane per game; boards of at
+ * most 16 cells test for a line with the win-mask table of crl_ttt_create when it lives on the launching device. */
+int crl_ttt_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                        uint32_t *occ, int8_t *winner, int8_t *to_move, const int8_t *seat,
+                        const int64_t *learner_action, uint32_t *tcount,
+                        int8_t *reward, uint8_t *done, int8_t *winners,
+                        int8_t *obs_board, uint32_t *valid, int rel_mod, uint32_t flags, void *stream);
+
 /* ------------------------------------------------------------------ Blokus (20 x 20, 4 players)
  * State (reference BlokusEnvironment.py:283-289: (Board, round_count, [AI x 4])):
  *   occ     uint32 [B][4][20]  bit x of occ[b][c][y] set = cell (x, y) holds colour c+1 (Board.board_contents[y][x])
@@ -551,6 +587,22 @@ int crl_blokus_rollout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t fi
 int crl_blokus_sample(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
                       const uint32_t *inventory, const int32_t *score, const int32_t *round, const int32_t *to_move,
                       uint32_t *tcount, int advance, int32_t *action, void *stream);
+
+/* crl_blokus_step_single: the contract above for Blokus.  learner_action v: without flags, v in
+ * [-1, CRL_BLOKUS_EXT_BASE + CRL_BLOKUS_EXT_IDS) is played as crl_blokus_step's int32 action v, v < -1 is a pass, larger
+ * values give CRL_BLOKUS_BAD_ACTION; with CRL_STEP_RANK_ACTION, v is a rank into the learner's ordered legal list (as
+ * crl_blokus_select) and a rank outside [0, count) is a pass.  A learner ply that hits a CRL_BLOKUS_*_ERROR code puts it
+ * into reward[b]; the state and tcount[b] stay as they were, no opponent plays, done[b] = 0.  At the end of a game reward[b]
+ * = the learner's rank in the final scores by crl_blokus_step's rule with the mover replaced by s (what the reference's
+ * next_state gives its mover, BlokusEnvironment.py:424-440), whoever made the last ply; winners uint8 [B] as crl_blokus_step.
+ * n_valid int32 [B] = the learner's number of legal actions, obs_* = crl_blokus_observe(player = s) (obs_board 4-byte
+ * aligned).  One wave per game: the board stays in LDS for every ply of the call (at most 7), and the learner's count and
+ * observation are computed from that copy. */
+int crl_blokus_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                           uint32_t *occ, uint32_t *inv, int32_t *score, int32_t *round, int32_t *to_move,
+                           const int8_t *seat, const int64_t *learner_action, uint32_t *tcount,
+                           int8_t *reward, uint8_t *done, uint8_t *winners, int32_t *n_valid,
+                           int8_t *obs_board, uint8_t *obs_pieces, int32_t *obs_score, uint32_t flags, void *stream);
 
 #ifdef __cplusplus
 }

@@ -110,6 +110,7 @@ PROTOTYPES = {
     "crl_ttt_sample": (_I, [_VP, _I64, _U64, _U64, _VP, _VP, _I, _VP, _VP]),
     "crl_ttt_step_observe": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 10 + [_I, _U32, _VP]),
     "crl_ttt_step_single": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 11 + [_I, _U32, _VP]),
+    "crl_ttt_playout": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 5 + [_I, _I] + [_VP] * 3 + [_U32, _VP]),
     "crl_blokus_create": (_I, [C.POINTER(_VP)]),
     "crl_blokus_placement": (_I, [_I, _I, _I, _VP]),
     "crl_blokus_stamps": (_I, [_VP, _I]),
@@ -127,6 +128,7 @@ PROTOTYPES = {
     "crl_blokus_sample": (_I, [_VP, _I64, _U64, _U64, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     "crl_blokus_step_observe": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 15 + [_U32, _VP]),
     "crl_blokus_step_single": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 15 + [_U32, _VP]),
+    "crl_blokus_playout": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 7 + [_I, _I] + [_VP] * 4 + [_U32, _VP]),
 }
 
 

@@ -71,6 +71,44 @@ def _want(t: torch.Tensor, dtype, shape, device, name):
     return t
 
 
+def _playout_args(playouts: int, candidates: Optional[torch.Tensor], B: int, device):
+    """(A, R) of a playout call, checked as the C entries check them (crl_*_playout: A, R in [1, 65535]); candidates int32
+    [B, A] or None (A = 1)."""
+    if isinstance(playouts, bool) or not isinstance(playouts, int) or not 1 <= playouts <= 65535:
+        raise ValueError("playouts must be an int in [1, 65535], got %r" % (playouts,))
+    if candidates is None:
+        return 1, playouts
+    if not isinstance(candidates, torch.Tensor) or candidates.dim() != 2 or candidates.shape[0] != B:
+        raise ValueError("candidates must be an int32 tensor of shape (%d, A)" % B)
+    A = int(candidates.shape[1])
+    if not 1 <= A <= 65535:
+        raise ValueError("candidates must have 1..65535 columns, got %d" % A)
+    _want(candidates, torch.int32, (B, A), device, "candidates")
+    return A, playouts
+
+
+def _playout_out(out: Optional[dict], B: int, A: int, P: int, device, score: bool):
+    """the output dict of a playout call: fresh, or `out` with every buffer checked"""
+    shapes = {"wins": (B, A, P), "draws": (B, A), "played": (B, A), "len_sum": (B, A)}
+    if score:
+        shapes["score_sum"] = (B, A, 4)
+    if out is None:
+        return {k: torch.empty(v, dtype=torch.int32, device=device) for k, v in shapes.items()}
+    for k, v in shapes.items():
+        if k not in out:
+            raise ValueError("out lacks %r" % k)
+        _want(out[k], torch.int32, v, device, "out[%r]" % k)
+    return out
+
+
+def _flat_mc_pick(value: torch.Tensor, played: torch.Tensor, ids: torch.Tensor):
+    """int64 [B]: ids[b, a] of the greatest value among the played rows (ties: the lowest a), -1 where none was played"""
+    value = torch.where(played > 0, value, torch.full_like(value, -1))
+    best = torch.argmax(value, dim=1, keepdim=True)                      # (the first of equal maxima)
+    pick = torch.gather(ids, 1, best).squeeze(1).to(torch.int64)
+    return torch.where(played.amax(dim=1) > 0, pick, torch.full_like(pick, -1))
+
+
 class _Ctx:
     """Owns one crl_ctx handle."""
 
@@ -537,6 +575,37 @@ class TTTBatch(_Waitable):
         out["reward"], out["winners"] = self.reward, self.winners
         return out
 
+    def playout(self, playouts: int, candidates: Optional[torch.Tensor] = None, seed: int = 0, out: Optional[dict] = None):
+        """Random playouts from every game's position, ONE launch (``crl_ttt_playout``): row (b, a) plays candidate cell
+        ``candidates[b, a]`` (int32 [B, A]; an occupied cell, -1 or a value outside [0, cells) skips the row) for the
+        player to move and then ``playouts`` random games to their end, on private copies; ``candidates=None`` evaluates
+        the position as it stands (A = 1).  Finished positions skip every row.  The draws are keyed by ``seed``, the game
+        ids and ``tcount`` as the counter base (which the call neither advances nor writes; the state is only read).
+        Returns {'wins' int32 [B, A, P], 'draws', 'played', 'len_sum' int32 [B, A]} (skipped rows are zeros); ``out``
+        reuses such a dict.  No host synchronisation; capturable into a graph."""
+        A, R = _playout_args(playouts, candidates, self.B, self.device)
+        out = _playout_out(out, self.B, A, self.P, self.device, score=False)
+        with _DevGuard(self.device):
+            check(self._lib.crl_ttt_playout(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
+                                            _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move), _ptr(self.tcount),
+                                            _ptr(candidates), A, R, _ptr(out["wins"]), _ptr(out["played"]),
+                                            _ptr(out["len_sum"]), 0, _stream()), "crl_ttt_playout")
+            torch.sub(out["played"], out["wins"].sum(dim=2, dtype=torch.int32), out=out["draws"])
+        return out
+
+    def flat_mc_action(self, playouts: int, seed: int = 0, out: Optional[dict] = None) -> torch.Tensor:
+        """Flat Monte Carlo for the player to move in every game: ``playout`` on every cell, value 2 * wins + draws of
+        the mover, the best cell (ties: the lowest) as an int64 [B] action for ``step_single``; -1 where no cell could be
+        played (the game is over).  ``out``: the playout dict to reuse.  No host synchronisation; capturable."""
+        cells = getattr(self, "_all_cells", None)
+        if cells is None:
+            cells = torch.arange(self.n_cells, dtype=torch.int32, device=self.device).expand(self.B, self.n_cells).contiguous()
+            self._all_cells = cells
+        o = self.playout(playouts, cells, seed, out)
+        mover = self.to_move.to(torch.int64).clamp(0, self.P - 1)       # (other values: the position skips every row)
+        mine = torch.gather(o["wins"], 2, mover.view(-1, 1, 1).expand(self.B, self.n_cells, 1)).squeeze(2)
+        return _flat_mc_pick(2 * mine + o["draws"], o["played"], cells)
+
     def _stats(self):
         return TTTStats(*[t.data_ptr() for t in (self.tcount, self.tstep, self.n_episodes, self.win_count,
                                                   self.draw_count, self.len_sum, self._results)])
@@ -818,6 +887,34 @@ class BlokusBatch(_Waitable):
                   "crl_blokus_step_single")
         out["reward"], out["winners"] = self.reward, self.winners
         return out
+
+    def playout(self, playouts: int, candidates: Optional[torch.Tensor] = None, seed: int = 0, out: Optional[dict] = None):
+        """Random playouts from every game's position, ONE launch (``crl_blokus_playout``): row (b, a) plays the dense id
+        ``candidates[b, a]`` (int32 [B, A]; anything that is not a legal action of the player to move skips the row) and
+        then ``playouts`` random games to their end, on private copies; ``candidates=None`` evaluates the position as it
+        stands (A = 1).  The draws are keyed by ``seed``, the game ids and ``tcount`` as the counter base (which the call
+        neither advances nor writes; the state is only read).  Returns {'wins' int32 [B, A, 4] (a shared best score
+        counts for every tied player), 'draws' (played - sum of wins, negative when ties count twice), 'played',
+        'len_sum' int32 [B, A], 'score_sum' int32 [B, A, 4]} (skipped rows are zeros); ``out`` reuses such a dict.  No
+        host synchronisation; capturable into a graph."""
+        A, R = _playout_args(playouts, candidates, self.B, self.device)
+        out = _playout_out(out, self.B, A, 4, self.device, score=True)
+        with _DevGuard(self.device):
+            check(self._lib.crl_blokus_playout(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
+                                               *self._state(), _ptr(self.tcount), _ptr(candidates), A, R,
+                                               _ptr(out["wins"]), _ptr(out["played"]), _ptr(out["len_sum"]),
+                                               _ptr(out["score_sum"]), 0, _stream()), "crl_blokus_playout")
+            torch.sub(out["played"], out["wins"].sum(dim=2, dtype=torch.int32), out=out["draws"])
+        return out
+
+    def flat_mc_action(self, candidates: torch.Tensor, playouts: int, seed: int = 0, out: Optional[dict] = None) -> torch.Tensor:
+        """Flat Monte Carlo over the dense-id ``candidates`` (int32 [B, A]) of the player to move: ``playout`` on each,
+        value = the mover's wins, the best candidate (ties: the lower index) as an int64 [B] action for ``step_single``;
+        -1 where no candidate was played.  ``out``: the playout dict to reuse.  No host synchronisation; capturable."""
+        A, _ = _playout_args(playouts, candidates, self.B, self.device)
+        o = self.playout(playouts, candidates, seed, out)
+        mover = (self.to_move.to(torch.int64) & 3).view(-1, 1, 1).expand(self.B, A, 1)
+        return _flat_mc_pick(torch.gather(o["wins"], 2, mover).squeeze(2), o["played"], candidates)
 
     def board(self):
         out = torch.empty((self.B, 20, 20), dtype=torch.int8, device=self.device)

@@ -1369,6 +1369,186 @@ blokus_rollout_kernel(const BlkTables *__restrict__ tables, const int64_t B, con
     }
 }
 
+// ---- batched random playouts (crl_blokus_playout; the contract is in include/colosseum_hip.h).  One wave per playout
+// i = (b * A + a) * R + r, the board in LDS, four waves per workgroup walking the playouts in a grid-stride loop.  The
+// candidate ply is checked as blokus_is_valid_kernel checks an id (on the allowed / corner rows of the pre-move board) and
+// played as blk_play plays a dense id (blk_apply of its decoded move); its terminal test is crl_blokus_step's (every player, the pre-move rows, the new inventories).  The
+// random plies are blokus_rollout_kernel's specialised ply -- blk_prologue, the count, blk_select on the scan in registers,
+// the terminal test on the pre-move board with its `dead` / `can_move` caches, blk_place_legal -- with inventories and
+// scores in vector registers as there, the 16 words of a Philox quadruple drawn together, and no reset: the loop ends at
+// the first terminal ply.  (A copy of the rollout's loop body rather than a helper shared with it: the rollout's code
+// stays what it was.)  Lane 0 adds the playout's outcome into its row (integer atomics onto the zeros the launcher wrote).
+__device__ __forceinline__ uint64_t blk_uniform64(const uint64_t v)
+{
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v)
+         | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32;
+}
+
+__global__ void __launch_bounds__(256, BLK_WAVES_PER_SIMD)
+blokus_playout_kernel(const BlkTables *__restrict__ tables, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
+                      const uint64_t first_env_id, const uint32_t *__restrict__ occ, const uint32_t *__restrict__ inv_g,
+                      const int32_t *__restrict__ score_g, const int32_t *__restrict__ round_g,
+                      const int32_t *__restrict__ to_move_g, const uint32_t *__restrict__ tcount,
+                      const int32_t *__restrict__ cand, const int A, const int R, const uint64_t n_playouts,
+                      uint32_t *__restrict__ wins, uint32_t *__restrict__ played, uint32_t *__restrict__ len_sum,
+                      int32_t *__restrict__ score_sum)
+{
+    __shared__ BlkTables T;
+    __shared__ WaveLds Lw[4];
+    for (int i = threadIdx.x; i < (int)(sizeof(BlkTables) / 4); i += blockDim.x)
+        reinterpret_cast<uint32_t *>(&T)[i] = reinterpret_cast<const uint32_t *>(tables)[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave_ = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    WaveLds &L = Lw[wave_];
+    // rows -4..-1 and 20..27 of the padded ac[] rows and rows 28..30 of the pre-shifted table stay zero (as BLK_SHARED_SETUP)
+    for (int i = lane; i < 4 * 32; i += 64) L.ac[i >> 5][i & 31] = make_uint2(0u, 0u);
+    for (int i = lane; i < 3 * 9; i += 64) L.u.sh[28 + i / 9][i % 9] = make_uint2(0u, 0u);
+    const uint32_t piece_cells = lane < 24 ? T.ncell[lane] : 0u;
+    const BlkOwners owners = blk_shape_owners(T, lane);
+    for (uint64_t i = (uint64_t)blockIdx.x * 4u + (uint32_t)wave_; i < n_playouts; i += (uint64_t)gridDim.x * 4u) {
+        // (b, a, r) of the playout: wave-uniform, kept in scalar registers (the 64-bit divisions leave them in vector ones)
+        const uint64_t row = blk_uniform64(i / (uint32_t)R);
+        const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(i - row * (uint32_t)R));
+        const int64_t b = (int64_t)blk_uniform64(row / (uint32_t)A);
+        const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(row - (uint64_t)b * (uint32_t)A));
+        int round = __builtin_amdgcn_readfirstlane(round_g[b]), pl = __builtin_amdgcn_readfirstlane(to_move_g[b]) & 3;
+        for (int k = lane; k < 4 * BN; k += 64) L.occ[k / BN][k % BN] = occ[b * 4 * BN + k];
+        uint32_t vinv = inv_g[b * 4 + (lane & 3)];
+        int vscore = score_g[b * 4 + (lane & 3)];
+        wave_sync();
+        int len = 0;
+        bool over = false;
+        if (cand != nullptr) {
+            // the candidate: a dense id that is a legal action of the mover (blokus_is_valid_kernel's test), else skip the row
+            const int id = __builtin_amdgcn_readfirstlane(cand[b * A + a]);
+            blk_prep(L, lane, round);                            // every player's rows of the PRE-move board (:424)
+            const uint32_t ip = (uint32_t)__builtin_amdgcn_readlane((int)vinv, pl);
+            bool good = false;
+            BlkMove mv = {0, 0, 0, 0, 0};
+            if (id >= 0 && id < ACTION_IDS) {
+                mv = blk_decode(id);
+                const ShapeRegs s = blk_load_shape(T, mv.piece, mv.orient);
+                if (((ip >> mv.piece) & 1u) && mv.shift < s.n) {
+                    int ox = 0, oy = 0;
+#pragma unroll
+                    for (int j = 0; j < 5; ++j) { ox = (j == mv.shift) ? s.sh(j) : ox; oy = (j == mv.shift) ? s.ro(j) : oy; }
+                    bool cell_ok = true;
+                    if (lane < s.n) {
+                        int cx = 0, cy = 0;
+#pragma unroll
+                        for (int j = 0; j < 5; ++j) { cx = (j == lane) ? s.sh(j) : cx; cy = (j == lane) ? s.ro(j) : cy; }
+                        const int x = mv.x + cx - ox, y = mv.y + cy - oy;
+                        const bool on = x >= 0 && x < BN && y >= 0 && y < BN;
+                        CRL_BOUNDS_LT(on ? y + 4 : 4, 32, 340);
+                        cell_ok = on && ((L.ac[pl][on ? y + 4 : 4].x >> (x + 8)) & 1u);
+                    }
+                    CRL_BOUNDS_LT(mv.y + 4, 32, 341);
+                    const bool anchor = (L.ac[pl][mv.y + 4].y >> (mv.x + 8)) & 1u;
+                    good = anchor && __ballot(!cell_ok) == 0ull;
+                }
+            }
+            if (!good) continue;                                 // (wave-uniform) the row is skipped: nothing to add
+            uint32_t inv[4];
+            int score[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                inv[c] = (uint32_t)__builtin_amdgcn_readlane((int)vinv, c);
+                score[c] = __builtin_amdgcn_readlane(vscore, c);
+            }
+            (void)blk_apply(T, L, pl, mv, inv, score, lane);    // blk_play of a dense id (legal: it returns 0)
+            bool any_move = false;
+            for (int q = 0; q < 4 && !any_move; ++q) {           // old board, old round, NEW inventories (:424)
+                uint32_t iq = 0;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) iq = (c == q) ? inv[c] : iq;
+                any_move = blk_exists(T, L, q, iq, lane, &owners);
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                vinv = (lane & 3) == c ? inv[c] : vinv;
+                vscore = (lane & 3) == c ? score[c] : vscore;
+            }
+            over = !any_move;
+            round += (pl == 3) ? 1 : 0;                          // :446-447
+            pl = (pl + 1) & 3;
+            len = 1;
+        }
+        uint32_t winners_mask = 0;
+        if (over) {
+            const int score[4] = {__builtin_amdgcn_readlane(vscore, 0), __builtin_amdgcn_readlane(vscore, 1),
+                                  __builtin_amdgcn_readlane(vscore, 2), __builtin_amdgcn_readlane(vscore, 3)};
+            winners_mask = (uint32_t)blk_outcome(false, 0, score).winners;
+        }
+        // ---- random plies: blokus_rollout_kernel's ply under the playout's counter and tag, up to the first terminal one
+        const uint32_t g = (uint32_t)(first_env_id + (uint64_t)b), c2 = (a << 16) | r;
+        uint32_t tc = tcount ? (uint32_t)__builtin_amdgcn_readfirstlane((int)tcount[b]) : 0u;
+        uint32_t dead = 0, can_move = 0, rnd_word = 0u;
+        for (int t = 0; !over; ++t) {
+            const uint32_t ip = (uint32_t)__builtin_amdgcn_readlane((int)vinv, pl);
+            const BlkPrologue pro = blk_prologue(L, lane, round, pl, ip, owners);
+            uint32_t piece_incl = 0u, piece_cnt = 0u, total = 0u;
+            if (!((dead >> pl) & 1u) && pro.anchor_rows != 0u) {
+                const int lo = __builtin_ctz(pro.anchor_rows), hi = 31 - __builtin_clz(pro.anchor_rows);
+                total = blk_count_batches(T, L, lane, pro.items, lo, hi, &piece_incl, &piece_cnt);
+            }
+            if (total == 0 && round >= 1) dead |= 1u << pl;
+            if ((tc & 15u) == 0u || t == 0) {                    // lane j < 16: the word of step counter (tc & ~15) + j
+                uint32_t k0 = seed_lo, k1 = seed_hi;
+                asm volatile("" : "+s"(k0), "+s"(k1));
+                const philox_out r4 = philox4x32_10(g, ((tc >> 4) << 2) + (uint32_t)((lane >> 2) & 3), c2, CRL_TAG_BLOKUS_PLAYOUT, k0, k1);
+                const int ws = lane & 3;
+                rnd_word = ws == 0 ? r4.w[0] : ws == 1 ? r4.w[1] : ws == 2 ? r4.w[2] : r4.w[3];
+            }
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)rnd_word, (int)(tc & 15u));
+            tc += 1;
+            bool any_move = false;
+            BlkMove mv = {0, 0, 0, 0, 0};
+            if (total > 0) {
+                mv = blk_select<true>(T, L, pl, ip, __umulhi(word, total), lane, piece_incl, piece_cnt, piece_cells);
+                any_move = total > (uint32_t)__builtin_amdgcn_readlane((int)piece_cnt, mv.piece);
+            }
+            if (!any_move && (can_move & ~(1u << pl))) any_move = true;
+            for (int q = 0; q < 4 && !any_move; ++q) {           // the others, on the PRE-move board (:424)
+                if (q == pl || ((dead >> q) & 1u)) continue;
+                blk_prep(L, lane, round, q);
+                const uint32_t iq = (uint32_t)__builtin_amdgcn_readlane((int)vinv, q);
+                any_move = blk_exists(T, L, q, iq, lane, &owners);
+                if (any_move) can_move |= 1u << q;
+                if (!any_move && round >= 1) dead |= 1u << q;
+            }
+            if (total > 0) {
+                const int n = __builtin_amdgcn_readlane((int)piece_cells, mv.piece);
+                blk_place_legal(T, L, pl, mv, lane, n);
+                const uint32_t left = vinv & ~(1u << mv.piece);  // ai.py:44-54 for the mover's lane(s)
+                const bool me = (lane & 3) == pl;
+                vscore += me ? n + (left == 0u ? (mv.piece == 0 ? 20 : 15) : 0) : 0;
+                vinv = me ? left : vinv;
+                can_move = 0;
+            }
+            if (pl == 3) can_move = 0;
+            round += (pl == 3) ? 1 : 0;
+            pl = (pl + 1) & 3;
+            len += 1;
+            if (!any_move) {                                     // terminal (BlokusEnvironment.py:424-440)
+                const int score[4] = {__builtin_amdgcn_readlane(vscore, 0), __builtin_amdgcn_readlane(vscore, 1),
+                                      __builtin_amdgcn_readlane(vscore, 2), __builtin_amdgcn_readlane(vscore, 3)};
+                winners_mask = (uint32_t)blk_outcome(false, 0, score).winners;
+                over = true;
+            }
+        }
+        if (lane < 4) atomicAdd(&score_sum[row * 4 + lane], vscore);
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if ((winners_mask >> c) & 1u) atomicAdd(&wins[row * 4 + c], 1u);
+            atomicAdd(&played[row], 1u);
+            atomicAdd(&len_sum[row], (uint32_t)len);
+        }
+        wave_sync();                                             // (the next playout overwrites L.occ)
+    }
+}
+
 __global__ void __launch_bounds__(256)
 blokus_reset_kernel(const int64_t B, const uint8_t *__restrict__ mask, uint32_t *__restrict__ occ, uint32_t *__restrict__ inv,
                     int32_t *__restrict__ score, int32_t *__restrict__ round, int32_t *__restrict__ to_move)
@@ -1981,6 +2161,35 @@ int crl_blokus_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_
                        (const BlkTables *)ctx->blokus, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
                        occ, inv, score, round, to_move, seat, learner_action, tcount, reward, done, winners, n_valid,
                        obs_board, obs_pieces, obs_score, flags);
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_blokus_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                       const uint32_t *occ, const uint32_t *inv, const int32_t *score, const int32_t *round,
+                       const int32_t *to_move, const uint32_t *tcount,
+                       const int32_t *cand, int A, int R,
+                       uint32_t *wins, uint32_t *played, uint32_t *len_sum, int32_t *score_sum,
+                       uint32_t flags, void *stream)
+{
+    // (the pointer and argument checks come before the context's: they need no device)
+    CRL_REQUIRE(occ && inv && score && round && to_move, "crl_blokus_playout: NULL state pointer");
+    CRL_REQUIRE(wins && played && len_sum && score_sum, "crl_blokus_playout: NULL output pointer");
+    CRL_REQUIRE(R >= 1 && R <= 65535, "crl_blokus_playout: R=%d out of range 1..65535", R);
+    CRL_REQUIRE(A >= 1 && A <= 65535, "crl_blokus_playout: A=%d out of range 1..65535", A);
+    CRL_REQUIRE(cand != nullptr || A == 1, "crl_blokus_playout: A=%d with cand == NULL (must be 1)", A);
+    CRL_REQUIRE(flags == 0, "crl_blokus_playout: unknown flags 0x%x", flags);
+    BLK_CTX_CHECK("crl_blokus_playout");
+    const uint64_t rows = (uint64_t)B * (uint64_t)A, n_playouts = rows * (uint64_t)R;
+    CRL_HIP(hipMemsetAsync(wins, 0, rows * 4 * sizeof(uint32_t), (hipStream_t)stream));   // the rows are sums of atomics
+    CRL_HIP(hipMemsetAsync(played, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
+    CRL_HIP(hipMemsetAsync(len_sum, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
+    CRL_HIP(hipMemsetAsync(score_sum, 0, rows * 4 * sizeof(int32_t), (hipStream_t)stream));
+    const uint64_t want = (n_playouts + 3u) / 4u;           // a grid-stride loop past 2^20 workgroups
+    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));
+    hipLaunchKernelGGL(blokus_playout_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const BlkTables *)ctx->blokus, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
+                       occ, inv, score, round, to_move, tcount, cand, A, R, n_playouts, wins, played, len_sum, score_sum);
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }

@@ -620,6 +620,120 @@ ttt_step_single_kernel(const ttt_dirs dd, const uint32_t inv_cells, const int64_
     ttt_write_boards<P>(s_occ, s_seat, dd.n_cells, inv_cells, rel_mod, g0, B, obs);
 }
 
+// ---- batched random playouts (crl_ttt_playout; the contract is in include/colosseum_hip.h).  One lane per playout, the
+// flat lane index i = (b * A + a) * R + r (r fastest): the lanes of one row are neighbours, so a row is one segment of a
+// wave (R <= 64 and aligned) or spans several waves.  A lane loads its position (the R lanes of a row read the same words:
+// cache hits), plays the candidate ply if there is one and then random plies until the first terminal one; the wave runs
+// until its longest playout ends.  The draws are the rollout's agent under the playout tag and the third counter word
+// (a << 16) | r: one Philox block per eight step counters, kept in registers and its word picked as the rollout's
+// next_word does (ttt_agent_word would redo the ten rounds on every ply), the cell out of the rollout's rank table.  Outcomes leave through ballots: per row segment of the wave and output word, a popcount of the
+// segment's bits (the plies as six bit planes), so that one head lane per segment issues one store -- or, for a row that
+// also has lanes in other waves, one integer atomic onto the zeros the launcher wrote.
+template <int P, int ND, bool WT>
+__global__ void __launch_bounds__(256)
+ttt_playout_kernel(const ttt_dirs dd, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
+                   const uint64_t first_env_id, const uint32_t *__restrict__ occ, const int8_t *__restrict__ winner,
+                   const int8_t *__restrict__ to_move, const uint32_t *__restrict__ tcount, const int32_t *__restrict__ cand,
+                   const int A, const int R, const uint64_t n_lanes, uint32_t *__restrict__ wins,
+                   uint32_t *__restrict__ played, uint32_t *__restrict__ len_sum, const uint32_t *__restrict__ win_tab)
+{
+    constexpr bool SMALL = WT;                                   // (WT: at most 16 cells)
+    __shared__ uint8_t rank_tab[256 * 8];
+    __shared__ uint32_t win_bits[WT ? 2048 : 1];
+    ttt_fill_rank_table(rank_tab);
+    if (WT) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(win_tab);
+        uint4 *dst = reinterpret_cast<uint4 *>(win_bits);
+        dst[threadIdx.x] = src[threadIdx.x];
+        dst[threadIdx.x + 256] = src[threadIdx.x + 256];
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t wave0 = (uint64_t)blockIdx.x * 256u + (threadIdx.x & ~63u); wave0 < n_lanes; wave0 += stride) {
+        // (b, a, r) of this lane: one 64-bit division per wave (wave-uniform), then a 32-bit one per lane
+        const uint64_t row0 = wave0 / (uint32_t)R;
+        const uint32_t r0 = (uint32_t)(wave0 - row0 * (uint32_t)R);
+        const uint32_t q = (r0 + lane) / (uint32_t)R;
+        const uint64_t row = row0 + q;
+        const uint32_t r = r0 + lane - q * (uint32_t)R;
+        const bool live = wave0 + lane < n_lanes;
+        const int64_t b = live ? (int64_t)(row / (uint32_t)A) : 0;
+        const uint32_t a = (uint32_t)(row - (uint64_t)b * (uint32_t)A);
+        int wn = -1, len = 0;
+        bool play = false;
+        if (live) {
+            uint32_t o[P], all = 0;
+#pragma unroll
+            for (int p = 0; p < P; ++p) { o[p] = occ[p * B + b]; all |= o[p]; }
+            int w = winner[b], tm = to_move[b];
+            play = w < 0 && all != dd.full && (unsigned)tm < (unsigned)P;   // a position that is over skips every row
+            int first = -1;
+            if (play && cand != nullptr) {                      // the candidate: an empty cell, else the row is skipped
+                first = cand[b * A + a];
+                play = first >= 0 && first < dd.n_cells && !((all >> (first & 31)) & 1u);
+            }
+            if (play) {
+                const uint32_t g = (uint32_t)(first_env_id + (uint64_t)b), c2 = (a << 16) | r;
+                uint32_t c = tcount ? tcount[b] : 0u;
+                philox_out rnd = philox4x32_10<true>(g, c >> 3, c2, CRL_TAG_TTT_PLAYOUT, seed_lo, seed_hi);
+                int term = 0, rw, ws = -1;
+                if (first >= 0) {                               // the candidate ply: no draw
+                    ttt_step_core<P, ND, WT>(dd, o, w, tm, first, rw, term, ws, win_bits);
+                    len = 1;
+                }
+                while (!term) {                                 // random plies on a running game (the rollout's draw)
+                    all = 0;
+#pragma unroll
+                    for (int p = 0; p < P; ++p) all |= o[p];
+                    const uint32_t empty = dd.full & ~all;
+                    const uint32_t n_empty = (uint32_t)__popc(empty);           // (not 0: the game is running)
+                    const uint32_t sel = (c >> 1) & 3u;
+                    uint32_t word = rnd.w[0];
+                    word = (sel == 1) ? rnd.w[1] : word;
+                    word = (sel == 2) ? rnd.w[2] : word;
+                    word = (sel == 3) ? rnd.w[3] : word;
+                    word = (c & 1u) ? word * (n_empty + 1u) : word;
+                    const int act = (int)nth_set_bit_tab<SMALL>(rank_tab, empty, __umulhi(word, n_empty));
+                    ttt_step_core<P, ND, WT>(dd, o, w, tm, act, rw, term, ws, win_bits);
+                    len += 1;
+                    c += 1u;
+                    if ((c & 7u) == 0u && !term) rnd = philox4x32_10<true>(g, c >> 3, c2, CRL_TAG_TTT_PLAYOUT, seed_lo, seed_hi);
+                }
+                wn = ws;
+            }
+        }
+        // ---- per row segment of this wave: the lanes from a head (r == 0, or lane 0) to the next head
+        const unsigned long long heads = __ballot(live && (lane == 0u || r == 0u));
+        const unsigned long long above = lane == 63u ? 0ull : heads & (~0ull << (lane + 1u));
+        const uint32_t end = above ? (uint32_t)__builtin_ctzll(above) : 64u;
+        const unsigned long long seg = (end == 64u ? ~0ull : ((1ull << end) - 1ull)) & (~0ull << lane);
+        const bool head = (heads >> lane) & 1ull;
+        const bool whole = r == 0u && end - lane == (uint32_t)R;           // the row has no lane in another wave
+        uint32_t cnt[P], n_played, plies = 0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) cnt[p] = (uint32_t)__builtin_popcountll(__ballot(play && wn == p) & seg);
+        n_played = (uint32_t)__builtin_popcountll(__ballot(play) & seg);
+#pragma unroll
+        for (int k = 0; k < 6; ++k)                              // len <= cells + 1 <= 33 < 2^6
+            plies += (uint32_t)__builtin_popcountll(__ballot(play && ((len >> k) & 1)) & seg) << k;
+        if (head) {
+            if (whole) {
+#pragma unroll
+                for (int p = 0; p < P; ++p) wins[row * P + p] = cnt[p];
+                played[row] = n_played;
+                len_sum[row] = plies;
+            } else if (n_played) {
+#pragma unroll
+                for (int p = 0; p < P; ++p)
+                    if (cnt[p]) atomicAdd(&wins[row * P + p], cnt[p]);
+                atomicAdd(&played[row], n_played);
+                atomicAdd(&len_sum[row], plies);
+            }
+        }
+    }
+}
+
 // the rollout's random agent for one step
 __global__ void __launch_bounds__(256)
 ttt_sample_kernel(const int P, const uint32_t full, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
@@ -1029,6 +1143,47 @@ int crl_ttt_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t f
         else TTT_SINGLE_LAUNCH(13, false);
     });
 #undef TTT_SINGLE_LAUNCH
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_ttt_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                    const uint32_t *occ, const int8_t *winner, const int8_t *to_move, const uint32_t *tcount,
+                    const int32_t *cand, int A, int R,
+                    uint32_t *wins, uint32_t *played, uint32_t *len_sum, uint32_t flags, void *stream)
+{
+    TTT_CTX_CHECK("crl_ttt_playout");
+    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_playout: NULL state pointer");
+    CRL_REQUIRE(wins && played && len_sum, "crl_ttt_playout: NULL output pointer");
+    CRL_REQUIRE(R >= 1 && R <= 65535, "crl_ttt_playout: R=%d out of range 1..65535", R);
+    CRL_REQUIRE(A >= 1 && A <= 65535, "crl_ttt_playout: A=%d out of range 1..65535", A);
+    CRL_REQUIRE(cand != nullptr || A == 1, "crl_ttt_playout: A=%d with cand == NULL (must be 1)", A);
+    CRL_REQUIRE(flags == 0, "crl_ttt_playout: unknown flags 0x%x", flags);
+    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "crl_ttt_playout: a board of %d cells for %d players (as crl_ttt_step_single)",
+                ctx->ttt.n_cells, ctx->ttt.P);
+    const ttt_dirs dd = dirs_of(ctx);
+    const uint32_t *win_tab = nullptr;                      // the <= 16-cell win table, when it lives on this device
+    if (ctx->ttt_win_dev) {
+        int dev = -1;
+        if (hipGetDevice(&dev) == hipSuccess && dev == ctx->ttt_win_device) win_tab = ctx->ttt_win_dev;
+    }
+    const uint64_t rows = (uint64_t)B * (uint64_t)A, n_lanes = rows * (uint64_t)R;
+    // rows that span waves are summed by atomics: every output starts from zero
+    CRL_HIP(hipMemsetAsync(wins, 0, rows * ctx->ttt.P * sizeof(uint32_t), (hipStream_t)stream));
+    CRL_HIP(hipMemsetAsync(played, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
+    CRL_HIP(hipMemsetAsync(len_sum, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
+    const uint64_t want = (n_lanes + 255u) / 256u;          // a grid-stride loop past 2^20 workgroups
+    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));
+#define TTT_PLAYOUT_LAUNCH(ND_, WT_)                                                                                      \
+    hipLaunchKernelGGL((ttt_playout_kernel<PP, ND_, WT_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, dd, B,        \
+                       (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, tcount, cand, A, R,    \
+                       n_lanes, wins, played, len_sum, win_tab)
+    TTT_DISPATCH_P(ctx->ttt.P, {
+        if (dd.n_dirs <= 4 && dd.n_cells <= 16 && win_tab != nullptr) TTT_PLAYOUT_LAUNCH(4, true);
+        else if (dd.n_dirs <= 4) TTT_PLAYOUT_LAUNCH(4, false);
+        else TTT_PLAYOUT_LAUNCH(13, false);
+    });
+#undef TTT_PLAYOUT_LAUNCH
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }

@@ -80,7 +80,9 @@ const char *crl_last_error(void);
  * 109: crl_blokus_step / _step_observe place ANY action as the reference's next_state does (numpy index rules, extended ids,
  *      CRL_BLOKUS_*_ERROR codes in the reward slot).  110: crl_tron_next_state_inplace64 (+ _host) / _relative_player_inplace64.  111: crl_ttt_step_board_host.
  * 112: crl_tron_sample_avoid / crl_tron_rollout_avoid (the scripted avoid agent), crl_tron_step_single.
- * 113: crl_ttt_step_single / crl_blokus_step_single (one learner against the random agent), CRL_STEP_RANK_ACTION. */
+ * 113: crl_ttt_step_single / crl_blokus_step_single (one learner against the random agent), CRL_STEP_RANK_ACTION.
+ *      crl_ttt_playout / crl_blokus_playout (batched random playouts) were added under 113: new entries and new Philox
+ *      tags only, no existing struct, argument list or RNG contract changed. */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -603,6 +605,59 @@ int crl_blokus_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_
                            const int8_t *seat, const int64_t *learner_action, uint32_t *tcount,
                            int8_t *reward, uint8_t *done, uint8_t *winners, int32_t *n_valid,
                            int8_t *obs_board, uint8_t *obs_pieces, int32_t *obs_score, uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------ batched random playouts (turn-based games)
+ * crl_ttt_playout / crl_blokus_playout: from each of B positions, play R games of the random agent to their end and count
+ * who won -- the evaluation step of flat Monte Carlo and of MCTS with random rollouts.  One launch, no host sync.
+ *
+ * Inputs are read only: the state arrays (occ, winner / inv, score, round, to_move) have the layouts of the game's other
+ * entries and are never written.  tcount uint32 [B] is the step-counter base of the RNG contract below; NULL means 0.
+ * Rows: cand int32 [B][A], or NULL with A == 1.  Row (b, a) evaluates candidate cand[b][a], a move of the player
+ * p0 = to_move[b]; with cand == NULL row (b, 0) evaluates the position as it stands (no candidate ply).
+ * Playouts: row (b, a) plays R playouts r = 0 .. R-1, each on a private copy of position b:
+ *   1. the candidate ply, if there is a candidate, applied as crl_*_step applies that action; it consumes no random draw;
+ *   2. then random-agent plies k = 0, 1, ..., each the random agent's action applied as crl_*_step applies it;
+ *   3. the playout stops at the first ply (1. or 2.) that crl_*_step would report terminal; nothing is ever reset.
+ * Random stream: ply k of part 2 has step counter c = tcount[b] + k (uint32 arithmetic) and game id g = first_env_id + b
+ * (low 32 bits); its draw is the game's random agent (crl_*_rollout, stated with crl_ttt_rollout / crl_blokus_rollout above)
+ * with the third counter word (a << 16) | r in place of 0 and its own tag:
+ *   TicTacToe  w = Philox(ctr={g, c >> 3, (a << 16) | r, 0x54500000}, seed)[(c >> 1) & 3]; the even / odd mixed-radix rule
+ *              and r' = mulhi32(draw, n) are crl_ttt_rollout's: the ply marks empty cell number r' in row-major order;
+ *   Blokus     w = Philox(ctr={g, c >> 2, (a << 16) | r, 0x42500000}, seed)[c & 3]; the mover plays legal action number
+ *              mulhi32(w, n) of its n legal actions in reference order, '' (pass) when n = 0, as crl_blokus_rollout.
+ * So with cand == NULL a playout is crl_*_rollout on a copy of the state under that counter and tag, stopped at its first
+ * terminal ply.
+ * Outputs, every row written (overwritten, never accumulated; a skipped row holds zeros):
+ *   played  uint32 [B][A]     R, or 0 when the row is skipped;
+ *   wins    uint32 [B][A][P]  playouts won by player p: TicTacToe the terminal step's winner (draws are
+ *                             played - sum_p wins); Blokus bit p of the terminal step's winners mask, so a tie counts for
+ *                             every tied player;
+ *   len_sum uint32 [B][A]     plies played over the R playouts, the candidate ply included;
+ *   score_sum int32 [B][A][4] (Blokus) the sum of the final score[c].
+ * Argument checks (CRL_EINVAL, with a crl_last_error message, before any device work): NULL state / output pointers, B out
+ * of range (as the game's other entries), R or A outside [1, 65535], A != 1 with cand == NULL, flags != 0, and per game below.
+ * Lanes are indexed with 64-bit arithmetic: B * A * R may pass 2^31.
+ *
+ * TicTacToe: a candidate is played only if it lies in [0, cells) and names an empty cell; any other value (-1 padding
+ * included) skips its row.  A position that is over (winner[b] >= 0, or no empty cell) or whose to_move[b] is outside
+ * [0, P) skips every row.  The context must have cells >= P (as crl_ttt_step_single).  One lane per playout, flat lane
+ * index (b, a, r) with r fastest; boards of at most 16 cells test for a line with the win-mask table of crl_ttt_create when
+ * it lives on the launching device.  A wave's outcomes are summed per row inside the wave (ballots) before one store or
+ * integer atomic per row segment and output word, so the results do not depend on the order of the waves. */
+int crl_ttt_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                    const uint32_t *occ, const int8_t *winner, const int8_t *to_move, const uint32_t *tcount,
+                    const int32_t *cand, int A, int R,
+                    uint32_t *wins, uint32_t *played, uint32_t *len_sum, uint32_t flags, void *stream);
+/* Blokus: the mover is p0 = to_move[b] & 3.  A candidate is played only if it is a dense id (< CRL_BLOKUS_EXT_BASE) that
+ * is a legal action of p0 by crl_blokus_is_valid's definition; anything else skips its row.  Blokus keeps no "game over"
+ * field, so a finished position needs no special case: its first random ply is a pass and the step reports it terminal.
+ * One wave per playout with the board in LDS; each ply is crl_blokus_rollout's. */
+int crl_blokus_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                       const uint32_t *occ, const uint32_t *inv, const int32_t *score, const int32_t *round,
+                       const int32_t *to_move, const uint32_t *tcount,
+                       const int32_t *cand, int A, int R,
+                       uint32_t *wins, uint32_t *played, uint32_t *len_sum, int32_t *score_sum,
+                       uint32_t flags, void *stream);
 
 #ifdef __cplusplus
 }

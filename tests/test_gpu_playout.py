@@ -1,0 +1,318 @@
+"""Batched random playouts on the GPU (crl_ttt_playout / crl_blokus_playout): bit-exact against the numpy restatement of
+the header's contract (tests/playout_ref.py) on ragged batches of random positions, the outcome counts of every
+reachable 3x3 position against exact probabilities, flat Monte Carlo against the random agent through the single-player
+vector env, lane indices past 2^31, graph capture, determinism, read-only inputs, and a smoke run of
+tools/playout_rate.py."""
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import playout_ref as R
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+def _u32(t):
+    return _np(t).view(np.uint32)
+
+
+# ------------------------------------------------------------------ TicTacToe positions
+def _ttt_positions(dims, K, P, B, rng):
+    """B random positions: random plies from the empty board, some games played past their end (finished, not reset)"""
+    from oracle import oracle as O
+    st = O.TTTState(dims, K, P, B)
+    for b in range(B):
+        one = O.TTTState(dims, K, P, 1)
+        for _ in range(int(rng.integers(0, one.n_cells + 1))):
+            bd = one.board()[0]
+            empty = np.flatnonzero(bd < 0)
+            if len(empty) == 0 or (one.winner[0] >= 0 and rng.random() < 0.5):
+                break
+            O.ttt_step(one, np.array([rng.choice(empty)], np.int8))
+        st.occ[:, b], st.winner[b], st.to_move[b] = one.occ[:, 0], one.winner[0], one.to_move[0]
+    return st
+
+
+def _ttt_batch(st, first_env_id, tcount):
+    from colosseumrl_amd.batched import TTTBatch
+    tb = TTTBatch(st.dims, st.K, st.P, st.B, device=DEV, first_env_id=first_env_id)
+    tb.occ.copy_(torch.from_numpy(st.occ.view(np.int32)))
+    tb.winner.copy_(torch.from_numpy(st.winner))
+    tb.to_move.copy_(torch.from_numpy(st.to_move))
+    tb.tcount.copy_(torch.from_numpy(tcount.view(np.int32)))
+    return tb
+
+
+def _ttt_check(tb, st, tcount, Rn, cand, seed, first_env_id):
+    A = 1 if cand is None else cand.shape[1]
+    snap = [t.clone() for t in (tb.occ, tb.winner, tb.to_move, tb.tcount)]
+    out = tb.playout(Rn, None if cand is None else torch.from_numpy(cand.astype(np.int32)).to(DEV), seed)
+    wins, played, len_sum = R.ttt_playout(st, seed, Rn, cand=cand, A=A, first_env_id=first_env_id, tcount=tcount)
+    torch.cuda.synchronize()
+    assert np.array_equal(_u32(out["played"]), played)
+    assert np.array_equal(_u32(out["wins"]), wins)
+    assert np.array_equal(_u32(out["len_sum"]), len_sum)
+    assert np.array_equal(_np(out["draws"]), played.astype(np.int64) - wins.sum(axis=2))
+    for a, b in zip(snap, (tb.occ, tb.winner, tb.to_move, tb.tcount)):       # the inputs are read only
+        assert torch.equal(a, b)
+    return played
+
+
+# (shape, R with candidates, R without)
+TTT_CASES = [(((3, 3), 3, 2), 3, 100), (((3, 5), 3, 3), 1, 65), (((3, 3, 3), 3, 4), 3, 1), (((5, 5), 4, 3), 1, 65)]
+TTT_IDS = ["x".join(map(str, d)) + "k%dp%d" % (k, p) for (d, k, p), _, _ in TTT_CASES]
+
+
+@pytest.mark.parametrize("cfg,r_cand,r_none", TTT_CASES, ids=TTT_IDS)
+def test_ttt_against_restatement(cfg, r_cand, r_none):
+    dims, K, P = cfg
+    rng = np.random.default_rng(sum(dims) * 7 + P)
+    B, first_env_id, seed = 67, 1000 + P, 0xABCDEF0123 + P           # B: not a multiple of 64
+    st = _ttt_positions(dims, K, P, B, rng)
+    n = st.n_cells
+    tcount = rng.integers(0, 2 ** 32, size=B, dtype=np.uint64).astype(np.uint32)
+    tcount[:3] = [0, 2 ** 32 - 3, 5]                                  # a counter that wraps inside the playouts
+    tb = _ttt_batch(st, first_env_id, tcount)
+    cand = np.concatenate([np.tile(np.arange(n), (B, 1)), np.full((B, 1), -1), np.full((B, 1), n),
+                           rng.integers(-5, n + 40, size=(B, 2))], axis=1)
+    cand = np.ascontiguousarray(rng.permuted(cand, axis=1))
+    played = _ttt_check(tb, st, tcount, r_cand, cand, seed, first_env_id)
+    assert played.any() and not played.all()                         # both played and skipped rows
+    played = _ttt_check(tb, st, tcount, r_none, None, seed, first_env_id)
+    assert played.any() and not played.all()                         # finished positions are among them
+
+
+# ------------------------------------------------------------------ Blokus
+def _blokus_positions():
+    """an early, a mid-game and a finished position (random plies, no reset)"""
+    from oracle import oracle as O
+    rng = np.random.default_rng(4)
+    st = O.BlokusState(3)
+    for b, plies in enumerate((5, 44, None)):
+        one = O.BlokusState(1)
+        k = 0
+        while plies is None or k < plies:
+            ids = R.blokus_legal(one)
+            act = int(ids[rng.integers(len(ids))]) if len(ids) else -1
+            _, term, _ = O.blokus_step(one, np.array([act], np.int32))
+            k += 1
+            if term[0]:
+                break
+        for name in ("occ", "inv", "score", "round", "to_move"):
+            getattr(st, name)[b] = getattr(one, name)[0]
+    return st
+
+
+def _blokus_batch(st, first_env_id, tcount):
+    from colosseumrl_amd.batched import BlokusBatch
+    bb = BlokusBatch(st.B, device=DEV, first_env_id=first_env_id)
+    for name in ("occ", "inv", "score", "round", "to_move"):
+        getattr(bb, name).copy_(torch.from_numpy(getattr(st, name).view(np.int32)))
+    bb.tcount.copy_(torch.from_numpy(tcount.view(np.int32)))
+    return bb
+
+
+def test_blokus_against_restatement():
+    st = _blokus_positions()
+    rng = np.random.default_rng(9)
+    first_env_id, seed = 77, 31337
+    tcount = np.array([3, 17, 2 ** 32 - 2], np.uint32)
+    bb = _blokus_batch(st, first_env_id, tcount)
+    cand = np.full((3, 4), -1, np.int64)
+    for b in range(3):
+        legal = R.blokus_legal(R._blk_copy(st, b))
+        if len(legal):
+            cand[b, :2] = rng.choice(legal, size=2)
+        legal_set = set(int(i) for i in legal)
+        bad = int(rng.integers(0, 336000))
+        while bad in legal_set:
+            bad = int(rng.integers(0, 336000))
+        cand[b, 2] = bad                                              # a dense id that is not legal
+    snap = [t.clone() for t in (bb.occ, bb.inv, bb.score, bb.round, bb.to_move, bb.tcount)]
+    for c, Rn in ((cand, 2), (None, 3)):
+        A = 1 if c is None else 4
+        out = bb.playout(Rn, None if c is None else torch.from_numpy(c.astype(np.int32)).to(DEV), seed)
+        wins, played, len_sum, score_sum = R.blokus_playout(st, seed, Rn, cand=c, A=A, first_env_id=first_env_id,
+                                                            tcount=tcount)
+        torch.cuda.synchronize()
+        assert np.array_equal(_u32(out["played"]), played)
+        assert np.array_equal(_u32(out["wins"]), wins)
+        assert np.array_equal(_u32(out["len_sum"]), len_sum)
+        assert np.array_equal(_np(out["score_sum"]), score_sum)
+        assert played.any()
+    assert (played[2] == 3).all() and (len_sum[2] == 3).all()         # the finished position: one pass, terminal
+    for a, b in zip(snap, (bb.occ, bb.inv, bb.score, bb.round, bb.to_move, bb.tcount)):
+        assert torch.equal(a, b)
+
+
+def test_blokus_flat_mc_action_picks_a_candidate():
+    st = _blokus_positions()
+    bb = _blokus_batch(st, 0, np.zeros(3, np.uint32))
+    cand = torch.full((3, 3), -1, dtype=torch.int32, device=DEV)
+    for b in range(2):
+        legal = R.blokus_legal(R._blk_copy(st, b))
+        cand[b, :min(3, len(legal))] = torch.from_numpy(legal[:3].astype(np.int32))
+    act = bb.flat_mc_action(cand, 2, seed=5)
+    torch.cuda.synchronize()
+    assert act.dtype == torch.int64
+    a = _np(act)
+    assert a[0] in _np(cand[0]) and a[1] in _np(cand[1]) and a[2] == -1   # the finished game has no legal candidate
+
+
+# ------------------------------------------------------------------ statistics: every reachable 3x3 position
+def test_ttt_3x3_exact_outcome_probabilities():
+    from colosseumrl_amd.batched import TTTBatch
+    pos = R.reachable_3x3()
+    assert len(pos) == 4520
+    B, Rn = len(pos), 4096
+    tb = TTTBatch((3, 3), 3, 2, B, device=DEV)
+    occ = np.array([[x for x, _, _ in pos], [o for _, o, _ in pos]], np.uint32)
+    tb.occ.copy_(torch.from_numpy(occ.view(np.int32)))
+    tb.to_move.copy_(torch.tensor([m for _, _, m in pos], dtype=torch.int8))
+    out = tb.playout(Rn, seed=2024)
+    wins, draws, played = _np(out["wins"])[:, 0], _np(out["draws"])[:, 0], _np(out["played"])[:, 0]
+    assert (played == Rn).all()
+    memo = {}
+    worst = 0.0
+    for b, (x, o, m) in enumerate(pos):
+        p0, p1 = R.exact_3x3(x, o, m, memo)
+        for n, p in ((wins[b, 0], p0), (wins[b, 1], p1), (draws[b], 1.0 - p0 - p1)):
+            p = min(max(p, 0.0), 1.0)
+            dev = abs(int(n) - Rn * p)
+            assert dev <= 6 * math.sqrt(Rn * p * (1 - p)) + 1, (b, x, o, m, int(n), Rn * p)
+            worst = max(worst, dev / (math.sqrt(Rn * p * (1 - p)) + 1e-9) if p * (1 - p) > 0 else 0.0)
+    assert worst < 6
+
+
+# ------------------------------------------------------------------ flat Monte Carlo against the random agent
+def _flat_mc_rates(seat, batch=16384, playouts=256):
+    from colosseumrl_amd.vector import TicTacToeSinglePlayerVectorEnv
+    env = TicTacToeSinglePlayerVectorEnv((3, 3), 3, 2, batch, seat=seat, seed=7, device=DEV)
+    env.reset()
+    first = torch.zeros(batch, dtype=torch.bool, device=DEV)
+    result = torch.zeros(batch, dtype=torch.int8, device=DEV)
+    for _ in range(6):                                     # a 3x3 game gives the learner at most 5 turns
+        action = env.batch.flat_mc_action(playouts, seed=11)
+        _, reward, done, _ = env.step(action)
+        new = (done != 0) & ~first
+        result = torch.where(new, reward, result)
+        first |= done != 0
+    assert bool(first.all())
+    r = _np(result)
+    return float((r == 1).mean()), float((r == -1).mean())
+
+
+def test_flat_mc_beats_random():
+    win0, loss0 = _flat_mc_rates(0)
+    win1, loss1 = _flat_mc_rates(1)
+    # exact infinite-R rates: seat 0 wins 0.990, never loses; seat 1 wins 0.904, loses 0.036 (a random learner at seat 0
+    # loses 0.288)
+    assert win0 >= 0.975 and loss0 <= 0.005, (win0, loss0)
+    assert win1 >= 0.88 and loss1 <= 0.05, (win1, loss1)
+
+
+# ------------------------------------------------------------------ lane indices past 2^31
+def test_lane_index_past_2_31():
+    from oracle import oracle as O
+    rng = np.random.default_rng(5)
+    B, A, Rn, seed = 65536, 9, 4096, 99
+    assert B * A * Rn > 2 ** 31
+    st = O.TTTState((3, 3), 3, 2, B)
+    # running positions: k random plies, k < 5 (no line yet)
+    k = rng.integers(0, 5, size=B)
+    for ply in range(4):
+        bd = st.board()
+        act = np.array([rng.choice(np.flatnonzero(bd[b] < 0)) if ply < k[b] else -1 for b in range(B)], np.int8)
+        idx = np.flatnonzero(ply < k)
+        one = O.TTTState((3, 3), 3, 2, len(idx))
+        one.occ[:] = st.occ[:, idx]
+        one.to_move[:] = st.to_move[idx]
+        O.ttt_step(one, act[idx])
+        st.occ[:, idx], st.to_move[idx], st.winner[idx] = one.occ, one.to_move, one.winner
+    tcount = np.zeros(B, np.uint32)
+    tb = _ttt_batch(st, 0, tcount)
+    cells = torch.arange(9, dtype=torch.int32, device=DEV).expand(B, 9).contiguous()
+    out = tb.playout(Rn, cells, seed)
+    played, wins = _u32(out["played"]), _u32(out["wins"])
+    empty = (st.board() < 0)
+    assert np.array_equal(played, np.where(empty, Rn, 0).astype(np.uint32))
+    assert (wins.sum(axis=2) <= played).all()
+    # three rows whose lanes lie past 2^31 (one of them the very last), bit-exact
+    last = [(B - 1, int(np.flatnonzero(empty[B - 1])[-1]))]
+    rows = last + [(int(b), int(np.flatnonzero(empty[b])[0])) for b in (60000, 63001)]
+    for b, a in rows:
+        assert (b * A + a) * Rn >= 2 ** 31
+    w_ref, p_ref, l_ref = R.ttt_playout(st, seed, Rn, cand=cells.cpu().numpy(), A=A, rows=rows)
+    for b, a in rows:
+        assert np.array_equal(wins[b, a], w_ref[b, a]) and played[b, a] == p_ref[b, a]
+        assert _u32(out["len_sum"])[b, a] == l_ref[b, a]
+
+
+# ------------------------------------------------------------------ graph capture, determinism
+def test_graph_capture_and_determinism():
+    from colosseumrl_amd.vector import TicTacToeSinglePlayerVectorEnv
+    B, Rn, steps = 1000, 32, 5
+
+    def eager():
+        env = TicTacToeSinglePlayerVectorEnv((3, 3), 3, 2, B, seat=1, seed=3, device=DEV)
+        env.reset()
+        hist = []
+        for _ in range(steps):
+            a = env.batch.flat_mc_action(Rn, seed=21)
+            obs, reward, done, _ = env.step(a)
+            hist.append((a.clone(), obs["board"].clone(), reward.clone(), done.clone()))
+        return hist
+
+    ref = eager()
+    again = eager()
+    for x, y in zip(ref, again):
+        assert all(torch.equal(u, v) for u, v in zip(x, y))
+
+    env = TicTacToeSinglePlayerVectorEnv((3, 3), 3, 2, B, seat=1, seed=3, device=DEV)
+    env.reset()
+    po = env.batch.playout(Rn, torch.zeros((B, 9), dtype=torch.int32, device=DEV))   # the dict flat_mc_action reuses
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):                          # warm-up outside the capture (lazy buffers; the state is only read)
+        env.batch.flat_mc_action(Rn, seed=21, out=po)
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        a = env.batch.flat_mc_action(Rn, seed=21, out=po)
+        obs, reward, done, _ = env.step(a)
+    for k in range(steps):
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(a, ref[k][0]) and torch.equal(obs["board"], ref[k][1])
+        assert torch.equal(reward, ref[k][2]) and torch.equal(done, ref[k][3])
+
+    # another seed gives other playouts; the same seed the same
+    from colosseumrl_amd.batched import TTTBatch
+    tb = TTTBatch((3, 3), 3, 2, 256, device=DEV)
+    x = tb.playout(64, seed=1)["wins"].clone()
+    assert torch.equal(x, tb.playout(64, seed=1)["wins"])
+    assert not torch.equal(x, tb.playout(64, seed=2)["wins"])
+
+
+# ------------------------------------------------------------------ the rate tool
+def test_playout_rate_tool_smoke(tmp_path):
+    out = tmp_path / "rate.jsonl"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "playout_rate.py"), "--tiny", "--out", str(out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    import json
+    rows = [json.loads(line) for line in out.read_text().splitlines()]
+    assert {row["game"] for row in rows} == {"tictactoe", "blokus"}
+    assert all(row["playouts_per_s"] > 0 and row["plies_per_s"] > 0 for row in rows)

@@ -27,6 +27,8 @@ CRL_ROLLOUT_QUAD = 16
 CRL_ROLLOUT_QBITS = 32
 CRL_ROLLOUT_GQUAD = 64
 CRL_ROLLOUT_PAIR = 128
+CRL_PLAYOUT_AVOID = 1
+CRL_PLAYOUT_UNTIL_SEAT_DONE = 2
 
 _lib = None
 _lock = threading.Lock()
@@ -97,6 +99,7 @@ PROTOTYPES = {
     "crl_tron_rollout_avoid": (_I, [_VP, _I64, _U64, _U64, _I, C.c_double, _VP, _VP, _VP, _VP, TronStats, _U32, _VP]),
     "crl_tron_step_single": (_I, [_VP, _I64] + [_VP] * 9 + [_VP]),
     "crl_tron_check_state": (_I, [_VP, _I64, _VP, _VP, _VP, _VP]),
+    "crl_tron_playout": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 7 + [_I, _I, C.c_double, _I] + [_VP] * 4 + [_U32, _VP]),
     "crl_ttt_create": (_I, [_I, _I, _I, _I, _I, C.POINTER(_VP)]),
     "crl_ttt_lines": (_I, [_VP, _VP, _I]),
     "crl_ttt_reset": (_I, [_VP, _I64, _VP, _VP, _VP, _VP, _VP]),

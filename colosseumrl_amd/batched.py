@@ -101,6 +101,18 @@ def _playout_out(out: Optional[dict], B: int, A: int, P: int, device, score: boo
     return out
 
 
+def _tron_playout_out(out: Optional[dict], B: int, A: int, P: int, device):
+    """the output dict of a Tron playout call: fresh, or `out` with every buffer checked"""
+    shapes = {"wins": (B, A, P), "played": (B, A), "len_sum": (B, A), "ret_sum": (B, A)}
+    if out is None:
+        return {k: torch.empty(v, dtype=torch.int32, device=device) for k, v in shapes.items()}
+    for k, v in shapes.items():
+        if k not in out:
+            raise ValueError("out lacks %r" % k)
+        _want(out[k], torch.int32, v, device, "out[%r]" % k)
+    return out
+
+
 def _flat_mc_pick(value: torch.Tensor, played: torch.Tensor, ids: torch.Tensor):
     """int64 [B]: ids[b, a] of the greatest value among the played rows (ties: the lowest a), -1 where none was played"""
     value = torch.where(played > 0, value, torch.full_like(value, -1))
@@ -321,6 +333,60 @@ class TronBatch(_Waitable):
                                                   _ptr(self.dirs), _ptr(self.deaths), _ptr(out), _stream()),
                   "crl_tron_sample_avoid")
         return out
+
+    # -- batched playouts for one seat from every game's position (flat Monte Carlo's evaluation)
+    def playout(self, playouts: int, candidates: Optional[torch.Tensor] = None, seed: int = 0, agent: str = "random",
+                noise: float = 0.1, seat: Optional[torch.Tensor] = None, until: str = "end", max_steps: int = 0,
+                out: Optional[dict] = None):
+        """Playouts from every game's position, ONE launch (``crl_tron_playout``): row (b, a) plays first action
+        ``candidates[b, a]`` (int32 [B, A]: 0 forward, 1 right, 2 left; any other value skips the row) for the seat
+        ``seat[b]`` (int8 [B]; None: player 0) and then ``playouts`` games on private copies, every player on ``agent``
+        ("random", or "avoid" with ``noise``).  ``candidates=None`` evaluates the position as it stands (A = 1).  A playout
+        stops at the first terminal step; ``until="seat_done"`` also after the step in which the seat dies, ``max_steps``
+        > 0 after that many steps.  The draws are keyed by ``seed``, the game ids and ``tcount`` as the counter base (the
+        state is only read).  Returns {'wins' int32 [B, A, P], 'played', 'len_sum', 'ret_sum' int32 [B, A]} (``ret_sum``:
+        the seat's summed rewards; skipped rows are zeros); ``out`` reuses such a dict.  No host synchronisation;
+        capturable into a graph."""
+        A, R = _playout_args(playouts, candidates, self.B, self.device)
+        if agent not in ("random", "avoid"):
+            raise ValueError("agent must be 'random' or 'avoid', got %r" % (agent,))
+        if until not in ("end", "seat_done"):
+            raise ValueError("until must be 'end' or 'seat_done', got %r" % (until,))
+        if isinstance(noise, bool) or not isinstance(noise, (int, float)) or not 0.0 <= float(noise) <= 1.0:
+            raise ValueError("noise must be a number in [0, 1], got %r" % (noise,))
+        if isinstance(max_steps, bool) or not isinstance(max_steps, int) or not 0 <= max_steps <= 65535:
+            raise ValueError("max_steps must be an int in [0, 65535], got %r" % (max_steps,))
+        if seat is not None:
+            if not isinstance(seat, torch.Tensor):
+                raise ValueError("seat must be an int8 tensor of shape (%d,)" % self.B)
+            _want(seat, torch.int8, (self.B,), self.device, "seat")
+        out = _tron_playout_out(out, self.B, A, self.P, self.device)
+        flags = (_native.CRL_PLAYOUT_AVOID if agent == "avoid" else 0) | \
+                (_native.CRL_PLAYOUT_UNTIL_SEAT_DONE if until == "seat_done" else 0)
+        with _DevGuard(self.device):
+            check(self._lib.crl_tron_playout(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
+                                             _ptr(self.board), _ptr(self.heads), _ptr(self.dirs), _ptr(self.deaths),
+                                             _ptr(self.tcount), _ptr(seat), _ptr(candidates), A, R, float(noise), max_steps,
+                                             _ptr(out["wins"]), _ptr(out["played"]), _ptr(out["len_sum"]),
+                                             _ptr(out["ret_sum"]), flags, _stream()), "crl_tron_playout")
+        return out
+
+    def flat_mc_action(self, playouts: int, seed: int = 0, agent: str = "random", noise: float = 0.1,
+                       seat: Optional[torch.Tensor] = None, until: str = "end", max_steps: int = 0,
+                       out: Optional[dict] = None) -> torch.Tensor:
+        """Flat Monte Carlo for the seat in every game: ``playout`` on the three first actions [0, 1, 2], value = the mean
+        ``ret_sum``, the best action (ties: the lowest) as int64 [B] in {0, 1, 2} for ``step_single``; -1 where every row
+        was skipped (the seat is dead or the game is over).  ``out``: the playout dict to reuse.  No host
+        synchronisation; capturable."""
+        _playout_args(playouts, None, self.B, self.device)
+        cands = getattr(self, "_moves3", None)
+        if cands is None:
+            cands = torch.arange(3, dtype=torch.int32, device=self.device).expand(self.B, 3).contiguous()
+            self._moves3 = cands
+        o = self.playout(playouts, cands, seed, agent, noise, seat, until, max_steps, out)
+        # (returns go below -1: the pick compares mean returns shifted above _flat_mc_pick's -1 for unplayed rows)
+        mean = o["ret_sum"].to(torch.float64) / float(playouts)
+        return _flat_mc_pick(mean - mean.amin(dim=1, keepdim=True), o["played"], cands)
 
     # -- T fused steps with every player on the avoid agent, auto-reset
     def rollout_avoid(self, steps: int, seed: int = 0, noise: float = 0.1):

@@ -4906,6 +4906,232 @@ tron_step_single_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_t 
     }
 }
 
+// ---- batched playouts (crl_tron_playout; the contract is in include/colosseum_hip.h).  One lane per playout, the flat
+// lane index i = (b * A + a) * R + r (r fastest), S lanes per wave (64, or 32 on boards above 128x128).  A playout never
+// writes a board back, and a step needs only occupancy plus the heads (a cell is occupied iff its value is > 0; the owner
+// of a hit cell matters only for the head-on rule, and the player whose head is there IS that owner by the invariant
+// board[heads[p]] == p + 1).  So each lane keeps a private occupancy bitboard in LDS, built from the byte board with
+// aligned dword loads (every dword loaded holds at least one byte of the row), word w of slot s at w * nslots + s: lanes
+// probing the same word index hit distinct banks.  Each step: the decisions (random digits, or the avoid agent's three
+// clamped probes of the pre-step bitboard), then the reference's sequential order on registers (CyTronGrid.pyx:15-62).
+// Outcomes are summed per row segment of the wave by shuffles (segmented suffix sums): one store per whole row, else one
+// integer atomic per output word onto the zeros the launcher wrote.
+__device__ __forceinline__ uint32_t tron_occ_nibble(const uint32_t x)
+{
+    // bit 7 of each byte: the byte is in 1..127 (> 0 as int8); then bits 7, 15, 23, 31 -> bits 0..3
+    const uint32_t m = ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) & ~x & 0x80808080u;
+    return (((m >> 7) * 0x00204081u) >> 21) & 0xfu;
+}
+
+template <int P, bool AVOID>
+__global__ void __launch_bounds__(256)
+tron_playout_kernel(const TronGeom g, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
+                    const uint64_t first_env_id, const int8_t *__restrict__ board, const int16_t *__restrict__ heads,
+                    const int8_t *__restrict__ dirs, const int8_t *__restrict__ deaths, const uint32_t *__restrict__ tcount,
+                    const int8_t *__restrict__ seat_in, const int32_t *__restrict__ cand, const int A, const int R,
+                    const uint64_t thr, const int max_steps, const int until_seat_done, const int S, const int nwords,
+                    const uint64_t n_lanes, uint32_t *__restrict__ wins, uint32_t *__restrict__ played,
+                    uint32_t *__restrict__ len_sum, int32_t *__restrict__ ret_sum)
+{
+    extern __shared__ uint32_t s_bits[];
+    const int N = g.N, NN = g.NN;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wpb = blockDim.x >> 6;                       // waves per workgroup
+    const int nslots = (int)wpb * S;
+    const int slot = (int)(threadIdx.x >> 6) * S + (int)lane;  // (used only by lanes < S)
+    const uint64_t stride = (uint64_t)gridDim.x * wpb * (uint32_t)S;
+    for (uint64_t wave0 = ((uint64_t)blockIdx.x * wpb + (threadIdx.x >> 6)) * (uint32_t)S; wave0 < n_lanes; wave0 += stride) {
+        // (b, a, r) of this lane: one 64-bit division per wave (wave-uniform), then 32-bit ones per lane
+        const uint64_t row0 = wave0 / (uint32_t)R;
+        const uint32_t r0 = (uint32_t)(wave0 - row0 * (uint32_t)R);
+        const uint32_t q = (r0 + lane) / (uint32_t)R;
+        const uint64_t row = row0 + q;
+        const uint32_t r = r0 + lane - q * (uint32_t)R;
+        const bool live = lane < (uint32_t)S && wave0 + lane < n_lanes;
+        const int64_t b = live ? (int64_t)(row / (uint32_t)A) : 0;
+        const uint32_t a = (uint32_t)(row - (uint64_t)b * (uint32_t)A);
+        bool play = false;
+        int sp = 0, len = 0, sa = 0, wm = 0;
+        if (live) {
+            sp = seat_in ? (int)seat_in[b] : 0;
+            int h[P], x[P], y[P], d[P];
+            uint32_t alive = 0;
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                h[p] = min(max((int)heads[p * B + b], 0), NN - 1);    // (a broken state: wrong results, no wild access)
+                y[p] = (int)__umulhi((uint32_t)h[p], g.inv_n);
+                x[p] = h[p] - y[p] * N;
+                d[p] = dirs[p * B + b] & 3;
+                alive |= (deaths[p * B + b] == 0 ? 1u : 0u) << p;
+            }
+            play = (unsigned)sp < (unsigned)P && ((alive >> sp) & 1u) && (P == 1 || __popc(alive) >= 2);
+            int first = -1;
+            if (play && cand != nullptr) {                      // the seat's first action: 0, 1, 2, else the row is skipped
+                first = cand[b * A + a];
+                play = (unsigned)first <= 2u;
+            }
+            if (play) {
+                // ---- the occupancy bitboard of position b
+                const uintptr_t addr = reinterpret_cast<uintptr_t>(board + b * NN);
+                const uint32_t off = (uint32_t)(addr & 3u);
+                const uint32_t *src = reinterpret_cast<const uint32_t *>(addr - off);
+                const int nd = (NN + (int)off + 3) >> 2;
+                uint64_t acc = tron_occ_nibble(src[0]) >> off;
+                int fill = 4 - (int)off, w = 0;
+                for (int i = 1; i < nd; ++i) {
+                    acc |= (uint64_t)tron_occ_nibble(src[i]) << fill;
+                    fill += 4;
+                    if (fill >= 32) {
+                        CRL_BOUNDS_LT(w, nwords, 160);
+                        s_bits[w * nslots + slot] = (uint32_t)acc;
+                        ++w;
+                        acc >>= 32;
+                        fill -= 32;
+                    }
+                }
+                if (w < nwords) s_bits[w * nslots + slot] = (uint32_t)acc;
+                // ---- the playout
+                const uint32_t gid = (uint32_t)(first_env_id + (uint64_t)b), c2 = (a << 16) | r;
+                uint32_t c = tcount ? tcount[b] : 0u;
+                uint32_t wa0 = 0u, wa1 = 0u, wa2 = 0u, wa3 = 0u, wb0 = 0u, wb1 = 0u, wb2 = 0u, wb3 = 0u;   // Philox blocks, quads 0 / 1
+                for (;;) {
+                    int code[P];
+                    if constexpr (AVOID) {
+#pragma unroll
+                        for (int p = 0; p < P; ++p) {
+                            code[p] = 0;
+                            if ((alive >> p) & 1u) {
+                                const int c_f = tron_avoid_cell(N, x[p], y[p], d[p]);
+                                const int c_r = tron_avoid_cell(N, x[p], y[p], d[p] + 1);
+                                const int c_l = tron_avoid_cell(N, x[p], y[p], d[p] + 3);
+                                CRL_BOUNDS_LT(c_f, NN, 161);
+                                CRL_BOUNDS_LT(c_r, NN, 162);
+                                CRL_BOUNDS_LT(c_l, NN, 163);
+                                const int o_f = (s_bits[(c_f >> 5) * nslots + slot] >> (c_f & 31)) & 1;
+                                const int o_r = (s_bits[(c_r >> 5) * nslots + slot] >> (c_r & 31)) & 1;
+                                const int o_l = (s_bits[(c_l >> 5) * nslots + slot] >> (c_l & 31)) & 1;
+                                const philox_out wv = philox4x32_10(gid, c, c2, CRL_TAG_TRON_AVOID_PLAYOUT | (uint32_t)p, seed_lo, seed_hi);
+                                const uint32_t a3 = __umulhi(wv.w[1], 3u);
+                                const bool left_first = (wv.w[2] >> 31) != 0u;
+                                const bool first_free = (left_first ? o_l : o_r) == 0;
+                                const int side = (left_first == first_free) ? 3 : 1;
+                                code[p] = ((uint64_t)wv.w[0] < thr) ? (int)(a3 + (a3 >> 1)) : (o_f == 0 ? 0 : side);
+                            }
+                        }
+                    } else {
+                        if (len == 0 || (c & 7u) == 0u) {
+                            const philox_out wv = philox4x32_10(gid, c >> 3, c2, CRL_TAG_TRON_PLAYOUT, seed_lo, seed_hi);
+                            wa0 = wv.w[0]; wa1 = wv.w[1]; wa2 = wv.w[2]; wa3 = wv.w[3];
+                            if constexpr (P > 4) {
+                                const philox_out wu = philox4x32_10(gid, c >> 3, c2, CRL_TAG_TRON_PLAYOUT | 1u, seed_lo, seed_hi);
+                                wb0 = wu.w[0]; wb1 = wu.w[1]; wb2 = wu.w[2]; wb3 = wu.w[3];
+                            }
+                        }
+                        const uint32_t sel = (c & 7u) >> 1;
+                        const uint32_t word_a = sel == 0u ? wa0 : sel == 1u ? wa1 : sel == 2u ? wa2 : wa3;
+                        const uint32_t word_b = sel == 0u ? wb0 : sel == 1u ? wb1 : sel == 2u ? wb2 : wb3;
+#pragma unroll
+                        for (int p = 0; p < P; ++p) {
+                            constexpr uint32_t kPow3[8] = {1u, 3u, 9u, 27u, 81u, 243u, 729u, 2187u};
+                            const uint32_t v = (p < 4 ? word_a : word_b) * ((c & 1u) ? kPow3[4 + (p & 3)] : kPow3[p & 3]);
+                            const uint32_t a3 = __umulhi(v, 3u);
+                            code[p] = (int)(a3 + (a3 >> 1));
+                        }
+                    }
+                    if (len == 0 && first >= 0) {               // step 0: the seat plays its candidate, no draw
+#pragma unroll
+                        for (int p = 0; p < P; ++p) code[p] = (p == sp) ? first + (first >> 1) : code[p];
+                    }
+                    // ---- the step, in the reference's sequential order; straight-line (selects, one LDS read and
+                    //      write per player: the slot is private, so rewriting an unchanged word is harmless)
+#pragma unroll
+                    for (int i = 0; i < P; ++i) {
+                        const bool run = (alive >> i) & 1u;     // :16 (may have been killed head-on by j < i)
+                        const int dir = (d[i] + code[i]) & 3;
+                        d[i] = run ? dir : d[i];                // :44
+                        const int nx = x[i] + (dir == 1) - (dir == 3);
+                        const int ny = y[i] + (dir == 2) - (dir == 0);
+                        const bool oob = (unsigned)nx >= (unsigned)N || (unsigned)ny >= (unsigned)N;
+                        const int cell = oob ? h[i] : ny * N + nx;
+                        CRL_BOUNDS_LT(cell, NN, 164);
+                        const int wi = (cell >> 5) * nslots + slot;
+                        const uint32_t word = s_bits[wi], bit = 1u << (cell & 31);
+                        const bool occupied = (word & bit) != 0u;
+                        const bool crash = run & !oob & occupied;   // :51-57: I die; the head-on owner dies too
+                        const bool moved = run & !oob & !occupied;  // :60-62
+                        alive &= ~((uint32_t)(run & (oob | occupied)) << i);   // (:47-48 for oob)
+#pragma unroll
+                        for (int o = 0; o < P; ++o)
+                            if (o != i) alive &= ~((uint32_t)(crash & (h[o] == cell)) << o);
+                        s_bits[wi] = moved ? (word | bit) : word;
+                        h[i] = moved ? cell : h[i];
+                        x[i] = moved ? nx : x[i];
+                        y[i] = moved ? ny : y[i];
+                    }
+                    len += 1;
+                    const bool seat_alive = (alive >> sp) & 1u;
+                    sa += seat_alive ? 1 : 0;
+                    if (__popc(alive) <= 1) { wm = (int)alive; break; }     // TronGridEnvironment.py:309-321
+                    if (until_seat_done && !seat_alive) break;
+                    if (len == max_steps) break;                // (max_steps = 0: no cap)
+                    c += 1u;
+                }
+            }
+        }
+        // ---- per row segment of this wave: the lanes from a head (r == 0, or lane 0) to the next head (lane S ends the last).
+        // Segmented suffix sums by shuffles (six steps): the head lane ends with its segment's totals.  The counts (at most
+        // 64 per segment) travel as 8-bit fields, four per word: played, seat won, wins of each player.
+        const unsigned long long heads_m = __ballot((live && (lane == 0u || r == 0u)) || lane == (uint32_t)S);
+        const unsigned long long above = lane == 63u ? 0ull : heads_m & (~0ull << (lane + 1u));
+        const uint32_t end = above ? (uint32_t)__builtin_ctzll(above) : 64u;
+        const bool head = live && ((heads_m >> lane) & 1ull);
+        const bool whole = r == 0u && end - lane == (uint32_t)R;           // the row has no lane in another wave
+        constexpr int kWords = (P + 2 + 3) / 4;
+        uint32_t cw[kWords];
+#pragma unroll
+        for (int k = 0; k < kWords; ++k) cw[k] = 0u;
+        cw[0] = play ? 1u | ((uint32_t)((wm >> (sp & 7)) & 1) << 8) : 0u;
+#pragma unroll
+        for (int p = 0; p < P; ++p) cw[(p + 2) >> 2] |= (play ? (uint32_t)((wm >> p) & 1) : 0u) << (((p + 2) & 3) * 8);
+        uint32_t plies = play ? (uint32_t)len : 0u, alive_steps = play ? (uint32_t)sa : 0u;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const bool take = lane + (uint32_t)off < end;
+            const uint32_t t0 = __shfl_down(plies, off), t1 = __shfl_down(alive_steps, off);
+            plies += take ? t0 : 0u;
+            alive_steps += take ? t1 : 0u;
+#pragma unroll
+            for (int k = 0; k < kWords; ++k) {
+                const uint32_t t = __shfl_down(cw[k], off);
+                cw[k] += take ? t : 0u;
+            }
+        }
+        uint32_t cnt[P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) cnt[p] = (cw[(p + 2) >> 2] >> (((p + 2) & 3) * 8)) & 0xffu;
+        const uint32_t n_played = cw[0] & 0xffu, seat_wins = (cw[0] >> 8) & 0xffu;
+        // the seat's rewards: +1 per step it ends alive, -1 per step it ends dead, +9 more at a terminal step it survives
+        const int32_t ret = (int32_t)(2u * alive_steps - plies + 9u * seat_wins);
+        if (head) {
+            if (whole) {
+#pragma unroll
+                for (int p = 0; p < P; ++p) wins[row * P + p] = cnt[p];
+                played[row] = n_played;
+                len_sum[row] = plies;
+                ret_sum[row] = ret;
+            } else if (n_played) {
+#pragma unroll
+                for (int p = 0; p < P; ++p)
+                    if (cnt[p]) atomicAdd(&wins[row * P + p], cnt[p]);
+                atomicAdd(&played[row], n_played);
+                atomicAdd(&len_sum[row], plies);
+                atomicAdd(&ret_sum[row], ret);
+            }
+        }
+    }
+}
+
+
 } // namespace
 
 #define TRON_DISPATCH_P(P_, CALL)          \
@@ -5362,6 +5588,59 @@ int crl_tron_step_single(const crl_ctx *ctx, int64_t B, int8_t *board, int16_t *
         hipLaunchKernelGGL((tron_step_single_kernel<PP>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, cfg, g, B,
                            board, heads, dirs, deaths, actions, learner_action, reward, done, terminal);
     });
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_tron_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                     const int8_t *board, const int16_t *heads, const int8_t *dirs, const int8_t *deaths,
+                     const uint32_t *tcount, const int8_t *seat, const int32_t *cand, int A, int R,
+                     double noise, int max_steps,
+                     uint32_t *wins, uint32_t *played, uint32_t *len_sum, int32_t *ret_sum,
+                     uint32_t flags, void *stream)
+{
+    TRON_CTX_CHECK("crl_tron_playout");
+    CRL_REQUIRE(board && heads && dirs && deaths, "crl_tron_playout: NULL state pointer");
+    CRL_REQUIRE(wins && played && len_sum && ret_sum, "crl_tron_playout: NULL output pointer");
+    CRL_REQUIRE(R >= 1 && R <= 65535, "crl_tron_playout: R=%d out of range 1..65535", R);
+    CRL_REQUIRE(A >= 1 && A <= 65535, "crl_tron_playout: A=%d out of range 1..65535", A);
+    CRL_REQUIRE(cand != nullptr || A == 1, "crl_tron_playout: A=%d with cand == NULL (must be 1)", A);
+    CRL_REQUIRE(noise >= 0.0 && noise <= 1.0, "crl_tron_playout: noise=%g not in [0, 1]", noise);
+    CRL_REQUIRE(max_steps >= 0 && max_steps <= 65535, "crl_tron_playout: max_steps=%d out of range 0..65535", max_steps);
+    CRL_REQUIRE((flags & ~(CRL_PLAYOUT_AVOID | CRL_PLAYOUT_UNTIL_SEAT_DONE)) == 0u, "crl_tron_playout: unknown flags 0x%x", flags);
+    const crl_tron_cfg &cfg = ctx->tron;
+    const TronGeom g = geom_of(cfg);
+    const uint64_t thr = tron_avoid_threshold(noise);
+    const int nwords = (g.NN + 31) >> 5;
+    // lanes per wave and waves per workgroup: every lane's bitboard in LDS, at most 128 KB per workgroup (N <= 181)
+    const int S = nwords <= 512 ? 64 : 32;
+    const int threads = nwords <= 64 ? 256 : 64;
+    const size_t lds = (size_t)(threads / 64) * S * nwords * sizeof(uint32_t);
+    const uint64_t rows = (uint64_t)B * (uint64_t)A, n_lanes = rows * (uint64_t)R;
+    hipStream_t s = (hipStream_t)stream;
+    // rows that span waves are summed by atomics: every output starts from zero
+    CRL_HIP(hipMemsetAsync(wins, 0, rows * cfg.P * sizeof(uint32_t), s));
+    CRL_HIP(hipMemsetAsync(played, 0, rows * sizeof(uint32_t), s));
+    CRL_HIP(hipMemsetAsync(len_sum, 0, rows * sizeof(uint32_t), s));
+    CRL_HIP(hipMemsetAsync(ret_sum, 0, rows * sizeof(int32_t), s));
+    const uint64_t per_block = (uint64_t)(threads / 64) * S;
+    const uint64_t want = (n_lanes + per_block - 1) / per_block;   // a grid-stride loop past 2^20 workgroups
+    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));
+    const int until = (flags & CRL_PLAYOUT_UNTIL_SEAT_DONE) ? 1 : 0;
+#define TRON_PLAYOUT_LAUNCH(AV_)                                                                                          \
+    do {                                                                                                                  \
+        const void *fn = reinterpret_cast<const void *>(&tron_playout_kernel<PP, AV_>);                                   \
+        if (lds > 64 * 1024) CRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
+        hipLaunchKernelGGL((tron_playout_kernel<PP, AV_>), dim3(blocks), dim3(threads), lds, s, g, B, (uint32_t)seed,      \
+                           (uint32_t)(seed >> 32), first_env_id, board, heads, dirs, deaths, tcount, seat, cand, A, R, thr, \
+                           max_steps, until, S, nwords, n_lanes, wins, played, len_sum, ret_sum);                         \
+    } while (0)
+    if (flags & CRL_PLAYOUT_AVOID) {
+        TRON_DISPATCH_P(cfg.P, TRON_PLAYOUT_LAUNCH(true));
+    } else {
+        TRON_DISPATCH_P(cfg.P, TRON_PLAYOUT_LAUNCH(false));
+    }
+#undef TRON_PLAYOUT_LAUNCH
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }

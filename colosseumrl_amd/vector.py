@@ -6,7 +6,7 @@ The reference exposes single games to RL libraries through ``RllibWrapper`` / ``
 reset/step contract for B games at once, with tensors instead of dicts of Python objects: actions in,
 observations / rewards / dones out, everything staying on the GPU, games auto-resetting when they end.
 """
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -88,6 +88,14 @@ class TronSinglePlayerVectorEnv:
                                               _ptr(self._actions), _ptr(action), _ptr(self.reward), _ptr(self.done),
                                               _ptr(self.terminal), _stream()), "crl_tron_step_single")
         return self.observation(), self.reward, self.done, {"terminal": self.terminal}
+
+    def flat_mc_action(self, playouts: int, seed: int = 1, max_steps: int = 0, out: Optional[dict] = None) -> torch.Tensor:
+        """Flat Monte Carlo for the learner: ``TronBatch.flat_mc_action`` with this env's own setting -- every player on
+        the avoid agent with the env's noise, seat 0, each playout ending with the learner's episode
+        (``until="seat_done"``), so a row's mean ``ret_sum`` is the expected episode return from here after that action.
+        ``seed`` keys the playouts (their draws never coincide with the env's own).  -> int64 [B] in {0, 1, 2}.  No host
+        synchronisation; capturable."""
+        return self.batch.flat_mc_action(playouts, seed, "avoid", self.noise, None, "seat_done", max_steps, out)
 
 
 class TicTacToeVectorEnv:

@@ -82,7 +82,8 @@ const char *crl_last_error(void);
  * 112: crl_tron_sample_avoid / crl_tron_rollout_avoid (the scripted avoid agent), crl_tron_step_single.
  * 113: crl_ttt_step_single / crl_blokus_step_single (one learner against the random agent), CRL_STEP_RANK_ACTION.
  *      crl_ttt_playout / crl_blokus_playout (batched random playouts) were added under 113: new entries and new Philox
- *      tags only, no existing struct, argument list or RNG contract changed. */
+ *      tags only, no existing struct, argument list or RNG contract changed.  So was crl_tron_playout (with
+ *      CRL_PLAYOUT_AVOID / CRL_PLAYOUT_UNTIL_SEAT_DONE), on the same terms. */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -279,6 +280,53 @@ int crl_tron_rollout_avoid(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_
 int crl_tron_step_single(const crl_ctx *ctx, int64_t B, int8_t *board, int16_t *heads, int8_t *dirs, int8_t *deaths,
                          const int8_t *actions, const int64_t *learner_action, int8_t *reward, uint8_t *done, uint8_t *terminal,
                          void *stream);
+
+/* ------------------------------------------------------------------ batched playouts (Tron)
+ * crl_tron_playout: from each of B positions, play R games to their end for a seat and count the outcomes -- the
+ * evaluation primitive of flat Monte Carlo (the Tron counterpart of crl_ttt_playout / crl_blokus_playout below).  One
+ * launch, no host sync.
+ * Inputs are read only: board / heads / dirs / deaths have crl_tron_step's layouts and are never written.  tcount uint32
+ * [B] is the counter base (NULL means 0).  seat int8 [B] is the player evaluated (NULL means player 0, the learner of
+ * TronSinglePlayerVectorEnv).  cand int32 [B][A] is the seat's first action in crl_tron_step_single's encoding (0 forward,
+ * 1 right, 2 left); any other value (-1 padding included) skips its row.  cand == NULL requires A == 1: the position is then
+ * evaluated as it stands (no forced first action, a = 0 below).
+ * Playout r = 0 .. R-1 of row (b, a), on a private copy of position b: step k = 0, 1, ... has counter c = tcount[b] + k
+ * (uint32).  At step 0 the seat plays cand[b][a] and uses no draw; every other player draws at c.  At every later step every
+ * live player draws, the seat included.  Each step is exactly crl_tron_step without reset (the reference's sequential order
+ * and head-on rule).  The playout stops after the first step crl_tron_step reports terminal (alive <= 1); with
+ * CRL_PLAYOUT_UNTIL_SEAT_DONE also after the step in which the seat dies (crl_tron_step_single's `done`); with max_steps > 0
+ * also after max_steps steps (0: no cap; every game ends within N*N steps).
+ * Agent: the random agent; with CRL_PLAYOUT_AVOID the avoid agent with `noise` (all players decide on the pre-step board).
+ * Random stream, g = low 32 bits of first_env_id + b, p the player:
+ *   random  W = Philox4x32-10(ctr = {g, c >> 3, (a << 16) | r, 0x54700000 | (p >> 2)}, key = {seed lo, seed hi}), then
+ *           crl_tron_rollout's digit rule with j = c & 7 and p & 3;
+ *   avoid   W = Philox4x32-10(ctr = {g, c, (a << 16) | r, 0x54610000 | p}, key = {seed lo, seed hi}), then
+ *           crl_tron_sample_avoid's rule (threshold, clamped probes, side bit).
+ * The tags differ from every other stream's, so a playout never sees an env's real future draws.
+ * Outputs, every row written (overwritten, never accumulated; a skipped row holds zeros):
+ *   played  uint32 [B][A]     R, or 0 when the row is skipped;
+ *   wins    uint32 [B][A][P]  playouts whose last step was terminal with bit p set in the winners mask (a capped or
+ *                             seat-done stop that is not terminal counts for nobody);
+ *   len_sum uint32 [B][A]     steps played, step 0 included;
+ *   ret_sum int32  [B][A]     the seat's crl_tron_step rewards summed over the steps played (with UNTIL_SEAT_DONE: the
+ *                             TronSinglePlayerVectorEnv episode return from that state and first action).
+ * Every row of position b is skipped when the seat is outside [0, P), the seat is dead (deaths[seat][b] != 0), or P >= 2 and
+ * fewer than two players are alive.  With P = 1 every playout is one terminal step.
+ * Argument checks (CRL_EINVAL, with a crl_last_error message, before any device work): NULL state / output pointers, B out
+ * of range, R or A outside [1, 65535], A != 1 with cand == NULL, noise outside [0, 1] or NaN, max_steps outside [0, 65535],
+ * flags other than the two below.  Lanes are indexed with 64-bit arithmetic: B * A * R may pass 2^31.
+ * Precondition: crl_tron_check_state's invariant, cells holding 0..P; a broken state gives wrong results, never a wild
+ * access.  One lane per playout on a private occupancy bitboard in LDS (a cell is occupied iff its value is > 0; the owner
+ * of a hit head is the player whose head is there); outcomes are summed per row inside the wave (shuffles) before one store
+ * or integer atomic per row segment and output word, so the results do not depend on the order of the waves. */
+#define CRL_PLAYOUT_AVOID           1u   /* crl_tron_playout: every player on the avoid agent (default: the random agent) */
+#define CRL_PLAYOUT_UNTIL_SEAT_DONE 2u   /* crl_tron_playout: also stop after the step in which the seat dies */
+int crl_tron_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                     const int8_t *board, const int16_t *heads, const int8_t *dirs, const int8_t *deaths,
+                     const uint32_t *tcount, const int8_t *seat, const int32_t *cand, int A, int R,
+                     double noise, int max_steps,
+                     uint32_t *wins, uint32_t *played, uint32_t *len_sum, int32_t *ret_sum,
+                     uint32_t flags, void *stream);
 
 /* replaces CyTronGrid.relative_player_inplace (CyTronGrid.pyx:65-71) + the rolls of
  * TronGridEnvironment.state_to_observation (TronGridEnvironment.py:385-405), fully observable branch.

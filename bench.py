@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched random-agent rollout (BASELINE.json metric) + the evidence around it.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A PLAIN run (no --full) does only what the headline needs: set-up, the W + K region, the --dump-outputs files, the line.
+--full adds the evidence around it (OUTPUT below); the headline region and `value` are the same either way.
 
 HEADLINE (the contract line).  One "step" = one env-step of EVERY game of the batch (Tron: all live players move).
 The workload is BASELINE.json configs[1]: 4-player 20x20 Tron, 65,536 games per GPU, uniform random agent drawn from
@@ -21,8 +24,10 @@ script starts `python -m torch.distributed.run --nproc-per-node N` on itself as 
 touched the GPU, passes the child's stdout through and exits with its code; with fewer than N devices visible it exits
 2 and says so on stdout.  It never measures fewer GPUs than it was asked for.
 
-OUTPUT.  stdout carries exactly ONE line: the compact contract object (< 4 KB: the contract fields, `roofline`,
-`cpu_baseline`, `summary`).  Everything else (N = 1, unless --only-headline) goes to bench_detail.json next to this
+OUTPUT.  stdout carries exactly ONE line: the compact contract object (< 4 KB: the contract fields and `config`; with
+--full also `roofline`, `cpu_baseline`, `summary`, and at N > 1 `collective`: the cost of the collective, timed in further
+regions).  A plain run writes no detail file.  With --full everything else (N = 1, unless --only-headline: then the
+roofline, box probe and CPU baseline of the headline workload only) goes to bench_detail.json next to this
 script (and gpurun_out/bench_detail.json when that directory exists) and, as one line, to stderr:
   roofline      the contract's formula: `achieved` = SURVEY 8(d)'s algorithmic bytes per env-step x the env-steps of one
                 launch / the launch's duration (HIP events attached to the dispatch; the marker-event figure beside it),
@@ -434,6 +439,11 @@ class Plumbing:
             self.dist.barrier()
             self.sync()
 
+    def close(self):
+        if self.use_dist and self.dist.is_initialized():
+            self.dist.barrier()
+            self.dist.destroy_process_group()
+
     def max_over_ranks(self, values):
         if not self.use_dist:
             return [float(v) for v in values]
@@ -595,8 +605,17 @@ def write_outputs(path, arrays):
         np.save(os.path.join(path, name + ".npy"), a)
 
 
+def gather_description(pl, rows):
+    """`config.gather` of the line: the collective inside the timed region, if any, and the size of the rows it ships."""
+    if not pl.use_dist:
+        return "none (single process, no process group)"
+    return "rccl %s, %d-byte rows" % ("gather to rank 0 (torch.distributed.gather)" if COLLECTIVE == "gather" else "all_gather_into_tensor",
+                                      int(rows.shape[-1] * rows.element_size()))
+
+
 def contract_record(workload, batch, world, steps, warmup, chunk, meas, launch_s, launch_source, copy_gbs, gather_desc):
-    """The contract fields + `roofline` of one measured region (`meas` = contract_region's result on rank 0)."""
+    """The contract fields + `roofline` of one measured region (`meas` = contract_region's result on rank 0); without a
+    launch time (`launch_s` None: a plain run times no launch on its own) the record has no `roofline`."""
     game = WORKLOADS[workload][0]
     mean_len, n_ep = mean_episode_len(meas["rows"])
     steps_per_launch = min(chunk, steps)
@@ -613,8 +632,10 @@ def contract_record(workload, batch, world, steps, warmup, chunk, meas, launch_s
                    "gather": gather_desc,
                    "device_warmup": "none: `value` is the first W + K region of the process"},
         "timed_region_ms": elapsed * 1e3,
-        "roofline": roofline(workload, batch, steps_per_launch, launch_s, mean_len, copy_gbs, launch_source),
     }
+    if launch_s is None:
+        return rec
+    rec["roofline"] = roofline(workload, batch, steps_per_launch, launch_s, mean_len, copy_gbs, launch_source)
     if steps % steps_per_launch:
         # the roofline describes the dominant (first) launch shape; the mean launch time is an approximation then
         rec["roofline"]["note"] = "launches of the timed region are not equal-sized; launch_ms is their mean"
@@ -1105,11 +1126,14 @@ LINE_LIMIT = 4096
 def compact_line(full):
     """The ONE stdout line: the contract fields, `config`, `roofline` and `cpu_baseline` as scalars, `summary` -- cut down
     from the full record `full` (which goes to bench_detail.json).  Always below LINE_LIMIT bytes: if a summary ever
-    outgrows it, the summary's optional sections are dropped, never a contract field."""
+    outgrows it, the summary's optional sections are dropped, never a contract field.  The record of a plain run has no
+    `roofline`: its line is the contract fields + `config`."""
     line = {k: full[k] for k in CONTRACT_KEYS}
     line["value"] = _sig(full["value"], 6)
     line["ms_per_step"] = _sig(full["ms_per_step"], 6)
     line["config"] = {k: full["config"][k] for k in CONFIG_KEYS if k in full["config"]}
+    if "roofline" not in full:
+        return line
     r = dict(full["roofline"])
     r["valu_frac"] = (r.get("valu_issue") or {}).get("frac")
     if r.get("note"):
@@ -1189,13 +1213,20 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=0, help="games per GPU (default: the workload's)")
     ap.add_argument("--chunk", type=int, default=0, help="env-steps fused into one kernel launch (default: the workload's)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region, measure the evidence around it: roofline (launch timing passes, copy "
+                         "bandwidth, box issue probe), the collective's cost at N > 1, and at N = 1 warmed / seeds / "
+                         "steady_state / others / step_api / out_of_cache / dropin and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--device-warmup", action="store_true",
-                    help="with --only-headline: also run the W + K region again after ~90 ms of device warm-up (`value_warmed`; "
-                         "the full run always does).  `value` is the first W + K region of the process either way")
+                    help="with --full --only-headline: also run the W + K region again after ~90 ms of device warm-up "
+                         "(`value_warmed`; the full run always does).  `value` is the first W + K region of the process either way")
     ap.add_argument("--gather-probe", action="store_true",
-                    help="single process only: afterwards, create a one-rank RCCL group and time the region with / without the gather")
-    ap.add_argument("--only-headline", action="store_true", help="skip warmed / steady_state / seeds / others / step_api / dropin (profiling runs)")
+                    help="with --full, single process only: afterwards, create a one-rank RCCL group and time the region "
+                         "with / without the gather")
+    ap.add_argument("--only-headline", action="store_true",
+                    help="with --full: skip warmed / steady_state / seeds / others / step_api / dropin (profiling runs); "
+                         "a plain run measures the headline only anyway")
     ap.add_argument("--only-step-api", action="store_true", help="run just the per-step API section (profiling runs)")
     ap.add_argument("--only-dropin", action="store_true", help="run just the single-state drop-in latency section")
     ap.add_argument("--only-out-of-cache", action="store_true",
@@ -1302,6 +1333,8 @@ def main(argv=None):
         bad = "--steps must be >= 1 and --warmup >= 0 (got %d, %d)" % (args.steps, args.warmup)
     elif args.dump_outputs and (args.only_dropin or args.only_out_of_cache or args.only_step_api):
         bad = "--dump-outputs writes the timed rollout's outputs; --only-dropin / --only-out-of-cache / --only-step-api run none"
+    elif (args.device_warmup or args.gather_probe) and not args.full:
+        bad = "--device-warmup / --gather-probe add measurements of their own to the evidence: give --full as well"
     if bad:
         if rank == 0:
             fail(bad)
@@ -1365,9 +1398,19 @@ def main(argv=None):
     # to the dispatch).  CRL_BENCH_REGION_EVENTS=1 puts the markers back into the region (single process only).
     region_events = events if (not pl.use_dist and os.environ.get("CRL_BENCH_REGION_EVENTS") == "1") else None
 
-    # ---- THE measurement: the first W + K region of the process.  Everything below it is evidence around it.
+    # ---- THE measurement: the first W + K region of the process.  Everything below it is evidence around it (--full).
     meas = contract_region(pl, sr, args.steps, args.warmup, args.seed, args.chunk, region_events)
     dumped = timed_outputs(game, sr.stepper, meas["rows"]) if args.dump_outputs and rank == 0 else None
+    if not args.full:                                      # a plain run: the line of that region, nothing measured after it
+        if rank == 0:
+            out = contract_record(args.workload, batch, world, args.steps, args.warmup, args.chunk, meas, None, None, None,
+                                  gather_description(pl, meas["rows"]))
+            out["config"]["completion"] = pl.completion()
+            emit(out, detail_paths=())
+            if dumped is not None:
+                write_outputs(args.dump_outputs, dumped)
+        pl.close()
+        return
     kernel_s = meas["marker_s"]
     if kernel_s is None:
         kernel_s = launch_time_pass(torch, sr, args.steps, args.seed, args.chunk, events)
@@ -1389,11 +1432,8 @@ def main(argv=None):
                              "timed shape; marker events recorded around such a launch: %.2f us" % (kernel_s * 1e6))
         box_cold = box_issue_probe(torch, device)          # the box as it is right behind the contract region
         row_bytes = int(meas["rows"].shape[-1] * meas["rows"].element_size())
-        gather_desc = ("rccl %s, %d-byte rows" % ("gather to rank 0 (torch.distributed.gather)" if COLLECTIVE == "gather"
-                                                 else "all_gather_into_tensor", row_bytes)) if pl.use_dist \
-            else "none (single process, no process group)"
         out = contract_record(args.workload, batch, world, args.steps, args.warmup, args.chunk, meas, launch_s, launch_source,
-                              copy_gbs, gather_desc)
+                              copy_gbs, gather_description(pl, meas["rows"]))
         out.update({"kernel_ms": kernel_s * 1e3, "kernel_ms_dispatch": kernel_dispatch_s * 1e3 if kernel_dispatch_s else None,
                     "kernel_ms_source": ("HIP marker events around the launches of the timed region" if region_events else
                                          "HIP marker events around the launches of one more region of the same shape, right after the timed "
@@ -1479,9 +1519,7 @@ def main(argv=None):
         emit(out, name="bench_detail.json" if full_run else "bench_detail_n%d%s.json" % (world, "_rccl" if pl.use_dist else "_headline"))
         if dumped is not None:
             write_outputs(args.dump_outputs, dumped)
-    if pl.use_dist and dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
+    pl.close()
 
 
 if __name__ == "__main__":

@@ -117,6 +117,39 @@ def test_compact_line_is_small_and_carries_roofline_and_cpu_baseline(tmp_path):
         assert k in detail and k not in rec
 
 
+def test_plain_record_line_is_the_contract_fields_and_config(tmp_path):
+    """A plain run (no --full) times no launch of its own: its record has no `roofline`, and its line carries the contract
+    fields + `config` only -- the same values a --full record of the same region puts there."""
+    full = _canned_full()
+    plain = {k: full[k] for k in bench.CONTRACT_KEYS}
+    plain.update(config=dict(full["config"]), timed_region_ms=full["timed_region_ms"])
+    out = io.StringIO()
+    line = bench.emit(plain, out=out, detail_paths=())
+    assert out.getvalue() == line + "\n" and not list(tmp_path.iterdir())
+    rec = json.loads(line)
+    assert set(rec) == set(bench.CONTRACT_KEYS) | {"config"}
+    want = json.loads(bench.emit(_canned_full(), out=io.StringIO(), detail_paths=[str(tmp_path / "d.json")]))
+    assert all(rec[k] == want[k] for k in bench.CONTRACT_KEYS) and rec["config"] == want["config"]
+
+
+def test_contract_record_without_a_launch_time_has_no_roofline():
+    from colosseumrl_amd.parallel import ShardedRollout
+    pl = bench.Plumbing(torch, dist, torch.device("cpu"), False)
+    sr = ShardedRollout(LiveRowsStepper, 32)
+    meas = bench.contract_region(pl, sr, steps=20, warmup=5, seed=0, chunk=8192)
+    rec = bench.contract_record(WL, 32, 1, 20, 5, 8192, meas, None, None, None, bench.gather_description(pl, meas["rows"]))
+    assert "roofline" not in rec and rec["config"]["gather"].startswith("none")
+    assert rec["value"] == pytest.approx(32 * 20 / meas["elapsed"]) and rec["ms_per_step"] == pytest.approx(meas["elapsed"] * 1e3 / 20)
+    with_roof = bench.contract_record(WL, 32, 1, 20, 5, 8192, meas, meas["elapsed"], "test", None, "none")
+    assert with_roof["roofline"]["frac"] > 0 and {k: with_roof[k] for k in rec if k != "config"} == {k: rec[k] for k in rec if k != "config"}
+
+
+def test_bench_extra_measurements_need_full(no_gpu_context):
+    for flag in ("--device-warmup", "--gather-probe"):
+        rc, out, _ = _run_bench(["--steps", "20", "--warmup", "5", flag])
+        assert rc != 0 and "--full" in json.loads(out.strip())["error"], (flag, out)
+
+
 def test_cpu_baseline_value_is_the_best_thread_count():
     cb = bench.cpu_baseline(WL, seconds=0.4)
     tried = {k: v["value"] for k, v in cb.items() if k.startswith("threads_")}

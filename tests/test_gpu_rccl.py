@@ -106,10 +106,11 @@ def _one_json_line(stdout):
 
 
 def test_bench_driver_style_line(run_fresh):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's N = 1 command, minus the slow evidence sections):
-    stdout is ONE compact line; its episodes / mean_episode_len describe the W + K = 25 steps that were timed -- not the
-    hundreds of steps the later timing passes add to the stepper (round 3's live-buffer bug: 3.1e6 episodes, 9.25)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--only-headline",
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` (the driver's N = 1 command with the evidence of the headline
+    workload, minus the slow sections): stdout is ONE compact line; its episodes / mean_episode_len describe the W + K = 25
+    steps that were timed -- not the hundreds of steps the later timing passes add to the stepper (round 3's live-buffer
+    bug: 3.1e6 episodes, 9.25)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--only-headline",
            "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "LOCAL_RANK")}
     rc, out, err = run_fresh(cmd, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"), cwd=ROOT, timeout=600, split=True)
@@ -130,10 +131,28 @@ def test_bench_driver_style_line(run_fresh):
     assert "RCCL" not in err and "NCCL version" not in err      # the contract run creates no process group
 
 
+def test_bench_plain_run_is_the_headline_alone(run_fresh):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5`, exactly the driver's N = 1 command: ONE line with the contract fields
+    of the W + K region and nothing measured after it (no roofline, CPU baseline or summary: those are --full)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "LOCAL_RANK")}
+    rc, out, err = run_fresh(cmd, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"), cwd=ROOT, timeout=300, split=True)
+    assert rc == 0, err[-3000:]
+    rec = _one_json_line(out)
+    assert rec["metric"] == "env-steps/sec" and rec["unit"] == "env-steps/s" and rec["higher_is_better"] is True and rec["dtype"] == "int8"
+    assert rec["n_gpus"] == 1 and rec["steps"] == 20 and rec["warmup"] == 5 and rec["config"]["gather"].startswith("none")
+    assert rec["config"]["workload"] == "tron_p4_n20_b65536" and rec["config"]["launches"] == 1
+    assert 1.5e5 < rec["config"]["episodes"] <= 65536 * 25 // 2 and abs(rec["config"]["mean_episode_len"] - 8.45) < 0.1
+    assert rec["value"] == pytest.approx(65536 * 20 / (rec["ms_per_step"] * 20 * 1e-3), rel=1e-4) and rec["value"] > 1e9
+    assert "crl_stream_wait_mapped" in rec["config"]["completion"]
+    assert not {"roofline", "cpu_baseline", "summary", "collective"} & set(rec)
+
+
 def test_bench_self_launch_runs_ranks_under_rccl(run_fresh):
     """`--gpus N` without a launcher starts N ranks under torch.distributed.run as a child process (CRL_BENCH_SELF_LAUNCH=1
-    forces that path at N = 1 on this one-GPU box): one line, n_gpus = the ranks RCCL saw, the gather inside the region."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--only-headline",
+    forces that path at N = 1 on this one-GPU box): one line, n_gpus = the ranks RCCL saw, the gather inside the region;
+    with --full the collective's cost timed in further regions."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--only-headline",
            "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "LOCAL_RANK")}
     rc, out, err = run_fresh(cmd, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0", CRL_BENCH_SELF_LAUNCH="1"), cwd=ROOT, timeout=600, split=True)

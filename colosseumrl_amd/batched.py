@@ -240,8 +240,8 @@ class TronBatch(_Waitable):
 
     # -- next_state for all games; actions int8 [P, B] in {0, +1, -1}
     def step(self, actions: torch.Tensor, auto_reset: bool = False, kernel: str = "auto"):
-        """next_state of every game (``crl_tron_step``).  ``kernel``: "auto", or pin one of the two interchangeable kernels --
-        "bytes" (byte probes in HBM) / "staged" (boards read once into LDS; ignored where the board shape does not allow it)."""
+        """next_state of every game (``crl_tron_step``).  ``kernel``: "auto", "bytes" or "staged" -- all three run the one
+        kernel (byte probes in HBM); "bytes" / "staged" are accepted for callers that pinned one of the two kernels it had."""
         _want(actions, torch.int8, (self.P, self.B), self.device, "actions")
         flags = (CRL_STEP_AUTO_RESET if auto_reset else 0) | _STEP_KERNEL_FLAGS[kernel]
         with torch.cuda.device(self.device):

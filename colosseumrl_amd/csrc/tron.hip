@@ -40,8 +40,7 @@
 //   crl_tron_step_observe    23.1 / 25.9   51.0 / 47.4   120.8 / 88.9   244.4 / 168.4  480-558 / 415-472
 //   crl_tron_observe_all     21.7 / 20.6   43.7 / 38.9    98.1 / 79.0   191.9 / 149.8  385-391 / 397-448
 // observe_all: nontemporal always.  step_observe: nontemporal once the call's boards in + out (131 MB at 65,536 games,
-// where plain stores are absorbed by the 256 MiB Infinity Cache) exceed 192 MiB.  CRL_NT_STREAM=0 / 1 (A/B builds) forces
-// one form everywhere.
+// where plain stores are absorbed by the 256 MiB Infinity Cache) exceed 192 MiB.
 typedef uint32_t crl_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void crl_stream_store16(void *ptr, const uint4 v, const bool nt)
 {
@@ -51,18 +50,8 @@ __device__ __forceinline__ void crl_stream_store16(void *ptr, const uint4 v, con
 constexpr int64_t kStreamNtBytes = (int64_t)192 << 20;
 inline bool crl_stream_nt(const int64_t bytes_per_call, const bool small_default)
 {
-#ifdef CRL_NT_STREAM
-    return CRL_NT_STREAM != 0;
-#else
     return bytes_per_call > kStreamNtBytes ? true : small_default;
-#endif
 }
-#ifndef CRL_SO_HOIST
-#define CRL_SO_HOIST 1                 // tron_step_observe_kernel: the stepping lanes' player vectors are loaded ahead of the board staging (A/B switch)
-#endif
-#ifndef CRL_STEP_DEFAULT_STAGED
-#define CRL_STEP_DEFAULT_STAGED 0      // crl_tron_step's default kernel: 0 = byte probes, 1 = boards staged through LDS (A/B: profiles/r5_step_ab.json)
-#endif
 #include <type_traits>
 #include <algorithm>
 
@@ -1114,17 +1103,14 @@ __device__ unsigned long long g_quad_stamps[4096 * 4];
 #define QUAD_STAMP(i) do { } while (0)
 #endif
 
-#ifndef CRL_QUAD_WG
-#define CRL_QUAD_WG 256          /* threads per workgroup (diagnostic builds: 512 / 1024, tools/README.md) */
-#endif
 template <int RS>
-__global__ void __launch_bounds__(CRL_QUAD_WG, 1024 / CRL_QUAD_WG)
+__global__ void __launch_bounds__(256, 4)
 tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad pad, const int64_t B,
                          const uint32_t seed_lo, const uint32_t seed_hi, const uint64_t first_env_id, const int T,
                          int8_t *__restrict__ board, int16_t *__restrict__ heads, int8_t *__restrict__ dirs,
                          int8_t *__restrict__ deaths, const crl_tron_stats st)
 {
-    constexpr int kGames = CRL_QUAD_WG / 4, kWaveGames = 16;
+    constexpr int kGames = 64, kWaveGames = 16;
     constexpr int kRowDwords = RS / 4;
     constexpr uint32_t step4 = (uint32_t)((-RS) & 0xff) | (1u << 8) | ((uint32_t)RS << 16) | (0xffu << 24);
     constexpr int OB = 3;                                       // P <= 4: owners 1..4, 5 tag bits
@@ -1335,9 +1321,6 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
     const bool uni_wave = __builtin_amdgcn_ballot_w64(tc != (uint32_t)__builtin_amdgcn_readfirstlane((int)tc)) == 0ull;
     int sneg2 = __builtin_amdgcn_readfirstlane(neg2);
     uint32_t sdry2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)dry2);
-#ifdef CRL_DIAG_STALE_PROBE
-    uint32_t stale_raw = 0;
-#endif
     auto one_step = [&](auto uni_tag) {
         constexpr bool UNI = decltype(uni_tag)::value;
         const bool run = a != 0;
@@ -1355,13 +1338,7 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
         const int x1 = tq ^ tron_quad<0x39>(h), x2 = tq ^ tron_quad<0x4E>(h), x3 = tq ^ tron_quad<0x93>(h);
         const int y1 = tq ^ tron_quad<0x39>(tq), y2 = tq ^ tron_quad<0x4E>(tq);
         uint32_t near = min(min(min(min((uint32_t)x1, (uint32_t)x2), (uint32_t)x3), (uint32_t)y1), (uint32_t)y2);
-#ifdef CRL_DIAG_STALE_PROBE      /* diagnostic builds only (WRONG results): the step decides on the PREVIOUS step's probe word, so that the
-                                   probe's latency is hidden completely -- the upper bound of what a software-pipelined probe could buy */
-        asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(stale_raw), "+v"(near) : : "memory");
-        { const uint32_t t_ = raw; raw = stale_raw; stale_raw = t_; }
-#else
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(raw), "+v"(near) : : "memory");   // (near: the test runs while the probe is out)
-#endif
         // The common path, for every lane and without a branch: each player on its own (correct unless players interact).
         const uint32_t m = min(raw ^ tagbits, raw ^ 0xf8u);
         const bool dead = run & ((m - 1u) < 7u);                // :47-57
@@ -1375,14 +1352,7 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
         CRL_BOUNDS_IN(h, mine, mine + pad.stride, 102);        // ... and so does the trail store
         *(lds_u8 *)(uintptr_t)(uint32_t)h = (uint8_t)stamp;
         bool alive_now = moved;
-#if defined(CRL_DIAG_NO_SLOW)      /* diagnostic builds only (WRONG results): what the interaction path costs the common one */
-        if (false && near == 0u) {
-#elif defined(CRL_DIAG_DETECT_ONLY) /* ... and with the detection kept but nothing behind it */
-        if (__builtin_amdgcn_ballot_w64(near == 0u) != 0ull) asm volatile("s_nop 0");
-        if (false) {
-#else
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(near == 0u) != 0ull, 0)) {
-#endif
             // Rare (1.3 % of wave-steps): some quad of the wave needs the reference's order.  A fix-up AFTER the common
             // path rather than an alternative to it -- as an if / else the join cost every step a dozen scalar
             // instructions merging lane masks and a copy of the selects (13 % of the kernel's time).  The pre-step state
@@ -2667,15 +2637,13 @@ tron_rollout_bits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
 //     quad, 16 bytes per lane and step (group t & 3 of the slab, an immediate offset: no address arithmetic), so it is
 //     fresh again four steps later; an episode shorter than that rewrites it at once.
 //   * Owners are not tracked: as above the state handed back is rebuilt by REPLAYING the unfinished episode on byte
-//     slabs.  The bit slabs are dead by then, and their LDS takes the byte slabs of 16 games at a time: four turns, each
-//     laid out and copied out by the whole workgroup and replayed by one wave with a lane per game (the same
-//     tron_resolve_lds as everywhere).
+//     slabs, in tron_replay_kernel behind this one (what it needs is in tcount / tstep by then).
 template <int P, bool LARGE>
 __global__ void __launch_bounds__(256, 4)
 tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad pad, const TronBits bits, const int64_t B,
                           const uint32_t seed_lo, const uint32_t seed_hi, const uint64_t first_env_id, const int T,
                           int8_t *__restrict__ board, int16_t *__restrict__ heads, int8_t *__restrict__ dirs,
-                          int8_t *__restrict__ deaths, const crl_tron_stats st, const int split_replay)
+                          int8_t *__restrict__ deaths, const crl_tron_stats st)
 {
     static_assert(P <= 4, "one lane per player, four lanes per game");
     constexpr int kGames = 64, kWaveGames = 16;
@@ -2683,13 +2651,10 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
     constexpr int kMaxW = (((kMaxN + 2) * (kMaxN + 1) + 31) / 32 + 3) & ~3;     // pattern words, a multiple of 4
     constexpr int kSlab = (kMaxW * 4 + 127) & ~127;                             // 256 / 128 bytes
     constexpr int kGroups = kSlab / 64;                                         // 64 bytes per quad and step: 4 / 2 groups
-    constexpr int RS = LARGE ? kRowBytesLarge : kRowBytesSmall;                 // byte slabs of the replay
     static_assert(kGroups <= 4, "a slab is rewritten within four steps");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     __shared__ uint8_t act_lut[84];
     __shared__ uint32_t wall_words[kSlab / 4];
-    __shared__ uint32_t r_tc[kGames];                           // hand-over to the replay: step counter at the end,
-    __shared__ int r_steps[kGames];                             // steps to replay (-1: T steps from the incoming state)
     QUAD_STAMP(0);
     tron_fill_action_lut(act_lut);
     const int N = g.N, NN = g.NN, S = N + 1;
@@ -2878,10 +2843,8 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
     // loop and its reset branches; one compare per step turns it into one)
     int a = (pvalid && k_in == 0) ? 1 : 0;
     auto store_group = [&](const int grp) {                     // my 16 bytes of group grp of the spare slab
-#ifndef CRL_DIAG_NO_REWRITE     /* diagnostic builds only (WRONG results): what the rolling rewrite of the spare slab costs */
         CRL_BOUNDS_IN(spare_p + 64 * grp, mine, mine + bits.stride - 15, 112);   // the rolling rewrite's 16 bytes
         *(lds_u128 *)(uintptr_t)(uint32_t)(spare_p + 64 * grp) = fresh[grp];
-#endif
     };
     // When every game of the wave enters with its step counter a multiple of four (launches of 4 k steps keep it so),
     // `acts` can only run dry at the end of a four-step trip: the countdown is then kept per trip, not per step.
@@ -2909,11 +2872,7 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
         // other's bit, whichever the LDS serves first: that is an interaction, and the fix-up below sorts it out.
         uint32_t word;
         CRL_BOUNDS_IN(wa, mine, mine + bits.stride, 111);       // the probed word lies in my game's two slabs + junk words
-#ifdef CRL_QBITS_PROBE_THEN_OR     /* the round-2 form, kept for A/B builds */
-        asm volatile("ds_read_b32 %0, %1" : "=v"(word) : "v"(wa) : "memory");
-#else
         asm volatile("ds_or_rtn_b32 %0, %1, %2" : "=v"(word) : "v"(wa), "v"(bit) : "memory");
-#endif
         // right behind the probe: the LDS serves a wave's requests in order, so the store runs while the wave waits
         if constexpr (GRP < kGroups) store_group(GRP);
         const int x1 = tq ^ tron_quad<0x39>(pos), x2 = tq ^ tron_quad<0x4E>(pos), x3 = tq ^ tron_quad<0x93>(pos);
@@ -2926,25 +2885,14 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
         const int pos_was = pos;
         d8 = run ? dir8 : d8;                                   // :44 the direction is committed even if the move dies
         pos = moved ? tgt : pos;
-#ifdef CRL_QBITS_PROBE_THEN_OR
-        atomicOr((unsigned int *)(lds + ((moved ? wa : jaddr) - lds0)), bit);
-#endif
         bool alive_now = moved;
-#if defined(CRL_DIAG_NO_SLOW)      /* diagnostic builds only (WRONG results): what the interaction path costs the common one */
-        if (false && near == 0u) {
-#elif defined(CRL_DIAG_DETECT_ONLY) /* ... and with the detection kept but nothing behind it */
-        if (__builtin_amdgcn_ballot_w64(near == 0u) != 0ull) asm volatile("s_nop 0");
-        if (false) {
-#else
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(near == 0u) != 0ull, 0)) {
-#endif
             // rare fix-up: take back the bits the common path set (those cells were empty), then the quad's four players
             // in the reference's order from the pre-step state, redundantly in its four lanes
             if (moved) atomicAnd((unsigned int *)(lds + (wa - lds0)), ~bit);
             const int d = (run ? (dir8 - (int)(acts << 3)) >> 3 : d8 >> 3) & 3, dir = (dir8 >> 3) & 3;
             const int al = run ? 1 : 0;
             int oc = (word & bit) ? 1 : 0;
-#ifndef CRL_QBITS_PROBE_THEN_OR
             {   // the probe set its bit in the same operation: a player that found the bit of an EMPTY cell set by a player of
                 // its game that entered the cell in this very step must see the cell as it was before the step (had the cell
                 // been occupied before, nobody would have entered it)
@@ -2956,7 +2904,6 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
                 const int entered = (tq == t1 ? m1 : 0) | (tq == t2 ? m2 : 0) | (tq == t3 ? m3 : 0);
                 oc = entered ? 0 : oc;
             }
-#endif
             int ps[4] = {tron_quad<0x00>(pos_was), tron_quad<0x55>(pos_was), tron_quad<0xAA>(pos_was), tron_quad<0xFF>(pos_was)};
             int ds[4] = {tron_quad<0x00>(d), tron_quad<0x55>(d), tron_quad<0xAA>(d), tron_quad<0xFF>(d)};
             int al4[4] = {tron_quad<0x00>(al), tron_quad<0x55>(al), tron_quad<0xAA>(al), tron_quad<0xFF>(al)};
@@ -3058,7 +3005,7 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
         if ((T & 3) > 2) one_step(std::integral_constant<int, 2>{}, std::false_type{}, false);
     }
     QUAD_STAMP(2);
-    // ---- statistics (my player's columns; the game's by lane 0 of the quad) and the hand-over to the replay
+    // ---- statistics (my player's columns; the game's by lane 0 of the quad)
     const uint32_t n_ep = wn >> 16, wins = wn & 0xffffu;
     const int done_last = (int)((marks & 0xffffu) >> 1), done_prev = (int)(marks >> 17), last_alive = (int)(marks & 1u);
     const uint32_t tc = tc_in + (uint32_t)T;
@@ -3078,10 +3025,6 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
         if (row) { row[3 + p] = (int32_t)wc; row[3 + P + p] = rs; }
         if (pk) pk[4 + p] = (uint16_t)rs;
     }
-    if (p == 0) {
-        r_tc[slot] = tc;
-        r_steps[slot] = gvalid ? (n_ep ? (int)ts : -1) : 0;
-    }
     if (gvalid && p == 0) {
         const uint32_t ne = old_n_ep + n_ep, ls = old_len_sum + (ts_at_entry + (uint32_t)T - ts);
         st.tcount[b] = tc;
@@ -3095,45 +3038,6 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
         if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = n_ep > 0 ? lw : (int32_t)old_last_w; }
         if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(n_ep > 0 ? (uint32_t)lw : old_last_w); pk[3] = (uint16_t)ts; }
     }
-    // the replay as a kernel of its own behind this one (tron_replay_kernel: what it needs is in tcount / tstep by now)
-    if (split_replay) { QUAD_STAMP(3); return; }
-    __syncthreads();                                            // bit slabs are dead from here; byte slabs reuse the LDS
-
-    // ---- replay of the unfinished episodes on byte slabs: rebuilds board / heads / dirs / deaths (helpers above).  Four
-    // turns of 16 games: the workgroup lays out fresh boards, wave `turn` replays with a lane per game, the workgroup
-    // copies out.
-    for (int turn = 0; turn < kGames / kWaveGames; ++turn) {
-        tron_replay_fresh_slabs<RS>(lds0, pad, N, kWaveGames, (int)threadIdx.x, 256);
-        __syncthreads();
-        if ((int)threadIdx.x < kWaveGames) tron_replay_stamp_heads<P, RS>(cfg, g, lds0 + (int)threadIdx.x * pad.stride);
-        __syncthreads();
-        const int64_t gbase = (int64_t)blockIdx.x * kGames + turn * kWaveGames;     // first game of this turn
-        const int n_turn = (int)((B - gbase) < kWaveGames ? (B - gbase > 0 ? B - gbase : 0) : kWaveGames);
-        if (wave == turn) {                                     // a lane per game; lanes 16.. idle along on slabs 0..15
-            const int gl = lane & (kWaveGames - 1);
-            const bool lvalid = lane < n_turn;                  // (n_turn <= 16)
-            const int rsteps = lvalid ? r_steps[turn * kWaveGames + gl] : 0;
-            const bool from_start = rsteps >= 0;                // else: from the state the launch came in with
-            const int steps_r = lvalid ? (from_start ? rsteps : T) : 0;
-            int replay_len = steps_r;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) replay_len = max(replay_len, __shfl_xor(replay_len, off, CRL_WAVE));
-            const int bmine = lds0 + gl * pad.stride;
-            if (__builtin_amdgcn_ballot_w64(lvalid && !from_start)) {            // somebody resumes from the incoming board
-                tron_replay_copy_in<RS>(board + gbase * NN, n_turn, lds0, pad, g, lane);
-                if (lvalid && from_start) tron_replay_refresh_slab<P, RS>(cfg, g, bmine);
-            }
-            tron_replay_lane<P, RS>(cfg, g, pad, bmine, act_lut, lvalid, from_start, steps_r, replay_len,
-                                    r_tc[turn * kWaveGames + gl], (uint32_t)(first_env_id + (uint64_t)(lvalid ? gbase + gl : 0)),
-                                    seed_lo, seed_hi, gbase + gl, B, heads, dirs, deaths);
-        }
-        __syncthreads();
-        tron_replay_copy_out<RS>(board + gbase * NN, n_turn, lds0, pad, g, (int)threadIdx.x, 256);
-        __syncthreads();
-    }
-#ifdef CRL_QUAD_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     QUAD_STAMP(3);
 }
 
@@ -3853,7 +3757,7 @@ tron_step_observe_kernel(const crl_tron_cfg cfg, const TronGeom g, const uint32_
         }
         if (!actions) c_in = valid ? tcount[b] : 0u;
     };
-    if (CRL_SO_HOIST && stepper) load_players();
+    if (stepper) load_players();                                // in flight together with the board loads
     // ---- phase A: boards HBM -> LDS, coalesced 16-byte loads, up to 4 in flight per thread
     for (int base = threadIdx.x; base < total; base += 4 * 256) {
         uint4 v[4];
@@ -3874,7 +3778,6 @@ tron_step_observe_kernel(const crl_tron_cfg cfg, const TronGeom g, const uint32_
     __syncthreads();
     // ---- phase B: one lane per game plays the step on its LDS board
     if (stepper) {
-        if (!CRL_SO_HOIST) load_players();
         if (!actions) {                                         // the rollout's random agent at this game's step counter
             tron_sample_actions<P>((uint32_t)(first_env_id + (uint64_t)b), c_in, seed_lo, seed_hi, act);
             if (valid) tcount[b] = c_in + 1u;
@@ -4175,89 +4078,6 @@ tron_step_observe_flat_kernel(const crl_tron_cfg cfg, const TronGeom g, const ui
             o.w = tron_relabel4<P>(v.w, p, lut_lo[p], lut_hi[p]);
             crl_stream_store16(obs_board + (int64_t)p * plane + gofs, o, nt);
         }
-    }
-}
-
-// crl_tron_step through LDS: the workgroup reads its G boards ONCE, coalesced 16-byte loads (phase A of the fused kernel
-// above), one lane per game plays the step on the LDS copy and mirrors the <= P trail bytes to HBM, and the boards of the
-// games that were reset are rewritten by all threads.  Against tron_step_kernel's byte probes (each a 64-byte sector, ~10x
-// the algorithmic bytes: profiles/traffic_step_api.json) this streams N*N bytes per game in and probes for free.
-template <int P, int G>
-__global__ void __launch_bounds__(256)
-tron_step_staged_kernel(const crl_tron_cfg cfg, const TronGeom g, const uint32_t inv_cp, const int64_t B,
-                        int8_t *__restrict__ board, int16_t *__restrict__ heads, int8_t *__restrict__ dirs,
-                        int8_t *__restrict__ deaths, const int8_t *__restrict__ actions,
-                        int8_t *__restrict__ rewards, uint8_t *__restrict__ terminal, uint8_t *__restrict__ winners,
-                        const uint32_t flags)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int NN = g.NN, SLAB = NN + 16;                        // NN % 16 == 0: 16-byte LDS accesses stay aligned
-    const int cp = NN >> 4;                                     // 16-byte chunks per board
-    const int64_t g0 = (int64_t)blockIdx.x * G;
-    const int n_game = (int)((B - g0) < G ? (B - g0) : G);
-    const int total = n_game * cp;
-    uint8_t *rflag = lds + G * SLAB;                            // [G] this game was reset by the step
-    __shared__ int any_reset;
-    if (threadIdx.x == 0) any_reset = 0;
-    // the stepping lanes' player vectors: in flight together with the board loads
-    TronRegs<P> s;
-    int act[P], rew[P];
-    const int e = threadIdx.x;
-    const bool stepper = e < G, valid = stepper && e < n_game;
-    const int64_t b = g0 + (valid ? e : 0);
-    if (stepper) {
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            s.h[p] = valid ? heads[p * B + b] : 0;
-            s.d[p] = valid ? dirs[p * B + b] : 0;
-            s.k[p] = valid ? deaths[p * B + b] : 1;
-            act[p] = valid ? actions[p * B + b] : 0;
-        }
-    }
-    for (int base = threadIdx.x; base < total; base += 4 * 256) {
-        uint4 v[4];
-        int dst[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = base + u * 256;
-            const int cc = c < total ? c : 0;
-            const int ee = cp == 1 ? cc : (int)__umulhi((uint32_t)cc, inv_cp);
-            const int off = (cc - ee * cp) << 4;
-            dst[u] = c < total ? ee * SLAB + off : -1;
-            v[u] = *reinterpret_cast<const uint4 *>(board + (g0 + ee) * NN + off);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (dst[u] >= 0) *reinterpret_cast<uint4 *>(lds + dst[u]) = v[u];
-    }
-    __syncthreads();
-    if (stepper) {
-        tron_split_heads<P>(g, s);
-        int term, wm;
-        const DualBoard bd{lds + e * SLAB, board + b * NN CRL_CELLS_INIT(NN)};
-        tron_step_core<P>(g, bd, valid, s, act, rew, term, wm);
-        const bool do_reset = valid && term && (flags & CRL_STEP_AUTO_RESET);
-        rflag[e] = do_reset ? 1 : 0;
-        if (do_reset) { tron_regs_to_start<P>(cfg, g, s); any_reset = 1; }
-        if (valid) {
-#pragma unroll
-            for (int p = 0; p < P; ++p) {
-                rewards[p * B + b] = (int8_t)rew[p];
-                heads[p * B + b] = (int16_t)s.h[p];
-                dirs[p * B + b] = (int8_t)s.d[p];
-                deaths[p * B + b] = (int8_t)s.k[p];
-            }
-            terminal[b] = (uint8_t)term;
-            winners[b] = (uint8_t)wm;
-        }
-    }
-    if (!(flags & CRL_STEP_AUTO_RESET)) return;                 // (uniform)
-    __syncthreads();
-    if (!any_reset) return;                                     // (uniform: read after the barrier)
-    for (int c = threadIdx.x; c < total; c += 256) {            // new_state: the fresh board replaces the finished one
-        const int ee = cp == 1 ? c : (int)__umulhi((uint32_t)c, inv_cp);
-        const int off = (c - ee * cp) << 4;
-        if (rflag[ee]) *reinterpret_cast<uint4 *>(board + (g0 + ee) * NN + off) = tron_fresh_chunk16<P>(cfg, off);
     }
 }
 
@@ -5162,6 +4982,90 @@ int crl_tron_bounds(unsigned int *out4)
     return CRL_OK;
 }
 
+// opt in to > 64 KiB of dynamic LDS once per kernel instance and device (not per launch)
+template <auto Kernel>
+static int tron_opt_in_lds()
+{
+    static thread_local bool opted_in[64] = {};
+    int dev = 0;
+    CRL_HIP(hipGetDevice(&dev));
+    if (dev >= 0 && dev < 64 && opted_in[dev]) return CRL_OK;
+    CRL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsDynamic));
+    if (dev >= 0 && dev < 64) opted_in[dev] = true;
+    return CRL_OK;
+}
+
+// ---- crl_tron_rollout: which of its seven kernels plays a call ---------------------------------------------------------
+enum class TronRollout { Global, Bytes, Bits, Quad, QBits, GQuad, Pair };
+
+// The lane-per-player kernels (gquad, qbits + replay, pair, quad) keep a launch's episode, win and step counts in 14..16
+// bits: longer rollouts go out as several launches, which is the same rollout -- the state and the step counters carry over.
+constexpr int kTronLaunchMaxT = 16383;
+
+// Thresholds, from profiles/r5_shape_sweep.txt (`kernels`, 65,536 games unless said otherwise).
+// The lane-per-player kernel on boards in GLOBAL memory has no fixed cost (no copy in / out, no tags to strip, no replay):
+// a launch costs what its steps cost, 2-4.5 us each at 65,536 games of 20x20..40x40 (a probe pulls a cache line per byte).
+// So, unless a kernel is pinned, it takes:
+//  * a ONE-step launch on boards up to 20x20 (11 us against the byte-slab kernel's 13-16);
+//  * short launches on boards 21..40 wide, where the bitboard kernel's copy in + replay kernel is 45-90 us (70-170 us on
+//    boards that are not whole dwords a row): up to 18 steps (32 on the latter);
+//  * boards above 40x40, which nothing else plays out of LDS: with four players always up to 44x44, up to 200 steps up to
+//    56x56 and up to 48 steps above -- beyond that the lane-per-game global kernel, whose episode tags save the rewrite of a
+//    finished board (N * N bytes per reset) at the price of a pass over all boards at the end of the launch, and whose step
+//    gets cheaper with fewer players (a lane per game probes P cells; a lane per player idles, and shorter episodes mean
+//    more rewrites): three players up to 56 / 24 steps, one or two up to 24 / 14 (41x41, 65,536 two-player games: 2.7 us
+//    per step against this kernel's 6.8).
+// More than four players: the lane-per-game kernels.
+static bool tron_gquad_pays(const crl_tron_cfg &cfg, const int T)
+{
+    const int N = cfg.N;
+    if (N <= kLdsMaxNSmall) return T == 1;
+    if (N <= kLdsMaxNLarge) return T <= ((N & 3) == 0 ? 18 : 32);
+    if (cfg.P == 4) return N <= 44 || T <= (N <= 56 ? 200 : 48);
+    if (cfg.P == 3) return T <= (N <= 56 ? 56 : 24);
+    return T <= (N <= 56 ? 24 : 14);
+}
+// bitboards where they buy residency (boards above 20x20 fit 4x the games per CU); on small boards the byte kernel already
+// has every game resident and no replay to pay for
+constexpr int kBitsMinT = 256;
+// one or two players: two lanes per game (tron_rollout_pair_kernel) once the launch is long enough for its plainer copies
+// (65,536 games of two players, 2048 steps: 499 against 632 us at 20x20, 508 against 642 at 13x13; the pair kernel copies
+//  boards whose rows are not whole dwords byte by byte, which a launch of 256 steps earns back)
+constexpr int kPairMinTWideRows = 32, kPairMinT = 256;
+// (its slabs leave a SIMD two waves at 20x20, three from 15x15 down: with two it wins while the quad kernel's waves do not
+//  fill the chip either -- up to ~100,000 games -- and ties beyond: 262,144 games of 20x20, 512 steps: 607 against 583 us)
+constexpr size_t kPairThreeWavesLds = (size_t)160 * 1024;     // six workgroups' slabs per CU
+constexpr int64_t kPairMaxB = 98304;                            // ... or fewer games than this
+
+static TronRollout tron_pick_rollout(const crl_tron_cfg &cfg, const int64_t B, const int T, const uint32_t flags,
+                                     const bool aligned16)
+{
+    const bool small = cfg.N <= kLdsMaxNSmall;
+    const bool no_pin = !(flags & (CRL_ROLLOUT_NO_LDS | CRL_ROLLOUT_BYTES | CRL_ROLLOUT_BITS | CRL_ROLLOUT_QUAD | CRL_ROLLOUT_QBITS | CRL_ROLLOUT_PAIR));
+    const bool lds_fit = cfg.N <= kLdsMaxNLarge && aligned16;
+    if (cfg.P <= 4 && ((flags & CRL_ROLLOUT_GQUAD) || (no_pin && (tron_gquad_pays(cfg, T) || (!lds_fit && cfg.N <= kLdsMaxNLarge)))))
+        return TronRollout::GQuad;
+    if ((flags & CRL_ROLLOUT_NO_LDS) || !lds_fit) return TronRollout::Global;
+    // one lane per player, four per game: boards up to 20x20 with at most 4 players (see tron_rollout_quad_kernel); the
+    // default wherever it applies: 1.42e11 vs 1.24e11 env-steps/s for the lane-per-game byte kernel at 20x20, P = 4
+    const bool quad = small && cfg.P <= 4 && pad_of(cfg, kRowBytesSmall).sweep_rows == 1 &&
+                      !(flags & (CRL_ROLLOUT_BYTES | CRL_ROLLOUT_BITS | CRL_ROLLOUT_QBITS));
+    if (quad) {
+        const bool wide_rows = (cfg.N & 3) == 0 && cfg.N >= 8;
+        const bool pair_pays = (size_t)pad_of(cfg, kRowBytesSmall).stride * 64 * 6 <= kPairThreeWavesLds || B <= kPairMaxB;
+        if (cfg.P <= 2 && ((flags & CRL_ROLLOUT_PAIR) || (no_pin && T >= (wide_rows ? kPairMinTWideRows : kPairMinT) && pair_pays)))
+            return TronRollout::Pair;
+        return TronRollout::Quad;
+    }
+    // the same on bitboards (+ replay): boards above 20x20, where byte slabs would leave a CU with one wave per SIMD.
+    // Launches of any length: at 40x40 even a 16-step launch takes 0.15 ms against 0.25 ms on byte slabs (the replay is
+    // cheaper than moving 1,852-byte slabs through a lone wave per SIMD); tools/README.md
+    if (cfg.P <= 4 && ((flags & CRL_ROLLOUT_QBITS) || (!small && !(flags & (CRL_ROLLOUT_BYTES | CRL_ROLLOUT_BITS)))))
+        return TronRollout::QBits;
+    const bool bits = !(flags & CRL_ROLLOUT_BYTES) && ((flags & CRL_ROLLOUT_BITS) || (!small && T >= kBitsMinT));
+    return bits ? TronRollout::Bits : TronRollout::Bytes;
+}
+
 extern "C" {
 
 int crl_tron_create(int N, int P, const int16_t *start_heads, const int8_t *start_dirs, crl_ctx **out)
@@ -5226,30 +5130,11 @@ int crl_tron_step(const crl_ctx *ctx, int64_t B,
     const crl_tron_cfg &cfg = ctx->tron;
     CRL_REQUIRE(!(flags & CRL_STEP_AUTO_RESET) || ((cfg.N * cfg.N) % 16 != 0) || (((uintptr_t)board & 15) == 0),
                 "crl_tron_step: board must be 16-byte aligned");
+    // CRL_STEP_BYTES / CRL_STEP_STAGED are accepted and change nothing: one kernel, byte probes in HBM (boards staged
+    // through LDS were slower on every shape measured, profiles/r5_step_ab.json)
     hipStream_t s = (hipStream_t)stream;
     const TronGeom g = geom_of(cfg);
-    // Boards of whole 16-byte chunks that fit 64 (or 16) to a workgroup's LDS go through tron_step_staged_kernel (one coalesced
-    // read of every board); everything else, or flags & CRL_STEP_BYTES, through the byte probes of tron_step_kernel.  Identical
-    // results (tests run both); CRL_STEP_STAGED pins the LDS kernel where the shape allows it.
-    const int NN = cfg.N * cfg.N, slab = NN + 16;
-    const int G = (64 * slab + 64 <= 48 * 1024) ? 64 : (16 * slab + 16 <= 48 * 1024) ? 16 : 0;
-    const bool can_stage = (NN % 16) == 0 && G > 0 && (((uintptr_t)board & 15) == 0);
-    const bool staged = can_stage && !(flags & CRL_STEP_BYTES) && (CRL_STEP_DEFAULT_STAGED || (flags & CRL_STEP_STAGED));
     const uint32_t kflags = flags & CRL_STEP_AUTO_RESET;
-    if (staged) {
-        const uint32_t inv_cp = NN == 16 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint64_t)(NN / 16)) + 1u;
-        const size_t lds_bytes = (size_t)G * slab + G;
-        TRON_DISPATCH_P(cfg.P, {
-            if (G == 64)
-                hipLaunchKernelGGL((tron_step_staged_kernel<PP, 64>), dim3(blocks_for(B, 64)), dim3(256), lds_bytes, s, cfg, g, inv_cp, B,
-                                   board, heads, dirs, deaths, actions, rewards, terminal, winners, kflags);
-            else
-                hipLaunchKernelGGL((tron_step_staged_kernel<PP, 16>), dim3(blocks_for(B, 16)), dim3(256), lds_bytes, s, cfg, g, inv_cp, B,
-                                   board, heads, dirs, deaths, actions, rewards, terminal, winners, kflags);
-        });
-        CRL_LAUNCH_CHECK();
-        return CRL_OK;
-    }
     TRON_DISPATCH_P(cfg.P, {
         hipLaunchKernelGGL((tron_step_kernel<PP>), dim3(blocks_for(B, 256)), dim3(256), 0, s, cfg, g, B,
                            board, heads, dirs, deaths, actions, rewards, terminal, winners, kflags);
@@ -5281,53 +5166,14 @@ static int tron_rollout_impl(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
     const int NN = cfg.N * cfg.N;
     CRL_REQUIRE((NN % 16 != 0) || (((uintptr_t)board & 15) == 0), "crl_tron_rollout: board must be 16-byte aligned");
     if (T == 0) return CRL_OK;
+    const TronRollout kernel = tron_pick_rollout(cfg, B, T, flags, ((uintptr_t)board & 15) == 0);
     const TronGeom g = geom_of(cfg);
+    const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
     // LDS-resident kernels.  Byte slabs: 256 games per workgroup on boards up to 20x20, 64 (one wave) up to 40x40.
     // Bitboards (T >= 256): 256 games per workgroup either way; the replay takes the byte slabs one wave at a time
     // on the larger boards.
     const bool small = cfg.N <= kLdsMaxNSmall;
-    const int RS = small ? kRowBytesSmall : kRowBytesLarge;
-    const TronPad pad = pad_of(cfg, RS);
-    // The lane-per-player kernel on boards in GLOBAL memory has no fixed cost (no copy in / out, no tags to strip, no replay):
-    // a launch costs what its steps cost, 2-4.5 us each at 65,536 games of 20x20..40x40 (a probe pulls a cache line per byte).
-    // So, unless a kernel is pinned, it takes (profiles/r5_shape_sweep.txt, `kernels`):
-    //  * a ONE-step launch on boards up to 20x20 (11 us against the byte-slab kernel's 13-16);
-    //  * short launches on boards 21..40 wide, where the bitboard kernel's copy in + replay kernel is 45-90 us (70-170 us on
-    //    boards that are not whole dwords a row): up to 18 steps (32 on the latter);
-    //  * boards above 40x40, which nothing else plays out of LDS: with four players always up to 44x44, up to 200 steps up to
-    //    56x56 and up to 48 steps above -- beyond that the lane-per-game global kernel, whose episode tags save the rewrite of a
-    //    finished board (N * N bytes per reset) at the price of a pass over all boards at the end of the launch, and whose step
-    //    gets cheaper with fewer players (a lane per game probes P cells; a lane per player idles, and shorter episodes mean
-    //    more rewrites): three players up to 56 / 24 steps, one or two up to 24 / 14 (41x41, 65,536 two-player games: 2.7 us
-    //    per step against this kernel's 6.8).
-    // More than four players: the lane-per-game kernels.
-    const bool no_pin = !(flags & (CRL_ROLLOUT_NO_LDS | CRL_ROLLOUT_BYTES | CRL_ROLLOUT_BITS | CRL_ROLLOUT_QUAD | CRL_ROLLOUT_QBITS | CRL_ROLLOUT_PAIR));
-    // (65,536 games of two players, 2048 steps: 499 against 632 us at 20x20, 508 against 642 at 13x13; the pair kernel copies
-    //  boards whose rows are not whole dwords byte by byte, which a launch of 256 steps earns back: profiles/r5_shape_sweep.txt)
-    const int kPairMinT = ((cfg.N & 3) == 0 && cfg.N >= 8) ? 32 : 256;
-    const bool lds_fit = cfg.N <= kLdsMaxNLarge && (((uintptr_t)board & 15) == 0);
-    const bool wide_rows = (cfg.N & 3) == 0;
-    const bool gquad_pays = small ? T == 1
-                          : cfg.N <= kLdsMaxNLarge ? T <= (wide_rows ? 18 : 32)
-                          : cfg.P == 4 ? (cfg.N <= 44 || T <= (cfg.N <= 56 ? 200 : 48))
-                          : cfg.P == 3 ? T <= (cfg.N <= 56 ? 56 : 24)
-                                       : T <= (cfg.N <= 56 ? 24 : 14);
-    const bool use_gquad = cfg.P <= 4 && ((flags & CRL_ROLLOUT_GQUAD) || (no_pin && (gquad_pays || (!lds_fit && cfg.N <= kLdsMaxNLarge))));
-    const bool lds_ok = !(flags & CRL_ROLLOUT_NO_LDS) && !use_gquad && lds_fit;
-    if (use_gquad) {
-        constexpr int kQuadMaxT = 16383;                        // (16-bit episode / win / step counts per launch, as below)
-        for (int t0 = 0; t0 < T; t0 += kQuadMaxT) {
-            TRON_DISPATCH_P4(cfg.P, {
-                launch(tron_rollout_gquad_kernel<PP>, dim3(blocks_for(B, 64)), dim3(256), (size_t)0, t0 + kQuadMaxT >= T, cfg, g, B,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, std::min(kQuadMaxT, T - t0), board, heads, dirs, deaths, st);
-            });
-            CRL_LAUNCH_CHECK();
-        }
-        return CRL_OK;
-    }
-    // default: bitboards where they buy residency (boards above 20x20 fit 4x the games per CU); on small boards the
-    // byte kernel already has every game resident and no replay to pay for
-    const bool use_bits = lds_ok && !(flags & CRL_ROLLOUT_BYTES) && ((flags & CRL_ROLLOUT_BITS) || (!small && T >= 256));
+    const TronPad pad = pad_of(cfg, small ? kRowBytesSmall : kRowBytesLarge);
     TronBits bits;
     {
         const int max_n = small ? kLdsMaxNSmall : kLdsMaxNLarge;
@@ -5335,130 +5181,83 @@ static int tron_rollout_impl(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
         bits.stride = 2 * ((max_w * 4 + 127) & ~127) + 16;              // two 128-byte-aligned slabs of pattern words + a junk word
         bits.inv_s = (uint32_t)(((uint64_t)1 << 32) / (uint64_t)(cfg.N + 1)) + 1u;
     }
-    // one lane per player, four per game: boards up to 20x20 with at most 4 players (see tron_rollout_quad_kernel)
-    const bool quad_ok = lds_ok && small && cfg.P <= 4 && pad.sweep_rows == 1;
-    // the default wherever it applies: 1.42e11 vs 1.24e11 env-steps/s for the lane-per-game byte kernel at 20x20, P = 4
-    const bool use_quad = quad_ok && !(flags & (CRL_ROLLOUT_BYTES | CRL_ROLLOUT_BITS | CRL_ROLLOUT_QBITS));
-    // the same on bitboards (+ replay): boards above 20x20, where byte slabs would leave a CU with one wave per SIMD.
-    // Launches of any length: at 40x40 even a 16-step launch takes 0.15 ms against 0.25 ms on byte slabs (the replay is
-    // cheaper than moving 1,852-byte slabs through a lone wave per SIMD); tools/README.md
-    const bool qbits_ok = lds_ok && cfg.P <= 4;
-    const bool use_qbits = qbits_ok && !use_quad &&
-                           ((flags & CRL_ROLLOUT_QBITS) || (!small && !(flags & (CRL_ROLLOUT_BYTES | CRL_ROLLOUT_BITS))));
-    if (use_qbits) {
-        // four lanes of a game store 64 contiguous bytes per 16-byte rewrite store, which the LDS serves eight lanes (two
-        // games) at a time: a game stride of 16 dwords mod 32 banks keeps the two games on different banks (the
-        // lane-per-game kernel's 4 mod 32 would overlap them)
-        TronBits qb = bits;
-#ifndef CRL_QBITS_PAD
-#define CRL_QBITS_PAD 64            /* bytes behind a game's two slabs: the four junk words + bank padding (tools/lib_variant.sh) */
-#endif
-        qb.stride = bits.stride - 16 + CRL_QBITS_PAD;
-        const size_t lds_q = std::max((size_t)64 * qb.stride, (size_t)16 * pad.stride);
-        constexpr int kQuadMaxT = 16383;                        // (16-bit episode / win / step counts per launch, see below)
-#ifndef CRL_QBITS_SPLIT_REPLAY
-#define CRL_QBITS_SPLIT_REPLAY 1    /* the replay as a kernel of its own behind the bitboard kernel (0: inside it, four turns per workgroup) */
-#endif
-        const int split = CRL_QBITS_SPLIT_REPLAY;
-        for (int t0 = 0; t0 < T; t0 += kQuadMaxT) {
-            const int tt = std::min(kQuadMaxT, T - t0);
+    // the lane-per-player bitboard kernel: four lanes of a game store 64 contiguous bytes per 16-byte rewrite store, which
+    // the LDS serves eight lanes (two games) at a time: a game stride of 16 dwords mod 32 banks keeps the two games on
+    // different banks (the lane-per-game kernel's 4 mod 32 would overlap them)
+    constexpr int kQBitsPad = 64;                               // bytes behind a game's two slabs: the four junk words + bank padding
+    TronBits qb = bits;
+    qb.stride = bits.stride - 16 + kQBitsPad;
+    const size_t lds_q = std::max((size_t)64 * qb.stride, (size_t)16 * pad.stride);
+    // the lane-per-game kernels take all T steps in one launch, the lane-per-player ones at most kTronLaunchMaxT
+    const bool per_game = kernel == TronRollout::Global || kernel == TronRollout::Bytes || kernel == TronRollout::Bits;
+    const int chunk = per_game ? T : kTronLaunchMaxT;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int tt = std::min(chunk, T - t0);
+        const bool last = t0 + chunk >= T;
+        switch (kernel) {
+        case TronRollout::GQuad:
+            TRON_DISPATCH_P4(cfg.P, launch(tron_rollout_gquad_kernel<PP>, dim3(blocks_for(B, 64)), dim3(256), (size_t)0, last, cfg, g, B,
+                                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st));
+            break;
+        case TronRollout::QBits:                                // + the replay as a kernel of its own
             TRON_DISPATCH_P4(cfg.P, {
-                const bool last = t0 + kQuadMaxT >= T;
-                if (small)
-                    launch(tron_rollout_qbits_kernel<PP, false>, dim3(blocks_for(B, 64)), dim3(256), lds_q, last && !split, cfg, g, pad, qb, B,
-                           (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, tt, board, heads, dirs, deaths, st, split);
-                else
-                    launch(tron_rollout_qbits_kernel<PP, true>, dim3(blocks_for(B, 64)), dim3(256), lds_q, last && !split, cfg, g, pad, qb, B,
-                           (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, tt, board, heads, dirs, deaths, st, split);
-                if (split) {
-                    if (small)
-                        launch(tron_replay_kernel<PP, false>, dim3(blocks_for(B, 16)), dim3(64), (size_t)16 * pad.stride, last, cfg, g, pad, B,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, tt, board, heads, dirs, deaths, st);
-                    else
-                        launch(tron_replay_kernel<PP, true>, dim3(blocks_for(B, 16)), dim3(64), (size_t)16 * pad.stride, last, cfg, g, pad, B,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, tt, board, heads, dirs, deaths, st);
+                if (small) {
+                    launch(tron_rollout_qbits_kernel<PP, false>, dim3(blocks_for(B, 64)), dim3(256), lds_q, false, cfg, g, pad, qb, B,
+                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
+                    launch(tron_replay_kernel<PP, false>, dim3(blocks_for(B, 16)), dim3(64), (size_t)16 * pad.stride, last, cfg, g, pad, B,
+                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
+                } else {
+                    launch(tron_rollout_qbits_kernel<PP, true>, dim3(blocks_for(B, 64)), dim3(256), lds_q, false, cfg, g, pad, qb, B,
+                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
+                    launch(tron_replay_kernel<PP, true>, dim3(blocks_for(B, 16)), dim3(64), (size_t)16 * pad.stride, last, cfg, g, pad, B,
+                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
                 }
             });
-            CRL_LAUNCH_CHECK();
-        }
-        return CRL_OK;
-    }
-    // one or two players: two lanes per game (tron_rollout_pair_kernel) once the launch is long enough for its plainer copies
-    // (its slabs leave a SIMD two waves at 20x20, three from 15x15 down: with two it wins while the quad kernel's waves do not
-    //  fill the chip either -- up to ~100,000 games -- and ties beyond: 262,144 games of 20x20, 512 steps: 607 against 583 us)
-    const bool pair_pays = (size_t)pad.stride * 64 * 6 <= (size_t)160 * 1024 || B <= 98304;
-    const bool use_pair = quad_ok && cfg.P <= 2 && use_quad && ((flags & CRL_ROLLOUT_PAIR) || (no_pin && T >= kPairMinT && pair_pays));
-    if (use_pair) {
-        constexpr int kQuadMaxT = 16383;
-        for (int t0 = 0; t0 < T; t0 += kQuadMaxT) {
-            launch(tron_rollout_pair_kernel<kRowBytesSmall>, dim3(blocks_for(B, 64)), dim3(128), (size_t)64 * pad.stride,
-                   t0 + kQuadMaxT >= T, cfg, g, pad, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, std::min(kQuadMaxT, T - t0),
-                   board, heads, dirs, deaths, st);
-            CRL_LAUNCH_CHECK();
-        }
-        return CRL_OK;
-    }
-    if (use_quad) {
-        // (the kernel keeps a launch's episode, win and step counts in 14..16 bits: longer rollouts go out as several launches,
-        //  which is the same rollout -- the state and the step counters carry over)
-        constexpr int kQuadMaxT = 16383;
-        for (int t0 = 0; t0 < T; t0 += kQuadMaxT) {
-#if CRL_QUAD_WG > 256
-            {
-                static thread_local int opted = 0;
-                if (!opted) {
-                    CRL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tron_rollout_quad_kernel<kRowBytesSmall>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsDynamic));
-                    opted = 1;
+            break;
+        case TronRollout::Pair:
+            launch(tron_rollout_pair_kernel<kRowBytesSmall>, dim3(blocks_for(B, 64)), dim3(128), (size_t)64 * pad.stride, last,
+                   cfg, g, pad, B, seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
+            break;
+        case TronRollout::Quad:
+            launch(tron_rollout_quad_kernel<kRowBytesSmall>, dim3(blocks_for(B, 64)), dim3(256), (size_t)64 * pad.stride, last,
+                   cfg, g, pad, B, seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
+            break;
+        case TronRollout::Bits:
+        case TronRollout::Bytes: {
+            const bool use_bits = kernel == TronRollout::Bits;
+            const int threads = (use_bits || small) ? 256 : 64;
+            const size_t byte_slabs = (size_t)(small ? 256 : 64) * pad.stride;
+            const size_t lds_bytes = use_bits ? std::max(byte_slabs, (size_t)256 * bits.stride) : byte_slabs;
+            CRL_REQUIRE(lds_bytes <= (size_t)kLdsDynamic, "crl_tron_rollout: internal: %zu bytes of LDS", lds_bytes);
+            const dim3 grid(blocks_for(B, threads)), block(threads);
+            TRON_DISPATCH_P(cfg.P, {
+                if (use_bits && small) {
+                    if (const int rc = tron_opt_in_lds<tron_rollout_bits_kernel<PP, false>>()) return rc;
+                    launch(tron_rollout_bits_kernel<PP, false>, grid, block, lds_bytes, last, cfg, g, pad, bits, B,
+                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
+                } else if (use_bits) {
+                    if (const int rc = tron_opt_in_lds<tron_rollout_bits_kernel<PP, true>>()) return rc;
+                    launch(tron_rollout_bits_kernel<PP, true>, grid, block, lds_bytes, last, cfg, g, pad, bits, B,
+                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
+                } else if (small) {
+                    if (const int rc = tron_opt_in_lds<tron_rollout_lds_kernel<PP, kRowBytesSmall>>()) return rc;
+                    launch(tron_rollout_lds_kernel<PP, kRowBytesSmall>, grid, block, lds_bytes, last, cfg, g, pad, B,
+                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
+                } else {
+                    if (const int rc = tron_opt_in_lds<tron_rollout_lds_kernel<PP, kRowBytesLarge>>()) return rc;
+                    launch(tron_rollout_lds_kernel<PP, kRowBytesLarge>, grid, block, lds_bytes, last, cfg, g, pad, B,
+                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
                 }
-            }
-#endif
-            launch(tron_rollout_quad_kernel<kRowBytesSmall>, dim3(blocks_for(B, CRL_QUAD_WG / 4)), dim3(CRL_QUAD_WG), (size_t)(CRL_QUAD_WG / 4) * pad.stride,
-                   t0 + kQuadMaxT >= T, cfg, g, pad, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, std::min(kQuadMaxT, T - t0),
-                   board, heads, dirs, deaths, st);
-            CRL_LAUNCH_CHECK();
+            });
+            break;
         }
-        return CRL_OK;
+        case TronRollout::Global:
+            TRON_DISPATCH_P(cfg.P, launch(tron_rollout_kernel<PP>, dim3(blocks_for(B, 256)), dim3(256), (size_t)0, last, cfg, g, B,
+                                          seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st));
+            break;
+        }
+        CRL_LAUNCH_CHECK();
     }
-    const int threads = (use_bits || small) ? 256 : 64;
-    const size_t byte_slabs = (size_t)(small ? 256 : 64) * pad.stride;
-    const size_t lds_bytes = use_bits ? std::max(byte_slabs, (size_t)256 * bits.stride) : byte_slabs;
-    CRL_REQUIRE(!lds_ok || lds_bytes <= (size_t)kLdsDynamic, "crl_tron_rollout: internal: %zu bytes of LDS", lds_bytes);
-    TRON_DISPATCH_P(cfg.P, {
-        if (lds_ok) {
-            // opt in to > 64 KiB of dynamic LDS once per kernel instance and device (not per launch)
-            static thread_local int opted_in[4][64] = {{0}};
-            int dev = 0;
-            CRL_HIP(hipGetDevice(&dev));
-            const int which = (use_bits ? 2 : 0) + (small ? 1 : 0);
-            const void *fn = use_bits ? (small ? reinterpret_cast<const void *>(&tron_rollout_bits_kernel<PP, false>)
-                                               : reinterpret_cast<const void *>(&tron_rollout_bits_kernel<PP, true>))
-                                      : (small ? reinterpret_cast<const void *>(&tron_rollout_lds_kernel<PP, kRowBytesSmall>)
-                                               : reinterpret_cast<const void *>(&tron_rollout_lds_kernel<PP, kRowBytesLarge>));
-            if (dev < 0 || dev >= 64 || !opted_in[which][dev]) {
-                CRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsDynamic));
-                if (dev >= 0 && dev < 64) opted_in[which][dev] = 1;
-            }
-            const dim3 grid(blocks_for(B, threads));
-            const dim3 block(threads);
-            if (use_bits && small)
-                launch(tron_rollout_bits_kernel<PP, false>, grid, block, lds_bytes, true, cfg, g, pad, bits, B,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, T, board, heads, dirs, deaths, st);
-            else if (use_bits)
-                launch(tron_rollout_bits_kernel<PP, true>, grid, block, lds_bytes, true, cfg, g, pad, bits, B,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, T, board, heads, dirs, deaths, st);
-            else if (small)
-                launch(tron_rollout_lds_kernel<PP, kRowBytesSmall>, grid, block, lds_bytes, true, cfg, g, pad, B,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, T, board, heads, dirs, deaths, st);
-            else
-                launch(tron_rollout_lds_kernel<PP, kRowBytesLarge>, grid, block, lds_bytes, true, cfg, g, pad, B,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, T, board, heads, dirs, deaths, st);
-        } else {
-            launch(tron_rollout_kernel<PP>, dim3(blocks_for(B, 256)), dim3(256), (size_t)0, true, cfg, g, B,
-                   (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, T, board, heads, dirs, deaths, st);
-        }
-    });
-    CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
 
@@ -5556,9 +5355,8 @@ int crl_tron_rollout_avoid(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_
     const TronGeom g = geom_of(cfg);
     const uint64_t thr = tron_avoid_threshold(noise);
     hipStream_t s = (hipStream_t)stream;
-    constexpr int kMaxT = 16383;                                // (16-bit episode / win / step counts per launch)
-    for (int t0 = 0; t0 < T; t0 += kMaxT) {
-        const int Tl = std::min(kMaxT, T - t0);
+    for (int t0 = 0; t0 < T; t0 += kTronLaunchMaxT) {
+        const int Tl = std::min(kTronLaunchMaxT, T - t0);
         if (cfg.P <= 4) {
             TRON_DISPATCH_P4(cfg.P, {
                 hipLaunchKernelGGL((tron_rollout_avoid_kernel<PP>), dim3(blocks_for(B, 64)), dim3(256), 0, s, cfg, g, B,
@@ -5629,8 +5427,8 @@ int crl_tron_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t firs
     const int until = (flags & CRL_PLAYOUT_UNTIL_SEAT_DONE) ? 1 : 0;
 #define TRON_PLAYOUT_LAUNCH(AV_)                                                                                          \
     do {                                                                                                                  \
-        const void *fn = reinterpret_cast<const void *>(&tron_playout_kernel<PP, AV_>);                                   \
-        if (lds > 64 * 1024) CRL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
+        if (lds > 64 * 1024)                                                                                              \
+            if (const int rc = tron_opt_in_lds<tron_playout_kernel<PP, AV_>>()) return rc;                                \
         hipLaunchKernelGGL((tron_playout_kernel<PP, AV_>), dim3(blocks), dim3(threads), lds, s, g, B, (uint32_t)seed,      \
                            (uint32_t)(seed >> 32), first_env_id, board, heads, dirs, deaths, tcount, seat, cand, A, R, thr, \
                            max_steps, until, S, nwords, n_lanes, wins, played, len_sum, ret_sum);                         \

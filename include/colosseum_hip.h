@@ -48,9 +48,10 @@ extern "C" {
 
 /* flags for *_step */
 #define CRL_STEP_AUTO_RESET 1u  /* after writing the step outputs, reset every env that just became terminal */
-/* crl_tron_step only: pin one of its two interchangeable kernels (identical results; the default is the faster one) */
-#define CRL_STEP_BYTES      2u  /* byte probes in HBM, one lane per game, nothing staged */
-#define CRL_STEP_STAGED     4u  /* boards read once, coalesced, into LDS (boards of whole 16-byte chunks that fit; else ignored) */
+/* crl_tron_step only, kept for existing callers: accepted and change nothing, crl_tron_step has one kernel (byte probes in
+ * HBM; boards staged through LDS were slower on every shape measured and are gone) */
+#define CRL_STEP_BYTES      2u
+#define CRL_STEP_STAGED     4u
 /* crl_blokus_step_single only: the learner's action is a RANK into its ordered legal list (as crl_blokus_select) */
 #define CRL_STEP_RANK_ACTION 8u
 /* flags for crl_tron_rollout */

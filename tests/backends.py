@@ -72,7 +72,7 @@ class HipTron:
         self.tb.dirs.copy_(self._dev(dirs, t.int8))
         self.tb.deaths.copy_(self._dev(deaths, t.int8))
 
-    step_kernel = "auto"            # "bytes" / "staged" pin one of crl_tron_step's two interchangeable kernels
+    step_kernel = "auto"            # "bytes" / "staged": the flags crl_tron_step still accepts (one kernel either way)
 
     def step(self, actions, auto_reset=False):
         r, t, w = self.tb.step(self._dev(actions, self.torch.int8), auto_reset=auto_reset, kernel=self.step_kernel)

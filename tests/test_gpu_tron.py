@@ -12,6 +12,7 @@ TRAJ = ["n20p4", "n40p4", "n20p2", "n21p3", "n20p6", "n7p5", "n20p4_noreset", "n
 
 
 class HipTronStaged(HipTron):
+    """crl_tron_step with CRL_STEP_STAGED: the flag of the removed LDS kernel is still accepted and gives the same results."""
     step_kernel = "staged"
 
 
@@ -247,8 +248,8 @@ def test_relative_player_inplace64_golden(golden, name):
                                      (4, 2, 200, 12), (100, 4, 70, 30)])
 def test_step_vs_oracle_random(N, P, B, T, kernel):
     """Seeded random actions, ragged batch sizes (not a multiple of the wave or of a workgroup's 64 / 16 games), odd boards
-    (byte reset path), on both interchangeable kernels of crl_tron_step (byte probes / boards staged through LDS; boards that
-    are not whole 16-byte chunks or do not fit LDS take the byte kernel under either pin)."""
+    (byte reset path), under both kernel flags crl_tron_step still accepts (CRL_STEP_BYTES / CRL_STEP_STAGED: both run its
+    one kernel)."""
     rng = np.random.default_rng(N * 1000 + P)
     sh, sd = O.tron_start_positions(N, P)
     hip, orc = HipTron(N, P, B, sh, sd), OracleTron(N, P, B, sh, sd)

@@ -55,7 +55,6 @@ GPU_RUNS = [
     (["tools/kernel_ab.py", "20", "64"], "quad"),
     (["tools/debug/dropin_stress.py", "3", "1500"], "0 errors"),
     (["tools/debug/host_latency.py"], "region raw"),
-    (["tools/debug/step_ab.py", "quick"], "staged_over_bytes"),
     (["tools/debug/dropin_breakdown.py", "200"], "env_next_state"),
     (["tools/debug/shape_sweep.py", "19,24", "4", "4096,4099"], " 24  4    4099"),
     (["tools/debug/shape_sweep.py", "kernels", "24", "1,8", "4096"], "N=24 global"),

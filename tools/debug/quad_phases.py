@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Phase timeline of ONE launch of the lane-per-player byte kernel (diagnostic build: tools/lib_variant.sh stamps tron
--DCRL_QUAD_STAMPS [-DCRL_QUAD_SKEW=n]; run with CRL_LIB_PATH=build/ab_stamps/libcolosseum_hip.so):
+-DCRL_QUAD_STAMPS; run with CRL_LIB_PATH=build/ab_stamps/libcolosseum_hip.so):
 when, relative to the first wave's entry, the waves enter, have their boards in LDS, finish stepping and end.
     python tools/debug/quad_phases.py [steps [board width [kernel]]]
 (board widths 21..40 with kernel "qbits": the same four stamps in the lane-per-player bitboard kernel -- entry, bits laid out,
-steps done, end of the replay)"""
+steps done, end of the kernel; the replay runs in a kernel of its own behind it)"""
 import ctypes as C
 import os
 import sys

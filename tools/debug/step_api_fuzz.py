@@ -24,7 +24,7 @@ for case in range(n_cases):
         B = (B // 16 + 1) * 16                                  # whole 16-game groups: the flat-stream kernels of boards like 19 x 19
     T, seed, first = int(rng.integers(1, 40)), int(rng.integers(0, 2 ** 62)), int(rng.integers(0, 2 ** 40))
     a, b, c = (TronBatch(N, P, B, first_env_id=first) for _ in range(3))
-    step_kernel = ("auto", "bytes", "staged")[case % 3]        # crl_tron_step's interchangeable kernels (staged: where the board allows)
+    step_kernel = ("auto", "bytes", "staged")[case % 3]        # the kernel flags crl_tron_step still accepts (one kernel)
     for t in range(T):
         # (shapes the 16-byte fused kernel cannot take -- N*N % 16 != 0, P = 8 -- run the one-game-per-workgroup kernel)
         oa = a.step_observe(None, seed=seed)

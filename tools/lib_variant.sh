@@ -2,7 +2,7 @@
 # Build a VARIANT of libcolosseum_hip.so into build/ab_<tag>/ inside the tree (git-ignored, but it travels to the GPU box
 # with the snapshot, unlike /tmp) and print its path.  Only the named source is recompiled with the extra flags; the other
 # objects are taken from the shipped build.
-# usage: tools/lib_variant.sh <tag> <tron|ttt|blokus|capi> [extra hipcc flags, e.g. -DCRL_QUAD_SKEW=0]
+# usage: tools/lib_variant.sh <tag> <tron|ttt|blokus|capi> [extra hipcc flags, e.g. -DCRL_QUAD_STAMPS]
 set -euo pipefail
 TAG=$1; SRC=$2; shift 2
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

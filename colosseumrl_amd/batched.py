@@ -113,6 +113,36 @@ def _tron_playout_out(out: Optional[dict], B: int, A: int, P: int, device):
     return out
 
 
+def _territory_args(candidates: Optional[torch.Tensor], seat: Optional[torch.Tensor], B: int, device) -> int:
+    """A of a territory call, checked as the C entry checks it (crl_tron_territory: A in [1, 16]); candidates int32 [B, A] or
+    None (A = 1); seat int8 [B] or None."""
+    if seat is not None:
+        if not isinstance(seat, torch.Tensor):
+            raise ValueError("seat must be an int8 tensor of shape (%d,)" % B)
+        _want(seat, torch.int8, (B,), device, "seat")
+    if candidates is None:
+        return 1
+    if not isinstance(candidates, torch.Tensor) or candidates.dim() != 2 or candidates.shape[0] != B:
+        raise ValueError("candidates must be an int32 tensor of shape (%d, A)" % B)
+    A = int(candidates.shape[1])
+    if not 1 <= A <= 16:
+        raise ValueError("candidates must have 1..16 columns, got %d" % A)
+    _want(candidates, torch.int32, (B, A), device, "candidates")
+    return A
+
+
+def _territory_out(out: Optional[dict], B: int, A: int, P: int, device):
+    """the output dict of a territory call: fresh, or `out` with every buffer checked"""
+    spec = {"area": (torch.int32, (B, A, P)), "info": (torch.uint8, (B, A))}
+    if out is None:
+        return {k: torch.empty(shape, dtype=dt, device=device) for k, (dt, shape) in spec.items()}
+    for k, (dt, shape) in spec.items():
+        if k not in out:
+            raise ValueError("out lacks %r" % k)
+        _want(out[k], dt, shape, device, "out[%r]" % k)
+    return out
+
+
 def _flat_mc_pick(value: torch.Tensor, played: torch.Tensor, ids: torch.Tensor):
     """int64 [B]: ids[b, a] of the greatest value among the played rows (ties: the lowest a), -1 where none was played"""
     value = torch.where(played > 0, value, torch.full_like(value, -1))
@@ -387,6 +417,76 @@ class TronBatch(_Waitable):
         # (returns go below -1: the pick compares mean returns shifted above _flat_mc_pick's -1 for unplayed rows)
         mean = o["ret_sum"].to(torch.float64) / float(playouts)
         return _flat_mc_pick(mean - mean.amin(dim=1, keepdim=True), o["played"], cands)
+
+    # -- Voronoi territory of every game's position (the deterministic evaluator beside playout)
+    def territory(self, candidates: Optional[torch.Tensor] = None, seat: Optional[torch.Tensor] = None,
+                  out: Optional[dict] = None):
+        """Voronoi territory from every game's position, ONE launch (``crl_tron_territory``): ``area[b, a, p]`` is the
+        number of free cells player p reaches strictly before every other live player when the seat ``seat[b]`` (int8 [B];
+        None: player 0) first plays ``candidates[b, a]`` (int32 [B, A], A <= 16: 0 forward, 1 right, 2 left; any other
+        value skips the row).  ``candidates=None`` evaluates the position as it stands (A = 1, nobody forced).  Returns
+        {'area' int32 [B, A, P], 'info' uint8 [B, A]} -- info bit 0: the row was evaluated, bit 1: the forced cell is off
+        the board or occupied; skipped rows are zeros; ``out`` reuses such a dict.  The state is only read.  No host
+        synchronisation; capturable into a graph."""
+        A = _territory_args(candidates, seat, self.B, self.device)
+        out = _territory_out(out, self.B, A, self.P, self.device)
+        with _DevGuard(self.device):
+            check(self._lib.crl_tron_territory(self._ctx.handle, self.B, _ptr(self.board), _ptr(self.heads), _ptr(self.dirs),
+                                               _ptr(self.deaths), _ptr(seat), _ptr(candidates), A, _ptr(out["area"]),
+                                               _ptr(out["info"]), _stream()), "crl_tron_territory")
+        return out
+
+    def territory_action(self, seat: Optional[torch.Tensor] = None, out: Optional[dict] = None) -> torch.Tensor:
+        """The territory-greedy action for the seat in every game: ``territory`` on the three first actions [0, 1, 2],
+        score = the seat's area minus the best other live player's (a fatal action below every other), the best action
+        (ties: the lowest) as int64 [B] in {0, 1, 2} for ``step_single`` -- the noise-free rule of ``sample_territory``;
+        -1 where every row was skipped (the seat is dead).  ``out``: the territory dict to reuse.  No host
+        synchronisation; capturable."""
+        cands = getattr(self, "_moves3", None)
+        if cands is None:
+            cands = torch.arange(3, dtype=torch.int32, device=self.device).expand(self.B, 3).contiguous()
+            self._moves3 = cands
+        o = self.territory(cands, seat, out)
+        area = o["area"].to(torch.int64)                                          # [B, 3, P]
+        who = (torch.zeros((self.B,), dtype=torch.int64, device=self.device) if seat is None else seat.to(torch.int64))
+        who = who.clamp(0, self.P - 1).view(self.B, 1, 1).expand(self.B, 3, 1)
+        own = torch.gather(area, 2, who).squeeze(2)
+        others = (self.deaths.t() == 0).view(self.B, 1, self.P).expand(self.B, 3, self.P).clone()
+        others.scatter_(2, who, False)
+        rival = torch.where(others, area, torch.zeros_like(area)).amax(dim=2)     # (no other live player: 0)
+        score = torch.where((o["info"] & 2) != 0, torch.full_like(own, -(1 << 30)), own - rival)
+        score = torch.where((o["info"] & 1) != 0, score, torch.full_like(score, -(1 << 31)))
+        best = torch.argmax(score, dim=1)                                         # (the first of equal maxima)
+        return torch.where((o["info"] & 1).amax(dim=1) != 0, best, torch.full_like(best, -1))
+
+    # -- the territory-greedy scripted opponent for one step: int8 [P][B] actions in the step() encoding
+    def sample_territory(self, seed: int = 0, noise: float = 0.1, players=None, out: Optional[torch.Tensor] = None,
+                         advance: bool = True):
+        """Actions of the territory-greedy agent at each game's step counter (``tcount``), under the contract of
+        ``crl_tron_sample_territory`` (include/colosseum_hip.h): with probability ``noise`` a uniform action, else the
+        first action with the best Voronoi score (own area minus the best rival's), decided on the current (pre-step)
+        boards.  ``players`` / ``out`` / ``advance`` as ``sample_avoid``: only the named players' rows of ``out`` (int8
+        [P, B]; a new zeroed tensor when None) are written."""
+        P, B = self.P, self.B
+        if isinstance(noise, bool) or not isinstance(noise, (int, float)) or not 0.0 <= float(noise) <= 1.0:
+            raise ValueError("noise must be a number in [0, 1], got %r" % (noise,))
+        mask = (1 << P) - 1
+        if players is not None:
+            mask = 0
+            for p in players:
+                if not 0 <= int(p) < P:
+                    raise ValueError("sample_territory: player %d out of range 0..%d" % (int(p), P - 1))
+                mask |= 1 << int(p)
+        if out is None:
+            out = torch.zeros((P, B), dtype=torch.int8, device=self.device)
+        else:
+            _want(out, torch.int8, (P, B), self.device, "out")
+        with _DevGuard(self.device):
+            check(self._lib.crl_tron_sample_territory(self._ctx.handle, B, seed & (2 ** 64 - 1), self.first_env_id,
+                                                      _ptr(self.tcount), int(advance), float(noise), mask, _ptr(self.board),
+                                                      _ptr(self.heads), _ptr(self.dirs), _ptr(self.deaths), _ptr(out), _stream()),
+                  "crl_tron_sample_territory")
+        return out
 
     # -- T fused steps with every player on the avoid agent, auto-reset
     def rollout_avoid(self, steps: int, seed: int = 0, noise: float = 0.1):

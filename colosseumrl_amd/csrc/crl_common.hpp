@@ -1,6 +1,7 @@
 // crl_common.hpp -- shared pieces of libcolosseum_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -58,6 +59,32 @@ void crl_set_error(const char *fmt, ...);
     } while (0)
 
 #define CRL_LAUNCH_CHECK() CRL_HIP(hipGetLastError())
+
+// ---------------------------------------------------------------- shared by the tron translation units (tron.hip, tron_territory.hip)
+#define TRON_DISPATCH_P(P_, CALL)          \
+    switch (P_) {                          \
+        case 1: { constexpr int PP = 1; CALL; } break; \
+        case 2: { constexpr int PP = 2; CALL; } break; \
+        case 3: { constexpr int PP = 3; CALL; } break; \
+        case 4: { constexpr int PP = 4; CALL; } break; \
+        case 5: { constexpr int PP = 5; CALL; } break; \
+        case 6: { constexpr int PP = 6; CALL; } break; \
+        case 7: { constexpr int PP = 7; CALL; } break; \
+        case 8: { constexpr int PP = 8; CALL; } break; \
+        default: crl_set_error("tron: P=%d out of range 1..8", P_); return CRL_EINVAL; \
+    }
+
+#define TRON_CTX_CHECK(fn)                                                                  \
+    CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_TRON, fn ": ctx is not a tron context"); \
+    CRL_REQUIRE(B > 0 && B <= ((int64_t)1 << 31), fn ": B=%lld out of range", (long long)B)
+
+// the avoid agent's noise threshold (also the territory agent's): W[0] < thr is "noisy", thr = min(2^32, ceil(noise * 2^32))
+// in 64 bits
+static inline uint64_t tron_avoid_threshold(const double noise)
+{
+    const double x = ceil(noise * 4294967296.0);
+    return x >= 4294967296.0 ? ((uint64_t)1 << 32) : (uint64_t)x;
+}
 
 // ---------------------------------------------------------------- bounds asserts (diagnostic build: -DCRL_BOUNDS)
 // GPU AddressSanitizer is not available on this pool, so the data-dependent LDS / table accesses of the kernels carry
@@ -139,6 +166,7 @@ __device__ __forceinline__ philox_out philox4x32_10(uint32_t c0, uint32_t c1, ui
 
 #define CRL_TAG_TRON   0x54520000u
 #define CRL_TAG_TRON_AVOID 0x54410000u   /* the scripted SimpleAvoidAgent's draws (crl_tron_sample_avoid) */
+#define CRL_TAG_TRON_TERRITORY 0x54760000u   /* the territory-greedy agent's draws (crl_tron_sample_territory) */
 #define CRL_TAG_TTT    0x54540000u
 #define CRL_TAG_BLOKUS 0x424c0000u
 #define CRL_TAG_TTT_PLAYOUT    0x54500000u   /* random playouts (crl_ttt_playout) */

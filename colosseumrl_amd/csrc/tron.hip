@@ -4954,19 +4954,6 @@ tron_playout_kernel(const TronGeom g, const int64_t B, const uint32_t seed_lo, c
 
 } // namespace
 
-#define TRON_DISPATCH_P(P_, CALL)          \
-    switch (P_) {                          \
-        case 1: { constexpr int PP = 1; CALL; } break; \
-        case 2: { constexpr int PP = 2; CALL; } break; \
-        case 3: { constexpr int PP = 3; CALL; } break; \
-        case 4: { constexpr int PP = 4; CALL; } break; \
-        case 5: { constexpr int PP = 5; CALL; } break; \
-        case 6: { constexpr int PP = 6; CALL; } break; \
-        case 7: { constexpr int PP = 7; CALL; } break; \
-        case 8: { constexpr int PP = 8; CALL; } break; \
-        default: crl_set_error("tron: P=%d out of range 1..8", P_); return CRL_EINVAL; \
-    }
-
 #define TRON_DISPATCH_P4(P_, CALL)         \
     switch (P_) {                          \
         case 1: { constexpr int PP = 1; CALL; } break; \
@@ -5090,10 +5077,6 @@ int crl_tron_create(int N, int P, const int16_t *start_heads, const int8_t *star
     *out = c;
     return CRL_OK;
 }
-
-#define TRON_CTX_CHECK(fn)                                                                  \
-    CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_TRON, fn ": ctx is not a tron context"); \
-    CRL_REQUIRE(B > 0 && B <= ((int64_t)1 << 31), fn ": B=%lld out of range", (long long)B)
 
 int crl_tron_reset(const crl_ctx *ctx, int64_t B, const uint8_t *mask,
                    int8_t *board, int16_t *heads, int8_t *dirs, int8_t *deaths, void *stream)
@@ -5308,13 +5291,6 @@ int crl_tron_sample(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first
     });
     CRL_LAUNCH_CHECK();
     return CRL_OK;
-}
-
-// the avoid agent's noise threshold: W[0] < thr is "noisy", thr = min(2^32, ceil(noise * 2^32)) in 64 bits
-static uint64_t tron_avoid_threshold(const double noise)
-{
-    const double x = ceil(noise * 4294967296.0);
-    return x >= 4294967296.0 ? ((uint64_t)1 << 32) : (uint64_t)x;
 }
 
 int crl_tron_sample_avoid(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *tcount, int advance,

@@ -51,12 +51,17 @@ class TronSinglePlayerVectorEnv:
     ``info`` are buffers rewritten by every step as well.
     A step is two launches (opponents' actions, then step + done + reset) with no host synchronisation, and can be
     captured into a HIP graph (``torch.cuda.graph``).  The opponents' draws follow ``crl_tron_sample_avoid``'s contract
-    at each game's step counter, keyed by ``seed``."""
+    at each game's step counter, keyed by ``seed``.
+    ``opponent="territory"`` puts the opponents on the territory-greedy agent instead (``crl_tron_sample_territory``: the
+    first action with the best Voronoi score, with the same ``noise``): only the opponents' sampling launch changes."""
 
     def __init__(self, board_size: int = 15, num_players: int = 4, batch: int = 1024, noise: float = 0.1, seed: int = 0,
-                 spawn_offset: int = 2, device="cuda"):
+                 spawn_offset: int = 2, device="cuda", opponent: str = "avoid"):
         if num_players < 1:
             raise ValueError("num_players must be at least 1")
+        if opponent not in ("avoid", "territory"):
+            raise ValueError("opponent must be 'avoid' or 'territory', got %r" % (opponent,))
+        self.opponent = opponent
         self.batch = TronBatch(board_size, num_players, batch, device=device, spawn_offset=spawn_offset)
         self.num_players, self.num_envs = num_players, batch
         self.noise, self.seed = float(noise), int(seed)
@@ -82,7 +87,8 @@ class TronSinglePlayerVectorEnv:
         if action.dtype != torch.int64 or tuple(action.shape) != (b.B,) or action.device != b.device or not action.is_contiguous():
             raise ValueError("action must be a contiguous int64 tensor of shape (%d,) on %s" % (b.B, b.device))
         if self._opponents:
-            b.sample_avoid(self.seed, self.noise, players=self._opponents, out=self._actions)
+            sample = b.sample_territory if self.opponent == "territory" else b.sample_avoid
+            sample(self.seed, self.noise, players=self._opponents, out=self._actions)
         with _DevGuard(b.device):
             check(b._lib.crl_tron_step_single(b._ctx.handle, b.B, _ptr(b.board), _ptr(b.heads), _ptr(b.dirs), _ptr(b.deaths),
                                               _ptr(self._actions), _ptr(action), _ptr(self.reward), _ptr(self.done),
@@ -96,6 +102,12 @@ class TronSinglePlayerVectorEnv:
         ``seed`` keys the playouts (their draws never coincide with the env's own).  -> int64 [B] in {0, 1, 2}.  No host
         synchronisation; capturable."""
         return self.batch.flat_mc_action(playouts, seed, "avoid", self.noise, None, "seat_done", max_steps, out)
+
+    def territory_action(self, out: Optional[dict] = None) -> torch.Tensor:
+        """The territory-greedy action for the learner: ``TronBatch.territory_action`` for seat 0 -- the first action with
+        the best Voronoi score (own area minus the best live opponent's).  -> int64 [B] in {0, 1, 2}.  Deterministic; no
+        host synchronisation; capturable."""
+        return self.batch.territory_action(None, out)
 
 
 class TicTacToeVectorEnv:

@@ -84,7 +84,8 @@ const char *crl_last_error(void);
  * 113: crl_ttt_step_single / crl_blokus_step_single (one learner against the random agent), CRL_STEP_RANK_ACTION.
  *      crl_ttt_playout / crl_blokus_playout (batched random playouts) were added under 113: new entries and new Philox
  *      tags only, no existing struct, argument list or RNG contract changed.  So was crl_tron_playout (with
- *      CRL_PLAYOUT_AVOID / CRL_PLAYOUT_UNTIL_SEAT_DONE), on the same terms. */
+ *      CRL_PLAYOUT_AVOID / CRL_PLAYOUT_UNTIL_SEAT_DONE), on the same terms, and so were crl_tron_territory /
+ *      crl_tron_sample_territory (Voronoi territory and the territory-greedy agent: two new entries, one new Philox tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -328,6 +329,57 @@ int crl_tron_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t firs
                      double noise, int max_steps,
                      uint32_t *wins, uint32_t *played, uint32_t *len_sum, int32_t *ret_sum,
                      uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------ Voronoi territory (Tron)
+ * crl_tron_territory: for each of B positions and A forced first actions of a seat, the number of free cells every player
+ * reaches strictly before every other player -- Tron's deterministic evaluator, an evaluation primitive beside
+ * crl_tron_playout that needs no playouts.  One launch, no host sync.  No reference counterpart.
+ * Definitions.  A cell is FREE iff its board value is 0; player p is LIVE iff deaths[p] == 0.  For a live player p the FIRST
+ * CELLS F_p are the cells the actions forward / right / left lead to from (heads[p], dirs[p]) -- directions as in
+ * CyTronGrid.pyx: 0 up, 1 right, 2 down, 3 left, a right turn is +1 mod 4 --, keeping those that are on the board and
+ * free.  The cell behind the head is never a first cell, even where it is free (it is at the start layout).
+ * Row (b, a) with a forced candidate cand[b][a] in {0 forward, 1 right, 2 left} (crl_tron_playout's encoding): the seat's
+ * F is only that action's cell, and empty when that cell is off the board or occupied -- the row is then FATAL for the seat.
+ *   d_p(c)        = 1 + the length of the shortest 4-connected path through free cells from any cell of F_p to the free
+ *                   cell c; infinite if there is none.
+ *   area[b][a][p] = the number of free cells c with d_p(c) finite and d_p(c) < d_q(c) for every other live q.
+ * Dead players get 0.  A cell reached first by two or more players at the same distance belongs to nobody.
+ * Inputs are read only: board / heads / dirs / deaths have crl_tron_step's layouts.  seat int8 [B] is the player forced
+ * (NULL means player 0); cand int32 [B][A].  cand == NULL requires A == 1: nobody is forced and seat is not read.
+ * Outputs, every row overwritten (never accumulated):
+ *   area int32 [B][A][P]   (the layout of crl_tron_playout's wins);
+ *   info uint8 [B][A]      bit 0: the row was evaluated; bit 1: the seat's forced cell is off the board or occupied.
+ * A row is skipped (zeros, info 0) when a candidate is given and the seat is outside [0, P), the seat is dead, or the
+ * candidate is outside 0..2 (-1 padding included).  A position with one live player or none is still evaluated: the area
+ * is then that player's reachable cells.
+ * Argument checks (CRL_EINVAL, with a crl_last_error message, before any device work): NULL state / output pointers, B out
+ * of range, A outside [1, 16], A != 1 with cand == NULL, a context that is not a Tron context.  Rows are indexed with 64-bit
+ * arithmetic.  Precondition as crl_tron_playout: heads outside the board are clamped onto it (wrong results, never a
+ * wild access).
+ * Method: a level-synchronous multi-source flood on occupancy bitboards; per level and live player new_p = expand(front_p)
+ * & free, cells in two or more new_p are contested, area_p += popcount(new_p & ~contested), then free &= ~(union of new_p)
+ * and front_p = new_p (contested cells stay in the frontiers: ties propagate).  Flooding only through cells nobody has
+ * claimed is exact: a player arriving at a claimed cell later can neither win nor tie anything beyond it.  A flood ends when
+ * a level adds no cell, and in any case after N*N levels.  Boards up to 64x64: one lane per board row (a 32- or 64-bit
+ * word), floor(64 / N) rows (b, a) per wave, vertical neighbours by DPP wave shifts, frontiers and sums in registers.
+ * Boards 65..181 wide: one workgroup per row (b, a), bitboards in LDS. */
+int crl_tron_territory(const crl_ctx *ctx, int64_t B, const int8_t *board, const int16_t *heads, const int8_t *dirs,
+                       const int8_t *deaths, const int8_t *seat, const int32_t *cand, int A, int32_t *area, uint8_t *info,
+                       void *stream);
+
+/* The territory-greedy scripted agent: crl_tron_sample_avoid's argument list and its player_mask / advance / actions
+ * semantics (rows outside the mask are not written, dead players get 0, advance != 0 increments tcount; the same checks).
+ * For each live masked player p of global game g = first_env_id + b at step counter c = tcount[b]:
+ *   W = Philox4x32-10(ctr = {g, c, p, 0x54760000}, key = {seed lo, seed hi})            (a domain tag of its own)
+ *   noisy  iff  W[0] < thr, thr as crl_tron_sample_avoid's;  noisy: a = mulhi32(W[1], 3): 0 forward, 1 right, 2 left;
+ *   else:  the three candidates a = 0, 1, 2 are evaluated as crl_tron_territory rows with seat = p:
+ *          score_a = area[p] - max over the other live q of area[q]  (no other live player: area[p]); a fatal candidate
+ *          scores below every non-fatal one; the best score plays, ties go to the lowest index (forward, right, left).
+ * All players decide on the pre-step board.  actions[p*B+b] in the crl_tron_step encoding (0, +1, -1).  One launch: one
+ * wave (boards above 64x64: one workgroup) per game floods its 3 x (masked players) candidates. */
+int crl_tron_sample_territory(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *tcount, int advance,
+                              double noise, uint32_t player_mask, const int8_t *board, const int16_t *heads, const int8_t *dirs,
+                              const int8_t *deaths, int8_t *actions, void *stream);
 
 /* replaces CyTronGrid.relative_player_inplace (CyTronGrid.pyx:65-71) + the rolls of
  * TronGridEnvironment.state_to_observation (TronGridEnvironment.py:385-405), fully observable branch.

@@ -1,0 +1,274 @@
+"""Voronoi territory on the GPU: crl_tron_territory and crl_tron_sample_territory bit-exact against the numpy restatement
+(tests/territory_ref.py) over board sizes on both kernel families, ragged batches, mixed seats and candidates and the
+hand-made boards; TronSinglePlayerVectorEnv(opponent="territory") against a host replay (also from a HIP graph); and one
+strength check of the territory learner."""
+import numpy as np
+import pytest
+import torch
+
+from tests import avoid_ref
+from tests import territory_ref as R
+
+pytestmark = pytest.mark.gpu
+
+
+def _tb(N, P, B, **kw):
+    from colosseumrl_amd.batched import TronBatch
+    return TronBatch(N, P, B, device="cuda:0", **kw)
+
+
+def _put(tb, st):
+    tb.board.copy_(torch.from_numpy(np.ascontiguousarray(st.board)))
+    tb.heads.copy_(torch.from_numpy(np.ascontiguousarray(st.heads)))
+    tb.dirs.copy_(torch.from_numpy(np.ascontiguousarray(st.dirs)))
+    tb.deaths.copy_(torch.from_numpy(np.ascontiguousarray(st.deaths)))
+
+
+def _state(tb):
+    return [t.cpu().numpy() for t in (tb.board, tb.heads, tb.dirs, tb.deaths)]
+
+
+def _midgame(N, P, B, seed):
+    """a TronBatch of mid-game positions (random play, dead players included) and the same state on the host"""
+    if N == 4 and P > 4:                                        # no ring layout there: the oracle's positions from R.start_layout
+        sh, sd = R.start_layout(N, P)
+        tb = _tb(N, P, B, start=(sh.tolist(), sd.tolist()))
+        st = R.positions(N, P, B, seed=seed, avoid=False, start=(sh, sd))
+        _put(tb, st)
+        return tb, [st.board, st.heads, st.dirs, st.deaths]
+    tb = _tb(N, P, B)
+    tb.rollout(max(3, N // 3), seed=seed)
+    torch.cuda.synchronize()
+    return tb, _state(tb)
+
+
+def _check_territory(tb, st, rng):
+    N, P, B = tb.N, tb.P, tb.B
+    board, heads, dirs, deaths = st
+    # nobody forced
+    o = tb.territory()
+    want, winfo = R.territory(N, board, heads, dirs, deaths)
+    assert np.array_equal(o["area"].cpu().numpy(), want) and np.array_equal(o["info"].cpu().numpy(), winfo)
+    # all three candidates, seat 0 (NULL), reusing the buffers
+    c3 = np.tile(np.arange(3, dtype=np.int32), (B, 1))
+    out = {"area": torch.full((B, 3, P), -7, dtype=torch.int32, device=tb.device),
+           "info": torch.full((B, 3), 9, dtype=torch.uint8, device=tb.device)}
+    o = tb.territory(torch.from_numpy(c3).cuda(), out=out)
+    want, winfo = R.territory(N, board, heads, dirs, deaths, None, c3)
+    assert o is out
+    assert np.array_equal(o["area"].cpu().numpy(), want) and np.array_equal(o["info"].cpu().numpy(), winfo)
+    # mixed seats (some out of range, some dead) and candidates with padding
+    seat = rng.integers(-1, P + 1, size=B).astype(np.int8)
+    cand = rng.integers(-1, 4, size=(B, 5)).astype(np.int32)
+    o = tb.territory(torch.from_numpy(cand).cuda(), torch.from_numpy(seat).cuda())
+    want, winfo = R.territory(N, board, heads, dirs, deaths, seat, cand)
+    assert np.array_equal(o["area"].cpu().numpy(), want) and np.array_equal(o["info"].cpu().numpy(), winfo)
+    assert (winfo == 0).any() or B < 4
+    # territory_action == the arg-max of the scores of territory
+    for s in (None, np.clip(seat, 0, P - 1).astype(np.int8)):
+        act = tb.territory_action(None if s is None else torch.from_numpy(s).cuda()).cpu().numpy()
+        sp = np.zeros(B, np.int64) if s is None else s.astype(np.int64)
+        a3, i3 = R.territory(N, board, heads, dirs, deaths, sp, c3)
+        best = np.where(i3[:, 0] != 0, np.argmax(R.scores(a3, i3, deaths, sp), axis=1), -1)
+        assert np.array_equal(act, best)
+    for a, b in zip(_state(tb), st):                            # inputs unchanged
+        assert np.array_equal(a, b)
+
+
+# (4x4 with more than four players starts from R.start_layout's checkerboard: the ring layout has no room there)
+@pytest.mark.parametrize("N,P", [(N, P) for N in (4, 5, 13, 15, 19, 20, 21, 32, 33, 40, 63, 64) for P in range(1, 9)])
+def test_territory_matches_restatement(N, P):
+    B = 37 if N <= 21 else 9
+    tb, st = _midgame(N, P, B, seed=N * 10 + P)
+    _check_territory(tb, st, np.random.default_rng(N * 100 + P))
+
+
+@pytest.mark.parametrize("N,P", [(N, P) for N in (65, 100, 181) for P in range(1, 9)])
+def test_territory_matches_restatement_wide_boards(N, P):
+    tb, st = _midgame(N, P, 3 if N == 65 else 2, seed=N + P)
+    _check_territory(tb, st, np.random.default_rng(N + P))
+
+
+@pytest.mark.parametrize("N,B", [(19, 1), (19, 2), (19, 4), (15, 5), (13, 1), (20, 1001), (40, 3), (5, 11), (5, 4099)])
+def test_territory_ragged_batches(N, B):
+    tb, st = _midgame(N, 4, B, seed=B)
+    _check_territory(tb, st, np.random.default_rng(B))
+
+
+def test_territory_avoid_play_positions():
+    for N, P in ((13, 3), (19, 4), (20, 6), (40, 4)):
+        st = R.positions(N, P, 60, seed=N, avoid=True)
+        tb = _tb(N, P, 60)
+        _put(tb, st)
+        _check_territory(tb, [st.board, st.heads, st.dirs, st.deaths], np.random.default_rng(N))
+
+
+def test_territory_hand_boards():
+    expected = {"behind": [[0]], "walled": [[0, 18]], "spiral": [[198]], "corridor": [[2, 2]]}
+    for name, v in R.hand_boards().items():
+        tb = _tb(v["N"], v["P"], 1, start=(v["heads"][:, 0].tolist(), v["dirs"][:, 0].tolist()))   # (3x3 has no layout of its own)
+        tb.board.copy_(torch.from_numpy(v["board"]))
+        tb.heads.copy_(torch.from_numpy(v["heads"]))
+        tb.dirs.copy_(torch.from_numpy(v["dirs"]))
+        tb.deaths.copy_(torch.from_numpy(v["deaths"]))
+        o = tb.territory()
+        assert o["area"].cpu().numpy()[0].tolist() == expected[name], name
+        assert o["info"].cpu().numpy().tolist() == [[1]]
+        if name == "corridor":
+            cand = torch.tensor([[0, 1, 2, -1, 3]], dtype=torch.int32, device=tb.device)
+            o = tb.territory(cand)
+            assert o["area"].cpu().numpy()[0].tolist() == [[2, 2], [0, 7], [0, 7], [0, 0], [0, 0]]
+            assert o["info"].cpu().numpy()[0].tolist() == [1, 3, 3, 0, 0]
+            assert tb.territory_action().cpu().numpy().tolist() == [0]
+        assert np.array_equal(tb.board.cpu().numpy(), v["board"])
+
+
+# ---- the agent
+@pytest.mark.parametrize("N,P,B", [(15, 4, 300), (19, 4, 130), (13, 3, 77), (20, 2, 65), (40, 4, 21), (33, 6, 10), (5, 2, 500),
+                                   (64, 8, 4), (70, 3, 3)] + [(65, P, 2) for P in range(1, 9)]
+                                  + [(100, 5, 2), (181, 1, 2), (181, 8, 2)])
+@pytest.mark.parametrize("noise", [0.0, 0.1, 1.0])
+def test_sample_territory_matches_restatement(N, P, B, noise):
+    seed, first = 0xC0FFEE + N, 5
+    tb = _tb(N, P, B, first_env_id=first)
+    tb.rollout(max(3, N // 3), seed=N)
+    torch.cuda.synchronize()
+    st = _state(tb)
+    c0 = tb.tcount.cpu().numpy().view(np.uint32).copy()
+    a1 = tb.sample_territory(seed, noise, advance=False)
+    assert np.array_equal(tb.tcount.cpu().numpy().view(np.uint32), c0)
+    a2 = tb.sample_territory(seed, noise, advance=True)
+    assert np.array_equal(tb.tcount.cpu().numpy().view(np.uint32), c0 + 1)
+    want = R.decide(N, *st, np.arange(B) + first, c0, seed, noise)
+    assert np.array_equal(a1.cpu().numpy(), want) and torch.equal(a1, a2)
+    for a, b in zip(_state(tb), st):
+        assert np.array_equal(a, b)
+    # a partial mask: the other rows stay as they were
+    players = [p for p in range(P) if p % 2 == 1]
+    full = tb.sample_territory(seed, noise, advance=False)      # (at the advanced counter)
+    fill = torch.full((P, B), 77, dtype=torch.int8, device=tb.device)
+    out = tb.sample_territory(seed, noise, players=players, out=fill.clone(), advance=False)
+    for p in range(P):
+        assert torch.equal(out[p], full[p] if p in players else fill[p]), p
+
+
+class _HostSingle:
+    """Host replay of TronSinglePlayerVectorEnv(opponent="territory"): learner = player 0, done resets."""
+
+    def __init__(self, N, P, B, sh, sd, seed, noise):
+        self.loop = avoid_ref.HostLoop(N, P, B, sh, sd)
+        self.seed, self.noise = seed, noise
+
+    def step(self, action):
+        from oracle import oracle as O
+        st = self.loop.st
+        act = R.decide(st.N, st.board, st.heads, st.dirs, st.deaths, np.arange(st.B), st.tcount, self.seed, self.noise,
+                       players=range(1, st.P))
+        st.tcount += 1
+        act[0] = np.array([0, 1, -1], np.int8)[action]
+        rew, term, _ = O.tron_step(st, act)
+        done = (term != 0) | (st.deaths[0] != 0)
+        self.loop.reset_games(done)
+        return rew[0].copy(), done.astype(np.uint8), term.copy()
+
+
+def test_single_player_env_with_territory_opponents_matches_host_replay():
+    from colosseumrl_amd.vector import TronSinglePlayerVectorEnv
+    N, P, B, K, seed, noise = 15, 4, 96, 300, 21, 0.1
+    env = TronSinglePlayerVectorEnv(N, P, B, noise=noise, seed=seed, device="cuda:0", opponent="territory")
+    host = _HostSingle(N, P, B, env.batch.start_heads, env.batch.start_dirs, seed, noise)
+    env.reset()
+    rng = np.random.default_rng(0)
+    n_done = 0
+    for t in range(K):
+        if t % 3 == 0:                                          # the learner mixes its own territory rule with random moves
+            a = env.territory_action().cpu().numpy()
+            st = host.loop.st
+            assert np.array_equal(a, R.greedy_action(N, st.board, st.heads, st.dirs, st.deaths, np.zeros(B, np.int64)))
+        else:
+            a = rng.integers(0, 3, size=B)
+        obs, rew, done, info = env.step(torch.from_numpy(a).cuda())
+        hr, hd, ht = host.step(a)
+        assert np.array_equal(rew.cpu().numpy(), hr) and np.array_equal(done.cpu().numpy(), hd)
+        assert np.array_equal(info["terminal"].cpu().numpy(), ht)
+        st = host.loop.st
+        assert np.array_equal(obs["board"].reshape(B, -1).cpu().numpy(), st.board)
+        assert np.array_equal(obs["heads"].cpu().numpy(), st.heads) and np.array_equal(obs["deaths"].cpu().numpy(), st.deaths)
+        n_done += int(hd.sum())
+    assert n_done > 0
+
+
+def test_default_opponent_is_unchanged():
+    from colosseumrl_amd.vector import TronSinglePlayerVectorEnv
+    a = TronSinglePlayerVectorEnv(15, 4, 64, noise=0.1, seed=3, device="cuda:0")
+    b = TronSinglePlayerVectorEnv(15, 4, 64, noise=0.1, seed=3, device="cuda:0", opponent="avoid")
+    a.reset(), b.reset()
+    act = torch.zeros(64, dtype=torch.int64, device="cuda:0")
+    for _ in range(30):
+        a.step(act), b.step(act)
+    assert torch.equal(a.batch.board, b.batch.board) and torch.equal(a.done, b.done)
+
+
+def test_territory_env_graph_replay():
+    from colosseumrl_amd.vector import TronSinglePlayerVectorEnv
+    N, P, B, seed, noise = 19, 3, 64, 8, 0.1
+    env = TronSinglePlayerVectorEnv(N, P, B, noise=noise, seed=seed, device="cuda:0", opponent="territory")
+    host = _HostSingle(N, P, B, env.batch.start_heads, env.batch.start_dirs, seed, noise)
+    env.reset()
+    action = torch.zeros((B,), dtype=torch.int64, device="cuda:0")
+    rng = np.random.default_rng(1)
+    a = rng.integers(0, 3, size=B)
+    action.copy_(torch.from_numpy(a))
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        env.step(action)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    host.step(a)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):                                   # a chain of two kernels: no parallel branches
+        obs, rew, done, info = env.step(action)
+    for _ in range(25):
+        a = rng.integers(0, 3, size=B)
+        action.copy_(torch.from_numpy(a))
+        g.replay()
+        hr, hd, _ = host.step(a)
+        torch.cuda.synchronize()
+        assert np.array_equal(rew.cpu().numpy(), hr) and np.array_equal(done.cpu().numpy(), hd)
+        assert np.array_equal(obs["board"].reshape(B, -1).cpu().numpy(), host.loop.st.board)
+        assert np.array_equal(obs["heads"].cpu().numpy(), host.loop.st.heads)
+
+
+def _first_episode_win_rate(policy, batch, seed, max_t=400):
+    from colosseumrl_amd.vector import TronSinglePlayerVectorEnv
+    env = TronSinglePlayerVectorEnv(15, 4, batch, noise=0.1, seed=seed, device="cuda:0")
+    env.reset()
+    won = torch.zeros(batch, dtype=torch.bool, device="cuda:0")
+    live = torch.ones(batch, dtype=torch.bool, device="cuda:0")
+    gen = torch.Generator(device="cuda:0").manual_seed(seed)
+    for t in range(max_t):
+        _, reward, done, _ = env.step(policy(env, gen))
+        won |= live & (reward == 10)
+        live &= done == 0
+        if t % 20 == 19 and not bool(live.any()):
+            break
+    assert not bool(live.any())
+    return won.double().mean().item()
+
+
+def test_territory_learner_beats_avoid_and_random_learners():
+    """2,048 games of 15x15, 4 players, avoid opponents with noise 0.1, identical seeds: first-episode win rates."""
+    def territory(env, gen):
+        return env.territory_action()
+
+    def avoid(env, gen):
+        act = env.batch.sample_avoid(99, env.noise, players=[0], advance=False)[0].to(torch.int64)
+        return torch.where(act < 0, 2, act)
+
+    def uniform(env, gen):
+        return torch.randint(0, 3, (env.num_envs,), device="cuda:0", generator=gen)
+
+    w = {name: _first_episode_win_rate(pol, 2048, 5) for name, pol in (("territory", territory), ("avoid", avoid), ("random", uniform))}
+    print("first-episode win rates:", w)
+    assert w["territory"] > w["avoid"] and w["territory"] > w["random"], w

@@ -11,11 +11,12 @@ No CPU path exists here: constructing a stepper without a visible MI355X raises.
 from typing import Optional, Sequence
 
 import ctypes as C
+import functools
 
 import torch
 
 from . import _native
-from ._native import CRL_STEP_AUTO_RESET, CRL_STEP_RANK_ACTION, TronStats, TTTStats, check
+from ._native import CRL_STEP_AUTO_RESET, CRL_STEP_RANK_ACTION, NativeError, check
 from .envs.tron import layout as tron_layout
 
 
@@ -43,8 +44,8 @@ _STEP_KERNEL_FLAGS = {"auto": 0, "bytes": _native.CRL_STEP_BYTES, "staged": _nat
 
 
 class _DevGuard:
-    """``torch.cuda.device(dev)`` only when `dev` is not already current (the context manager costs several
-    microseconds per call, which is visible next to a 20-step rollout launch)."""
+    """Makes `dev` the current device for a block, only when it is not already (torch's own context manager costs
+    several microseconds per call, which is visible next to a 20-step rollout launch)."""
     __slots__ = ("dev", "prev")
 
     def __init__(self, dev):
@@ -71,71 +72,67 @@ def _want(t: torch.Tensor, dtype, shape, device, name):
     return t
 
 
-def _playout_args(playouts: int, candidates: Optional[torch.Tensor], B: int, device):
-    """(A, R) of a playout call, checked as the C entries check them (crl_*_playout: A, R in [1, 65535]); candidates int32
-    [B, A] or None (A = 1)."""
-    if isinstance(playouts, bool) or not isinstance(playouts, int) or not 1 <= playouts <= 65535:
-        raise ValueError("playouts must be an int in [1, 65535], got %r" % (playouts,))
-    if candidates is None:
-        return 1, playouts
-    if not isinstance(candidates, torch.Tensor) or candidates.dim() != 2 or candidates.shape[0] != B:
+def _seed(seed: int) -> int:
+    """the seed as the C entries take it (uint64)"""
+    return seed & (2 ** 64 - 1)
+
+
+def _int_in(name: str, v, lo: int, hi: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError("%s must be an int in [%d, %d], got %r" % (name, lo, hi, v))
+    return v
+
+
+def _unit(name: str, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) <= 1.0:       # (NaN fails the comparison)
+        raise ValueError("%s must be a number in [0, 1], got %r" % (name, v))
+    return float(v)
+
+
+def _candidates(cand: Optional[torch.Tensor], B: int, device, max_a: int) -> int:
+    """A of a playout / territory call, checked as the C entries check it (A in [1, max_a]: 65535 for crl_*_playout, 16 for
+    crl_tron_territory); candidates int32 [B, A] or None (A = 1)."""
+    if cand is None:
+        return 1
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or cand.shape[0] != B:
         raise ValueError("candidates must be an int32 tensor of shape (%d, A)" % B)
-    A = int(candidates.shape[1])
-    if not 1 <= A <= 65535:
-        raise ValueError("candidates must have 1..65535 columns, got %d" % A)
-    _want(candidates, torch.int32, (B, A), device, "candidates")
-    return A, playouts
+    A = int(cand.shape[1])
+    if not 1 <= A <= max_a:
+        raise ValueError("candidates must have 1..%d columns, got %d" % (max_a, A))
+    _want(cand, torch.int32, (B, A), device, "candidates")
+    return A
 
 
-def _playout_out(out: Optional[dict], B: int, A: int, P: int, device, score: bool):
-    """the output dict of a playout call: fresh, or `out` with every buffer checked"""
-    shapes = {"wins": (B, A, P), "draws": (B, A), "played": (B, A), "len_sum": (B, A)}
-    if score:
-        shapes["score_sum"] = (B, A, 4)
-    if out is None:
-        return {k: torch.empty(v, dtype=torch.int32, device=device) for k, v in shapes.items()}
-    for k, v in shapes.items():
-        if k not in out:
-            raise ValueError("out lacks %r" % k)
-        _want(out[k], torch.int32, v, device, "out[%r]" % k)
-    return out
-
-
-def _tron_playout_out(out: Optional[dict], B: int, A: int, P: int, device):
-    """the output dict of a Tron playout call: fresh, or `out` with every buffer checked"""
-    shapes = {"wins": (B, A, P), "played": (B, A), "len_sum": (B, A), "ret_sum": (B, A)}
-    if out is None:
-        return {k: torch.empty(v, dtype=torch.int32, device=device) for k, v in shapes.items()}
-    for k, v in shapes.items():
-        if k not in out:
-            raise ValueError("out lacks %r" % k)
-        _want(out[k], torch.int32, v, device, "out[%r]" % k)
-    return out
-
-
-def _territory_args(candidates: Optional[torch.Tensor], seat: Optional[torch.Tensor], B: int, device) -> int:
-    """A of a territory call, checked as the C entry checks it (crl_tron_territory: A in [1, 16]); candidates int32 [B, A] or
-    None (A = 1); seat int8 [B] or None."""
+def _seat(seat: Optional[torch.Tensor], B: int, device):
+    """seat int8 [B], or None (player 0)"""
     if seat is not None:
         if not isinstance(seat, torch.Tensor):
             raise ValueError("seat must be an int8 tensor of shape (%d,)" % B)
         _want(seat, torch.int8, (B,), device, "seat")
-    if candidates is None:
-        return 1
-    if not isinstance(candidates, torch.Tensor) or candidates.dim() != 2 or candidates.shape[0] != B:
-        raise ValueError("candidates must be an int32 tensor of shape (%d, A)" % B)
-    A = int(candidates.shape[1])
-    if not 1 <= A <= 16:
-        raise ValueError("candidates must have 1..16 columns, got %d" % A)
-    _want(candidates, torch.int32, (B, A), device, "candidates")
-    return A
+    return seat
 
 
-def _territory_out(out: Optional[dict], B: int, A: int, P: int, device):
-    """the output dict of a territory call: fresh, or `out` with every buffer checked"""
-    spec = {"area": (torch.int32, (B, A, P)), "info": (torch.uint8, (B, A))}
+def _player_mask(players, P: int, who: str) -> int:
+    """bit p set for every player id in `players` (None: all P)"""
+    if players is None:
+        return (1 << P) - 1
+    mask = 0
+    for p in players:
+        if not 0 <= int(p) < P:
+            raise ValueError("%s: player %d out of range 0..%d" % (who, int(p), P - 1))
+        mask |= 1 << int(p)
+    return mask
+
+
+def _alloc(spec: dict, device, make=torch.empty) -> dict:
+    """a fresh dict of buffers; spec: name -> (dtype, shape)"""
+    return {k: make(shape, dtype=dt, device=device) for k, (dt, shape) in spec.items()}
+
+
+def _out_dict(out: Optional[dict], spec: dict, device) -> dict:
+    """the output dict of a call: fresh, or `out` with every buffer checked"""
     if out is None:
-        return {k: torch.empty(shape, dtype=dt, device=device) for k, (dt, shape) in spec.items()}
+        return _alloc(spec, device)
     for k, (dt, shape) in spec.items():
         if k not in out:
             raise ValueError("out lacks %r" % k)
@@ -164,6 +161,33 @@ class _Ctx:
                 self.handle = None
         except Exception:  # interpreter shutdown
             pass
+
+
+class _Stepper:
+    """What every stepper class shares: how it is constructed (`_open`) and how it launches (`_call`)."""
+
+    def _open(self, device, first_env_id: int, create: str, *args):
+        """Resolves `device` (a ROCm device; the current one when no index is given), makes the context with the entry
+        `create(*args, &handle)` and sets `_lib`, `_ctx` and `first_env_id`."""
+        self._lib = _native.require_gpu()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise NativeError("%s needs a ROCm device; there is no CPU path" % type(self).__name__)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        handle = C.c_void_p()
+        with torch.cuda.device(self.device):     # (a context may keep tables on the device: TicTacToe's win masks do)
+            check(getattr(self._lib, create)(*args, C.byref(handle)), create)
+        self._ctx = _Ctx(handle)
+        self.first_env_id = int(first_env_id)
+
+    def _call(self, name: str, *args):
+        """One launch: the entry `name(ctx, B, *args, stream)` on torch's CURRENT stream of the stepper's device, which is
+        made current for the call only where it is not (`_DevGuard`)."""
+        with _DevGuard(self.device):
+            rc = getattr(self._lib, name)(self._ctx.handle, self.B, *args, _stream())
+        if rc:
+            check(rc, name)
 
 
 class _Waitable:
@@ -200,34 +224,71 @@ class _Waitable:
             check(rc, "crl_stream_wait_mapped")
 
 
-class TronBatch(_Waitable):
+def _per_game(B, P):
+    return (B,)
+
+
+def _per_player(B, P):
+    return (P, B)
+
+
+_STAT_ATTR = {"results": "_results", "packed": "_packed"}     # the two struct fields that are private attributes
+
+
+class _RolloutStepper(_Stepper, _Waitable):
+    """A stepper with fused rollouts: ``wait()`` and the rollout statistics.  A class lists its statistics columns ONCE, in
+    `STATS`: column -> (dtype, shape as a function of (B, P)), in the order of the fields of `STATS_STRUCT`, the ctypes
+    struct the C entries take by value (checked when the class is made).  The tensors (attributes of the column's name;
+    ``_results`` / ``_packed`` for those two), `_stats()` and `reset_stats()` all come from that table."""
+    STATS_STRUCT = None
+    STATS = {}
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        fields = [name for name, _ in cls.STATS_STRUCT._fields_]
+        if list(cls.STATS) != fields:
+            raise TypeError("%s.STATS lists %s, %s has %s" % (cls.__name__, list(cls.STATS), cls.STATS_STRUCT.__name__, fields))
+
+    @classmethod
+    def _stat_spec(cls, B: int, P: int) -> dict:
+        """attribute -> (dtype, shape) of the statistics tensors of B games with P players"""
+        return {_STAT_ATTR.get(k, k): (dt, shape(B, P)) for k, (dt, shape) in cls.STATS.items()}
+
+    def _stat_tensors(self):
+        return [getattr(self, _STAT_ATTR.get(k, k)) for k in self.STATS]
+
+    def _stats(self):
+        return self.STATS_STRUCT(*[t.data_ptr() for t in self._stat_tensors()])
+
+    def reset_stats(self):
+        for t in self._stat_tensors():
+            t.zero_()
+
+
+class TronBatch(_RolloutStepper):
     """B games of N x N Tron with P players (reference: envs/tron/TronGridEnvironment.py).
 
     State tensors (device):
       board  int8 [B, N*N]; heads int16 [P, B]; dirs int8 [P, B]; deaths int8 [P, B]
     """
+    STATS_STRUCT = _native.TronStats
+    STATS = {"tcount": (torch.int32, _per_game), "tstep": (torch.int32, _per_game), "n_episodes": (torch.int32, _per_game),
+             "win_count": (torch.int32, _per_player), "len_sum": (torch.int32, _per_game), "ret_sum": (torch.int32, _per_player),
+             "last_winners": (torch.uint8, _per_game), "last_len": (torch.int16, _per_game),
+             "results": (torch.int32, lambda B, P: (B, 3 + 2 * P)),               # packed by the rollout kernels
+             # the same row in 16-bit fields (include/colosseum_hip.h, crl_tron_stats.packed): 16 bytes per game at P = 4
+             "packed": (torch.int16, lambda B, P: (B, (4 + P + 1) & ~1))}
 
     def __init__(self, board_size: int = 19, num_players: int = 4, batch: int = 1, device="cuda",
                  ring_offset: int = 1, spawn_offset: int = 2,
                  start: Optional[Sequence[Sequence[int]]] = None, first_env_id: int = 0):
-        lib = _native.require_gpu()
         self.N, self.P, self.B = int(board_size), int(num_players), int(batch)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _native.NativeError("TronBatch needs a ROCm device; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
         if start is None:
             start = tron_layout.start_positions(self.N, self.P, ring_offset, [spawn_offset] * self.P)
         self.start_heads = [int(h) for h in start[0]]
         self.start_dirs = [int(d) for d in start[1]]
-        sh = (C.c_int16 * self.P)(*self.start_heads)
-        sd = (C.c_int8 * self.P)(*self.start_dirs)
-        handle = C.c_void_p()
-        check(lib.crl_tron_create(self.N, self.P, sh, sd, C.byref(handle)), "crl_tron_create")
-        self._ctx = _Ctx(handle)
-        self._lib = lib
-        self.first_env_id = int(first_env_id)
+        self._open(device, first_env_id, "crl_tron_create", self.N, self.P, (C.c_int16 * self.P)(*self.start_heads),
+                   (C.c_int8 * self.P)(*self.start_dirs))
         dev, B, P, NN = self.device, self.B, self.P, self.N * self.N
         with torch.cuda.device(dev):
             self.board = torch.zeros((B, NN), dtype=torch.int8, device=dev)
@@ -237,35 +298,23 @@ class TronBatch(_Waitable):
             self.rewards = torch.zeros((P, B), dtype=torch.int8, device=dev)
             self.terminal = torch.zeros((B,), dtype=torch.uint8, device=dev)
             self.winners = torch.zeros((B,), dtype=torch.uint8, device=dev)
-            # rollout bookkeeping
-            self.tcount = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.tstep = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.n_episodes = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.win_count = torch.zeros((P, B), dtype=torch.int32, device=dev)
-            self.len_sum = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.ret_sum = torch.zeros((P, B), dtype=torch.int32, device=dev)
-            self.last_winners = torch.zeros((B,), dtype=torch.uint8, device=dev)
-            self.last_len = torch.zeros((B,), dtype=torch.int16, device=dev)
-            self._results = torch.zeros((B, 3 + 2 * P), dtype=torch.int32, device=dev)   # packed by the rollout kernels
-            # the same row in 16-bit fields (include/colosseum_hip.h, crl_tron_stats.packed): 16 bytes per game at P = 4
-            self._packed = torch.zeros((B, (4 + P + 1) & ~1), dtype=torch.int16, device=dev)
+            self.__dict__.update(_alloc(self._stat_spec(B, P), dev, torch.zeros))       # rollout bookkeeping
         self._stat_steps = 0                      # rollout steps the running totals span (since reset_stats)
         self._rollout_args = None
         self.reset()
         self._open_wait()
 
+    def _state(self):
+        return (_ptr(self.board), _ptr(self.heads), _ptr(self.dirs), _ptr(self.deaths))
+
     # -- new_state for all (or masked) games
     def reset(self, mask: Optional[torch.Tensor] = None):
         if mask is not None:
             _want(mask, torch.uint8, (self.B,), self.device, "mask")
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_tron_reset(self._ctx.handle, self.B, _ptr(mask), _ptr(self.board), _ptr(self.heads),
-                                           _ptr(self.dirs), _ptr(self.deaths), _stream()), "crl_tron_reset")
+        self._call("crl_tron_reset", _ptr(mask), *self._state())
 
     def reset_stats(self):
-        for t in (self.tcount, self.tstep, self.n_episodes, self.win_count, self.len_sum, self.ret_sum,
-                  self.last_winners, self.last_len, self._results, self._packed):
-            t.zero_()
+        super().reset_stats()
         self._stat_steps = 0
 
     # -- next_state for all games; actions int8 [P, B] in {0, +1, -1}
@@ -274,17 +323,15 @@ class TronBatch(_Waitable):
         kernel (byte probes in HBM); "bytes" / "staged" are accepted for callers that pinned one of the two kernels it had."""
         _want(actions, torch.int8, (self.P, self.B), self.device, "actions")
         flags = (CRL_STEP_AUTO_RESET if auto_reset else 0) | _STEP_KERNEL_FLAGS[kernel]
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_tron_step(self._ctx.handle, self.B, _ptr(self.board), _ptr(self.heads), _ptr(self.dirs),
-                                          _ptr(self.deaths), _ptr(actions), _ptr(self.rewards), _ptr(self.terminal),
-                                          _ptr(self.winners), flags, _stream()),
-                  "crl_tron_step")
+        self._call("crl_tron_step", *self._state(), _ptr(actions), _ptr(self.rewards), _ptr(self.terminal),
+                   _ptr(self.winners), flags)
         return self.rewards, self.terminal, self.winners
 
-    def _stats(self):
-        return TronStats(*[t.data_ptr() for t in (self.tcount, self.tstep, self.n_episodes, self.win_count,
-                                                   self.len_sum, self.ret_sum, self.last_winners, self.last_len,
-                                                   self._results, self._packed)])
+    def _bind_rollout(self):
+        """the state / statistics arguments of the rollout entries: the tensors are never reallocated, so they are bound
+        once, at the first rollout"""
+        self._rollout_args = (*self._state(), self._stats())
+        return self._rollout_args
 
     # -- T fused random-agent steps with auto-reset
     def rollout(self, steps: int, seed: int = 0, use_lds: bool = True, kernel: str = "auto", events=None):
@@ -298,31 +345,30 @@ class TronBatch(_Waitable):
         flags = _ROLLOUT_KERNEL_FLAGS[kernel]
         if not use_lds:
             flags = _native.CRL_ROLLOUT_NO_LDS
-        if self._rollout_args is None:       # the state / statistics tensors are never reallocated: bind them once
-            self._rollout_args = (_ptr(self.board), _ptr(self.heads), _ptr(self.dirs), _ptr(self.deaths), self._stats())
+        steps, args = int(steps), self._rollout_args or self._bind_rollout()
+        # `_call` written out: this launch is the benchmark's timed region, where one more Python frame per launch shows,
+        # and the timed entry takes its events after the stream
         with _DevGuard(self.device):
             if events is None:
-                rc = self._lib.crl_tron_rollout(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id, int(steps),
-                                                *self._rollout_args, flags, _stream())
+                rc = self._lib.crl_tron_rollout(self._ctx.handle, self.B, _seed(seed), self.first_env_id, steps, *args, flags,
+                                                _stream())
             else:
-                handles = [C.c_void_p(e.cuda_event) if e is not None else None for e in events]
                 if any(e is not None and not e.cuda_event for e in events):
                     raise ValueError("rollout(events=...): record() each event once before passing it (torch creates the "
                                      "HIP event lazily)")
-                rc = self._lib.crl_tron_rollout_timed(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
-                                                      int(steps), *self._rollout_args, flags, _stream(), handles[0], handles[1])
+                handles = [C.c_void_p(e.cuda_event) if e is not None else None for e in events]
+                rc = self._lib.crl_tron_rollout_timed(self._ctx.handle, self.B, _seed(seed), self.first_env_id, steps, *args,
+                                                      flags, _stream(), handles[0], handles[1])
         if rc:
             check(rc, "crl_tron_rollout")
-        self._stat_steps += int(steps)
+        self._stat_steps += steps
 
     def check_state(self) -> int:
         """Number of games whose state breaks the invariant of every reset / step / rollout product that the LDS
         rollout kernels rely on (heads on the board, ``board[heads[p]] == p + 1``); 0 unless states were hand-made.
         Synchronises."""
         bad = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_tron_check_state(self._ctx.handle, self.B, _ptr(self.board), _ptr(self.heads), _ptr(bad),
-                                                 _stream()), "crl_tron_check_state")
+        self._call("crl_tron_check_state", _ptr(self.board), _ptr(self.heads), _ptr(bad))
         return int(bad.item())
 
     # -- the rollout's random agent for one step: int8 [P][B] actions in the step() encoding
@@ -331,9 +377,7 @@ class TronBatch(_Waitable):
         moves on, so ``step(sample(seed), auto_reset=True)`` T times == ``rollout(T, seed)``.  Overwrite the rows of
         the players you control."""
         act = torch.empty((self.P, self.B), dtype=torch.int8, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_tron_sample(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
-                                            _ptr(self.tcount), int(advance), _ptr(act), _stream()), "crl_tron_sample")
+        self._call("crl_tron_sample", _seed(seed), self.first_env_id, _ptr(self.tcount), int(advance), _ptr(act))
         return act
 
     # -- the reference's scripted opponent (SimpleAvoidAgent) for one step: int8 [P][B] actions in the step() encoding
@@ -345,23 +389,17 @@ class TronBatch(_Waitable):
         (int8 [P, B]; a new zeroed tensor when None) are written, so a caller writes its learner's row and lets this fill
         in the opponents.  With ``advance`` the counter moves on, so ``step(sample_avoid(seed, noise), auto_reset=True)``
         T times == ``rollout_avoid(T, seed, noise)``."""
-        P, B = self.P, self.B
+        return self._sample_scripted("sample_avoid", seed, noise, players, out, advance)
+
+    def _sample_scripted(self, agent: str, seed, noise, players, out, advance):
+        """`sample_avoid` / `sample_territory`: the entry crl_tron_<agent> for the rows of `players` in `out`"""
+        mask = _player_mask(players, self.P, agent)
         if out is None:
-            out = torch.zeros((P, B), dtype=torch.int8, device=self.device)
+            out = torch.zeros((self.P, self.B), dtype=torch.int8, device=self.device)
         else:
-            _want(out, torch.int8, (P, B), self.device, "out")
-        mask = (1 << P) - 1
-        if players is not None:
-            mask = 0
-            for p in players:
-                if not 0 <= int(p) < P:
-                    raise ValueError("sample_avoid: player %d out of range 0..%d" % (int(p), P - 1))
-                mask |= 1 << int(p)
-        with _DevGuard(self.device):
-            check(self._lib.crl_tron_sample_avoid(self._ctx.handle, B, seed & (2 ** 64 - 1), self.first_env_id, _ptr(self.tcount),
-                                                  int(advance), float(noise), mask, _ptr(self.board), _ptr(self.heads),
-                                                  _ptr(self.dirs), _ptr(self.deaths), _ptr(out), _stream()),
-                  "crl_tron_sample_avoid")
+            _want(out, torch.int8, (self.P, self.B), self.device, "out")
+        self._call("crl_tron_" + agent, _seed(seed), self.first_env_id, _ptr(self.tcount), int(advance), float(noise), mask,
+                   *self._state(), _ptr(out))
         return out
 
     # -- batched playouts for one seat from every game's position (flat Monte Carlo's evaluation)
@@ -377,29 +415,29 @@ class TronBatch(_Waitable):
         state is only read).  Returns {'wins' int32 [B, A, P], 'played', 'len_sum', 'ret_sum' int32 [B, A]} (``ret_sum``:
         the seat's summed rewards; skipped rows are zeros); ``out`` reuses such a dict.  No host synchronisation;
         capturable into a graph."""
-        A, R = _playout_args(playouts, candidates, self.B, self.device)
+        R = _int_in("playouts", playouts, 1, 65535)
+        A = _candidates(candidates, self.B, self.device, 65535)
         if agent not in ("random", "avoid"):
             raise ValueError("agent must be 'random' or 'avoid', got %r" % (agent,))
         if until not in ("end", "seat_done"):
             raise ValueError("until must be 'end' or 'seat_done', got %r" % (until,))
-        if isinstance(noise, bool) or not isinstance(noise, (int, float)) or not 0.0 <= float(noise) <= 1.0:
-            raise ValueError("noise must be a number in [0, 1], got %r" % (noise,))
-        if isinstance(max_steps, bool) or not isinstance(max_steps, int) or not 0 <= max_steps <= 65535:
-            raise ValueError("max_steps must be an int in [0, 65535], got %r" % (max_steps,))
-        if seat is not None:
-            if not isinstance(seat, torch.Tensor):
-                raise ValueError("seat must be an int8 tensor of shape (%d,)" % self.B)
-            _want(seat, torch.int8, (self.B,), self.device, "seat")
-        out = _tron_playout_out(out, self.B, A, self.P, self.device)
+        noise = _unit("noise", noise)
+        _int_in("max_steps", max_steps, 0, 65535)
+        _seat(seat, self.B, self.device)
+        i32, BA = torch.int32, (self.B, A)
+        out = _out_dict(out, {"wins": (i32, BA + (self.P,)), "played": (i32, BA), "len_sum": (i32, BA), "ret_sum": (i32, BA)},
+                        self.device)
         flags = (_native.CRL_PLAYOUT_AVOID if agent == "avoid" else 0) | \
                 (_native.CRL_PLAYOUT_UNTIL_SEAT_DONE if until == "seat_done" else 0)
-        with _DevGuard(self.device):
-            check(self._lib.crl_tron_playout(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
-                                             _ptr(self.board), _ptr(self.heads), _ptr(self.dirs), _ptr(self.deaths),
-                                             _ptr(self.tcount), _ptr(seat), _ptr(candidates), A, R, float(noise), max_steps,
-                                             _ptr(out["wins"]), _ptr(out["played"]), _ptr(out["len_sum"]),
-                                             _ptr(out["ret_sum"]), flags, _stream()), "crl_tron_playout")
+        self._call("crl_tron_playout", _seed(seed), self.first_env_id, *self._state(), _ptr(self.tcount), _ptr(seat),
+                   _ptr(candidates), A, R, noise, max_steps, _ptr(out["wins"]), _ptr(out["played"]), _ptr(out["len_sum"]),
+                   _ptr(out["ret_sum"]), flags)
         return out
+
+    @functools.cached_property
+    def _moves3(self):
+        """int32 [B, 3]: the three first actions [0, 1, 2] of every game (made at the first use)"""
+        return torch.arange(3, dtype=torch.int32, device=self.device).expand(self.B, 3).contiguous()
 
     def flat_mc_action(self, playouts: int, seed: int = 0, agent: str = "random", noise: float = 0.1,
                        seat: Optional[torch.Tensor] = None, until: str = "end", max_steps: int = 0,
@@ -408,11 +446,8 @@ class TronBatch(_Waitable):
         ``ret_sum``, the best action (ties: the lowest) as int64 [B] in {0, 1, 2} for ``step_single``; -1 where every row
         was skipped (the seat is dead or the game is over).  ``out``: the playout dict to reuse.  No host
         synchronisation; capturable."""
-        _playout_args(playouts, None, self.B, self.device)
-        cands = getattr(self, "_moves3", None)
-        if cands is None:
-            cands = torch.arange(3, dtype=torch.int32, device=self.device).expand(self.B, 3).contiguous()
-            self._moves3 = cands
+        _int_in("playouts", playouts, 1, 65535)
+        cands = self._moves3
         o = self.playout(playouts, cands, seed, agent, noise, seat, until, max_steps, out)
         # (returns go below -1: the pick compares mean returns shifted above _flat_mc_pick's -1 for unplayed rows)
         mean = o["ret_sum"].to(torch.float64) / float(playouts)
@@ -428,12 +463,10 @@ class TronBatch(_Waitable):
         {'area' int32 [B, A, P], 'info' uint8 [B, A]} -- info bit 0: the row was evaluated, bit 1: the forced cell is off
         the board or occupied; skipped rows are zeros; ``out`` reuses such a dict.  The state is only read.  No host
         synchronisation; capturable into a graph."""
-        A = _territory_args(candidates, seat, self.B, self.device)
-        out = _territory_out(out, self.B, A, self.P, self.device)
-        with _DevGuard(self.device):
-            check(self._lib.crl_tron_territory(self._ctx.handle, self.B, _ptr(self.board), _ptr(self.heads), _ptr(self.dirs),
-                                               _ptr(self.deaths), _ptr(seat), _ptr(candidates), A, _ptr(out["area"]),
-                                               _ptr(out["info"]), _stream()), "crl_tron_territory")
+        _seat(seat, self.B, self.device)
+        A = _candidates(candidates, self.B, self.device, 16)
+        out = _out_dict(out, {"area": (torch.int32, (self.B, A, self.P)), "info": (torch.uint8, (self.B, A))}, self.device)
+        self._call("crl_tron_territory", *self._state(), _ptr(seat), _ptr(candidates), A, _ptr(out["area"]), _ptr(out["info"]))
         return out
 
     def territory_action(self, seat: Optional[torch.Tensor] = None, out: Optional[dict] = None) -> torch.Tensor:
@@ -442,11 +475,7 @@ class TronBatch(_Waitable):
         (ties: the lowest) as int64 [B] in {0, 1, 2} for ``step_single`` -- the noise-free rule of ``sample_territory``;
         -1 where every row was skipped (the seat is dead).  ``out``: the territory dict to reuse.  No host
         synchronisation; capturable."""
-        cands = getattr(self, "_moves3", None)
-        if cands is None:
-            cands = torch.arange(3, dtype=torch.int32, device=self.device).expand(self.B, 3).contiguous()
-            self._moves3 = cands
-        o = self.territory(cands, seat, out)
+        o = self.territory(self._moves3, seat, out)
         area = o["area"].to(torch.int64)                                          # [B, 3, P]
         who = (torch.zeros((self.B,), dtype=torch.int64, device=self.device) if seat is None else seat.to(torch.int64))
         who = who.clamp(0, self.P - 1).view(self.B, 1, 1).expand(self.B, 3, 1)
@@ -467,39 +496,17 @@ class TronBatch(_Waitable):
         first action with the best Voronoi score (own area minus the best rival's), decided on the current (pre-step)
         boards.  ``players`` / ``out`` / ``advance`` as ``sample_avoid``: only the named players' rows of ``out`` (int8
         [P, B]; a new zeroed tensor when None) are written."""
-        P, B = self.P, self.B
-        if isinstance(noise, bool) or not isinstance(noise, (int, float)) or not 0.0 <= float(noise) <= 1.0:
-            raise ValueError("noise must be a number in [0, 1], got %r" % (noise,))
-        mask = (1 << P) - 1
-        if players is not None:
-            mask = 0
-            for p in players:
-                if not 0 <= int(p) < P:
-                    raise ValueError("sample_territory: player %d out of range 0..%d" % (int(p), P - 1))
-                mask |= 1 << int(p)
-        if out is None:
-            out = torch.zeros((P, B), dtype=torch.int8, device=self.device)
-        else:
-            _want(out, torch.int8, (P, B), self.device, "out")
-        with _DevGuard(self.device):
-            check(self._lib.crl_tron_sample_territory(self._ctx.handle, B, seed & (2 ** 64 - 1), self.first_env_id,
-                                                      _ptr(self.tcount), int(advance), float(noise), mask, _ptr(self.board),
-                                                      _ptr(self.heads), _ptr(self.dirs), _ptr(self.deaths), _ptr(out), _stream()),
-                  "crl_tron_sample_territory")
-        return out
+        _unit("noise", noise)          # (ValueError here; sample_avoid leaves a bad noise to its C entry: NativeError)
+        return self._sample_scripted("sample_territory", seed, noise, players, out, advance)
 
     # -- T fused steps with every player on the avoid agent, auto-reset
     def rollout_avoid(self, steps: int, seed: int = 0, noise: float = 0.1):
         """``rollout`` with every player on the reference's ``SimpleAvoidAgent(noise)`` instead of the random agent
         (``crl_tron_rollout_avoid``): the same statistics tensors, ``results()`` rows and step counter."""
-        if self._rollout_args is None:
-            self._rollout_args = (_ptr(self.board), _ptr(self.heads), _ptr(self.dirs), _ptr(self.deaths), self._stats())
-        with _DevGuard(self.device):
-            rc = self._lib.crl_tron_rollout_avoid(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id, int(steps),
-                                                  float(noise), *self._rollout_args, 0, _stream())
-        if rc:
-            check(rc, "crl_tron_rollout_avoid")
-        self._stat_steps += int(steps)
+        steps = int(steps)
+        self._call("crl_tron_rollout_avoid", _seed(seed), self.first_env_id, steps, float(noise),
+                   *(self._rollout_args or self._bind_rollout()), 0)
+        self._stat_steps += steps
 
     # -- state_to_observation for all games; player int8 [B]
     def observe(self, player: torch.Tensor):
@@ -508,24 +515,16 @@ class TronBatch(_Waitable):
         oh = torch.empty_like(self.heads)
         od = torch.empty_like(self.dirs)
         ok = torch.empty_like(self.deaths)
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_tron_observe(self._ctx.handle, self.B, _ptr(self.board), _ptr(self.heads), _ptr(self.dirs),
-                                             _ptr(self.deaths), _ptr(player), _ptr(ob), _ptr(oh), _ptr(od), _ptr(ok),
-                                             _stream()), "crl_tron_observe")
+        self._call("crl_tron_observe", *self._state(), _ptr(player), _ptr(ob), _ptr(oh), _ptr(od), _ptr(ok))
         return {"board": ob.view(self.B, self.N, self.N), "heads": oh, "directions": od, "deaths": ok}
 
     # -- state_to_observation of every game for every observer in one pass
     def observe_all(self, out: Optional[dict] = None):
         """{'board': int8 [P, B, N, N], 'heads': int16 [P, P, B], 'directions' / 'deaths': int8 [P, P, B]};
         slice [p] is what player p observes.  Pass a previous result as `out` to reuse its buffers."""
-        P, B, N = self.P, self.B, self.N
-        if out is None:
-            out = self.observe_all_buffers()
-        with _DevGuard(self.device):
-            check(self._lib.crl_tron_observe_all(self._ctx.handle, B, _ptr(self.board), _ptr(self.heads), _ptr(self.dirs),
-                                                 _ptr(self.deaths), _ptr(out["board"]), _ptr(out["heads"]),
-                                                 _ptr(out["directions"]), _ptr(out["deaths"]), _stream()),
-                  "crl_tron_observe_all")
+        out = out or self.observe_all_buffers()
+        self._call("crl_tron_observe_all", *self._state(), _ptr(out["board"]), _ptr(out["heads"]), _ptr(out["directions"]),
+                   _ptr(out["deaths"]))
         return out
 
     # -- [sample ->] next_state -> state_to_observation of all observers, one launch
@@ -537,34 +536,40 @@ class TronBatch(_Waitable):
         {'board' [P, B, N, N], 'heads' [P, P, B], 'directions', 'deaths', 'rewards' [P, B], 'terminal' [B], 'winners' [B]}.
         Equals ``step(sample(seed) or actions, auto_reset); observe_all()``; one launch on every board size and player
         count.  Pass a previous result as `out` to reuse its observation buffers."""
-        P, B, N = self.P, self.B, self.N
         if actions is not None:
-            _want(actions, torch.int8, (P, B), self.device, "actions")
-        if out is None:
-            out = self.observe_all_buffers()
-        with _DevGuard(self.device):
-            check(self._lib.crl_tron_step_observe(self._ctx.handle, B, seed & (2 ** 64 - 1), self.first_env_id,
-                                                  _ptr(self.board), _ptr(self.heads), _ptr(self.dirs), _ptr(self.deaths),
-                                                  _ptr(actions), _ptr(self.tcount), _ptr(self.rewards), _ptr(self.terminal),
-                                                  _ptr(self.winners), _ptr(out["board"]), _ptr(out["heads"]),
-                                                  _ptr(out["directions"]), _ptr(out["deaths"]),
-                                                  CRL_STEP_AUTO_RESET if auto_reset else 0, _stream()), "crl_tron_step_observe")
+            _want(actions, torch.int8, (self.P, self.B), self.device, "actions")
+        out = out or self.observe_all_buffers()
+        self._call("crl_tron_step_observe", _seed(seed), self.first_env_id, *self._state(), _ptr(actions), _ptr(self.tcount),
+                   _ptr(self.rewards), _ptr(self.terminal), _ptr(self.winners), _ptr(out["board"]), _ptr(out["heads"]),
+                   _ptr(out["directions"]), _ptr(out["deaths"]), CRL_STEP_AUTO_RESET if auto_reset else 0)
         out["rewards"], out["terminal"], out["winners"] = self.rewards, self.terminal, self.winners
         return out
 
     def observe_all_buffers(self):
         P, B, N = self.P, self.B, self.N
-        return {"board": torch.empty((P, B, N, N), dtype=torch.int8, device=self.device),
-                "heads": torch.empty((P, P, B), dtype=torch.int16, device=self.device),
-                "directions": torch.empty((P, P, B), dtype=torch.int8, device=self.device),
-                "deaths": torch.empty((P, P, B), dtype=torch.int8, device=self.device)}
+        return _alloc({"board": (torch.int8, (P, B, N, N)), "heads": (torch.int16, (P, P, B)),
+                       "directions": (torch.int8, (P, P, B)), "deaths": (torch.int8, (P, P, B))}, self.device)
+
+    # -- the learner's action index + the opponents' actions -> next_state, done, reset of done games, one launch
+    def step_single(self, actions: torch.Tensor, learner_action: torch.Tensor, reward: torch.Tensor, done: torch.Tensor,
+                    terminal: torch.Tensor):
+        """One step of "learner = player 0 against scripted opponents" in every game (``crl_tron_step_single``): player 0
+        plays ``learner_action`` (int64 [B]: 0 forward, 1 right, 2 left), the others their rows of ``actions`` (int8 [P, B] in
+        the ``step`` encoding, e.g. filled by ``sample_avoid(players=...)``; row 0 is ignored); games that are done
+        restart.  Writes the caller's ``reward`` int8 [B] (the learner's), ``done`` uint8 [B] (learner dead or game over)
+        and ``terminal`` uint8 [B] (the game itself ended).  No host synchronisation; capturable into a graph."""
+        _want(actions, torch.int8, (self.P, self.B), self.device, "actions")
+        _want(learner_action, torch.int64, (self.B,), self.device, "learner_action")
+        _want(reward, torch.int8, (self.B,), self.device, "reward")
+        _want(done, torch.uint8, (self.B,), self.device, "done")
+        _want(terminal, torch.uint8, (self.B,), self.device, "terminal")
+        self._call("crl_tron_step_single", *self._state(), _ptr(actions), _ptr(learner_action), _ptr(reward), _ptr(done),
+                   _ptr(terminal))
 
     # -- compute_ranking for all games: int8 [P, B], 0 = best
     def ranking(self):
         out = torch.empty((self.P, self.B), dtype=torch.int8, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_tron_ranking(self._ctx.handle, self.B, _ptr(self.board), _ptr(self.deaths), _ptr(out),
-                                             _stream()), "crl_tron_ranking")
+        self._call("crl_tron_ranking", _ptr(self.board), _ptr(self.deaths), _ptr(out))
         return out
 
     def results(self, copy: bool = True):
@@ -603,30 +608,24 @@ class TronBatch(_Waitable):
         return torch.stack(cols, dim=1).to(torch.int16).contiguous()
 
 
-class TTTBatch(_Waitable):
+class TTTBatch(_RolloutStepper):
     """B games of n-player TicTacToe on a dims board, K in a row (reference: envs/tictactoe/*).
 
     State tensors (device): occ int32 [P, B] bit masks; winner int8 [B] (-1 none); to_move int8 [B].
     """
 
+    STATS_STRUCT = _native.TTTStats
+    STATS = {"tcount": (torch.int32, _per_game), "tstep": (torch.int32, _per_game), "n_episodes": (torch.int32, _per_game),
+             "win_count": (torch.int32, _per_player), "draw_count": (torch.int32, _per_game), "len_sum": (torch.int32, _per_game),
+             "results": (torch.int32, lambda B, P: (B, 3 + P))}
+
     def __init__(self, dims: Sequence[int] = (3, 3), k: int = 3, num_players: int = 2, batch: int = 1,
                  device="cuda", first_env_id: int = 0):
-        lib = _native.require_gpu()
         self.dims = tuple(int(d) for d in dims)
         d3 = (1,) * (3 - len(self.dims)) + self.dims
         self.K, self.P, self.B = int(k), int(num_players), int(batch)
         self.n_cells = d3[0] * d3[1] * d3[2]
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _native.NativeError("TTTBatch needs a ROCm device; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        handle = C.c_void_p()
-        with torch.cuda.device(self.device):     # (boards of <= 16 cells: the context keeps its win-mask table on THIS device)
-            check(lib.crl_ttt_create(d3[0], d3[1], d3[2], self.K, self.P, C.byref(handle)), "crl_ttt_create")
-        self._ctx = _Ctx(handle)
-        self._lib = lib
-        self.first_env_id = int(first_env_id)
+        self._open(device, first_env_id, "crl_ttt_create", d3[0], d3[1], d3[2], self.K, self.P)
         dev, B, P = self.device, self.B, self.P
         with torch.cuda.device(dev):
             self.occ = torch.zeros((P, B), dtype=torch.int32, device=dev)
@@ -635,18 +634,8 @@ class TTTBatch(_Waitable):
             self.reward = torch.zeros((B,), dtype=torch.int8, device=dev)
             self.terminal = torch.zeros((B,), dtype=torch.uint8, device=dev)
             self.winners = torch.zeros((B,), dtype=torch.int8, device=dev)
-            self.tcount = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.tstep = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.n_episodes = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.win_count = torch.zeros((P, B), dtype=torch.int32, device=dev)
-            self.draw_count = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.len_sum = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self._results = torch.zeros((B, 3 + P), dtype=torch.int32, device=dev)
+            self.__dict__.update(_alloc(self._stat_spec(B, P), dev, torch.zeros))
         self._open_wait()
-
-    def reset_stats(self):
-        for t in (self.tcount, self.tstep, self.n_episodes, self.win_count, self.draw_count, self.len_sum, self._results):
-            t.zero_()
 
     def lines(self):
         buf = (C.c_uint32 * 256)()
@@ -656,45 +645,40 @@ class TTTBatch(_Waitable):
     def reset(self, mask: Optional[torch.Tensor] = None):
         if mask is not None:
             _want(mask, torch.uint8, (self.B,), self.device, "mask")
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_ttt_reset(self._ctx.handle, self.B, _ptr(mask), _ptr(self.occ), _ptr(self.winner),
-                                          _ptr(self.to_move), _stream()), "crl_ttt_reset")
+        self._call("crl_ttt_reset", _ptr(mask), _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move))
 
     def step(self, action: torch.Tensor, auto_reset: bool = False):
         _want(action, torch.int8, (self.B,), self.device, "action")
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_ttt_step(self._ctx.handle, self.B, _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move),
-                                         _ptr(action), _ptr(self.reward), _ptr(self.terminal), _ptr(self.winners),
-                                         CRL_STEP_AUTO_RESET if auto_reset else 0, _stream()), "crl_ttt_step")
+        self._call("crl_ttt_step", _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move), _ptr(action), _ptr(self.reward),
+                   _ptr(self.terminal), _ptr(self.winners), CRL_STEP_AUTO_RESET if auto_reset else 0)
         return self.reward, self.terminal, self.winners
 
     def valid_mask(self):
         out = torch.empty((self.B,), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_ttt_valid(self._ctx.handle, self.B, _ptr(self.occ), _ptr(out), _stream()), "crl_ttt_valid")
+        self._call("crl_ttt_valid", _ptr(self.occ), _ptr(out))
         return out
 
     def sample(self, seed: int = 0, advance: bool = True):
         """The rollout's random agent for one step: int8 [B] flat cell (uniform over the empty cells, -1 on a full
         board) at each game's step counter; ``step(sample(seed), auto_reset=True)`` T times == ``rollout(T, seed)``."""
         act = torch.empty((self.B,), dtype=torch.int8, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_ttt_sample(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id, _ptr(self.occ),
-                                           _ptr(self.tcount), int(advance), _ptr(act), _stream()), "crl_ttt_sample")
+        self._call("crl_ttt_sample", _seed(seed), self.first_env_id, _ptr(self.occ), _ptr(self.tcount), int(advance), _ptr(act))
         return act
 
     def board(self, player: Optional[torch.Tensor] = None, rel_mod: Optional[int] = None):
         out = torch.empty((self.B, self.n_cells), dtype=torch.int8, device=self.device)
         if player is not None:
             _want(player, torch.int8, (self.B,), self.device, "player")
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_ttt_board(self._ctx.handle, self.B, _ptr(self.occ), _ptr(player),
-                                          int(rel_mod if rel_mod else self.P), _ptr(out), _stream()), "crl_ttt_board")
+        self._call("crl_ttt_board", _ptr(self.occ), _ptr(player), int(rel_mod if rel_mod else self.P), _ptr(out))
         return out
 
     def observe(self, player: torch.Tensor, rel_mod: Optional[int] = None):
         """state_to_observation for all games: board with ids relative to player[b] (reference 2p:382-407)."""
         return {"board": self.board(player, rel_mod)}
+
+    def _obs_spec(self):
+        """the buffers `step_observe` and `step_single` fill for the next mover / the learner"""
+        return {"board": (torch.int8, (self.B, self.n_cells)), "valid": (torch.int32, (self.B,))}
 
     def step_observe(self, action: Optional[torch.Tensor] = None, seed: int = 0, auto_reset: bool = True,
                      rel_mod: Optional[int] = None, out: Optional[dict] = None):
@@ -704,15 +688,11 @@ class TTTBatch(_Waitable):
         'reward', 'terminal', 'winners'}.  Equals ``step(...); valid_mask(); board(to_move, rel_mod)``."""
         if action is not None:
             _want(action, torch.int8, (self.B,), self.device, "action")
-        if out is None:
-            out = {"board": torch.empty((self.B, self.n_cells), dtype=torch.int8, device=self.device),
-                   "valid": torch.empty((self.B,), dtype=torch.int32, device=self.device)}
-        with _DevGuard(self.device):
-            check(self._lib.crl_ttt_step_observe(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
-                                                 _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move), _ptr(action),
-                                                 _ptr(self.tcount), _ptr(self.reward), _ptr(self.terminal), _ptr(self.winners),
-                                                 _ptr(out["board"]), _ptr(out["valid"]), int(rel_mod if rel_mod else self.P),
-                                                 CRL_STEP_AUTO_RESET if auto_reset else 0, _stream()), "crl_ttt_step_observe")
+        out = out or _alloc(self._obs_spec(), self.device)
+        self._call("crl_ttt_step_observe", _seed(seed), self.first_env_id, _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move),
+                   _ptr(action), _ptr(self.tcount), _ptr(self.reward), _ptr(self.terminal), _ptr(self.winners),
+                   _ptr(out["board"]), _ptr(out["valid"]), int(rel_mod if rel_mod else self.P),
+                   CRL_STEP_AUTO_RESET if auto_reset else 0)
         out["mover"], out["reward"], out["terminal"], out["winners"] = self.to_move, self.reward, self.terminal, self.winners
         return out
 
@@ -728,16 +708,10 @@ class TTTBatch(_Waitable):
         _want(seat, torch.int8, (self.B,), self.device, "seat")
         if learner_action is not None:
             _want(learner_action, torch.int64, (self.B,), self.device, "learner_action")
-        if out is None:
-            out = {"board": torch.empty((self.B, self.n_cells), dtype=torch.int8, device=self.device),
-                   "valid": torch.empty((self.B,), dtype=torch.int32, device=self.device),
-                   "done": torch.empty((self.B,), dtype=torch.uint8, device=self.device)}
-        with _DevGuard(self.device):
-            check(self._lib.crl_ttt_step_single(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
-                                                _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move), _ptr(seat),
-                                                _ptr(learner_action), _ptr(self.tcount), _ptr(self.reward), _ptr(out["done"]),
-                                                _ptr(self.winners), _ptr(out["board"]), _ptr(out["valid"]),
-                                                int(rel_mod if rel_mod else self.P), 0, _stream()), "crl_ttt_step_single")
+        out = out or _alloc(dict(self._obs_spec(), done=(torch.uint8, (self.B,))), self.device)
+        self._call("crl_ttt_step_single", _seed(seed), self.first_env_id, _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move),
+                   _ptr(seat), _ptr(learner_action), _ptr(self.tcount), _ptr(self.reward), _ptr(out["done"]), _ptr(self.winners),
+                   _ptr(out["board"]), _ptr(out["valid"]), int(rel_mod if rel_mod else self.P), 0)
         out["reward"], out["winners"] = self.reward, self.winners
         return out
 
@@ -749,38 +723,34 @@ class TTTBatch(_Waitable):
         ids and ``tcount`` as the counter base (which the call neither advances nor writes; the state is only read).
         Returns {'wins' int32 [B, A, P], 'draws', 'played', 'len_sum' int32 [B, A]} (skipped rows are zeros); ``out``
         reuses such a dict.  No host synchronisation; capturable into a graph."""
-        A, R = _playout_args(playouts, candidates, self.B, self.device)
-        out = _playout_out(out, self.B, A, self.P, self.device, score=False)
-        with _DevGuard(self.device):
-            check(self._lib.crl_ttt_playout(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
-                                            _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move), _ptr(self.tcount),
-                                            _ptr(candidates), A, R, _ptr(out["wins"]), _ptr(out["played"]),
-                                            _ptr(out["len_sum"]), 0, _stream()), "crl_ttt_playout")
-            torch.sub(out["played"], out["wins"].sum(dim=2, dtype=torch.int32), out=out["draws"])
+        R = _int_in("playouts", playouts, 1, 65535)
+        A = _candidates(candidates, self.B, self.device, 65535)
+        i32, BA = torch.int32, (self.B, A)
+        out = _out_dict(out, {"wins": (i32, BA + (self.P,)), "draws": (i32, BA), "played": (i32, BA), "len_sum": (i32, BA)},
+                        self.device)
+        self._call("crl_ttt_playout", _seed(seed), self.first_env_id, _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move),
+                   _ptr(self.tcount), _ptr(candidates), A, R, _ptr(out["wins"]), _ptr(out["played"]), _ptr(out["len_sum"]), 0)
+        torch.sub(out["played"], out["wins"].sum(dim=2, dtype=torch.int32), out=out["draws"])
         return out
+
+    @functools.cached_property
+    def _all_cells(self):
+        """int32 [B, cells]: every cell of every game, `flat_mc_action`'s candidates (made at the first use)"""
+        return torch.arange(self.n_cells, dtype=torch.int32, device=self.device).expand(self.B, self.n_cells).contiguous()
 
     def flat_mc_action(self, playouts: int, seed: int = 0, out: Optional[dict] = None) -> torch.Tensor:
         """Flat Monte Carlo for the player to move in every game: ``playout`` on every cell, value 2 * wins + draws of
         the mover, the best cell (ties: the lowest) as an int64 [B] action for ``step_single``; -1 where no cell could be
         played (the game is over).  ``out``: the playout dict to reuse.  No host synchronisation; capturable."""
-        cells = getattr(self, "_all_cells", None)
-        if cells is None:
-            cells = torch.arange(self.n_cells, dtype=torch.int32, device=self.device).expand(self.B, self.n_cells).contiguous()
-            self._all_cells = cells
+        cells = self._all_cells
         o = self.playout(playouts, cells, seed, out)
         mover = self.to_move.to(torch.int64).clamp(0, self.P - 1)       # (other values: the position skips every row)
         mine = torch.gather(o["wins"], 2, mover.view(-1, 1, 1).expand(self.B, self.n_cells, 1)).squeeze(2)
         return _flat_mc_pick(2 * mine + o["draws"], o["played"], cells)
 
-    def _stats(self):
-        return TTTStats(*[t.data_ptr() for t in (self.tcount, self.tstep, self.n_episodes, self.win_count,
-                                                  self.draw_count, self.len_sum, self._results)])
-
     def rollout(self, steps: int, seed: int = 0):
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_ttt_rollout(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id, int(steps),
-                                            _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move), self._stats(),
-                                            _stream()), "crl_ttt_rollout")
+        self._call("crl_ttt_rollout", _seed(seed), self.first_env_id, int(steps), _ptr(self.occ), _ptr(self.winner),
+                   _ptr(self.to_move), self._stats())
 
     def results(self, copy: bool = True):
         """int32 [B, 3+P] = n_episodes, len_sum, draw_count, win_count[P]; written by the rollout kernel at the end of
@@ -792,24 +762,17 @@ class TTTBatch(_Waitable):
         return torch.stack(cols, dim=1).contiguous()
 
 
-class TTTBoards:
+class TTTBoards(_Stepper):
     """B TicTacToe games held in the REFERENCE's layout (``board int8 [B, cells]`` with -1 = empty, ``winner``,
     ``to_move``) and stepped there by ``crl_ttt_step_board`` / ``crl_ttt_observe_board`` -- what the single-state
     drop-in classes run at B = 1; `TTTBatch` (bit masks) is the layout for throughput."""
 
     def __init__(self, dims: Sequence[int] = (3, 3), k: int = 3, num_players: int = 2, batch: int = 1, device="cuda"):
-        lib = _native.require_gpu()
         self.dims = tuple(int(d) for d in dims)
         d3 = (1,) * (3 - len(self.dims)) + self.dims
         self.K, self.P, self.B = int(k), int(num_players), int(batch)
         self.n_cells = d3[0] * d3[1] * d3[2]
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        handle = C.c_void_p()
-        check(lib.crl_ttt_create(d3[0], d3[1], d3[2], self.K, self.P, C.byref(handle)), "crl_ttt_create")
-        self._ctx = _Ctx(handle)
-        self._lib = lib
+        self._open(device, 0, "crl_ttt_create", d3[0], d3[1], d3[2], self.K, self.P)
         dev, B = self.device, self.B
         self.board = torch.full((B, self.n_cells), -1, dtype=torch.int8, device=dev)
         self.winner = torch.full((B,), -1, dtype=torch.int8, device=dev)
@@ -822,11 +785,9 @@ class TTTBoards:
 
     def step(self, action: torch.Tensor, auto_reset: bool = False, rel_mod: Optional[int] = None):
         _want(action, torch.int8, (self.B,), self.device, "action")
-        with _DevGuard(self.device):
-            check(self._lib.crl_ttt_step_board(self._ctx.handle, self.B, _ptr(self.board), _ptr(self.winner), _ptr(self.to_move),
-                                               _ptr(action), _ptr(self.reward), _ptr(self.terminal), _ptr(self.winners),
-                                               _ptr(self.valid), _ptr(self.obs), int(rel_mod if rel_mod else self.P),
-                                               CRL_STEP_AUTO_RESET if auto_reset else 0, _stream()), "crl_ttt_step_board")
+        self._call("crl_ttt_step_board", _ptr(self.board), _ptr(self.winner), _ptr(self.to_move), _ptr(action), _ptr(self.reward),
+                   _ptr(self.terminal), _ptr(self.winners), _ptr(self.valid), _ptr(self.obs),
+                   int(rel_mod if rel_mod else self.P), CRL_STEP_AUTO_RESET if auto_reset else 0)
         return self.reward, self.terminal, self.winners
 
     def observe(self, player: Optional[torch.Tensor] = None, rel_mod: Optional[int] = None):
@@ -835,14 +796,12 @@ class TTTBoards:
             _want(player, torch.int8, (self.B,), self.device, "player")
         obs = torch.empty_like(self.board)
         valid = torch.empty_like(self.valid)
-        with _DevGuard(self.device):
-            check(self._lib.crl_ttt_observe_board(self._ctx.handle, self.B, _ptr(self.board), _ptr(player),
-                                                  int(rel_mod if rel_mod else self.P), _ptr(obs), _ptr(valid), _stream()),
-                  "crl_ttt_observe_board")
+        self._call("crl_ttt_observe_board", _ptr(self.board), _ptr(player), int(rel_mod if rel_mod else self.P), _ptr(obs),
+                   _ptr(valid))
         return obs, valid
 
 
-class BlokusBatch(_Waitable):
+class BlokusBatch(_RolloutStepper):
     """B games of 4-player 20x20 Blokus (reference: envs/blokus/*).
 
     State tensors (device): occ int32 [B, 4, 20] row bitboards per colour; inv int32 [B, 4] piece masks;
@@ -850,22 +809,15 @@ class BlokusBatch(_Waitable):
     ``((piece*400 + y*20 + x)*8 + orientation)*5 + shift`` (-1 = pass), see ``envs.blokus.actions``.
     """
     MASK_WORDS = 10500
+    STATS_STRUCT = _native.BlokusStats
+    STATS = {"tcount": (torch.int32, _per_game), "tstep": (torch.int32, _per_game), "n_episodes": (torch.int32, _per_game),
+             "win_count": (torch.int32, _per_player), "len_sum": (torch.int32, _per_game), "score_sum": (torch.int32, _per_player),
+             "results": (torch.int32, lambda B, P: (B, 10))}
 
     def __init__(self, batch: int = 1, device="cuda", first_env_id: int = 0):
-        lib = _native.require_gpu()
         self.B = int(batch)
         self.P = 4
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _native.NativeError("BlokusBatch needs a ROCm device; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        handle = C.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib.crl_blokus_create(C.byref(handle)), "crl_blokus_create")
-        self._ctx = _Ctx(handle)
-        self._lib = lib
-        self.first_env_id = int(first_env_id)
+        self._open(device, first_env_id, "crl_blokus_create")
         dev, B = self.device, self.B
         with torch.cuda.device(dev):
             self.occ = torch.zeros((B, 4, 20), dtype=torch.int32, device=dev)
@@ -876,13 +828,7 @@ class BlokusBatch(_Waitable):
             self.reward = torch.zeros((B,), dtype=torch.int8, device=dev)
             self.terminal = torch.zeros((B,), dtype=torch.uint8, device=dev)
             self.winners = torch.zeros((B,), dtype=torch.uint8, device=dev)
-            self.tcount = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.tstep = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.n_episodes = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.win_count = torch.zeros((4, B), dtype=torch.int32, device=dev)
-            self.len_sum = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self.score_sum = torch.zeros((4, B), dtype=torch.int32, device=dev)
-            self._results = torch.zeros((B, 10), dtype=torch.int32, device=dev)
+            self.__dict__.update(_alloc(self._stat_spec(B, 4), dev, torch.zeros))
         self.reset()
         self._open_wait()
 
@@ -892,15 +838,12 @@ class BlokusBatch(_Waitable):
     def reset(self, mask: Optional[torch.Tensor] = None):
         if mask is not None:
             _want(mask, torch.uint8, (self.B,), self.device, "mask")
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_blokus_reset(self._ctx.handle, self.B, _ptr(mask), *self._state(), _stream()), "crl_blokus_reset")
+        self._call("crl_blokus_reset", _ptr(mask), *self._state())
 
     def step(self, action: torch.Tensor, auto_reset: bool = False):
         _want(action, torch.int32, (self.B,), self.device, "action")
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_blokus_step(self._ctx.handle, self.B, *self._state(), _ptr(action), _ptr(self.reward),
-                                            _ptr(self.terminal), _ptr(self.winners),
-                                            CRL_STEP_AUTO_RESET if auto_reset else 0, _stream()), "crl_blokus_step")
+        self._call("crl_blokus_step", *self._state(), _ptr(action), _ptr(self.reward), _ptr(self.terminal), _ptr(self.winners),
+                   CRL_STEP_AUTO_RESET if auto_reset else 0)
         return self.reward, self.terminal, self.winners
 
     def valid(self, player: Optional[torch.Tensor] = None, want_mask: bool = False):
@@ -910,9 +853,7 @@ class BlokusBatch(_Waitable):
             _want(player, torch.int8, (self.B,), self.device, "player")
         count = torch.empty((self.B,), dtype=torch.int32, device=self.device)
         mask = torch.empty((self.B, self.MASK_WORDS), dtype=torch.int32, device=self.device) if want_mask else None
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_blokus_valid(self._ctx.handle, self.B, *self._state(), _ptr(player), _ptr(count),
-                                             _ptr(mask), _stream()), "crl_blokus_valid")
+        self._call("crl_blokus_valid", *self._state(), _ptr(player), _ptr(count), _ptr(mask))
         return (count, mask) if want_mask else count
 
     def valid_list(self, cap: int = 2048, player: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
@@ -924,9 +865,7 @@ class BlokusBatch(_Waitable):
         count = torch.empty((self.B,), dtype=torch.int32, device=self.device)
         ids = out if out is not None else torch.full((self.B, int(cap)), -1, dtype=torch.int32, device=self.device)
         _want(ids, torch.int32, (self.B, int(cap)), self.device, "out")
-        with _DevGuard(self.device):
-            check(self._lib.crl_blokus_valid_list(self._ctx.handle, self.B, *self._state(), _ptr(player), _ptr(ids),
-                                                  _ptr(count), int(cap), _stream()), "crl_blokus_valid_list")
+        self._call("crl_blokus_valid_list", *self._state(), _ptr(player), _ptr(ids), _ptr(count), int(cap))
         return count, ids
 
     def select(self, rank: torch.Tensor, player: Optional[torch.Tensor] = None):
@@ -937,9 +876,7 @@ class BlokusBatch(_Waitable):
             _want(player, torch.int8, (self.B,), self.device, "player")
         act = torch.empty((self.B,), dtype=torch.int32, device=self.device)
         count = torch.empty((self.B,), dtype=torch.int32, device=self.device)
-        with _DevGuard(self.device):
-            check(self._lib.crl_blokus_select(self._ctx.handle, self.B, *self._state(), _ptr(player), _ptr(rank), _ptr(act),
-                                              _ptr(count), _stream()), "crl_blokus_select")
+        self._call("crl_blokus_select", *self._state(), _ptr(player), _ptr(rank), _ptr(act), _ptr(count))
         return act, count
 
     def is_valid(self, action: torch.Tensor, player: Optional[torch.Tensor] = None):
@@ -948,9 +885,7 @@ class BlokusBatch(_Waitable):
         if player is not None:
             _want(player, torch.int8, (self.B,), self.device, "player")
         ok = torch.empty((self.B,), dtype=torch.uint8, device=self.device)
-        with _DevGuard(self.device):
-            check(self._lib.crl_blokus_is_valid(self._ctx.handle, self.B, *self._state(), _ptr(player), _ptr(action), _ptr(ok),
-                                                _stream()), "crl_blokus_is_valid")
+        self._call("crl_blokus_is_valid", *self._state(), _ptr(player), _ptr(action), _ptr(ok))
         return ok
 
     def fits(self, action: torch.Tensor, player: torch.Tensor):
@@ -960,25 +895,19 @@ class BlokusBatch(_Waitable):
         _want(action, torch.int32, (self.B,), self.device, "action")
         _want(player, torch.int8, (self.B,), self.device, "player")
         ok = torch.empty((self.B,), dtype=torch.uint8, device=self.device)
-        with _DevGuard(self.device):
-            check(self._lib.crl_blokus_fits(self._ctx.handle, self.B, _ptr(self.occ), _ptr(player), _ptr(action), _ptr(ok),
-                                            _stream()), "crl_blokus_fits")
+        self._call("crl_blokus_fits", _ptr(self.occ), _ptr(player), _ptr(action), _ptr(ok))
         return ok
 
     def set_board(self, board: torch.Tensor):
         """Loads ``Board.board_contents`` (int8 [B, 20, 20], 0 empty else colour) into the row bitboards."""
         _want(board, torch.int8, (self.B, 20, 20), self.device, "board")
-        with _DevGuard(self.device):
-            check(self._lib.crl_blokus_pack(self._ctx.handle, self.B, _ptr(board), _ptr(self.occ), _stream()), "crl_blokus_pack")
+        self._call("crl_blokus_pack", _ptr(board), _ptr(self.occ))
 
     def sample(self, seed: int = 0, advance: bool = True):
         """The rollout's random agent for one step: int32 [B] dense action id of a uniformly drawn legal action of the
         player to move (-1 = pass); ``step(sample(seed), auto_reset=True)`` T times == ``rollout(T, seed)``."""
         act = torch.empty((self.B,), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_blokus_sample(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
-                                              *self._state(), _ptr(self.tcount), int(advance), _ptr(act), _stream()),
-                  "crl_blokus_sample")
+        self._call("crl_blokus_sample", _seed(seed), self.first_env_id, *self._state(), _ptr(self.tcount), int(advance), _ptr(act))
         return act
 
     def observe(self, player: torch.Tensor):
@@ -987,10 +916,14 @@ class BlokusBatch(_Waitable):
         ob = torch.empty((self.B, 20, 20), dtype=torch.int8, device=self.device)
         op = torch.empty((self.B, 4, 21), dtype=torch.uint8, device=self.device)
         osc = torch.empty((self.B, 4), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_blokus_observe(self._ctx.handle, self.B, _ptr(self.occ), _ptr(self.inv), _ptr(self.score),
-                                               _ptr(player), _ptr(ob), _ptr(op), _ptr(osc), _stream()), "crl_blokus_observe")
+        self._call("crl_blokus_observe", _ptr(self.occ), _ptr(self.inv), _ptr(self.score), _ptr(player), _ptr(ob), _ptr(op),
+                   _ptr(osc))
         return {"board": ob, "pieces": op, "score": osc, "player": player.view(self.B, 1)}
+
+    def _obs_spec(self):
+        """the buffers `step_observe` and `step_single` fill for the next mover / the learner"""
+        return {"board": (torch.int8, (self.B, 20, 20)), "pieces": (torch.uint8, (self.B, 4, 21)),
+                "score": (torch.int32, (self.B, 4)), "n_valid": (torch.int32, (self.B,))}
 
     def step_observe(self, action: Optional[torch.Tensor] = None, seed: int = 0, auto_reset: bool = True,
                      out: Optional[dict] = None, list_cap: int = 0):
@@ -1003,19 +936,10 @@ class BlokusBatch(_Waitable):
         between) and adds 'ids' int32 [B, list_cap]: the ordered legal ids a policy picks from (-1 beyond 'n_valid')."""
         if action is not None:
             _want(action, torch.int32, (self.B,), self.device, "action")
-        if out is None:
-            out = {"board": torch.empty((self.B, 20, 20), dtype=torch.int8, device=self.device),
-                   "pieces": torch.empty((self.B, 4, 21), dtype=torch.uint8, device=self.device),
-                   "score": torch.empty((self.B, 4), dtype=torch.int32, device=self.device),
-                   "player": torch.empty((self.B, 1), dtype=torch.int8, device=self.device),
-                   "n_valid": torch.empty((self.B,), dtype=torch.int32, device=self.device)}
-        with _DevGuard(self.device):
-            check(self._lib.crl_blokus_step_observe(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
-                                                    *self._state(), _ptr(action), _ptr(self.tcount), _ptr(self.reward),
-                                                    _ptr(self.terminal), _ptr(self.winners), _ptr(out["n_valid"]),
-                                                    _ptr(out["board"]), _ptr(out["pieces"]), _ptr(out["score"]),
-                                                    _ptr(out["player"]), CRL_STEP_AUTO_RESET if auto_reset else 0, _stream()),
-                  "crl_blokus_step_observe")
+        out = out or _alloc(dict(self._obs_spec(), player=(torch.int8, (self.B, 1))), self.device)
+        self._call("crl_blokus_step_observe", _seed(seed), self.first_env_id, *self._state(), _ptr(action), _ptr(self.tcount),
+                   _ptr(self.reward), _ptr(self.terminal), _ptr(self.winners), _ptr(out["n_valid"]), _ptr(out["board"]),
+                   _ptr(out["pieces"]), _ptr(out["score"]), _ptr(out["player"]), CRL_STEP_AUTO_RESET if auto_reset else 0)
         out["reward"], out["terminal"], out["winners"] = self.reward, self.terminal, self.winners
         if list_cap > 0:
             ids = out.get("ids")
@@ -1038,19 +962,10 @@ class BlokusBatch(_Waitable):
         _want(seat, torch.int8, (self.B,), self.device, "seat")
         if learner_action is not None:
             _want(learner_action, torch.int64, (self.B,), self.device, "learner_action")
-        if out is None:
-            out = {"board": torch.empty((self.B, 20, 20), dtype=torch.int8, device=self.device),
-                   "pieces": torch.empty((self.B, 4, 21), dtype=torch.uint8, device=self.device),
-                   "score": torch.empty((self.B, 4), dtype=torch.int32, device=self.device),
-                   "n_valid": torch.empty((self.B,), dtype=torch.int32, device=self.device),
-                   "done": torch.empty((self.B,), dtype=torch.uint8, device=self.device)}
-        with _DevGuard(self.device):
-            check(self._lib.crl_blokus_step_single(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
-                                                   *self._state(), _ptr(seat), _ptr(learner_action), _ptr(self.tcount),
-                                                   _ptr(self.reward), _ptr(out["done"]), _ptr(self.winners),
-                                                   _ptr(out["n_valid"]), _ptr(out["board"]), _ptr(out["pieces"]),
-                                                   _ptr(out["score"]), CRL_STEP_RANK_ACTION if rank else 0, _stream()),
-                  "crl_blokus_step_single")
+        out = out or _alloc(dict(self._obs_spec(), done=(torch.uint8, (self.B,))), self.device)
+        self._call("crl_blokus_step_single", _seed(seed), self.first_env_id, *self._state(), _ptr(seat), _ptr(learner_action),
+                   _ptr(self.tcount), _ptr(self.reward), _ptr(out["done"]), _ptr(self.winners), _ptr(out["n_valid"]),
+                   _ptr(out["board"]), _ptr(out["pieces"]), _ptr(out["score"]), CRL_STEP_RANK_ACTION if rank else 0)
         out["reward"], out["winners"] = self.reward, self.winners
         return out
 
@@ -1063,43 +978,33 @@ class BlokusBatch(_Waitable):
         counts for every tied player), 'draws' (played - sum of wins, negative when ties count twice), 'played',
         'len_sum' int32 [B, A], 'score_sum' int32 [B, A, 4]} (skipped rows are zeros); ``out`` reuses such a dict.  No
         host synchronisation; capturable into a graph."""
-        A, R = _playout_args(playouts, candidates, self.B, self.device)
-        out = _playout_out(out, self.B, A, 4, self.device, score=True)
-        with _DevGuard(self.device):
-            check(self._lib.crl_blokus_playout(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id,
-                                               *self._state(), _ptr(self.tcount), _ptr(candidates), A, R,
-                                               _ptr(out["wins"]), _ptr(out["played"]), _ptr(out["len_sum"]),
-                                               _ptr(out["score_sum"]), 0, _stream()), "crl_blokus_playout")
-            torch.sub(out["played"], out["wins"].sum(dim=2, dtype=torch.int32), out=out["draws"])
+        R = _int_in("playouts", playouts, 1, 65535)
+        A = _candidates(candidates, self.B, self.device, 65535)
+        i32, BA = torch.int32, (self.B, A)
+        out = _out_dict(out, {"wins": (i32, BA + (4,)), "draws": (i32, BA), "played": (i32, BA), "len_sum": (i32, BA),
+                              "score_sum": (i32, BA + (4,))}, self.device)
+        self._call("crl_blokus_playout", _seed(seed), self.first_env_id, *self._state(), _ptr(self.tcount), _ptr(candidates), A, R,
+                   _ptr(out["wins"]), _ptr(out["played"]), _ptr(out["len_sum"]), _ptr(out["score_sum"]), 0)
+        torch.sub(out["played"], out["wins"].sum(dim=2, dtype=torch.int32), out=out["draws"])
         return out
 
     def flat_mc_action(self, candidates: torch.Tensor, playouts: int, seed: int = 0, out: Optional[dict] = None) -> torch.Tensor:
         """Flat Monte Carlo over the dense-id ``candidates`` (int32 [B, A]) of the player to move: ``playout`` on each,
         value = the mover's wins, the best candidate (ties: the lower index) as an int64 [B] action for ``step_single``;
         -1 where no candidate was played.  ``out``: the playout dict to reuse.  No host synchronisation; capturable."""
-        A, _ = _playout_args(playouts, candidates, self.B, self.device)
+        _int_in("playouts", playouts, 1, 65535)
+        A = _candidates(candidates, self.B, self.device, 65535)
         o = self.playout(playouts, candidates, seed, out)
         mover = (self.to_move.to(torch.int64) & 3).view(-1, 1, 1).expand(self.B, A, 1)
         return _flat_mc_pick(torch.gather(o["wins"], 2, mover).squeeze(2), o["played"], candidates)
 
     def board(self):
         out = torch.empty((self.B, 20, 20), dtype=torch.int8, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_blokus_board(self._ctx.handle, self.B, _ptr(self.occ), _ptr(out), _stream()), "crl_blokus_board")
+        self._call("crl_blokus_board", _ptr(self.occ), _ptr(out))
         return out
 
-    def _stats(self):
-        return _native.BlokusStats(*[t.data_ptr() for t in (self.tcount, self.tstep, self.n_episodes, self.win_count,
-                                                            self.len_sum, self.score_sum, self._results)])
-
-    def reset_stats(self):
-        for t in (self.tcount, self.tstep, self.n_episodes, self.win_count, self.len_sum, self.score_sum, self._results):
-            t.zero_()
-
     def rollout(self, steps: int, seed: int = 0):
-        with torch.cuda.device(self.device):
-            check(self._lib.crl_blokus_rollout(self._ctx.handle, self.B, seed & (2 ** 64 - 1), self.first_env_id, int(steps),
-                                               *self._state(), self._stats(), _stream()), "crl_blokus_rollout")
+        self._call("crl_blokus_rollout", _seed(seed), self.first_env_id, int(steps), *self._state(), self._stats())
 
     def results(self, copy: bool = True):
         """int32 [B, 10] = n_episodes, len_sum, win_count[4], score_sum[4]; written by the rollout kernel at the end of

@@ -10,8 +10,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from ._native import check
-from .batched import BlokusBatch, TronBatch, TTTBatch, _DevGuard, _ptr, _stream
+from .batched import BlokusBatch, TronBatch, TTTBatch, _want
 
 
 class TronVectorEnv:
@@ -84,15 +83,11 @@ class TronSinglePlayerVectorEnv:
 
     def step(self, action: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict]:
         b = self.batch
-        if action.dtype != torch.int64 or tuple(action.shape) != (b.B,) or action.device != b.device or not action.is_contiguous():
-            raise ValueError("action must be a contiguous int64 tensor of shape (%d,) on %s" % (b.B, b.device))
+        _want(action, torch.int64, (b.B,), b.device, "action")
         if self._opponents:
             sample = b.sample_territory if self.opponent == "territory" else b.sample_avoid
             sample(self.seed, self.noise, players=self._opponents, out=self._actions)
-        with _DevGuard(b.device):
-            check(b._lib.crl_tron_step_single(b._ctx.handle, b.B, _ptr(b.board), _ptr(b.heads), _ptr(b.dirs), _ptr(b.deaths),
-                                              _ptr(self._actions), _ptr(action), _ptr(self.reward), _ptr(self.done),
-                                              _ptr(self.terminal), _stream()), "crl_tron_step_single")
+        b.step_single(self._actions, action, self.reward, self.done, self.terminal)
         return self.observation(), self.reward, self.done, {"terminal": self.terminal}
 
     def flat_mc_action(self, playouts: int, seed: int = 1, max_steps: int = 0, out: Optional[dict] = None) -> torch.Tensor:
@@ -198,11 +193,6 @@ def _seat_tensor(seat, P: int, B: int, device) -> torch.Tensor:
     return torch.full((B,), int(seat), dtype=torch.int8, device=device)
 
 
-def _check_action(action: torch.Tensor, B: int, device):
-    if action.dtype != torch.int64 or tuple(action.shape) != (B,) or action.device != device or not action.is_contiguous():
-        raise ValueError("action must be a contiguous int64 tensor of shape (%d,) on %s" % (B, device))
-
-
 class TicTacToeSinglePlayerVectorEnv:
     """B TicTacToe games of one learner against the random agent in every other seat: the turn-based counterpart of
     ``TronSinglePlayerVectorEnv``.  ``seat`` (an int, or an int8 [B] tensor: a seat per game, so that one learner trains on
@@ -237,7 +227,7 @@ class TicTacToeSinglePlayerVectorEnv:
         return self._step(None)[0]
 
     def step(self, action: torch.Tensor):
-        _check_action(action, self.num_envs, self.batch.device)
+        _want(action, torch.int64, (self.num_envs,), self.batch.device, "action")
         return self._step(action)
 
 
@@ -287,5 +277,5 @@ class BlokusSinglePlayerVectorEnv:
         return self._step(None)[0]
 
     def step(self, action: torch.Tensor):
-        _check_action(action, self.num_envs, self.batch.device)
+        _want(action, torch.int64, (self.num_envs,), self.batch.device, "action")
         return self._step(action)

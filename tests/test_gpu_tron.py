@@ -160,7 +160,8 @@ def test_next_state_inplace64_wild_actions_and_directions_golden(golden, obs):
     assert (dirs < 0).sum() > 100                                 # the negative directions are really there
 
 
-@pytest.mark.parametrize("N,P,B,T", [(20, 4, 300, 40), (40, 4, 64, 60), (19, 3, 77, 40), (9, 8, 130, 30), (5, 2, 100, 20)])
+@pytest.mark.parametrize("N,P,B,T", [(20, 4, 300, 40), (40, 4, 64, 60), (19, 3, 77, 40), (9, 8, 130, 30), (5, 2, 100, 20),
+                                     (64, 8, 33, 30), (100, 4, 17, 30), (181, 4, 5, 30)])
 def test_next_state_inplace64_vs_oracle_random(N, P, B, T):
     """Seeded random play: the int64 in-place entry (with and without the fused observations) against the oracle's step
     and observe on the same states; terminal games are reset on both sides."""
@@ -560,7 +561,8 @@ def test_largest_board_and_single_game():
 
 
 @pytest.mark.parametrize("N,P,B", [(20, 4, 5000), (9, 6, 777), (13, 8, 300), (40, 4, 1024), (19, 4, 4096), (19, 4, 4099), (15, 3, 1008), (39, 8, 64),
-                                   (5, 2, 1), (19, 4, 1), (7, 3, 3), (21, 7, 1001), (5, 4, 2), (19, 4, 65553)])
+                                   (5, 2, 1), (19, 4, 1), (7, 3, 3), (21, 7, 1001), (5, 4, 2), (19, 4, 65553),
+                                   (57, 5, 33), (181, 8, 3)])
 def test_observe_all_matches_per_player_observe(N, P, B):
     """The fused all-observers pass (v_perm table for P <= 7, arithmetic for P = 8, byte path for odd boards)
     equals P single-observer calls, which equal the oracle."""
@@ -590,12 +592,17 @@ def test_observe_all_matches_per_player_observe(N, P, B):
                                    # ... and batches that are not a multiple of 16 games of such boards (the observers' planes off the 16-byte grid)
                                    (19, 4, 20000 + 9), (15, 3, 1001), (39, 4, 100 + 3), (19, 8, 1024 + 9), (5, 2, 7), (19, 4, 1), (21, 7, 70),
                                    # eight players: the fused kernels relabel by arithmetic (cell values 0..8 do not fit the permute table)
-                                   (20, 8, 1024 + 7), (19, 8, 1024), (40, 8, 160)])
+                                   (20, 8, 1024 + 7), (19, 8, 1024), (40, 8, 160),
+                                   # the LDS limit's edges: 64 games per workgroup up to 27x27, 16 from 28x28 (fused) to 52x52 and
+                                   # (flat) 55x55; from 56x56 the one-game-per-workgroup kernel, up to 32 KiB of LDS at 181x181
+                                   (27, 4, 130), (28, 4, 130), (52, 4, 70), (55, 4, 67), (56, 4, 70), (56, 8, 17), (57, 3, 33),
+                                   (64, 8, 65), (100, 4, 17), (181, 1, 3), (181, 4, 5), (181, 8, 2)])
 def test_step_observe_fused_matches_three_calls_and_oracle(N, P, B):
     """crl_tron_step_observe (one launch: [sample ->] next_state -> state_to_observation of all P players) equals
     crl_tron_sample + crl_tron_step + crl_tron_observe_all on a twin batch and the oracle stepped in lockstep: 64 and 16
-    games per workgroup (LDS limit), ragged batches, auto-reset on and off, external and sampled actions, and the
-    boards / player counts that run the one-game-per-workgroup kernel instead (N*N % 16 != 0, P = 8)."""
+    games per workgroup (LDS limit), ragged batches, auto-reset on and off, external and sampled actions; boards with
+    N*N % 16 != 0 (the flat-stream kernel) and P = 8 (relabelling by arithmetic); and the boards of 56x56 and above, of
+    which 16 no longer fit the LDS, which run the one-game-per-workgroup kernel instead."""
     import torch
     from colosseumrl_amd.batched import TronBatch
     seed, first = 77, 900

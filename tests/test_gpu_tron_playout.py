@@ -67,14 +67,33 @@ CASES = [  # N, P, agent, noise, until, max_steps, forced first action
     (181, 1, "random", 0.1, "end", 0, True),
     (7, 1, "avoid", 0.0, "end", 0, False),
     (12, 8, "random", 0.1, "end", 0, True),
+    # the remaining tron_playout_kernel<P, AVOID> instances: random P = 3, 5, 7 and avoid P = 2, 5, 6, 7
+    (13, 3, "random", 0.1, "end", 0, True),
+    (21, 5, "random", 0.1, "seat_done", 0, False),
+    (33, 7, "random", 0.1, "end", 0, True),
+    (15, 2, "avoid", 0.1, "end", 0, True),
+    (20, 5, "avoid", 0.1, "seat_done", 0, False),
+    (24, 6, "avoid", 0.3, "end", 0, True),
+    (16, 7, "avoid", 0.1, "end", 0, False),
+    # the launch geometry's edges: 64 | 65 bitboard words (45 | 46: 256 -> 64 threads) and 512 | 513 (128 | 129: 64 -> 32
+    # lanes per wave; 128 KiB of opt-in LDS at 128)
+    (45, 4, "random", 0.1, "end", 0, True),
+    (46, 4, "avoid", 0.5, "end", 0, False),
+    (128, 4, "random", 0.1, "seat_done", 0, False),
+    (129, 4, "avoid", 0.5, "end", 60, True),
 ]
 
 
 @pytest.mark.parametrize("case", CASES, ids=["N%d_P%d_%s_%g_%s_cap%d_%s" % (c[0], c[1], c[2], c[3], c[4], c[5], "cand" if c[6] else "none")
                                              for c in CASES])
 def test_against_restatement(case):
+    _check_against_restatement(case)
+
+
+def _check_against_restatement(case, B=23, Rn=5, A=4, dead_seat=True):
+    """B positions, A candidate columns (the last one padding) of Rn playouts each: every output against the restatement."""
     N, P, agent, noise, until, max_steps, forced = case
-    B, Rn, seed = 23, 5, 1234 + N * 8 + P
+    seed = 1234 + N * 8 + P
     rng = np.random.default_rng(N * 100 + P)
     tb, st = _positions(N, P, B, seed)
     tcount = (np.uint32(0xFFFFFFF0) + rng.integers(0, 40, size=B).astype(np.uint32)).astype(np.uint32)   # wraps past 2^32
@@ -82,14 +101,13 @@ def test_against_restatement(case):
     _upload(tb, st, tcount, first_env_id)
     seat = rng.integers(0, P, size=B).astype(np.int8)
     seat[0], seat[1] = -1, P                                   # out of range: skipped
-    if P >= 2:
+    if P >= 2 and dead_seat:
         seat[2] = 1
         st.deaths[1, 2] = st.deaths[1, 2] or 1                 # a dead seat: skipped
         tb.deaths.copy_(torch.from_numpy(st.deaths))
     if forced:
-        cand = rng.integers(0, 3, size=(B, 4)).astype(np.int32)
-        cand[:, 3] = rng.choice([-1, 3, 7, 2], size=B)          # padding / invalid values skip their rows
-        A = 4
+        cand = rng.integers(0, 3, size=(B, A)).astype(np.int32)
+        cand[:, A - 1] = rng.choice([-1, 3, 7, 2], size=B)      # padding / invalid values skip their rows
     else:
         cand, A = None, 1
     snap = [t.clone() for t in (tb.board, tb.heads, tb.dirs, tb.deaths, tb.tcount)]
@@ -106,6 +124,7 @@ def test_against_restatement(case):
     assert np.array_equal(_np(out["wins"]), w)
     assert np.array_equal(_np(out["len_sum"]), l)
     assert np.array_equal(_np(out["ret_sum"]), r)
+    return p
 
 
 def test_exact_outcome_probabilities():

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from tests import playout_ref as R
+from tests import ttt_probes as TP
 
 pytestmark = pytest.mark.gpu
 
@@ -29,22 +30,6 @@ def _u32(t):
 
 
 # ------------------------------------------------------------------ TicTacToe positions
-def _ttt_positions(dims, K, P, B, rng):
-    """B random positions: random plies from the empty board, some games played past their end (finished, not reset)"""
-    from oracle import oracle as O
-    st = O.TTTState(dims, K, P, B)
-    for b in range(B):
-        one = O.TTTState(dims, K, P, 1)
-        for _ in range(int(rng.integers(0, one.n_cells + 1))):
-            bd = one.board()[0]
-            empty = np.flatnonzero(bd < 0)
-            if len(empty) == 0 or (one.winner[0] >= 0 and rng.random() < 0.5):
-                break
-            O.ttt_step(one, np.array([rng.choice(empty)], np.int8))
-        st.occ[:, b], st.winner[b], st.to_move[b] = one.occ[:, 0], one.winner[0], one.to_move[0]
-    return st
-
-
 def _ttt_batch(st, first_env_id, tcount):
     from colosseumrl_amd.batched import TTTBatch
     tb = TTTBatch(st.dims, st.K, st.P, st.B, device=DEV, first_env_id=first_env_id)
@@ -70,24 +55,17 @@ def _ttt_check(tb, st, tcount, Rn, cand, seed, first_env_id):
     return played
 
 
-# (shape, R with candidates, R without)
-TTT_CASES = [(((3, 3), 3, 2), 3, 100), (((3, 5), 3, 3), 1, 65), (((3, 3, 3), 3, 4), 3, 1), (((5, 5), 4, 3), 1, 65)]
-TTT_IDS = ["x".join(map(str, d)) + "k%dp%d" % (k, p) for (d, k, p), _, _ in TTT_CASES]
+# (shape, R with candidates, R without, candidate cells per game or None = every cell): every <P, win table / 4 directions /
+# 13 directions> instance of the kernel
+TTT_CASES = TP.PLAYOUT_CASES
+TTT_IDS = TP.INSTANCE_IDS
 
 
-@pytest.mark.parametrize("cfg,r_cand,r_none", TTT_CASES, ids=TTT_IDS)
-def test_ttt_against_restatement(cfg, r_cand, r_none):
-    dims, K, P = cfg
-    rng = np.random.default_rng(sum(dims) * 7 + P)
-    B, first_env_id, seed = 67, 1000 + P, 0xABCDEF0123 + P           # B: not a multiple of 64
-    st = _ttt_positions(dims, K, P, B, rng)
-    n = st.n_cells
-    tcount = rng.integers(0, 2 ** 32, size=B, dtype=np.uint64).astype(np.uint32)
-    tcount[:3] = [0, 2 ** 32 - 3, 5]                                  # a counter that wraps inside the playouts
+@pytest.mark.parametrize("cfg,r_cand,r_none,n_cand", TTT_CASES, ids=TTT_IDS)
+def test_ttt_against_restatement(cfg, r_cand, r_none, n_cand):
+    st, tcount, rng, first_env_id, seed = TP.playout_case_inputs(cfg)    # 67 positions: not a multiple of 64
     tb = _ttt_batch(st, first_env_id, tcount)
-    cand = np.concatenate([np.tile(np.arange(n), (B, 1)), np.full((B, 1), -1), np.full((B, 1), n),
-                           rng.integers(-5, n + 40, size=(B, 2))], axis=1)
-    cand = np.ascontiguousarray(rng.permuted(cand, axis=1))
+    cand = TP.playout_candidates(st.n_cells, st.B, rng, n_cand)           # every cell, -1, n and random values, shuffled
     played = _ttt_check(tb, st, tcount, r_cand, cand, seed, first_env_id)
     assert played.any() and not played.all()                         # both played and skipped rows
     played = _ttt_check(tb, st, tcount, r_none, None, seed, first_env_id)

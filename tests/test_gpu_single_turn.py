@@ -7,12 +7,13 @@ import pytest
 import torch
 
 from tests import single_ref as R
+from tests import ttt_probes as TP
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-TTT_CONFIGS = [((3, 3), 3, 2), ((3, 5), 3, 3), ((3, 3, 3), 3, 4), ((5, 5), 4, 3)]
-TTT_IDS = ["x".join(map(str, d)) + "k%dp%d" % (k, p) for d, k, p in TTT_CONFIGS]
+TTT_CONFIGS = TP.INSTANCE_ROWS              # every <P, win table / 4 directions / 13 directions> instance of the kernel
+TTT_IDS = TP.INSTANCE_IDS
 
 
 def _np(t):
@@ -54,21 +55,17 @@ def test_ttt_against_restatement(dims, K, P, mixed):
     _ttt_compare(tb, st, seat, None, seed)
     n_done = 0
     for _ in range(18):
-        bd = st.board()
-        act = np.empty(B, np.int64)
-        for b in range(B):
-            empty = np.flatnonzero(bd[b] < 0)
-            kind = rng.integers(0, 8)
-            if kind == 0:
-                act[b] = -1                                          # pass
-            elif kind == 1 and (bd[b] >= 0).any():
-                act[b] = int(rng.choice(np.flatnonzero(bd[b] >= 0)))  # occupied cell
-            elif kind == 2:
-                act[b] = int(rng.choice([st.n_cells, 127, -2, -129, 2 ** 33, -(2 ** 40)]))   # out of range
-            else:
-                act[b] = int(rng.choice(empty)) if len(empty) else -1
+        act = TP.single_turn_actions(st, rng)                        # empty and occupied cells, passes, values out of range
         n_done += int(_ttt_compare(tb, st, seat, act, seed).sum())
     assert n_done > 0
+
+
+@pytest.mark.parametrize("dims,K,P", [((4, 4), 4, 4), ((16,), 6, 7)], ids=["4x4k4p4", "16k6p7"])
+def test_ttt_against_restatement_without_the_win_table(dims, K, P, monkeypatch):
+    """Boards of at most 16 cells on a context without the table of winning masks (CRL_TTT_NO_WIN_TABLE makes crl_ttt_create
+    skip it): the kernel's shift-and test instead of the lookup."""
+    monkeypatch.setenv("CRL_TTT_NO_WIN_TABLE", "1")
+    test_ttt_against_restatement(dims, K, P, True)
 
 
 def _ttt_agent_action(tb, seed):

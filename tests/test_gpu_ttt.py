@@ -19,7 +19,8 @@ def test_2p_exhaustive_tree_kat():
     assert count_games(HipTTT) == (255168, 131184, 77904, 46080)
 
 
-@pytest.mark.parametrize("dims,K,P", [((3, 3), 3, 2), ((3, 5), 3, 3), ((3, 3, 3), 3, 4), ((5, 5), 4, 3), ((4, 8), 4, 5), ((2, 4, 4), 3, 8)])
+@pytest.mark.parametrize("dims,K,P", [((3, 3), 3, 2), ((3, 5), 3, 3), ((3, 3, 3), 3, 4), ((5, 5), 4, 3), ((4, 8), 4, 5), ((2, 4, 4), 3, 8),
+                                      ((2, 3), 2, 1), ((5, 5), 5, 6), ((6, 5), 6, 7), ((2, 2, 8), 2, 6)])
 def test_lines_and_step_vs_oracle(dims, K, P):
     B, T = 3001, 45
     hip, orc = HipTTT(dims, K, P, B), OracleTTT(dims, K, P, B)
@@ -230,7 +231,9 @@ def test_vector_env_adapters_vs_oracle():
 
 
 @pytest.mark.parametrize("dims,K,P,B,rel_mod", [((3, 3), 3, 2, 1000 + 7, None), ((3, 5), 3, 3, 513, None), ((3, 3, 3), 3, 4, 300, 3),
-                                                ((5, 5), 4, 3, 4096 + 1, None), ((1, 1), 2, 2, 70, None), ((4, 8), 4, 5, 257, None)])
+                                                ((5, 5), 4, 3, 4096 + 1, None), ((1, 1), 2, 2, 70, None), ((4, 8), 4, 5, 257, None),
+                                                ((2, 3), 2, 1, 300, None), ((5, 5), 5, 6, 513, None), ((6, 5), 6, 7, 257, None),
+                                                ((2, 4, 4), 2, 8, 300, None)])
 def test_step_observe_fused_matches_separate_calls(dims, K, P, B, rel_mod):
     """crl_ttt_step_observe (one launch: [sample ->] next_state -> valid mask + observation of the next mover) equals
     crl_ttt_sample + crl_ttt_step + crl_ttt_valid + crl_ttt_board on a twin batch: sampled and external actions (incl.
@@ -259,7 +262,8 @@ def test_step_observe_fused_matches_separate_calls(dims, K, P, B, rel_mod):
     assert int(b.terminal.sum()) >= 0
 
 
-@pytest.mark.parametrize("dims,K,P,rel_mod", [((3, 3), 3, 2, 2), ((3, 5), 3, 3, 3), ((3, 3, 3), 3, 4, 4), ((5, 5), 4, 3, 3), ((4, 8), 4, 8, 8)])
+@pytest.mark.parametrize("dims,K,P,rel_mod", [((3, 3), 3, 2, 2), ((3, 5), 3, 3, 3), ((3, 3, 3), 3, 4, 4), ((5, 5), 4, 3, 3), ((4, 8), 4, 8, 8),
+                                              ((2, 3), 2, 1, 1), ((5, 5), 5, 5, 5), ((6, 5), 6, 6, 6), ((2, 2, 4), 2, 7, 7)])
 def test_single_state_one_call_form_matches_the_two_call_form(dims, K, P, rel_mod):
     """crl_ttt_step_board_host (the state by value in the kernel arguments, completion published by the kernel, one blocking
     call) against crl_ttt_step_board + crl_stream_wait_mapped on the same states: random games incl. occupied / empty / ''

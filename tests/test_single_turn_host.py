@@ -8,8 +8,9 @@ import numpy as np
 import pytest
 
 from tests import single_ref as R
+from tests import ttt_probes as TP
 
-TTT_CONFIGS = [((3, 3), 3, 2), ((3, 5), 3, 3), ((3, 3, 3), 3, 4), ((5, 5), 4, 3)]
+TTT_CONFIGS = TP.INSTANCE_ROWS              # the rows tests/test_gpu_single_turn.py runs
 
 
 def _ttt_learner_is_agent(seed):
@@ -18,7 +19,7 @@ def _ttt_learner_is_agent(seed):
     return policy
 
 
-@pytest.mark.parametrize("dims,K,P", TTT_CONFIGS, ids=["x".join(map(str, d)) + "k%dp%d" % (k, p) for d, k, p in TTT_CONFIGS])
+@pytest.mark.parametrize("dims,K,P", TTT_CONFIGS, ids=TP.INSTANCE_IDS)
 def test_ttt_learner_as_agent_is_the_rollout(dims, K, P):
     from oracle import oracle as O
     B, seed, calls = 3 * P, 0x5EED + P, 14

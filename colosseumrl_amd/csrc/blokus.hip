@@ -559,6 +559,15 @@ __device__ __forceinline__ BlkPrologue blk_prologue(WaveLds &L, const int lane, 
 
 struct BlkMove { int piece, x, y, orient, shift; };
 
+// inv[q] (or score[q]) for a q that is no compile-time constant: a chain of selects, so that the four entries stay in registers
+__device__ __forceinline__ uint32_t blk_pick(const uint32_t (&inv)[4], const int q)
+{
+    uint32_t v = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v = (c == q) ? inv[c] : v;
+    return v;
+}
+
 // the r-th (0-based) legal action of player q in reference order; blk_count() must have filled L.pcnt
 // HAVE_INCL: `piece_incl` is the scan blk_count handed out (the rollout keeps it in a register); else it is redone here
 template <bool HAVE_INCL = false>
@@ -703,10 +712,7 @@ __device__ __forceinline__ int blk_apply(const BlkTables &T, WaveLds &L, const i
     int x = mv.x + (int)(cc & 15u) - ox, y = mv.y + (int)(cc >> 4) - oy;
     const bool mine = lane < n;
     if (__ballot(mine && (x < -BN || x >= BN || y < -BN || y >= BN)) != 0ull) return CRL_BLOKUS_INDEX_ERROR;
-    uint32_t held = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) held = (c == q) ? inv[c] : held;
-    if (!((held >> mv.piece) & 1u)) return CRL_BLOKUS_VALUE_ERROR;
+    if (!((blk_pick(inv, q) >> mv.piece) & 1u)) return CRL_BLOKUS_VALUE_ERROR;
     x += x < 0 ? BN : 0;                                   // numpy's negative indices
     y += y < 0 ? BN : 0;
     if (mine) {
@@ -808,6 +814,12 @@ __device__ __forceinline__ BlkMove blk_decode(const int id)
     return mv;
 }
 
+// the dense id of a move on the board: blk_decode's inverse
+__device__ __forceinline__ int blk_encode(const BlkMove &mv)
+{
+    return ((mv.piece * 400 + mv.y * BN + mv.x) * 8 + mv.orient) * 5 + mv.shift;
+}
+
 // what the step entries accept: the dense ids above and, from CRL_BLOKUS_EXT_BASE on, ids whose index lies anywhere in
 // [-20, 20) x [-20, 20) (next_state takes whatever string_to_action parsed, BlokusEnvironment.py:417); false: no such action
 __device__ __forceinline__ bool blk_decode_any(const int id, BlkMove &mv)
@@ -833,7 +845,100 @@ __device__ __forceinline__ int blk_play(const BlkTables &T, WaveLds &L, const in
     return blk_apply(T, L, q, mv, inv, score, lane);
 }
 
-#define BLK_SHARED_SETUP()                                                                        \
+// the random agent's 32-bit draw for the ply at step counter tc of game g (the rollout draws the same words sixteen plies
+// at a time): Philox block tc >> 2, word tc & 3; the ply plays legal action number hi32(draw * len(valid_actions))
+__device__ __forceinline__ uint32_t blk_agent_word(const uint32_t g, const uint32_t tc, const uint32_t seed_lo, const uint32_t seed_hi)
+{
+    const philox_out rnd = philox4x32_10(g, tc >> 2, 0u, CRL_TAG_BLOKUS, seed_lo, seed_hi);
+    const uint32_t sel = tc & 3u;
+    return sel == 0 ? rnd.w[0] : sel == 1 ? rnd.w[1] : sel == 2 ? rnd.w[2] : rnd.w[3];
+}
+
+// next_state's terminal test (BlokusEnvironment.py:424): does anybody have a move -- on the OLD board and in the OLD round
+// (the allowed / corner rows of every player as blk_prep built them before the move), with the NEW inventories
+__device__ __forceinline__ bool blk_anyone_moves(const BlkTables &T, WaveLds &L, const uint32_t (&inv)[4], const int lane,
+                                                 const BlkOwners *owners = nullptr)
+{
+    bool any_move = false;
+    for (int q = 0; q < 4 && !any_move; ++q) any_move = blk_exists(T, L, q, blk_pick(inv, q), lane, owners);
+    return any_move;
+}
+
+// the round and the mover of the ply after pl's (:446-447).  By value, as BlkPly below: a round or a mover that came back
+// through a reference would reach the code behind it (the counts, the observation's rotation) as a value out of memory,
+// of which the compiler no longer knows that it is below 4.
+__device__ __forceinline__ int blk_next_round(const int round, const int pl) { return round + ((pl == 3) ? 1 : 0); }
+__device__ __forceinline__ int blk_next_mover(const int pl) { return (pl + 1) & 3; }
+
+// what a ply leaves: status = 0 or blk_play's code -- the reference raises then, so the state stays what it was and the code
+// goes out in the reward slot --, the outcome (blk_outcome), and the round and the mover of the next ply
+struct BlkPly { int status, reward, terminal, winners, round, pl; };
+
+// next_state (:417-447) for an id as the step entries take it ('' = pass below 0, :418), on blk_prep's rows of the pre-move board
+__device__ __forceinline__ BlkPly blk_next_state(const BlkTables &T, WaveLds &L, const int id, uint32_t (&inv)[4], int (&score)[4],
+                                                 const int round, const int pl, const int lane)
+{
+    const int status = id >= 0 ? blk_play(T, L, pl, id, inv, score, lane) : 0;
+    if (status != 0) return BlkPly{status, status, 0, 0, round, pl};
+    const BlkOutcome out = blk_outcome(blk_anyone_moves(T, L, inv, lane), pl, score);
+    return BlkPly{0, out.reward, out.terminal, out.winners, blk_next_round(round, pl), blk_next_mover(pl)};
+}
+
+// One game of crl_blokus_step / crl_blokus_step_observe once its id is known: next_state, the outcome to memory, the restart
+// of a finished game under CRL_STEP_AUTO_RESET, the state back to memory.  Returns the ply with the round and the mover as
+// they were stored.
+__device__ __forceinline__ BlkPly blk_step_game(const BlkTables &T, WaveLds &L, const int64_t b, const int lane, const int id,
+                                                uint32_t (&inv)[4], int (&score)[4], const int round, const int pl, const uint32_t flags,
+                                                uint32_t *occ, uint32_t *inv_g, int32_t *score_g, int32_t *round_g, int32_t *to_move_g,
+                                                int8_t *reward, uint8_t *terminal, uint8_t *winners)
+{
+    BlkPly ply = blk_next_state(T, L, id, inv, score, round, pl, lane);
+    if (lane == 0) {
+        reward[b] = (int8_t)ply.reward;
+        terminal[b] = (uint8_t)ply.terminal;
+        winners[b] = (uint8_t)ply.winners;
+    }
+    if (ply.terminal && (flags & CRL_STEP_AUTO_RESET)) {
+        blk_fresh(L, lane, inv, score);
+        ply.round = 0;
+        ply.pl = 0;
+    }
+    blk_store_state(L, b, lane, occ, inv_g, score_g, inv, score);
+    if (lane == 0) { round_g[b] = ply.round; to_move_g[b] = ply.pl; }
+    return ply;
+}
+
+// is_valid_action (BlokusEnvironment.py:667-719: membership in valid_actions) of a decoded dense id without the enumeration:
+// the piece is held, `shift` names one of its cells, that cell's target is an anchor of player q, and every cell lands on
+// an allowed cell (blk_prep's rows of q).  FIT_ONLY: only the last condition (and the shift naming a cell) -- what
+// Board.check_orientation_shifts asks of ONE shift (board.py:156-168, computation.py:144-180 check_shifted): the index need
+// not be an anchor, the piece need not be held (iq is not read).  A cell off the board reads row 4 (in bounds) and fails.
+template <bool FIT_ONLY>
+__device__ __forceinline__ bool blk_move_legal(const BlkTables &T, const WaveLds &L, const int q, const uint32_t iq, const BlkMove &mv,
+                                               const int lane)
+{
+    const ShapeRegs s = blk_load_shape(T, mv.piece, mv.orient);
+    if (!(FIT_ONLY || ((iq >> mv.piece) & 1u)) || mv.shift >= s.n) return false;
+    int ox = 0, oy = 0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { ox = (j == mv.shift) ? s.sh(j) : ox; oy = (j == mv.shift) ? s.ro(j) : oy; }
+    bool cell_ok = true;
+    if (lane < s.n) {
+        int cx = 0, cy = 0;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) { cx = (j == lane) ? s.sh(j) : cx; cy = (j == lane) ? s.ro(j) : cy; }
+        const int x = mv.x + cx - ox, y = mv.y + cy - oy;
+        const bool on = x >= 0 && x < BN && y >= 0 && y < BN;
+        CRL_BOUNDS_LT(on ? y + 4 : 4, 32, 340);
+        cell_ok = on && ((L.ac[q][on ? y + 4 : 4].x >> (x + 8)) & 1u);
+    }
+    CRL_BOUNDS_LT(mv.y + 4, 32, 341);
+    const bool anchor = FIT_ONLY || ((L.ac[q][mv.y + 4].y >> (mv.x + 8)) & 1u);
+    return anchor && __ballot(!cell_ok) == 0ull;
+}
+
+// what every kernel that keeps a game per wave starts with: the tables staged in LDS, the wave's working set L ...
+#define BLK_WAVE_SETUP()                                                                          \
     __shared__ BlkTables T;                                                                       \
     __shared__ WaveLds Lw[4];                                                                     \
     for (int i = threadIdx.x; i < (int)(sizeof(BlkTables) / 4); i += blockDim.x)                  \
@@ -845,7 +950,11 @@ __device__ __forceinline__ int blk_play(const BlkTables &T, WaveLds &L, const in
     /* rows -4..-1 and 20..27 of the padded ac[] rows are zero for the whole launch (only 0..19 are rewritten) */     \
     for (int i = lane; i < 4 * 32; i += 64) L.ac[i >> 5][i & 31] = make_uint2(0u, 0u);            \
     /* ... and so are rows 28..30 of the pre-shifted table (the count passes rewrite rows 0..27 only) */          \
-    for (int i = lane; i < 3 * 9; i += 64) L.u.sh[28 + i / 9][i % 9] = make_uint2(0u, 0u);        \
+    for (int i = lane; i < 3 * 9; i += 64) L.u.sh[28 + i / 9][i % 9] = make_uint2(0u, 0u)
+
+// ... and, for the kernels with one wave per game (the playout walks its playouts in a loop instead), the wave's game b
+#define BLK_SHARED_SETUP()                                                                        \
+    BLK_WAVE_SETUP();                                                                             \
     const int64_t b = (int64_t)blockIdx.x * 4 + wave_;                                            \
     if (b >= B) return;
 
@@ -877,35 +986,10 @@ blokus_step_kernel(const BlkTables *__restrict__ tables, const int64_t B, uint32
     uint32_t inv[4];
     int score[4];
     blk_load_state(L, b, lane, occ, inv_g, score_g, inv, score);
-    int round = __builtin_amdgcn_readfirstlane(round_g[b]), pl = __builtin_amdgcn_readfirstlane(to_move_g[b]) & 3;
+    const int round = __builtin_amdgcn_readfirstlane(round_g[b]), pl = __builtin_amdgcn_readfirstlane(to_move_g[b]) & 3;
     blk_prep(L, lane, round);                                    // allowed / corner rows of the PRE-move board (:424)
     const int id = __builtin_amdgcn_readfirstlane(action[b]);
-    const int status = id >= 0 ? blk_play(T, L, pl, id, inv, score, lane) : 0;   // '' (pass) below 0 (:418)
-    BlkOutcome out = {status, 0, 0};                             // the reference raises: the state stays, the code goes out
-    if (status == 0) {
-        bool any_move = false;
-        for (int q = 0; q < 4 && !any_move; ++q) {               // old board, old round, NEW inventories (:424)
-            uint32_t iq = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) iq = (c == q) ? inv[c] : iq;
-            any_move = blk_exists(T, L, q, iq, lane);
-        }
-        out = blk_outcome(any_move, pl, score);
-        round += (pl == 3) ? 1 : 0;                              // :446-447
-        pl = (pl + 1) & 3;
-    }
-    if (lane == 0) {
-        reward[b] = (int8_t)out.reward;
-        terminal[b] = (uint8_t)out.terminal;
-        winners[b] = (uint8_t)out.winners;
-    }
-    if (out.terminal && (flags & CRL_STEP_AUTO_RESET)) {
-        blk_fresh(L, lane, inv, score);
-        round = 0;
-        pl = 0;
-    }
-    blk_store_state(L, b, lane, occ, inv_g, score_g, inv, score);
-    if (lane == 0) { round_g[b] = round; to_move_g[b] = pl; }
+    (void)blk_step_game(T, L, b, lane, id, inv, score, round, pl, flags, occ, inv_g, score_g, round_g, to_move_g, reward, terminal, winners);
 }
 
 // valid_actions: count, and optionally the dense id bitmap (bit id set = action id is legal)
@@ -921,9 +1005,7 @@ blokus_valid_kernel(const BlkTables *__restrict__ tables, const int64_t B, const
     blk_load_state(L, b, lane, occ, inv_g, score_g, inv, score);
     const int q = __builtin_amdgcn_readfirstlane(player ? (int)player[b] : to_move_g[b]) & 3;
     blk_prep(L, lane, __builtin_amdgcn_readfirstlane(round_g[b]));
-    uint32_t iq = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) iq = (c == q) ? inv[c] : iq;
+    const uint32_t iq = blk_pick(inv, q);
     const uint32_t total = blk_count(T, L, q, iq, lane);
     if (lane == 0 && count) count[b] = (int32_t)total;
     if (mask && total) {
@@ -947,7 +1029,7 @@ blokus_valid_kernel(const BlkTables *__restrict__ tables, const int64_t B, const
                         const int x = __builtin_ctz(hits);
                         hits &= hits - 1;
                         const int ax = x + s.sh(j) - 4, ay = y + s.ro(j) - 4;     // the anchor
-                        const int id = ((piece * 400 + ay * BN + ax) * 8 + o) * 5 + j;
+                        const int id = blk_encode(BlkMove{piece, ax, ay, o, j});
                         atomicOr(&m[id >> 5], 1u << (id & 31));
                     }
                 }
@@ -970,18 +1052,14 @@ blokus_sample_kernel(const BlkTables *__restrict__ tables, const int64_t B, cons
     blk_load_state(L, b, lane, occ, inv_g, score_g, inv, score);
     const int pl = __builtin_amdgcn_readfirstlane(to_move_g[b]) & 3;
     blk_prep(L, lane, __builtin_amdgcn_readfirstlane(round_g[b]));
-    uint32_t ip = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) ip = (c == pl) ? inv[c] : ip;
+    const uint32_t ip = blk_pick(inv, pl);
     const uint32_t total = blk_count(T, L, pl, ip, lane);
     const uint32_t tc = (uint32_t)__builtin_amdgcn_readfirstlane((int)tcount[b]);
-    const philox_out rnd = philox4x32_10((uint32_t)(first_env_id + (uint64_t)b), tc >> 2, 0u, CRL_TAG_BLOKUS, seed_lo, seed_hi);
-    const uint32_t sel = tc & 3u;
-    const uint32_t word = sel == 0 ? rnd.w[0] : sel == 1 ? rnd.w[1] : sel == 2 ? rnd.w[2] : rnd.w[3];
+    const uint32_t word = blk_agent_word((uint32_t)(first_env_id + (uint64_t)b), tc, seed_lo, seed_hi);
     int id = -1;
     if (total > 0) {
         const BlkMove mv = blk_select(T, L, pl, ip, __umulhi(word, total), lane);
-        id = ((mv.piece * 400 + mv.y * BN + mv.x) * 8 + mv.orient) * 5 + mv.shift;
+        id = blk_encode(mv);
     }
     if (lane == 0) {
         action[b] = id;
@@ -1048,71 +1126,41 @@ blokus_step_observe_kernel(const BlkTables *__restrict__ tables, const int64_t B
     uint32_t inv[4];
     int score[4];
     blk_load_state(L, b, lane, occ, inv_g, score_g, inv, score);
-    int round = __builtin_amdgcn_readfirstlane(round_g[b]), pl = __builtin_amdgcn_readfirstlane(to_move_g[b]) & 3;
+    const int round = __builtin_amdgcn_readfirstlane(round_g[b]), pl = __builtin_amdgcn_readfirstlane(to_move_g[b]) & 3;
     blk_prep(L, lane, round);                                    // allowed / corner rows of the PRE-move board (:424)
     int id;
     if (action) {
         id = __builtin_amdgcn_readfirstlane(action[b]);
     } else {                                                     // the rollout's random agent at this game's step counter
-        uint32_t ip = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) ip = (c == pl) ? inv[c] : ip;
+        const uint32_t ip = blk_pick(inv, pl);
         const uint32_t total = blk_count(T, L, pl, ip, lane);
         const uint32_t tc = (uint32_t)__builtin_amdgcn_readfirstlane((int)tcount[b]);
-        const philox_out rnd = philox4x32_10((uint32_t)(first_env_id + (uint64_t)b), tc >> 2, 0u, CRL_TAG_BLOKUS, seed_lo, seed_hi);
-        const uint32_t sel = tc & 3u;
-        const uint32_t word = sel == 0 ? rnd.w[0] : sel == 1 ? rnd.w[1] : sel == 2 ? rnd.w[2] : rnd.w[3];
+        const uint32_t word = blk_agent_word((uint32_t)(first_env_id + (uint64_t)b), tc, seed_lo, seed_hi);
         id = -1;
         if (total > 0) {
             const BlkMove mv = blk_select(T, L, pl, ip, __umulhi(word, total), lane);
-            id = ((mv.piece * 400 + mv.y * BN + mv.x) * 8 + mv.orient) * 5 + mv.shift;
+            id = blk_encode(mv);
         }
         if (lane == 0) tcount[b] = tc + 1u;
     }
-    const int status = id >= 0 ? blk_play(T, L, pl, id, inv, score, lane) : 0;   // '' (pass) below 0 (:418)
-    BlkOutcome out = {status, 0, 0};                             // the reference raises: the state stays, the code goes out
-    if (status == 0) {
-        bool any_move = false;
-        for (int q = 0; q < 4 && !any_move; ++q) {               // old board, old round, NEW inventories (:424)
-            uint32_t iq = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) iq = (c == q) ? inv[c] : iq;
-            any_move = blk_exists(T, L, q, iq, lane);
-        }
-        out = blk_outcome(any_move, pl, score);
-        round += (pl == 3) ? 1 : 0;                              // :446-447
-        pl = (pl + 1) & 3;
-    }
-    if (lane == 0) {
-        reward[b] = (int8_t)out.reward;
-        terminal[b] = (uint8_t)out.terminal;
-        winners[b] = (uint8_t)out.winners;
-    }
-    if (out.terminal && (flags & CRL_STEP_AUTO_RESET)) {
-        blk_fresh(L, lane, inv, score);
-        round = 0;
-        pl = 0;
-    }
-    blk_store_state(L, b, lane, occ, inv_g, score_g, inv, score);
-    if (lane == 0) { round_g[b] = round; to_move_g[b] = pl; }
+    const BlkPly ply = blk_step_game(T, L, b, lane, id, inv, score, round, pl, flags, occ, inv_g, score_g, round_g, to_move_g,
+                                     reward, terminal, winners);
     // ---- what the next mover needs: its number of legal actions on the NEW board ...
-    blk_prep(L, lane, round);
-    uint32_t ip = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) ip = (c == pl) ? inv[c] : ip;
-    const uint32_t total = blk_count(T, L, pl, ip, lane);
-    if (lane == 0) { n_valid[b] = (int32_t)total; obs_player[b] = (int8_t)pl; }
+    blk_prep(L, lane, ply.round);
+    const uint32_t total = blk_count(T, L, ply.pl, blk_pick(inv, ply.pl), lane);
+    if (lane == 0) { n_valid[b] = (int32_t)total; obs_player[b] = (int8_t)ply.pl; }
     // ... and its observation (:752-768)
-    blk_write_observation(L.occ, inv, score, pl, b, lane, obs_board, obs_pieces, obs_score);
+    blk_write_observation(L.occ, inv, score, ply.pl, b, lane, obs_board, obs_pieces, obs_score);
 }
 
 // ---- one learner against the random agent (crl_blokus_step_single; the contract is in include/colosseum_hip.h): per game
 // an optional learner ply, then the random agent for every other seat until it is the learner's turn again -- across the
 // end of a game and its restart -- and the learner's count and observation of what that leaves.  The wave that owns the
 // game plays every ply (at most 1 + 6) on its LDS copy of the board: one load and one store of the state per call, where
-// a chain of step_observe calls reloads the board and rebuilds the allowed / corner rows per ply.  Each ply is that of
-// blokus_step_observe_kernel (the draw of blokus_sample_kernel, blk_play, the terminal test on the pre-move board); the
-// loop runs on wave-uniform values (mover, seat, step counter), so it costs no divergence.
+// a chain of step_observe calls reloads the board and rebuilds the allowed / corner rows per ply.  Each ply is made of what
+// blokus_step_observe_kernel's is: blk_agent_word's draw, blk_encode of the selected move, blk_next_state.  Its own are the
+// learner's action (an id or a rank), the learner's reward and the restart without a flag.  The loop runs on wave-uniform
+// values (mover, seat, step counter), so it costs no divergence.
 __global__ void __launch_bounds__(256, BLK_WAVES_PER_SIMD)
 blokus_step_single_kernel(const BlkTables *__restrict__ tables, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
                           const uint64_t first_env_id, uint32_t *__restrict__ occ, uint32_t *__restrict__ inv_g,
@@ -1135,9 +1183,7 @@ blokus_step_single_kernel(const BlkTables *__restrict__ tables, const int64_t B,
     for (; plies >= 8 || (pl != s && plies < 6); ) {
         const bool learner = plies >= 8;
         blk_prep(L, lane, round);                                // allowed / corner rows of the PRE-move board (:424)
-        uint32_t ip = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) ip = (c == pl) ? inv[c] : ip;
+        const uint32_t ip = blk_pick(inv, pl);
         int id = -1;
         if (learner && !(flags & CRL_STEP_RANK_ACTION)) {                             // crl_blokus_step's int32 action; v < -1 is the pass
             const int64_t v = learner_action[b];
@@ -1149,33 +1195,22 @@ blokus_step_single_kernel(const BlkTables *__restrict__ tables, const int64_t B,
             if (learner) {
                 r = learner_action[b];
             } else {                                             // the random agent at this game's step counter
-                const philox_out rnd = philox4x32_10((uint32_t)(first_env_id + (uint64_t)b), tc >> 2, 0u, CRL_TAG_BLOKUS, seed_lo, seed_hi);
-                const uint32_t sel = tc & 3u;
-                const uint32_t word = sel == 0 ? rnd.w[0] : sel == 1 ? rnd.w[1] : sel == 2 ? rnd.w[2] : rnd.w[3];
-                r = __umulhi(word, total);
+                r = __umulhi(blk_agent_word((uint32_t)(first_env_id + (uint64_t)b), tc, seed_lo, seed_hi), total);
             }
             const int ri = __builtin_amdgcn_readfirstlane(r >= 0 && r < (int64_t)total ? (int)r : -1);
             if (ri >= 0) {
                 const BlkMove mv = blk_select(T, L, pl, ip, (uint32_t)ri, lane);
-                id = ((mv.piece * 400 + mv.y * BN + mv.x) * 8 + mv.orient) * 5 + mv.shift;
+                id = blk_encode(mv);
             }
         }
         plies = learner ? 0 : plies + 1;
-        const int status = id >= 0 ? blk_play(T, L, pl, id, inv, score, lane) : 0;   // '' (pass) below 0 (:418)
-        if (status != 0) { rew = status; break; }                // (the learner's ply only: a drawn action is legal)
+        const BlkPly ply = blk_next_state(T, L, id, inv, score, round, pl, lane);
+        round = ply.round;                                       // (what they were when the ply raised)
+        pl = ply.pl;
+        if (ply.status != 0) { rew = ply.status; break; }        // (the learner's ply only: a drawn action is legal)
         tc += 1u;
-        bool any_move = false;
-        for (int q = 0; q < 4 && !any_move; ++q) {               // old board, old round, NEW inventories (:424)
-            uint32_t iq = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) iq = (c == q) ? inv[c] : iq;
-            any_move = blk_exists(T, L, q, iq, lane);
-        }
-        const BlkOutcome out = blk_outcome(any_move, pl, score);
-        round += (pl == 3) ? 1 : 0;                              // :446-447
-        pl = (pl + 1) & 3;
-        if (out.terminal) {                                      // the learner's rank (:424-440 with the mover = s), restart
-            dn_wn = 1 | out.winners << 1;
+        if (ply.terminal) {                                      // the learner's rank (:424-440 with the mover = s), restart
+            dn_wn = 1 | ply.winners << 1;
             rew = blk_outcome(false, s, score).reward;
             blk_fresh(L, lane, inv, score);
             round = 0;
@@ -1193,10 +1228,7 @@ blokus_step_single_kernel(const BlkTables *__restrict__ tables, const int64_t B,
     }
     // ---- what the learner needs: its number of legal actions and its observation (:453-500, :752-768)
     blk_prep(L, lane, round);
-    uint32_t is = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) is = (c == s) ? inv[c] : is;
-    const uint32_t total = blk_count(T, L, s, is, lane);
+    const uint32_t total = blk_count(T, L, s, blk_pick(inv, s), lane);
     if (lane == 0) n_valid[b] = (int32_t)total;
     blk_write_observation(L.occ, inv, score, s, b, lane, obs_board, obs_pieces, obs_score);
 }
@@ -1371,13 +1403,15 @@ blokus_rollout_kernel(const BlkTables *__restrict__ tables, const int64_t B, con
 
 // ---- batched random playouts (crl_blokus_playout; the contract is in include/colosseum_hip.h).  One wave per playout
 // i = (b * A + a) * R + r, the board in LDS, four waves per workgroup walking the playouts in a grid-stride loop.  The
-// candidate ply is checked as blokus_is_valid_kernel checks an id (on the allowed / corner rows of the pre-move board) and
-// played as blk_play plays a dense id (blk_apply of its decoded move); its terminal test is crl_blokus_step's (every player, the pre-move rows, the new inventories).  The
-// random plies are blokus_rollout_kernel's specialised ply -- blk_prologue, the count, blk_select on the scan in registers,
-// the terminal test on the pre-move board with its `dead` / `can_move` caches, blk_place_legal -- with inventories and
-// scores in vector registers as there, the 16 words of a Philox quadruple drawn together, and no reset: the loop ends at
-// the first terminal ply.  (A copy of the rollout's loop body rather than a helper shared with it: the rollout's code
-// stays what it was.)  Lane 0 adds the playout's outcome into its row (integer atomics onto the zeros the launcher wrote).
+// candidate ply shares its pieces with the step entries: blk_move_legal is blokus_is_valid_kernel's test of an id, blk_apply
+// plays the decoded move as blk_play does, blk_anyone_moves is crl_blokus_step's terminal test, blk_next_round / blk_next_mover
+// its advance.  The random plies are blokus_rollout_kernel's specialised ply -- blk_prologue, the count, blk_select on the scan
+// in registers, the terminal test on the pre-move board with its `dead` / `can_move` caches, blk_place_legal -- with
+// inventories and scores in vector registers as there, the 16 words of a Philox quadruple drawn together, and no reset: the
+// loop ends at the first terminal ply.  That loop body is NOT shared with the rollout, on purpose: with the ply in one
+// __forceinline__ helper called from both, blokus_rollout_kernel -- the benchmark's headline kernel, bound by instruction
+// issue -- went from 0 to 12 bytes of scratch, from 57 to 61 VGPRs and from 1772 to 1840 instructions.  Change both loops
+// together.  Lane 0 adds the playout's outcome into its row (integer atomics onto the zeros the launcher wrote).
 __device__ __forceinline__ uint64_t blk_uniform64(const uint64_t v)
 {
     return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v)
@@ -1393,17 +1427,7 @@ blokus_playout_kernel(const BlkTables *__restrict__ tables, const int64_t B, con
                       uint32_t *__restrict__ wins, uint32_t *__restrict__ played, uint32_t *__restrict__ len_sum,
                       int32_t *__restrict__ score_sum)
 {
-    __shared__ BlkTables T;
-    __shared__ WaveLds Lw[4];
-    for (int i = threadIdx.x; i < (int)(sizeof(BlkTables) / 4); i += blockDim.x)
-        reinterpret_cast<uint32_t *>(&T)[i] = reinterpret_cast<const uint32_t *>(tables)[i];
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int wave_ = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    WaveLds &L = Lw[wave_];
-    // rows -4..-1 and 20..27 of the padded ac[] rows and rows 28..30 of the pre-shifted table stay zero (as BLK_SHARED_SETUP)
-    for (int i = lane; i < 4 * 32; i += 64) L.ac[i >> 5][i & 31] = make_uint2(0u, 0u);
-    for (int i = lane; i < 3 * 9; i += 64) L.u.sh[28 + i / 9][i % 9] = make_uint2(0u, 0u);
+    BLK_WAVE_SETUP();
     const uint32_t piece_cells = lane < 24 ? T.ncell[lane] : 0u;
     const BlkOwners owners = blk_shape_owners(T, lane);
     for (uint64_t i = (uint64_t)blockIdx.x * 4u + (uint32_t)wave_; i < n_playouts; i += (uint64_t)gridDim.x * 4u) {
@@ -1424,31 +1448,9 @@ blokus_playout_kernel(const BlkTables *__restrict__ tables, const int64_t B, con
             const int id = __builtin_amdgcn_readfirstlane(cand[b * A + a]);
             blk_prep(L, lane, round);                            // every player's rows of the PRE-move board (:424)
             const uint32_t ip = (uint32_t)__builtin_amdgcn_readlane((int)vinv, pl);
-            bool good = false;
-            BlkMove mv = {0, 0, 0, 0, 0};
-            if (id >= 0 && id < ACTION_IDS) {
-                mv = blk_decode(id);
-                const ShapeRegs s = blk_load_shape(T, mv.piece, mv.orient);
-                if (((ip >> mv.piece) & 1u) && mv.shift < s.n) {
-                    int ox = 0, oy = 0;
-#pragma unroll
-                    for (int j = 0; j < 5; ++j) { ox = (j == mv.shift) ? s.sh(j) : ox; oy = (j == mv.shift) ? s.ro(j) : oy; }
-                    bool cell_ok = true;
-                    if (lane < s.n) {
-                        int cx = 0, cy = 0;
-#pragma unroll
-                        for (int j = 0; j < 5; ++j) { cx = (j == lane) ? s.sh(j) : cx; cy = (j == lane) ? s.ro(j) : cy; }
-                        const int x = mv.x + cx - ox, y = mv.y + cy - oy;
-                        const bool on = x >= 0 && x < BN && y >= 0 && y < BN;
-                        CRL_BOUNDS_LT(on ? y + 4 : 4, 32, 340);
-                        cell_ok = on && ((L.ac[pl][on ? y + 4 : 4].x >> (x + 8)) & 1u);
-                    }
-                    CRL_BOUNDS_LT(mv.y + 4, 32, 341);
-                    const bool anchor = (L.ac[pl][mv.y + 4].y >> (mv.x + 8)) & 1u;
-                    good = anchor && __ballot(!cell_ok) == 0ull;
-                }
-            }
-            if (!good) continue;                                 // (wave-uniform) the row is skipped: nothing to add
+            if (id < 0 || id >= ACTION_IDS) continue;            // (wave-uniform) the row is skipped: nothing to add
+            const BlkMove mv = blk_decode(id);
+            if (!blk_move_legal<false>(T, L, pl, ip, mv, lane)) continue;
             uint32_t inv[4];
             int score[4];
 #pragma unroll
@@ -1457,21 +1459,14 @@ blokus_playout_kernel(const BlkTables *__restrict__ tables, const int64_t B, con
                 score[c] = __builtin_amdgcn_readlane(vscore, c);
             }
             (void)blk_apply(T, L, pl, mv, inv, score, lane);    // blk_play of a dense id (legal: it returns 0)
-            bool any_move = false;
-            for (int q = 0; q < 4 && !any_move; ++q) {           // old board, old round, NEW inventories (:424)
-                uint32_t iq = 0;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) iq = (c == q) ? inv[c] : iq;
-                any_move = blk_exists(T, L, q, iq, lane, &owners);
-            }
+            over = !blk_anyone_moves(T, L, inv, lane, &owners);
+            round = blk_next_round(round, pl);
+            pl = blk_next_mover(pl);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 vinv = (lane & 3) == c ? inv[c] : vinv;
                 vscore = (lane & 3) == c ? score[c] : vscore;
             }
-            over = !any_move;
-            round += (pl == 3) ? 1 : 0;                          // :446-447
-            pl = (pl + 1) & 3;
             len = 1;
         }
         uint32_t winners_mask = 0;
@@ -1830,15 +1825,13 @@ blokus_select_kernel(const BlkTables *__restrict__ tables, const int64_t B, cons
     blk_load_state(L, b, lane, occ, inv_g, score_g, inv, score);
     const int q = __builtin_amdgcn_readfirstlane(player ? (int)player[b] : to_move_g[b]) & 3;
     blk_prep(L, lane, __builtin_amdgcn_readfirstlane(round_g[b]));
-    uint32_t iq = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) iq = (c == q) ? inv[c] : iq;
+    const uint32_t iq = blk_pick(inv, q);
     const uint32_t total = blk_count(T, L, q, iq, lane);
     const int r = __builtin_amdgcn_readfirstlane(rank[b]);
     int id = -1;
     if (r >= 0 && (uint32_t)r < total) {
         const BlkMove mv = blk_select(T, L, q, iq, (uint32_t)r, lane);
-        id = ((mv.piece * 400 + mv.y * BN + mv.x) * 8 + mv.orient) * 5 + mv.shift;
+        id = blk_encode(mv);
     }
     if (lane == 0) {
         action[b] = id;
@@ -1846,11 +1839,8 @@ blokus_select_kernel(const BlkTables *__restrict__ tables, const int64_t B, cons
     }
 }
 
-// is_valid_action (BlokusEnvironment.py:667-719: membership in valid_actions) without the enumeration: the piece is held,
-// `shift` names one of its cells, that cell's target is an anchor of the player, and every cell lands on an allowed cell.
-// FIT_ONLY: only the last condition (and the shift naming a cell) -- what Board.check_orientation_shifts asks of ONE shift
-// (board.py:156-168, computation.py:144-180 check_shifted): the index need not be an anchor, the piece need not be held;
-// inv_g / round_g / to_move_g are not read then.
+// blk_move_legal of action[b] for `player` (crl_blokus_is_valid), or its FIT_ONLY form (crl_blokus_fits): inv_g / round_g /
+// to_move_g are not read then.  An id outside the dense range is no action.
 template <bool FIT_ONLY>
 __global__ void __launch_bounds__(256, BLK_WAVES_PER_SIMD)
 blokus_is_valid_kernel(const BlkTables *__restrict__ tables, const int64_t B, const uint32_t *__restrict__ occ,
@@ -1864,26 +1854,7 @@ blokus_is_valid_kernel(const BlkTables *__restrict__ tables, const int64_t B, co
     blk_prep(L, lane, FIT_ONLY ? 1 : __builtin_amdgcn_readfirstlane(round_g[b]), q);
     const uint32_t iq = FIT_ONLY ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)inv_g[b * 4 + q]);
     const int id = __builtin_amdgcn_readfirstlane(action[b]);
-    bool good = false;
-    if (id >= 0 && id < ACTION_IDS) {
-        const BlkMove mv = blk_decode(id);
-        const ShapeRegs s = blk_load_shape(T, mv.piece, mv.orient);
-        if ((FIT_ONLY || ((iq >> mv.piece) & 1u)) && mv.shift < s.n) {
-            int ox = 0, oy = 0;
-#pragma unroll
-            for (int j = 0; j < 5; ++j) { ox = (j == mv.shift) ? s.sh(j) : ox; oy = (j == mv.shift) ? s.ro(j) : oy; }
-            bool cell_ok = true;
-            if (lane < s.n) {
-                int cx = 0, cy = 0;
-#pragma unroll
-                for (int j = 0; j < 5; ++j) { cx = (j == lane) ? s.sh(j) : cx; cy = (j == lane) ? s.ro(j) : cy; }
-                const int x = mv.x + cx - ox, y = mv.y + cy - oy;
-                cell_ok = x >= 0 && x < BN && y >= 0 && y < BN && ((L.ac[q][y + 4].x >> (x + 8)) & 1u);
-            }
-            const bool anchor = FIT_ONLY || ((L.ac[q][mv.y + 4].y >> (mv.x + 8)) & 1u);
-            good = anchor && __ballot(!cell_ok) == 0ull;
-        }
-    }
+    const bool good = id >= 0 && id < ACTION_IDS && blk_move_legal<FIT_ONLY>(T, L, q, iq, blk_decode(id), lane);
     if (lane == 0) ok[b] = good ? 1 : 0;
 }
 

@@ -164,6 +164,36 @@ __device__ __forceinline__ uint32_t ttt_agent_word(const uint32_t g, const uint3
     return (c & 1u) ? w * (uint32_t)(n_empty + 1) : w;
 }
 
+// every player's marks
+template <int P>
+__device__ __forceinline__ uint32_t ttt_union(const uint32_t (&o)[P])
+{
+    uint32_t all = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) all |= o[p];
+    return all;
+}
+
+// the random agent's move at step counter c of game g on a board whose marks are `all`: empty cell number
+// hi32(draw * n_empty) in row-major order, -1 (the pass) on a full board
+__device__ __forceinline__ int ttt_agent_move(const uint32_t full, const uint32_t all, const uint32_t g, const uint32_t c,
+                                              const uint32_t seed_lo, const uint32_t seed_hi)
+{
+    const uint32_t empty = full & ~all;
+    const int n_empty = __popc(empty);
+    return n_empty ? nth_set_bit(empty, (int)__umulhi(ttt_agent_word(g, c, n_empty, seed_lo, seed_hi), (uint32_t)n_empty)) : -1;
+}
+
+// the 8 KB win-mask table of a board of at most 16 cells from memory into LDS by the 256 threads of the workgroup, two
+// uint4 each (the caller puts a __syncthreads behind it)
+__device__ __forceinline__ void ttt_stage_win_table(uint32_t *win_bits, const uint32_t *__restrict__ win_tab)
+{
+    const uint4 *src = reinterpret_cast<const uint4 *>(win_tab);
+    uint4 *dst = reinterpret_cast<uint4 *>(win_bits);
+    dst[threadIdx.x] = src[threadIdx.x];
+    dst[threadIdx.x + 256] = src[threadIdx.x + 256];
+}
+
 template <int P, int ND>
 __global__ void __launch_bounds__(256)
 ttt_step_kernel(const ttt_dirs dd, const int64_t B, uint32_t *__restrict__ occ, int8_t *__restrict__ winner,
@@ -203,12 +233,7 @@ ttt_rollout_kernel(const ttt_dirs dd, const int64_t B, const uint32_t seed_lo, c
     __shared__ uint8_t rank_tab[256 * 8];
     __shared__ uint32_t win_bits[WT ? 2048 : 1];             // boards of <= 16 cells: bit m = the mask m holds a K-line
     ttt_fill_rank_table(rank_tab);
-    if (WT) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(win_tab);
-        uint4 *dst = reinterpret_cast<uint4 *>(win_bits);
-        dst[threadIdx.x] = src[threadIdx.x];
-        dst[threadIdx.x + 256] = src[threadIdx.x + 256];
-    }
+    if (WT) ttt_stage_win_table(win_bits, win_tab);
     __syncthreads();
     if (b >= B) return;
     uint32_t o[P], wins[P];
@@ -501,12 +526,8 @@ ttt_step_observe_kernel(const ttt_dirs dd, const uint32_t inv_cells, const int64
         if (action) {
             act = action[b];
         } else {                                    // the rollout's random agent at this game's step counter
-            uint32_t all = 0;
-#pragma unroll
-            for (int p = 0; p < P; ++p) all |= o[p];
-            const uint32_t empty = dd.full & ~all, c = tcount[b];
-            const int n_empty = __popc(empty);
-            act = n_empty ? nth_set_bit(empty, (int)__umulhi(ttt_agent_word((uint32_t)(first_env_id + (uint64_t)b), c, n_empty, seed_lo, seed_hi), (uint32_t)n_empty)) : -1;
+            const uint32_t c = tcount[b];
+            act = ttt_agent_move(dd.full, ttt_union<P>(o), (uint32_t)(first_env_id + (uint64_t)b), c, seed_lo, seed_hi);
             tcount[b] = c + 1u;
         }
         int r, t, ws;
@@ -553,10 +574,7 @@ ttt_step_single_kernel(const ttt_dirs dd, const uint32_t inv_cells, const int64_
     __shared__ int s_seat[256];
     __shared__ uint32_t win_bits[WT ? 2048 : 1];
     if (WT) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(win_tab);
-        uint4 *dst = reinterpret_cast<uint4 *>(win_bits);
-        dst[threadIdx.x] = src[threadIdx.x];
-        dst[threadIdx.x + 256] = src[threadIdx.x + 256];
+        ttt_stage_win_table(win_bits, win_tab);
         __syncthreads();
     }
     const int64_t g0 = (int64_t)blockIdx.x * 256;
@@ -581,12 +599,7 @@ ttt_step_single_kernel(const ttt_dirs dd, const uint32_t inv_cells, const int64_
                 const int64_t v = learner_action[b];
                 act = (v >= -1 && v < dd.n_cells) ? (int)v : -1;
             } else {                                // crl_ttt_sample at this game's step counter
-                uint32_t all = 0;
-#pragma unroll
-                for (int p = 0; p < P; ++p) all |= o[p];
-                const uint32_t empty = dd.full & ~all;
-                const int n_empty = __popc(empty);
-                act = n_empty ? nth_set_bit(empty, (int)__umulhi(ttt_agent_word(g, c, n_empty, seed_lo, seed_hi), (uint32_t)n_empty)) : -1;
+                act = ttt_agent_move(dd.full, ttt_union<P>(o), g, c, seed_lo, seed_hi);
                 ++opp;
             }
             c += 1u;
@@ -641,12 +654,7 @@ ttt_playout_kernel(const ttt_dirs dd, const int64_t B, const uint32_t seed_lo, c
     __shared__ uint8_t rank_tab[256 * 8];
     __shared__ uint32_t win_bits[WT ? 2048 : 1];
     ttt_fill_rank_table(rank_tab);
-    if (WT) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(win_tab);
-        uint4 *dst = reinterpret_cast<uint4 *>(win_bits);
-        dst[threadIdx.x] = src[threadIdx.x];
-        dst[threadIdx.x + 256] = src[threadIdx.x + 256];
-    }
+    if (WT) ttt_stage_win_table(win_bits, win_tab);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t stride = (uint64_t)gridDim.x * 256u;
@@ -683,10 +691,7 @@ ttt_playout_kernel(const ttt_dirs dd, const int64_t B, const uint32_t seed_lo, c
                     len = 1;
                 }
                 while (!term) {                                 // random plies on a running game (the rollout's draw)
-                    all = 0;
-#pragma unroll
-                    for (int p = 0; p < P; ++p) all |= o[p];
-                    const uint32_t empty = dd.full & ~all;
+                    const uint32_t empty = dd.full & ~ttt_union<P>(o);
                     const uint32_t n_empty = (uint32_t)__popc(empty);           // (not 0: the game is running)
                     const uint32_t sel = (c >> 1) & 3u;
                     uint32_t word = rnd.w[0];
@@ -744,6 +749,9 @@ ttt_sample_kernel(const int P, const uint32_t full, const int64_t B, const uint3
     if (b >= B) return;
     uint32_t all = 0;
     for (int p = 0; p < P; ++p) all |= occ[p * B + b];
+    // ttt_agent_move's rule with the draw made BEFORE the test for a full board, as this kernel always had it: through the
+    // helper (the draw behind the test) it compiles to 16 VGPRs / 20 SGPRs instead of 18 / 32, and a refactor that must
+    // leave every kernel's registers alone cannot take that
     const uint32_t empty = full & ~all, c = tcount[b];
     const int n_empty = __popc(empty);
     const uint32_t word = ttt_agent_word((uint32_t)(first_env_id + (uint64_t)b), c, n_empty, seed_lo, seed_hi);
@@ -849,18 +857,14 @@ ttt_step_board_kernel(const ttt_dirs dd, const int64_t B, int8_t *__restrict__ b
     } else {
         ttt_masks_of_board<P>(cells, dd.n_cells, o);
     }
-    uint32_t before = 0;
-#pragma unroll
-    for (int p = 0; p < P; ++p) before |= o[p];
+    const uint32_t before = ttt_union<P>(o);
     int w = by_value ? vec.winner : (int)winner[b], tm = by_value ? vec.to_move : (int)to_move[b], r, t, ws;
     const int pl = tm, act = by_value ? vec.action : (int)action[b];
     ttt_step_core<P, ND>(dd, o, w, tm, act, r, t, ws);
     reward[b] = (int8_t)r;
     terminal[b] = (uint8_t)t;
     winners[b] = (int8_t)ws;
-    uint32_t all = 0;
-#pragma unroll
-    for (int p = 0; p < P; ++p) all |= o[p];
+    uint32_t all = ttt_union<P>(o);
     if (t && (flags & CRL_STEP_AUTO_RESET)) {
 #pragma unroll
         for (int p = 0; p < P; ++p) o[p] = 0;
@@ -888,12 +892,7 @@ ttt_observe_board_kernel(const int n_cells, const uint32_t full, const int64_t B
     if (b >= B) return;
     uint32_t o[P];
     ttt_masks_of_board<P>(board + b * n_cells, n_cells, o);
-    if (valid) {
-        uint32_t all = 0;
-#pragma unroll
-        for (int p = 0; p < P; ++p) all |= o[p];
-        valid[b] = full & ~all;
-    }
+    if (valid) valid[b] = full & ~ttt_union<P>(o);
     if (obs) ttt_write_relative<P>(o, n_cells, player ? (int)player[b] : -1, rel_mod, obs + b * n_cells);
 }
 
@@ -936,20 +935,50 @@ int build_dirs(const crl_ttt_cfg &c, ttt_dirs &dd, uint32_t *lines, int &n_lines
 
 inline const ttt_dirs &dirs_of(const crl_ctx *ctx) { return ctx->ttt_dd; }     // built once, in crl_ttt_create
 
+// the win-mask table of a board of at most 16 cells, if it lives on the current device; else nullptr (there is none, or
+// the call runs on another device than crl_ttt_create did): the kernels then compute the line test
+inline const uint32_t *ttt_win_table_here(const crl_ctx *ctx)
+{
+    int dev = -1;
+    return ctx->ttt_win_dev && hipGetDevice(&dev) == hipSuccess && dev == ctx->ttt_win_device ? ctx->ttt_win_dev : nullptr;
+}
+
+// floor(2^32 / cells) + 1: ttt_write_boards divides by the cell count with one multiply-high
+inline uint32_t ttt_inv_cells(const int cells) { return cells == 1 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint64_t)cells) + 1u; }
+
 } // namespace
 
-#define TTT_DISPATCH_P(P_, CALL)           \
+#define TTT_DISPATCH_P(P_, ...)            \
     switch (P_) {                          \
-        case 1: { constexpr int PP = 1; CALL; } break; \
-        case 2: { constexpr int PP = 2; CALL; } break; \
-        case 3: { constexpr int PP = 3; CALL; } break; \
-        case 4: { constexpr int PP = 4; CALL; } break; \
-        case 5: { constexpr int PP = 5; CALL; } break; \
-        case 6: { constexpr int PP = 6; CALL; } break; \
-        case 7: { constexpr int PP = 7; CALL; } break; \
-        case 8: { constexpr int PP = 8; CALL; } break; \
+        case 1: { constexpr int PP = 1; __VA_ARGS__; } break; \
+        case 2: { constexpr int PP = 2; __VA_ARGS__; } break; \
+        case 3: { constexpr int PP = 3; __VA_ARGS__; } break; \
+        case 4: { constexpr int PP = 4; __VA_ARGS__; } break; \
+        case 5: { constexpr int PP = 5; __VA_ARGS__; } break; \
+        case 6: { constexpr int PP = 6; __VA_ARGS__; } break; \
+        case 7: { constexpr int PP = 7; __VA_ARGS__; } break; \
+        case 8: { constexpr int PP = 8; __VA_ARGS__; } break; \
         default: crl_set_error("ttt: P=%d out of range 1..8", P_); return CRL_EINVAL; \
     }
+
+// ---- which template instance of a kernel runs a context: the rule is stated here and nowhere else.  The statement(s) given
+// see PP = the player count and, with TTT_DISPATCH_ND, NDD = 4 for a board with at most 4 line directions (everything 1-D
+// and 2-D), else 13; with TTT_DISPATCH_ND_WT also WTT, the win test out of the table: only with NDD = 4, at most 16 cells
+// and the table on this device (win_tab_ = ttt_win_table_here).
+#define TTT_INSTANCE(ND_, WT_, ...) { constexpr int NDD = ND_; [[maybe_unused]] constexpr bool WTT = WT_; __VA_ARGS__; }
+#define TTT_DISPATCH_ND(ctx_, ...)                                                          \
+    TTT_DISPATCH_P((ctx_)->ttt.P, {                                                          \
+        if ((ctx_)->ttt_dd.n_dirs <= 4) TTT_INSTANCE(4, false, __VA_ARGS__)                  \
+        else TTT_INSTANCE(13, false, __VA_ARGS__)                                            \
+    })
+#define TTT_DISPATCH_ND_WT(ctx_, win_tab_, ...)                                             \
+    TTT_DISPATCH_P((ctx_)->ttt.P, {                                                          \
+        if ((ctx_)->ttt_dd.n_dirs > 4) TTT_INSTANCE(13, false, __VA_ARGS__)                  \
+        else if ((ctx_)->ttt_dd.n_cells <= 16 && (win_tab_) != nullptr) TTT_INSTANCE(4, true, __VA_ARGS__) \
+        else TTT_INSTANCE(4, false, __VA_ARGS__)                                             \
+    })
+// (every kernel here runs one game -- the playout: one playout -- per thread, 256 to a workgroup, on the caller's `stream`)
+#define TTT_LAUNCH(kernel, blocks, ...) hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__)
 
 #define TTT_CTX_CHECK(fn)                                                                  \
     CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_TTT, fn ": ctx is not a tictactoe context"); \
@@ -1021,7 +1050,7 @@ int crl_ttt_reset(const crl_ctx *ctx, int64_t B, const uint8_t *mask, uint32_t *
 {
     TTT_CTX_CHECK("crl_ttt_reset");
     CRL_REQUIRE(occ && winner && to_move, "crl_ttt_reset: NULL state pointer");
-    hipLaunchKernelGGL(ttt_reset_kernel, dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, ctx->ttt.P, B, mask, occ, winner, to_move);
+    TTT_LAUNCH(ttt_reset_kernel, blocks_for(B, 256), ctx->ttt.P, B, mask, occ, winner, to_move);
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
@@ -1034,14 +1063,8 @@ int crl_ttt_step(const crl_ctx *ctx, int64_t B, uint32_t *occ, int8_t *winner, i
     CRL_REQUIRE(action && reward && terminal && winners, "crl_ttt_step: NULL action/output pointer");
     CRL_REQUIRE((flags & ~CRL_STEP_AUTO_RESET) == 0, "crl_ttt_step: unknown flags 0x%x", flags);
     const ttt_dirs dd = dirs_of(ctx);
-    TTT_DISPATCH_P(ctx->ttt.P, {
-        if (dd.n_dirs <= 4)
-            hipLaunchKernelGGL((ttt_step_kernel<PP, 4>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd, B,
-                               occ, winner, to_move, action, reward, terminal, winners, flags);
-        else
-            hipLaunchKernelGGL((ttt_step_kernel<PP, 13>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd, B,
-                               occ, winner, to_move, action, reward, terminal, winners, flags);
-    });
+    TTT_DISPATCH_ND(ctx, TTT_LAUNCH((ttt_step_kernel<PP, NDD>), blocks_for(B, 256), dd, B, occ, winner, to_move, action, reward,
+                                    terminal, winners, flags));
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
@@ -1050,7 +1073,7 @@ int crl_ttt_valid(const crl_ctx *ctx, int64_t B, const uint32_t *occ, uint32_t *
 {
     TTT_CTX_CHECK("crl_ttt_valid");
     CRL_REQUIRE(occ && valid, "crl_ttt_valid: NULL pointer");
-    hipLaunchKernelGGL(ttt_valid_kernel, dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, ctx->ttt.P, ctx->ttt.full, B, occ, valid);
+    TTT_LAUNCH(ttt_valid_kernel, blocks_for(B, 256), ctx->ttt.P, ctx->ttt.full, B, occ, valid);
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
@@ -1062,11 +1085,8 @@ int crl_ttt_board(const crl_ctx *ctx, int64_t B, const uint32_t *occ, const int8
     CRL_REQUIRE(player == nullptr || rel_mod >= 1, "crl_ttt_board: rel_mod must be >= 1 when player is given");
     CRL_REQUIRE((((uintptr_t)board) & 3) == 0, "crl_ttt_board: board must be 4-byte aligned");
     const int cells = ctx->ttt.n_cells;
-    const uint32_t inv_cells = cells == 1 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint64_t)cells) + 1u;
-    TTT_DISPATCH_P(ctx->ttt.P, {
-        hipLaunchKernelGGL((ttt_board_kernel<PP>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream,
-                           cells, inv_cells, B, occ, player, rel_mod < 1 ? 1 : rel_mod, board);
-    });
+    TTT_DISPATCH_P(ctx->ttt.P, TTT_LAUNCH((ttt_board_kernel<PP>), blocks_for(B, 256), cells, ttt_inv_cells(cells), B, occ, player,
+                                          rel_mod < 1 ? 1 : rel_mod, board));
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
@@ -1077,8 +1097,8 @@ int crl_ttt_sample(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_
     TTT_CTX_CHECK("crl_ttt_sample");
     CRL_REQUIRE(occ && tcount && action, "crl_ttt_sample: NULL pointer");
     const ttt_dirs dd = dirs_of(ctx);
-    hipLaunchKernelGGL(ttt_sample_kernel, dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, ctx->ttt.P, dd.full, B,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, tcount, advance, action);
+    TTT_LAUNCH(ttt_sample_kernel, blocks_for(B, 256), ctx->ttt.P, dd.full, B,
+               (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, tcount, advance, action);
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
@@ -1096,17 +1116,9 @@ int crl_ttt_step_observe(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t 
     CRL_REQUIRE((flags & ~CRL_STEP_AUTO_RESET) == 0, "crl_ttt_step_observe: unknown flags 0x%x", flags);
     CRL_REQUIRE((((uintptr_t)obs_board) & 3) == 0, "crl_ttt_step_observe: obs_board must be 4-byte aligned");
     const ttt_dirs dd = dirs_of(ctx);
-    const uint32_t inv_cells = dd.n_cells == 1 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint64_t)dd.n_cells) + 1u;
-    TTT_DISPATCH_P(ctx->ttt.P, {
-        if (dd.n_dirs <= 4)
-            hipLaunchKernelGGL((ttt_step_observe_kernel<PP, 4>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd,
-                               inv_cells, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, action,
-                               tcount, reward, terminal, winners, obs_board, valid, rel_mod, flags);
-        else
-            hipLaunchKernelGGL((ttt_step_observe_kernel<PP, 13>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd,
-                               inv_cells, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, action,
-                               tcount, reward, terminal, winners, obs_board, valid, rel_mod, flags);
-    });
+    TTT_DISPATCH_ND(ctx, TTT_LAUNCH((ttt_step_observe_kernel<PP, NDD>), blocks_for(B, 256), dd, ttt_inv_cells(dd.n_cells), B,
+                                    (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, action, tcount,
+                                    reward, terminal, winners, obs_board, valid, rel_mod, flags));
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
@@ -1127,22 +1139,11 @@ int crl_ttt_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t f
                 "before the learner's turn)", ctx->ttt.n_cells, ctx->ttt.P);
     CRL_REQUIRE((((uintptr_t)obs_board) & 3) == 0, "crl_ttt_step_single: obs_board must be 4-byte aligned");
     const ttt_dirs dd = dirs_of(ctx);
-    const uint32_t inv_cells = dd.n_cells == 1 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint64_t)dd.n_cells) + 1u;
-    const uint32_t *win_tab = nullptr;                      // the <= 16-cell win table, when it lives on this device
-    if (ctx->ttt_win_dev) {
-        int dev = -1;
-        if (hipGetDevice(&dev) == hipSuccess && dev == ctx->ttt_win_device) win_tab = ctx->ttt_win_dev;
-    }
-#define TTT_SINGLE_LAUNCH(ND_, WT_)                                                                                       \
-    hipLaunchKernelGGL((ttt_step_single_kernel<PP, ND_, WT_>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd, \
-                       inv_cells, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, seat,   \
-                       learner_action, tcount, reward, done, winners, obs_board, valid, rel_mod, win_tab)
-    TTT_DISPATCH_P(ctx->ttt.P, {
-        if (dd.n_dirs <= 4 && dd.n_cells <= 16 && win_tab != nullptr) TTT_SINGLE_LAUNCH(4, true);
-        else if (dd.n_dirs <= 4) TTT_SINGLE_LAUNCH(4, false);
-        else TTT_SINGLE_LAUNCH(13, false);
-    });
-#undef TTT_SINGLE_LAUNCH
+    const uint32_t *win_tab = ttt_win_table_here(ctx);
+    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_step_single_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd,
+                                                ttt_inv_cells(dd.n_cells), B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
+                                                occ, winner, to_move, seat, learner_action, tcount, reward, done, winners,
+                                                obs_board, valid, rel_mod, win_tab));
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
@@ -1162,11 +1163,7 @@ int crl_ttt_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first
     CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "crl_ttt_playout: a board of %d cells for %d players (as crl_ttt_step_single)",
                 ctx->ttt.n_cells, ctx->ttt.P);
     const ttt_dirs dd = dirs_of(ctx);
-    const uint32_t *win_tab = nullptr;                      // the <= 16-cell win table, when it lives on this device
-    if (ctx->ttt_win_dev) {
-        int dev = -1;
-        if (hipGetDevice(&dev) == hipSuccess && dev == ctx->ttt_win_device) win_tab = ctx->ttt_win_dev;
-    }
+    const uint32_t *win_tab = ttt_win_table_here(ctx);
     const uint64_t rows = (uint64_t)B * (uint64_t)A, n_lanes = rows * (uint64_t)R;
     // rows that span waves are summed by atomics: every output starts from zero
     CRL_HIP(hipMemsetAsync(wins, 0, rows * ctx->ttt.P * sizeof(uint32_t), (hipStream_t)stream));
@@ -1174,16 +1171,9 @@ int crl_ttt_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first
     CRL_HIP(hipMemsetAsync(len_sum, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
     const uint64_t want = (n_lanes + 255u) / 256u;          // a grid-stride loop past 2^20 workgroups
     const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));
-#define TTT_PLAYOUT_LAUNCH(ND_, WT_)                                                                                      \
-    hipLaunchKernelGGL((ttt_playout_kernel<PP, ND_, WT_>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, dd, B,        \
-                       (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, tcount, cand, A, R,    \
-                       n_lanes, wins, played, len_sum, win_tab)
-    TTT_DISPATCH_P(ctx->ttt.P, {
-        if (dd.n_dirs <= 4 && dd.n_cells <= 16 && win_tab != nullptr) TTT_PLAYOUT_LAUNCH(4, true);
-        else if (dd.n_dirs <= 4) TTT_PLAYOUT_LAUNCH(4, false);
-        else TTT_PLAYOUT_LAUNCH(13, false);
-    });
-#undef TTT_PLAYOUT_LAUNCH
+    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_playout_kernel<PP, NDD, WTT>), blocks, dd, B, (uint32_t)seed,
+                                                (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, tcount, cand, A, R,
+                                                n_lanes, wins, played, len_sum, win_tab));
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
@@ -1209,14 +1199,8 @@ static int ttt_step_board_launch(const char *fn, const crl_ctx *ctx, int64_t B, 
         }
         vec.winner = winner[0]; vec.to_move = to_move[0]; vec.action = action[0];
     }
-    TTT_DISPATCH_P(ctx->ttt.P, {
-        if (dd.n_dirs <= 4)
-            hipLaunchKernelGGL((ttt_step_board_kernel<PP, 4>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd, B,
-                               board, winner, to_move, action, reward, terminal, winners, valid, obs_board, rm, flags, vec, by_value, flag, seq);
-        else
-            hipLaunchKernelGGL((ttt_step_board_kernel<PP, 13>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd, B,
-                               board, winner, to_move, action, reward, terminal, winners, valid, obs_board, rm, flags, vec, by_value, flag, seq);
-    });
+    TTT_DISPATCH_ND(ctx, TTT_LAUNCH((ttt_step_board_kernel<PP, NDD>), blocks_for(B, 256), dd, B, board, winner, to_move, action,
+                                    reward, terminal, winners, valid, obs_board, rm, flags, vec, by_value, flag, seq));
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
@@ -1247,10 +1231,8 @@ int crl_ttt_observe_board(const crl_ctx *ctx, int64_t B, const int8_t *board, co
     CRL_REQUIRE(board != nullptr, "crl_ttt_observe_board: board is NULL");
     CRL_REQUIRE(obs_board || valid, "crl_ttt_observe_board: nothing to compute (obs_board and valid are NULL)");
     CRL_REQUIRE(player == nullptr || rel_mod >= 1, "crl_ttt_observe_board: rel_mod must be >= 1 when player is given");
-    TTT_DISPATCH_P(ctx->ttt.P, {
-        hipLaunchKernelGGL((ttt_observe_board_kernel<PP>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream,
-                           ctx->ttt.n_cells, ctx->ttt.full, B, board, player, rel_mod < 1 ? 1 : rel_mod, obs_board, valid);
-    });
+    TTT_DISPATCH_P(ctx->ttt.P, TTT_LAUNCH((ttt_observe_board_kernel<PP>), blocks_for(B, 256), ctx->ttt.n_cells, ctx->ttt.full, B,
+                                          board, player, rel_mod < 1 ? 1 : rel_mod, obs_board, valid));
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
@@ -1264,22 +1246,9 @@ int crl_ttt_rollout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first
     CRL_REQUIRE(T >= 0 && T <= (1 << 24), "crl_ttt_rollout: T=%d out of range", T);
     if (T == 0) return CRL_OK;
     const ttt_dirs dd = dirs_of(ctx);
-    const uint32_t *win_tab = nullptr;                      // the <= 16-cell win table, when it lives on this device
-    if (ctx->ttt_win_dev) {
-        int dev = -1;
-        if (hipGetDevice(&dev) == hipSuccess && dev == ctx->ttt_win_device) win_tab = ctx->ttt_win_dev;
-    }
-    TTT_DISPATCH_P(ctx->ttt.P, {
-        if (dd.n_dirs <= 4 && dd.n_cells <= 16 && win_tab != nullptr)
-            hipLaunchKernelGGL((ttt_rollout_kernel<PP, 4, true>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd, B,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, T, occ, winner, to_move, st, win_tab);
-        else if (dd.n_dirs <= 4)
-            hipLaunchKernelGGL((ttt_rollout_kernel<PP, 4>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd, B,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, T, occ, winner, to_move, st, win_tab);
-        else
-            hipLaunchKernelGGL((ttt_rollout_kernel<PP, 13>), dim3(blocks_for(B, 256)), dim3(256), 0, (hipStream_t)stream, dd, B,
-                               (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, T, occ, winner, to_move, st, win_tab);
-    });
+    const uint32_t *win_tab = ttt_win_table_here(ctx);
+    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_rollout_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd, B, (uint32_t)seed,
+                                                (uint32_t)(seed >> 32), first_env_id, T, occ, winner, to_move, st, win_tab));
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }

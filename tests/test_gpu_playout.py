@@ -135,6 +135,35 @@ def test_blokus_against_restatement():
         assert torch.equal(a, b)
 
 
+def test_blokus_candidate_filter_is_is_valid():
+    """The playout plays a candidate exactly where crl_blokus_is_valid accepts it for the player to move (one membership
+    test, blk_move_legal, behind both): 64 candidates per position -- legal ids, uniform ids, the edges of the dense range."""
+    st = _blokus_positions()
+    rng = np.random.default_rng(21)
+    A, ids = 64, 336000
+    cand = np.full((3, A), -1, np.int64)
+    n_legal = []
+    for b in range(3):
+        legal = R.blokus_legal(R._blk_copy(st, b))
+        n_legal.append(len(legal))
+        k = min(24, len(legal))
+        cand[b, :k] = rng.choice(legal, size=k, replace=False)
+        cand[b, 24:60] = rng.integers(0, ids, size=36)
+        cand[b, 60:] = (-1, 0, ids - 1, ids)
+    assert n_legal[0] > 0 and n_legal[1] > 0 and n_legal[2] == 0       # (game 2 is the finished position)
+    tcount = np.zeros(3, np.uint32)
+    bb = _blokus_batch(st, 5, tcount)
+    cand_t = torch.from_numpy(cand.astype(np.int32)).to(DEV)
+    played = _u32(bb.playout(1, cand_t, 11)["played"])
+    ok = np.stack([_np(bb.is_valid(cand_t[:, a].contiguous())) for a in range(A)], axis=1)
+    torch.cuda.synchronize()
+    assert np.array_equal(played, ok.astype(np.uint32))
+    for b in range(2):
+        assert played[b].any() and not played[b].all()
+    assert not played[2].any()                                          # nothing is legal in a finished position
+    assert np.array_equal(R.blokus_playout(st, 11, 1, cand=cand, A=A, first_env_id=5, tcount=tcount)[1], played)
+
+
 def test_blokus_flat_mc_action_picks_a_candidate():
     st = _blokus_positions()
     bb = _blokus_batch(st, 0, np.zeros(3, np.uint32))

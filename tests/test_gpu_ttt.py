@@ -262,6 +262,50 @@ def test_step_observe_fused_matches_separate_calls(dims, K, P, B, rel_mod):
     assert int(b.terminal.sum()) >= 0
 
 
+@pytest.mark.parametrize("dims,K,P,no_table", [((3, 3), 3, 2, False), ((5, 5), 4, 2, False), ((3, 3, 3), 3, 3, False),
+                                               ((3, 3), 3, 2, True)],
+                         ids=["3x3_table", "5x5_nd4", "3x3x3_nd13", "3x3_no_table"])
+def test_instance_rule_step_observe_and_step_single_agree(dims, K, P, no_table, monkeypatch):
+    """The launchers pick a kernel's instance by one rule: <P, ND> for crl_ttt_step_observe, <P, ND, WT> for
+    crl_ttt_step_single (ND = 4 with the win table, ND = 4 without -- 25 cells, or a small board under CRL_TTT_NO_WIN_TABLE
+    -- and ND = 13).  Per context both families play the same game: 12 plies of step_observe with the built-in agent,
+    and step_single from the same start and seed with a learner that plays the agent's own draw, leave the same occ /
+    winner / to_move at the same step counter.  B = 257: one full workgroup plus one lane."""
+    import torch
+    from colosseumrl_amd.batched import TTTBatch
+    if no_table:
+        monkeypatch.setenv("CRL_TTT_NO_WIN_TABLE", "1")
+    B, seed, plies = 257, 77 + P, 12
+    a, b = TTTBatch(dims, K, P, B), TTTBatch(dims, K, P, B)
+    a.reset()
+    b.reset()
+    keys = ("occ", "winner", "to_move")
+    snaps = {k: [getattr(a, k).clone()] for k in keys}           # [k][t]: the state at step counter t
+    for t in range(plies):
+        a.step_observe(None, seed=seed, auto_reset=True)
+        for k in keys:
+            snaps[k].append(getattr(a, k).clone())
+    assert int(a.tcount.min()) == plies and int(a.tcount.max()) == plies
+    snaps = {k: torch.stack(v) for k, v in snaps.items()}         # occ: [13, P, B]; winner, to_move: [13, B]
+    seat = torch.from_numpy((np.arange(B) % P).astype(np.int8)).cuda()
+    games = torch.arange(B, device=seat.device)
+    compared = torch.zeros(B, dtype=torch.bool, device=seat.device)
+    counters = set()
+    b.step_single(seat, None, seed)                                # up to the learner's first turn
+    for call in range(plies + 1):
+        tc = b.tcount.to(torch.int64)
+        live = tc <= plies
+        if not bool(live.any()):
+            break
+        g, t = games[live], tc[live]
+        assert torch.equal(b.occ[:, g], snaps["occ"][t, :, g].T), call
+        assert torch.equal(b.winner[g], snaps["winner"][t, g]) and torch.equal(b.to_move[g], snaps["to_move"][t, g]), call
+        compared |= live
+        counters.update(int(x) for x in t.unique().cpu())
+        b.step_single(seat, b.sample(seed, advance=False).to(torch.int64), seed)
+    assert bool(compared.all()) and len(counters) >= plies // 2   # every game, at many different counters
+
+
 @pytest.mark.parametrize("dims,K,P,rel_mod", [((3, 3), 3, 2, 2), ((3, 5), 3, 3, 3), ((3, 3, 3), 3, 4, 4), ((5, 5), 4, 3, 3), ((4, 8), 4, 8, 8),
                                               ((2, 3), 2, 1, 1), ((5, 5), 5, 5, 5), ((6, 5), 6, 6, 6), ((2, 2, 4), 2, 7, 7)])
 def test_single_state_one_call_form_matches_the_two_call_form(dims, K, P, rel_mod):

@@ -89,6 +89,12 @@ def _unit(name: str, v) -> float:
     return float(v)
 
 
+def _one_of(name: str, v, choices):
+    if v not in choices:
+        raise ValueError("%s must be %s, got %r" % (name, " or ".join(repr(c) for c in choices), v))
+    return v
+
+
 def _candidates(cand: Optional[torch.Tensor], B: int, device, max_a: int) -> int:
     """A of a playout / territory call, checked as the C entries check it (A in [1, max_a]: 65535 for crl_*_playout, 16 for
     crl_tron_territory); candidates int32 [B, A] or None (A = 1)."""
@@ -665,6 +671,34 @@ class TTTBatch(_RolloutStepper):
         self._call("crl_ttt_sample", _seed(seed), self.first_env_id, _ptr(self.occ), _ptr(self.tcount), int(advance), _ptr(act))
         return act
 
+    # -- the tactical (win-or-block) agent; the contract is with crl_ttt_sample_tactical in include/colosseum_hip.h
+    AGENTS = ("random", "tactical")
+
+    def winning_cells(self):
+        """int32 [P, B]: per player the mask of empty cells that complete a K-line for it (``crl_ttt_winning_cells``) -- an
+        observation feature / action prior, and the set the tactical agent plays from."""
+        out = torch.empty((self.P, self.B), dtype=torch.int32, device=self.device)
+        self._call("crl_ttt_winning_cells", _ptr(self.occ), _ptr(out))
+        return out
+
+    def sample_tactical(self, seed: int = 0, noise: float = 0.1, advance: bool = True):
+        """The tactical agent for one step: int8 [B] flat cell at each game's step counter -- with probability ``noise`` a
+        uniform empty cell, else a winning cell of the mover if it has one, else a cell that blocks the earliest upcoming
+        player who has one, else a uniform empty cell; -1 on a full board.
+        ``step(sample_tactical(seed, noise), auto_reset=True)`` T times == ``rollout_tactical(T, seed, noise)``."""
+        noise = _unit("noise", noise)
+        act = torch.empty((self.B,), dtype=torch.int8, device=self.device)
+        self._call("crl_ttt_sample_tactical", _seed(seed), self.first_env_id, _ptr(self.occ), _ptr(self.to_move),
+                   _ptr(self.tcount), int(advance), noise, _ptr(act))
+        return act
+
+    def rollout_tactical(self, steps: int, seed: int = 0, noise: float = 0.1):
+        """``rollout`` with every seat on the tactical agent (``crl_ttt_rollout_tactical``): the same statistics tensors,
+        ``results()`` rows and step counter."""
+        noise = _unit("noise", noise)
+        self._call("crl_ttt_rollout_tactical", _seed(seed), self.first_env_id, int(steps), noise, _ptr(self.occ),
+                   _ptr(self.winner), _ptr(self.to_move), self._stats())
+
     def board(self, player: Optional[torch.Tensor] = None, rel_mod: Optional[int] = None):
         out = torch.empty((self.B, self.n_cells), dtype=torch.int8, device=self.device)
         if player is not None:
@@ -697,39 +731,48 @@ class TTTBatch(_RolloutStepper):
         return out
 
     def step_single(self, seat: torch.Tensor, learner_action: Optional[torch.Tensor] = None, seed: int = 0,
-                    rel_mod: Optional[int] = None, out: Optional[dict] = None):
+                    rel_mod: Optional[int] = None, out: Optional[dict] = None, opponent: str = "random", noise: float = 0.1):
         """One step of "learner at seat[b] against the random agent" in every game, ONE launch (``crl_ttt_step_single``):
         the learner plays ``learner_action`` (int64 [B]: a cell in [-1, cells), anything else passes) when it is its turn,
         the random agent plays every other seat until it is the learner's turn again, finished games restart on the way.
         ``learner_action=None`` only advances to the learner's turn.  seat int8 [B].  Returns
         {'board' int8 [B, cells] relative to the learner, 'valid' int32 [B] empties mask, 'reward' int8 [B] (+1 the learner
         won, -1 another player, 0 draw or not over), 'done' uint8 [B], 'winners' int8 [B]}; every ply, the learner's
-        included, advances ``tcount`` (the draws are ``sample``'s)."""
+        included, advances ``tcount`` (the draws are ``sample``'s).  ``opponent="tactical"``: every other seat plays the
+        tactical agent with ``noise`` instead (``crl_ttt_step_single_tactical``; the draws are ``sample_tactical``'s)."""
         _want(seat, torch.int8, (self.B,), self.device, "seat")
         if learner_action is not None:
             _want(learner_action, torch.int64, (self.B,), self.device, "learner_action")
+        tactical = _one_of("opponent", opponent, self.AGENTS) == "tactical"
+        noise = _unit("noise", noise)
         out = out or _alloc(dict(self._obs_spec(), done=(torch.uint8, (self.B,))), self.device)
-        self._call("crl_ttt_step_single", _seed(seed), self.first_env_id, _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move),
-                   _ptr(seat), _ptr(learner_action), _ptr(self.tcount), _ptr(self.reward), _ptr(out["done"]), _ptr(self.winners),
-                   _ptr(out["board"]), _ptr(out["valid"]), int(rel_mod if rel_mod else self.P), 0)
+        self._call("crl_ttt_step_single_tactical" if tactical else "crl_ttt_step_single", _seed(seed), self.first_env_id,
+                   _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move), _ptr(seat), _ptr(learner_action), _ptr(self.tcount),
+                   _ptr(self.reward), _ptr(out["done"]), _ptr(self.winners), _ptr(out["board"]), _ptr(out["valid"]),
+                   int(rel_mod if rel_mod else self.P), *((noise, 0) if tactical else (0,)))
         out["reward"], out["winners"] = self.reward, self.winners
         return out
 
-    def playout(self, playouts: int, candidates: Optional[torch.Tensor] = None, seed: int = 0, out: Optional[dict] = None):
+    def playout(self, playouts: int, candidates: Optional[torch.Tensor] = None, seed: int = 0, out: Optional[dict] = None,
+                agent: str = "random", noise: float = 0.1):
         """Random playouts from every game's position, ONE launch (``crl_ttt_playout``): row (b, a) plays candidate cell
         ``candidates[b, a]`` (int32 [B, A]; an occupied cell, -1 or a value outside [0, cells) skips the row) for the
         player to move and then ``playouts`` random games to their end, on private copies; ``candidates=None`` evaluates
         the position as it stands (A = 1).  Finished positions skip every row.  The draws are keyed by ``seed``, the game
         ids and ``tcount`` as the counter base (which the call neither advances nor writes; the state is only read).
         Returns {'wins' int32 [B, A, P], 'draws', 'played', 'len_sum' int32 [B, A]} (skipped rows are zeros); ``out``
-        reuses such a dict.  No host synchronisation; capturable into a graph."""
+        reuses such a dict.  ``agent="tactical"``: every ply after the candidate is the tactical agent's with ``noise``
+        (``crl_ttt_playout_tactical``, draws under a tag of their own).  No host synchronisation; capturable into a graph."""
         R = _int_in("playouts", playouts, 1, 65535)
         A = _candidates(candidates, self.B, self.device, 65535)
+        tactical = _one_of("agent", agent, self.AGENTS) == "tactical"
+        noise = _unit("noise", noise)
         i32, BA = torch.int32, (self.B, A)
         out = _out_dict(out, {"wins": (i32, BA + (self.P,)), "draws": (i32, BA), "played": (i32, BA), "len_sum": (i32, BA)},
                         self.device)
-        self._call("crl_ttt_playout", _seed(seed), self.first_env_id, _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move),
-                   _ptr(self.tcount), _ptr(candidates), A, R, _ptr(out["wins"]), _ptr(out["played"]), _ptr(out["len_sum"]), 0)
+        self._call("crl_ttt_playout_tactical" if tactical else "crl_ttt_playout", _seed(seed), self.first_env_id, _ptr(self.occ),
+                   _ptr(self.winner), _ptr(self.to_move), _ptr(self.tcount), _ptr(candidates), A, R, _ptr(out["wins"]),
+                   _ptr(out["played"]), _ptr(out["len_sum"]), *((noise, 0) if tactical else (0,)))
         torch.sub(out["played"], out["wins"].sum(dim=2, dtype=torch.int32), out=out["draws"])
         return out
 
@@ -738,12 +781,14 @@ class TTTBatch(_RolloutStepper):
         """int32 [B, cells]: every cell of every game, `flat_mc_action`'s candidates (made at the first use)"""
         return torch.arange(self.n_cells, dtype=torch.int32, device=self.device).expand(self.B, self.n_cells).contiguous()
 
-    def flat_mc_action(self, playouts: int, seed: int = 0, out: Optional[dict] = None) -> torch.Tensor:
+    def flat_mc_action(self, playouts: int, seed: int = 0, out: Optional[dict] = None, agent: str = "random",
+                       noise: float = 0.1) -> torch.Tensor:
         """Flat Monte Carlo for the player to move in every game: ``playout`` on every cell, value 2 * wins + draws of
         the mover, the best cell (ties: the lowest) as an int64 [B] action for ``step_single``; -1 where no cell could be
-        played (the game is over).  ``out``: the playout dict to reuse.  No host synchronisation; capturable."""
+        played (the game is over).  ``out``: the playout dict to reuse; ``agent`` / ``noise``: the playout policy, as
+        ``playout``.  No host synchronisation; capturable."""
         cells = self._all_cells
-        o = self.playout(playouts, cells, seed, out)
+        o = self.playout(playouts, cells, seed, out, agent, noise)
         mover = self.to_move.to(torch.int64).clamp(0, self.P - 1)       # (other values: the position skips every row)
         mine = torch.gather(o["wins"], 2, mover.view(-1, 1, 1).expand(self.B, self.n_cells, 1)).squeeze(2)
         return _flat_mc_pick(2 * mine + o["draws"], o["played"], cells)

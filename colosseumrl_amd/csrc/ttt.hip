@@ -194,6 +194,113 @@ __device__ __forceinline__ void ttt_stage_win_table(uint32_t *win_bits, const ui
     dst[threadIdx.x + 256] = src[threadIdx.x + 256];
 }
 
+// ---- the tactical (win-or-block) agent's two helpers; the contract is in include/colosseum_hip.h.  Used by the
+// ttt_*_tactical kernels and ttt_winning_cells_kernel only.
+//
+// The empty cells e of E with "m | 1 << e holds a K-line" for a player's marks m (m and E are disjoint).  Per direction and
+// window offset j the windows whose OTHER K - 1 cells are all in m are start & AND_{i != j} (m >> i s); their completing
+// cell is offset j, so the mask goes back up by j s.  K = 3, 4, 5 (K is wave-uniform: one scalar branch) share the partial
+// ANDs between the offsets.  Any other K counts instead: a window that lies in m | E and holds exactly one cell of E
+// (`one` = some cell, `two` = two or more) is completed by that cell -- two passes of K shift-ANDs, no per-offset array.
+// (Boards of at most 16 cells could look each empty cell up in the win-mask table instead: measured, that is slower --
+// DESIGN.md 4.5b.)  A used direction has (K - 1) s <= 31 (its windows stay on the board); an unused slot (ND above
+// n_dirs) has stride 0 and start 0, so no shift count ever reaches 32.  A player who HOLDS a line already (`hit`; no
+// state of a game that records its winner, but a hand-made one) wins with whatever it adds: every empty cell.
+template <int ND>
+__device__ __forceinline__ uint32_t ttt_winning_cells(const ttt_dirs &dd, const uint32_t m, const uint32_t E)
+{
+    uint32_t cells = 0, hit = 0;
+    const int K = dd.K;
+    if (K == 3) {
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            const int s = dd.stride[d];
+            const uint32_t st = dd.start[d], a1 = m >> s, a2 = m >> (2 * s), lo = st & m & a1;
+            cells |= (st & a1 & a2) | ((st & m & a2) << s) | (lo << (2 * s));
+            hit |= lo & a2;
+        }
+    } else if (K == 4) {
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            const int s = dd.stride[d];
+            const uint32_t st = dd.start[d], a1 = m >> s, a2 = m >> (2 * s), a3 = m >> (3 * s);
+            const uint32_t lo = st & m & a1, hi = st & a2 & a3;
+            cells |= (a1 & hi) | ((m & hi) << s) | ((lo & a3) << (2 * s)) | ((lo & a2) << (3 * s));
+            hit |= lo & hi;
+        }
+    } else if (K == 5) {
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            const int s = dd.stride[d];
+            const uint32_t st = dd.start[d], a1 = m >> s, a2 = m >> (2 * s), a3 = m >> (3 * s), a4 = m >> (4 * s);
+            const uint32_t lo = st & m & a1, hi = a3 & a4, lo3 = lo & a2, hi3 = st & a2 & hi;
+            cells |= (a1 & hi3) | ((m & hi3) << s) | ((lo & hi) << (2 * s)) | ((lo3 & a4) << (3 * s)) | ((lo3 & a3) << (4 * s));
+            hit |= lo3 & hi;
+        }
+    } else {
+        const uint32_t me = m | E;
+        uint32_t in[ND], one[ND], two[ND];
+#pragma unroll
+        for (int d = 0; d < ND; ++d) { in[d] = me; one[d] = E; two[d] = 0u; }
+        for (int i = 1; i < K; ++i) {
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                const int sh = i * dd.stride[d];
+                const uint32_t e = E >> sh;
+                in[d] &= me >> sh;
+                two[d] |= one[d] & e;
+                one[d] |= e;
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            in[d] &= dd.start[d];
+            hit |= in[d] & ~one[d];                                                // a window without a cell of E: a line
+            in[d] &= one[d] & ~two[d];                                             // the windows one cell short of a line
+        }
+        for (int i = 0; i < K; ++i) {
+#pragma unroll
+            for (int d = 0; d < ND; ++d) cells |= in[d] << (i * dd.stride[d]);     // (every cell of them; & E keeps the empty one)
+        }
+    }
+    return hit ? E : cells & E;
+}
+
+// the tactical agent's Philox block for step counter c of game g: one block serves the two plies 2 (c >> 1) and 2 (c >> 1) + 1
+// (c2 = 0 and CRL_TAG_TTT_TACTICAL, or (a << 16) | r and CRL_TAG_TTT_TACTICAL_PLAYOUT in a playout)
+__device__ __forceinline__ philox_out ttt_tactical_block(const uint32_t g, const uint32_t c, const uint32_t c2, const uint32_t tag,
+                                                         const uint32_t seed_lo, const uint32_t seed_hi)
+{
+    return philox4x32_10<true>(g, c >> 1, c2, tag, seed_lo, seed_hi);
+}
+
+// the tactical agent's move for the mover tm at step counter c, `rnd` the block of c: -1 (pass) without a mover or an empty
+// cell; else word 2 (c & 1) decides "noisy" (below thr) and the next word picks a cell of S -- all empty cells on a noisy
+// ply, else the first non-empty set of winning cells of the players tm, tm + 1, ... in turn order (its own win, then the
+// earliest threat), all empty cells when nobody has one.  The cascade stops at the first non-empty set (per lane).
+template <int P, int ND>
+__device__ __forceinline__ int ttt_tactical_move(const ttt_dirs &dd, const uint32_t (&o)[P], const int tm, const philox_out &rnd,
+                                                 const uint32_t c, const uint64_t thr)
+{
+    const uint32_t E = dd.full & ~ttt_union<P>(o);
+    if ((unsigned)tm >= (unsigned)P || E == 0u) return -1;
+    const uint32_t u = (c & 1u) ? rnd.w[2] : rnd.w[0], v = (c & 1u) ? rnd.w[3] : rnd.w[1];
+    uint32_t S = E;
+    if ((uint64_t)u >= thr) {
+        int q = tm;
+#pragma unroll 1
+        for (int i = 0; i < P; ++i) {
+            uint32_t m = 0;
+#pragma unroll
+            for (int p = 0; p < P; ++p) m = (p == q) ? o[p] : m;
+            const uint32_t W = ttt_winning_cells<ND>(dd, m, E);
+            if (W) { S = W; break; }
+            q = (q + 1 == P) ? 0 : q + 1;
+        }
+    }
+    return nth_set_bit(S, (int)__umulhi(v, (uint32_t)__popc(S)));
+}
+
 template <int P, int ND>
 __global__ void __launch_bounds__(256)
 ttt_step_kernel(const ttt_dirs dd, const int64_t B, uint32_t *__restrict__ occ, int8_t *__restrict__ winner,
@@ -759,6 +866,279 @@ ttt_sample_kernel(const int P, const uint32_t full, const int64_t B, const uint3
     if (advance) tcount[b] = c + 1u;
 }
 
+// ---- the tactical agent's kernels (crl_ttt_winning_cells, crl_ttt_*_tactical): one lane per game (the playout: per
+// playout).  The winning-cell sets are computed in every instance; the kernels that play plies test a ply's win out of the
+// win-mask table of a board of at most 16 cells as their random siblings do (WT).
+template <int P, int ND>
+__global__ void __launch_bounds__(256)
+ttt_winning_cells_kernel(const ttt_dirs dd, const int64_t B, const uint32_t *__restrict__ occ, uint32_t *__restrict__ cells)
+{
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    uint32_t o[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) o[p] = occ[p * B + b];
+    const uint32_t E = dd.full & ~ttt_union<P>(o);
+#pragma unroll
+    for (int p = 0; p < P; ++p) cells[p * B + b] = ttt_winning_cells<ND>(dd, o[p], E);
+}
+
+template <int P, int ND>
+__global__ void __launch_bounds__(256)
+ttt_sample_tactical_kernel(const ttt_dirs dd, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
+                           const uint64_t first_env_id, const uint64_t thr, const uint32_t *__restrict__ occ,
+                           const int8_t *__restrict__ to_move, uint32_t *__restrict__ tcount, const int advance,
+                           int8_t *__restrict__ action)
+{
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    uint32_t o[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) o[p] = occ[p * B + b];
+    const uint32_t c = tcount[b];
+    const philox_out rnd = ttt_tactical_block((uint32_t)(first_env_id + (uint64_t)b), c, 0u, CRL_TAG_TTT_TACTICAL, seed_lo, seed_hi);
+    action[b] = (int8_t)ttt_tactical_move<P, ND>(dd, o, to_move[b], rnd, c, thr);
+    if (advance) tcount[b] = c + 1u;
+}
+
+// T plies with every seat on the tactical agent: crl_ttt_rollout's general ply (ttt_step_core, the restart and the
+// statistics of its `ply`) with the tactical move; the Philox block stays in registers for its two plies
+template <int P, int ND, bool WT>
+__global__ void __launch_bounds__(256)
+ttt_rollout_tactical_kernel(const ttt_dirs dd, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
+                            const uint64_t first_env_id, const uint64_t thr, const int T, uint32_t *__restrict__ occ,
+                            int8_t *__restrict__ winner, int8_t *__restrict__ to_move, const crl_ttt_stats st,
+                            const uint32_t *__restrict__ win_tab)
+{
+    __shared__ uint32_t win_bits[WT ? 2048 : 1];
+    if (WT) {
+        ttt_stage_win_table(win_bits, win_tab);
+        __syncthreads();
+    }
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    uint32_t o[P], wins[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) { o[p] = occ[p * B + b]; wins[p] = 0; }
+    int w = winner[b], tm = to_move[b];
+    uint32_t tc = st.tcount[b], ts = st.tstep[b], n_ep = 0, draws = 0, len_sum = 0;
+    const uint32_t g = (uint32_t)(first_env_id + (uint64_t)b);
+    philox_out rnd = ttt_tactical_block(g, tc, 0u, CRL_TAG_TTT_TACTICAL, seed_lo, seed_hi);
+    for (int t = 0; t < T; ++t) {
+        const int action = ttt_tactical_move<P, ND>(dd, o, tm, rnd, tc, thr);
+        int r, term, ws;
+        ttt_step_core<P, ND, WT>(dd, o, w, tm, action, r, term, ws, win_bits);
+        ts += 1;
+        tc += 1;
+        if ((tc & 1u) == 0u) rnd = ttt_tactical_block(g, tc, 0u, CRL_TAG_TTT_TACTICAL, seed_lo, seed_hi);
+        if (term) {
+            n_ep += 1;
+            len_sum += ts;
+            draws += (ws < 0);
+#pragma unroll
+            for (int p = 0; p < P; ++p) { wins[p] += (ws == p); o[p] = 0; }
+            w = -1; tm = 0; ts = 0;
+        }
+    }
+    int32_t *row = st.results ? st.results + b * (3 + P) : nullptr;    // packed result row, as crl_ttt_rollout writes it
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        occ[p * B + b] = o[p];
+        const uint32_t wc = st.win_count[p * B + b] + wins[p];
+        st.win_count[p * B + b] = wc;
+        if (row) row[3 + p] = (int32_t)wc;
+    }
+    winner[b] = (int8_t)w;
+    to_move[b] = (int8_t)tm;
+    st.tcount[b] = tc;
+    st.tstep[b] = ts;
+    const uint32_t ne = st.n_episodes[b] + n_ep, dr = st.draw_count[b] + draws, ls = st.len_sum[b] + len_sum;
+    st.n_episodes[b] = ne;
+    st.draw_count[b] = dr;
+    st.len_sum[b] = ls;
+    if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = (int32_t)dr; }
+}
+
+// one learner against the tactical agent: ttt_step_single_kernel with the opponents' plies from ttt_tactical_move
+template <int P, int ND, bool WT>
+__global__ void __launch_bounds__(256)
+ttt_step_single_tactical_kernel(const ttt_dirs dd, const uint32_t inv_cells, const int64_t B, const uint32_t seed_lo,
+                                const uint32_t seed_hi, const uint64_t first_env_id, const uint64_t thr,
+                                uint32_t *__restrict__ occ, int8_t *__restrict__ winner, int8_t *__restrict__ to_move,
+                                const int8_t *__restrict__ seat, const int64_t *__restrict__ learner_action,
+                                uint32_t *__restrict__ tcount, int8_t *__restrict__ reward, uint8_t *__restrict__ done,
+                                int8_t *__restrict__ winners, int8_t *__restrict__ obs, uint32_t *__restrict__ valid,
+                                const int rel_mod, const uint32_t *__restrict__ win_tab)
+{
+    __shared__ uint32_t s_occ[P][256];
+    __shared__ int s_seat[256];
+    __shared__ uint32_t win_bits[WT ? 2048 : 1];
+    if (WT) {
+        ttt_stage_win_table(win_bits, win_tab);
+        __syncthreads();
+    }
+    const int64_t g0 = (int64_t)blockIdx.x * 256;
+    const int64_t b = g0 + threadIdx.x;
+    uint32_t o[P];
+    int s = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) o[p] = 0u;
+    if (b < B) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) o[p] = occ[p * B + b];
+        int w = winner[b], tm = to_move[b];
+        s = (int)seat[b] % P;
+        s += s < 0 ? P : 0;
+        uint32_t c = tcount[b];
+        const uint32_t g = (uint32_t)(first_env_id + (uint64_t)b);
+        int rew = 0, dn = 0, wout = -1;
+        bool learner = learner_action != nullptr && tm == s, have = false;
+        philox_out rnd = {};
+        for (int opp = 0; learner || (tm != s && opp < 2 * (P - 1)); ) {
+            int act;
+            if (learner) {                          // crl_ttt_step's int8 action for v in [-1, cells), else the pass
+                const int64_t v = learner_action[b];
+                act = (v >= -1 && v < dd.n_cells) ? (int)v : -1;
+            } else {                                // crl_ttt_sample_tactical at this game's step counter
+                if (!have || (c & 1u) == 0u) rnd = ttt_tactical_block(g, c, 0u, CRL_TAG_TTT_TACTICAL, seed_lo, seed_hi);
+                have = true;
+                act = ttt_tactical_move<P, ND>(dd, o, tm, rnd, c, thr);
+                ++opp;
+            }
+            c += 1u;
+            learner = false;
+            int r, t, ws;
+            ttt_step_core<P, ND, WT>(dd, o, w, tm, act, r, t, ws, win_bits);
+            if (t) {                                // the learner's outcome, restart (as ttt_step_single_kernel)
+                dn = 1;
+                wout = ws;
+                rew = ws < 0 ? 0 : (ws == s ? 1 : -1);
+#pragma unroll
+                for (int p = 0; p < P; ++p) o[p] = 0;
+                w = -1; tm = 0;
+            }
+        }
+        uint32_t all = 0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) { occ[p * B + b] = o[p]; all |= o[p]; }
+        winner[b] = (int8_t)w;
+        to_move[b] = (int8_t)tm;
+        tcount[b] = c;
+        reward[b] = (int8_t)rew;
+        done[b] = (uint8_t)dn;
+        winners[b] = (int8_t)wout;
+        valid[b] = dd.full & ~all;
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) s_occ[p][threadIdx.x] = o[p];
+    s_seat[threadIdx.x] = s;
+    __syncthreads();
+    ttt_write_boards<P>(s_occ, s_seat, dd.n_cells, inv_cells, rel_mod, g0, B, obs);
+}
+
+// the outcomes of one wave of playouts into their rows, ttt_playout_kernel's last paragraph word for word (as a function
+// of its own: called from there it cost the <8, 4, table> instance a register): lane `lane` played (play) playout r of
+// `row`, won by wn (-1: nobody) in len plies
+template <int P>
+__device__ __forceinline__ void ttt_playout_reduce(const bool live, const uint32_t lane, const uint32_t r, const int R, const uint64_t row,
+                                                   const bool play, const int wn, const int len, uint32_t *__restrict__ wins,
+                                                   uint32_t *__restrict__ played, uint32_t *__restrict__ len_sum)
+{
+    // ---- per row segment of this wave: the lanes from a head (r == 0, or lane 0) to the next head
+    const unsigned long long heads = __ballot(live && (lane == 0u || r == 0u));
+    const unsigned long long above = lane == 63u ? 0ull : heads & (~0ull << (lane + 1u));
+    const uint32_t end = above ? (uint32_t)__builtin_ctzll(above) : 64u;
+    const unsigned long long seg = (end == 64u ? ~0ull : ((1ull << end) - 1ull)) & (~0ull << lane);
+    const bool head = (heads >> lane) & 1ull;
+    const bool whole = r == 0u && end - lane == (uint32_t)R;           // the row has no lane in another wave
+    uint32_t cnt[P], n_played, plies = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) cnt[p] = (uint32_t)__builtin_popcountll(__ballot(play && wn == p) & seg);
+    n_played = (uint32_t)__builtin_popcountll(__ballot(play) & seg);
+#pragma unroll
+    for (int k = 0; k < 6; ++k)                              // len <= cells + 1 <= 33 < 2^6
+        plies += (uint32_t)__builtin_popcountll(__ballot(play && ((len >> k) & 1)) & seg) << k;
+    if (head) {
+        if (whole) {
+#pragma unroll
+            for (int p = 0; p < P; ++p) wins[row * P + p] = cnt[p];
+            played[row] = n_played;
+            len_sum[row] = plies;
+        } else if (n_played) {
+#pragma unroll
+            for (int p = 0; p < P; ++p)
+                if (cnt[p]) atomicAdd(&wins[row * P + p], cnt[p]);
+            atomicAdd(&played[row], n_played);
+            atomicAdd(&len_sum[row], plies);
+        }
+    }
+}
+
+// batched tactical playouts: ttt_playout_kernel's lanes, rows and reduction; every ply behind the candidate is the
+// tactical move under the playout tag, its Philox block kept in registers for the two plies it serves
+template <int P, int ND, bool WT>
+__global__ void __launch_bounds__(256)
+ttt_playout_tactical_kernel(const ttt_dirs dd, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
+                            const uint64_t first_env_id, const uint64_t thr, const uint32_t *__restrict__ occ,
+                            const int8_t *__restrict__ winner, const int8_t *__restrict__ to_move,
+                            const uint32_t *__restrict__ tcount, const int32_t *__restrict__ cand, const int A, const int R,
+                            const uint64_t n_lanes, uint32_t *__restrict__ wins, uint32_t *__restrict__ played,
+                            uint32_t *__restrict__ len_sum, const uint32_t *__restrict__ win_tab)
+{
+    __shared__ uint32_t win_bits[WT ? 2048 : 1];
+    if (WT) {
+        ttt_stage_win_table(win_bits, win_tab);
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t wave0 = (uint64_t)blockIdx.x * 256u + (threadIdx.x & ~63u); wave0 < n_lanes; wave0 += stride) {
+        // (b, a, r) of this lane, as ttt_playout_kernel
+        const uint64_t row0 = wave0 / (uint32_t)R;
+        const uint32_t r0 = (uint32_t)(wave0 - row0 * (uint32_t)R);
+        const uint32_t q = (r0 + lane) / (uint32_t)R;
+        const uint64_t row = row0 + q;
+        const uint32_t r = r0 + lane - q * (uint32_t)R;
+        const bool live = wave0 + lane < n_lanes;
+        const int64_t b = live ? (int64_t)(row / (uint32_t)A) : 0;
+        const uint32_t a = (uint32_t)(row - (uint64_t)b * (uint32_t)A);
+        int wn = -1, len = 0;
+        bool play = false;
+        if (live) {
+            uint32_t o[P];
+#pragma unroll
+            for (int p = 0; p < P; ++p) o[p] = occ[p * B + b];
+            const uint32_t all = ttt_union<P>(o);
+            int w = winner[b], tm = to_move[b];
+            play = w < 0 && all != dd.full && (unsigned)tm < (unsigned)P;   // a position that is over skips every row
+            int first = -1;
+            if (play && cand != nullptr) {                      // the candidate: an empty cell, else the row is skipped
+                first = cand[b * A + a];
+                play = first >= 0 && first < dd.n_cells && !((all >> (first & 31)) & 1u);
+            }
+            if (play) {
+                const uint32_t g = (uint32_t)(first_env_id + (uint64_t)b), c2 = (a << 16) | r;
+                uint32_t c = tcount ? tcount[b] : 0u;
+                philox_out rnd = ttt_tactical_block(g, c, c2, CRL_TAG_TTT_TACTICAL_PLAYOUT, seed_lo, seed_hi);
+                int term = 0, rw, ws = -1;
+                if (first >= 0) {                               // the candidate ply: no draw
+                    ttt_step_core<P, ND, WT>(dd, o, w, tm, first, rw, term, ws, win_bits);
+                    len = 1;
+                }
+                while (!term) {
+                    const int act = ttt_tactical_move<P, ND>(dd, o, tm, rnd, c, thr);
+                    ttt_step_core<P, ND, WT>(dd, o, w, tm, act, rw, term, ws, win_bits);
+                    len += 1;
+                    c += 1u;
+                    if ((c & 1u) == 0u && !term) rnd = ttt_tactical_block(g, c, c2, CRL_TAG_TTT_TACTICAL_PLAYOUT, seed_lo, seed_hi);
+                }
+                wn = ws;
+            }
+        }
+        ttt_playout_reduce<P>(live, lane, r, R, row, play, wn, len, wins, played, len_sum);
+    }
+}
+
 __global__ void __launch_bounds__(256)
 ttt_reset_kernel(const int P, const int64_t B, const uint8_t *__restrict__ mask, uint32_t *__restrict__ occ,
                  int8_t *__restrict__ winner, int8_t *__restrict__ to_move)
@@ -1249,6 +1629,109 @@ int crl_ttt_rollout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first
     const uint32_t *win_tab = ttt_win_table_here(ctx);
     TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_rollout_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd, B, (uint32_t)seed,
                                                 (uint32_t)(seed >> 32), first_env_id, T, occ, winner, to_move, st, win_tab));
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+// ---- the tactical agent's entries (the contract is in include/colosseum_hip.h)
+#define TTT_NOISE_CHECK(fn) CRL_REQUIRE(noise >= 0.0 && noise <= 1.0, fn ": noise=%g outside [0, 1]", noise)   /* (NaN fails too) */
+
+int crl_ttt_winning_cells(const crl_ctx *ctx, int64_t B, const uint32_t *occ, uint32_t *cells, void *stream)
+{
+    TTT_CTX_CHECK("crl_ttt_winning_cells");
+    CRL_REQUIRE(occ && cells, "crl_ttt_winning_cells: NULL pointer");
+    const ttt_dirs dd = dirs_of(ctx);
+    TTT_DISPATCH_ND(ctx, TTT_LAUNCH((ttt_winning_cells_kernel<PP, NDD>), blocks_for(B, 256), dd, B, occ, cells));
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_ttt_sample_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
+                            const int8_t *to_move, uint32_t *tcount, int advance, double noise, int8_t *action, void *stream)
+{
+    TTT_CTX_CHECK("crl_ttt_sample_tactical");
+    CRL_REQUIRE(occ && to_move && tcount && action, "crl_ttt_sample_tactical: NULL pointer");
+    TTT_NOISE_CHECK("crl_ttt_sample_tactical");
+    const ttt_dirs dd = dirs_of(ctx);
+    TTT_DISPATCH_ND(ctx, TTT_LAUNCH((ttt_sample_tactical_kernel<PP, NDD>), blocks_for(B, 256), dd, B, (uint32_t)seed,
+                                    (uint32_t)(seed >> 32), first_env_id, tron_avoid_threshold(noise), occ, to_move, tcount,
+                                    advance, action));
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_ttt_rollout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, double noise,
+                             uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats st, void *stream)
+{
+    TTT_CTX_CHECK("crl_ttt_rollout_tactical");
+    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_rollout_tactical: NULL state pointer");
+    CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.draw_count && st.len_sum,
+                "crl_ttt_rollout_tactical: NULL stats pointer");
+    CRL_REQUIRE(T >= 0 && T <= (1 << 24), "crl_ttt_rollout_tactical: T=%d out of range", T);
+    TTT_NOISE_CHECK("crl_ttt_rollout_tactical");
+    if (T == 0) return CRL_OK;
+    const ttt_dirs dd = dirs_of(ctx);
+    const uint32_t *win_tab = ttt_win_table_here(ctx);
+    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_rollout_tactical_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd, B, (uint32_t)seed,
+                                                (uint32_t)(seed >> 32), first_env_id, tron_avoid_threshold(noise), T, occ, winner,
+                                                to_move, st, win_tab));
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_ttt_step_single_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                                 uint32_t *occ, int8_t *winner, int8_t *to_move, const int8_t *seat,
+                                 const int64_t *learner_action, uint32_t *tcount,
+                                 int8_t *reward, uint8_t *done, int8_t *winners,
+                                 int8_t *obs_board, uint32_t *valid, int rel_mod, double noise, uint32_t flags, void *stream)
+{
+    TTT_CTX_CHECK("crl_ttt_step_single_tactical");
+    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_step_single_tactical: NULL state pointer");
+    CRL_REQUIRE(seat && tcount, "crl_ttt_step_single_tactical: NULL seat / tcount pointer");
+    CRL_REQUIRE(reward && done && winners && obs_board && valid, "crl_ttt_step_single_tactical: NULL output pointer");
+    CRL_REQUIRE(rel_mod >= 1, "crl_ttt_step_single_tactical: rel_mod must be >= 1");
+    TTT_NOISE_CHECK("crl_ttt_step_single_tactical");
+    CRL_REQUIRE(flags == 0, "crl_ttt_step_single_tactical: unknown flags 0x%x", flags);
+    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "crl_ttt_step_single_tactical: a board of %d cells for %d players (as "
+                "crl_ttt_step_single)", ctx->ttt.n_cells, ctx->ttt.P);
+    CRL_REQUIRE((((uintptr_t)obs_board) & 3) == 0, "crl_ttt_step_single_tactical: obs_board must be 4-byte aligned");
+    const ttt_dirs dd = dirs_of(ctx);
+    const uint32_t *win_tab = ttt_win_table_here(ctx);
+    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_step_single_tactical_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd,
+                                                ttt_inv_cells(dd.n_cells), B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
+                                                tron_avoid_threshold(noise), occ, winner, to_move, seat, learner_action, tcount,
+                                                reward, done, winners, obs_board, valid, rel_mod, win_tab));
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_ttt_playout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                             const uint32_t *occ, const int8_t *winner, const int8_t *to_move, const uint32_t *tcount,
+                             const int32_t *cand, int A, int R,
+                             uint32_t *wins, uint32_t *played, uint32_t *len_sum, double noise, uint32_t flags, void *stream)
+{
+    TTT_CTX_CHECK("crl_ttt_playout_tactical");
+    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_playout_tactical: NULL state pointer");
+    CRL_REQUIRE(wins && played && len_sum, "crl_ttt_playout_tactical: NULL output pointer");
+    CRL_REQUIRE(R >= 1 && R <= 65535, "crl_ttt_playout_tactical: R=%d out of range 1..65535", R);
+    CRL_REQUIRE(A >= 1 && A <= 65535, "crl_ttt_playout_tactical: A=%d out of range 1..65535", A);
+    CRL_REQUIRE(cand != nullptr || A == 1, "crl_ttt_playout_tactical: A=%d with cand == NULL (must be 1)", A);
+    TTT_NOISE_CHECK("crl_ttt_playout_tactical");
+    CRL_REQUIRE(flags == 0, "crl_ttt_playout_tactical: unknown flags 0x%x", flags);
+    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "crl_ttt_playout_tactical: a board of %d cells for %d players (as "
+                "crl_ttt_step_single)", ctx->ttt.n_cells, ctx->ttt.P);
+    const ttt_dirs dd = dirs_of(ctx);
+    const uint32_t *win_tab = ttt_win_table_here(ctx);
+    const uint64_t rows = (uint64_t)B * (uint64_t)A, n_lanes = rows * (uint64_t)R;
+    // rows that span waves are summed by atomics: every output starts from zero (as crl_ttt_playout)
+    CRL_HIP(hipMemsetAsync(wins, 0, rows * ctx->ttt.P * sizeof(uint32_t), (hipStream_t)stream));
+    CRL_HIP(hipMemsetAsync(played, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
+    CRL_HIP(hipMemsetAsync(len_sum, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
+    const uint64_t want = (n_lanes + 255u) / 256u;
+    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));
+    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_playout_tactical_kernel<PP, NDD, WTT>), blocks, dd, B, (uint32_t)seed,
+                                                (uint32_t)(seed >> 32), first_env_id, tron_avoid_threshold(noise), occ, winner,
+                                                to_move, tcount, cand, A, R, n_lanes, wins, played, len_sum, win_tab));
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }

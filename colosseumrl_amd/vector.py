@@ -10,7 +10,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .batched import BlokusBatch, TronBatch, TTTBatch, _want
+from .batched import BlokusBatch, TronBatch, TTTBatch, _unit, _want
 
 
 class TronVectorEnv:
@@ -208,17 +208,21 @@ class TicTacToeSinglePlayerVectorEnv:
     ``step`` / ``reset`` rewrites (clone what you keep).
     A step is ONE launch (``crl_ttt_step_single``) with no host synchronisation, and can be captured into a HIP graph
     (``torch.cuda.graph``).  The opponents' draws are ``crl_ttt_sample``'s at each game's step counter, keyed by ``seed``;
-    the learner's ply advances the counter as well."""
+    the learner's ply advances the counter as well.  ``opponent="tactical"`` seats the win-or-block agent with ``noise``
+    instead (``crl_ttt_step_single_tactical``, ``TTTBatch.sample_tactical``'s draws): still one launch per step."""
 
     def __init__(self, dims=(3, 3), k: int = 3, num_players: int = 2, batch: int = 1024, seat=0, seed: int = 0,
-                 device="cuda"):
+                 device="cuda", opponent: str = "random", noise: float = 0.1):
+        if opponent not in TTTBatch.AGENTS:
+            raise ValueError("opponent must be 'random' or 'tactical', got %r" % (opponent,))
+        self.opponent, self.noise = opponent, _unit("noise", noise)
         self.batch = TTTBatch(dims, k, num_players, batch, device=device)
         self.num_players, self.num_envs, self.seed = num_players, batch, int(seed)
         self.seat = _seat_tensor(seat, num_players, batch, self.batch.device)
         self._out = None
 
     def _step(self, action):
-        self._out = self.batch.step_single(self.seat, action, self.seed, out=self._out)
+        self._out = self.batch.step_single(self.seat, action, self.seed, out=self._out, opponent=self.opponent, noise=self.noise)
         o = self._out
         return {"board": o["board"]}, o["reward"], o["done"], {"valid": o["valid"], "winners": o["winners"]}
 

@@ -85,7 +85,9 @@ const char *crl_last_error(void);
  *      crl_ttt_playout / crl_blokus_playout (batched random playouts) were added under 113: new entries and new Philox
  *      tags only, no existing struct, argument list or RNG contract changed.  So was crl_tron_playout (with
  *      CRL_PLAYOUT_AVOID / CRL_PLAYOUT_UNTIL_SEAT_DONE), on the same terms, and so were crl_tron_territory /
- *      crl_tron_sample_territory (Voronoi territory and the territory-greedy agent: two new entries, one new Philox tag). */
+ *      crl_tron_sample_territory (Voronoi territory and the territory-greedy agent: two new entries, one new Philox tag).
+ *      So were crl_ttt_winning_cells and crl_ttt_sample_tactical / _rollout_tactical / _step_single_tactical /
+ *      _playout_tactical (the win-or-block agent of TicTacToe: five new entries, two new Philox tags). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -759,6 +761,55 @@ int crl_blokus_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t fi
                        const int32_t *cand, int A, int R,
                        uint32_t *wins, uint32_t *played, uint32_t *len_sum, int32_t *score_sum,
                        uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------ the tactical (win-or-block) agent of TicTacToe
+ * The standard scripted opponent of k-in-a-row games: take a winning cell if there is one, else block the next player who
+ * has one, else play at random.  No reference counterpart (the reference's only TicTacToe opponent is the random agent).
+ * Per game b with n cells and P players: o[q] = player q's marks, all = OR_q o[q], E = full & ~all (the empty cells), and
+ * win(m) = "m holds a K-window that stays on the board", exactly the test crl_ttt_step applies.
+ * Winning cells:  W_q = { e in E : win(o[q] | 1 << e) }, as a mask.
+ * Tactical move of the mover p = to_move[b] at step counter c of global game g = first_env_id + b:
+ *   1. p outside [0, P) or E == 0: the action is -1 (pass) and no draw is made.
+ *   2. w = Philox4x32-10(ctr = {g, c >> 1, c2, TAG}, key = {seed lo, seed hi}); u = w[2 (c & 1)], v = w[2 (c & 1) + 1]: one
+ *      Philox block per two plies.  crl_ttt_sample_tactical / _rollout_tactical / _step_single_tactical: c2 = 0 and
+ *      TAG = 0x54630000; crl_ttt_playout_tactical: c2 = (a << 16) | r and TAG = 0x54430000.  (The random agent's contract
+ *      above is untouched.)
+ *   3. noisy  iff  u < thr,  thr = min(2^32, ceil(noise * 2^32)) computed on the host in 64 bits, as crl_tron_sample_avoid:
+ *      noise = 0 is never noisy, noise = 1 always.
+ *   4. noisy: S = E.  Else S = the first non-empty set of W_p, W_{(p+1) mod P}, ..., W_{(p+P-1) mod P} -- the mover's own win
+ *      first, then the threat of the earliest player to come -- and S = E when all are empty.
+ *   5. the action is the mulhi32(v, popcount(S))-th set bit of S, ascending (row-major order).
+ * The agent reads occ and to_move only; like crl_ttt_sample it does not look at winner.
+ * Errors (CRL_EINVAL, with a crl_last_error message, before any device work): NULL pointers, B out of range, noise outside
+ * [0, 1] or NaN, and what the random-agent sibling of each entry checks (flags != 0, T, A, R, rel_mod, cells >= P).
+ * One lane per game (the playout: per playout).  W_q is computed with shift-ANDs per line direction on every board; the
+ * entries that play plies test a ply's win as their random siblings do (boards of at most 16 cells: the win-mask table of
+ * crl_ttt_create when it lives on the launching device).
+ *
+ * crl_ttt_winning_cells: cells uint32 [P][B] = W_q of every player, for observations and action priors. */
+int crl_ttt_winning_cells(const crl_ctx *ctx, int64_t B, const uint32_t *occ, uint32_t *cells, void *stream);
+/* action[b] = the tactical move at step counter tcount[b]; advance != 0 also increments tcount (passes included), as
+ * crl_ttt_sample does. */
+int crl_ttt_sample_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
+                            const int8_t *to_move, uint32_t *tcount, int advance, double noise, int8_t *action, void *stream);
+/* crl_ttt_rollout with EVERY seat on the tactical agent: the same auto-reset, crl_ttt_stats bookkeeping and results row,
+ * tcount advances by one per ply.
+ * T x (crl_ttt_sample_tactical(advance = 1); crl_ttt_step with CRL_STEP_AUTO_RESET) == crl_ttt_rollout_tactical(T). */
+int crl_ttt_rollout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, double noise,
+                             uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats stats, void *stream);
+/* crl_ttt_step_single word for word, except that in its step 2 the opponents' action is what
+ * crl_ttt_sample_tactical(advance = 1) returns on that state.  The learner's ply still consumes one counter value. */
+int crl_ttt_step_single_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                                 uint32_t *occ, int8_t *winner, int8_t *to_move, const int8_t *seat,
+                                 const int64_t *learner_action, uint32_t *tcount,
+                                 int8_t *reward, uint8_t *done, int8_t *winners,
+                                 int8_t *obs_board, uint32_t *valid, int rel_mod, double noise, uint32_t flags, void *stream);
+/* crl_ttt_playout word for word (rows, skipping, outputs, wave-order independence, 64-bit lane indexing), except that every
+ * ply after the candidate is the tactical move at step counter c = tcount[b] + k under the playout tag (2. above). */
+int crl_ttt_playout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                             const uint32_t *occ, const int8_t *winner, const int8_t *to_move, const uint32_t *tcount,
+                             const int32_t *cand, int A, int R,
+                             uint32_t *wins, uint32_t *played, uint32_t *len_sum, double noise, uint32_t flags, void *stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,10 @@
 //         unfinished episode is replayed on byte slabs at the end to recover owners.
 //   * global-memory, lane per game (more than 4 players or long launches on boards above 44x44): boards stay in HBM /
 //     Infinity Cache, same tagged cells, tags stripped in place at the end.
+// Stated once for the lane-per-player kernels and the replay behind qbits: tron_quad_all / tron_quad_mine (DPP gather of a
+// quad's four values, the select back), tron_seat_start (a seat's start cell and direction), tron_lane_totals_load (running
+// totals read at entry), tron_marks_decode (what a launch's two counting registers say), tron_wave_rewrite (wave-cooperative
+// new_state in global memory).  A kernel that keeps its own text of one says so at the place and why (docs/history.md).
 // plus crl_tron_ranking (compute_ranking, TronGridEnvironment.py:483-508), one wave per game.
 #include "crl_common.hpp"
 #include <hip/hip_ext.h>
@@ -533,7 +537,7 @@ tron_step_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_t B,
 
 // u16 entries per game of the 16-bit gather row (crl_tron_stats.packed): n_episodes, len_sum, last_winners, tstep,
 // ret_sum[P], rounded up to a whole number of dwords
-template <int P> constexpr int kTronPackedRow = (4 + P + 1) & ~1;
+constexpr int kTronPackedRow(const int P) { return (4 + P + 1) & ~1; }
 
 // per-lane rollout bookkeeping shared by the rollout kernels.  The running totals a launch adds to are read at kernel
 // entry (with every other global load of the prologue), not in the epilogue: a short launch otherwise ends on a chain
@@ -576,7 +580,7 @@ struct TronAcc {
     __device__ __forceinline__ void store(const crl_tron_stats &st, const int64_t B, const int64_t b) const
     {
         int32_t *row = st.results ? st.results + b * (3 + 2 * P) : nullptr;
-        uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow<P> : nullptr;
+        uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow(P) : nullptr;
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             const int r = old_ret[p] + ret[p];
@@ -1089,6 +1093,83 @@ __device__ __forceinline__ void tron_quad_actions(const uint32_t gid, const uint
     a_hi = s16[2] | s16[3] << 16;
 }
 
+// ---- what the lane-per-player rollout kernels share (quad, pair, gquad, qbits, avoid; the replay takes the first three) ------
+// v of each of the quad's four lanes.  All four broadcasts run in all lanes before any lane selects: no
+// short-circuit operator and no early-out around a DPP read, here or in the callers.
+__device__ __forceinline__ void tron_quad_all(const int v, int (&out)[4])
+{
+    out[0] = tron_quad<0x00>(v); out[1] = tron_quad<0x55>(v); out[2] = tron_quad<0xAA>(v); out[3] = tron_quad<0xFF>(v);
+}
+__device__ __forceinline__ int tron_quad_mine(const int p, const int (&arr)[4])    // the select back: seat p's entry
+{
+    // (all four read first: with the reads inside the selects the compiler turns the chain into arr[p], an indexed read of an
+    //  array that then lives in scratch memory)
+    const int a0 = arr[0], a1 = arr[1], a2 = arr[2], a3 = arr[3];
+    int r = a0; r = (p == 1) ? a1 : r;
+    r = (p == 2) ? a2 : r; r = (p == 3) ? a3 : r;
+    return r;
+}
+
+// seat p's cell and direction of the start layout (what a kernel makes of the cell -- LDS, bit or cell address -- is its own)
+struct TronSeatStart { int fh, fd; };
+__device__ __forceinline__ TronSeatStart tron_seat_start(const crl_tron_cfg &cfg, const int p)
+{
+    int fh = cfg.start_heads[0], fd = cfg.start_dirs[0];
+    fh = (p == 1) ? cfg.start_heads[1] : fh; fd = (p == 1) ? cfg.start_dirs[1] : fd;
+    fh = (p == 2) ? cfg.start_heads[2] : fh; fd = (p == 2) ? cfg.start_dirs[2] : fd;
+    fh = (p == 3) ? cfg.start_heads[3] : fh; fd = (p == 3) ? cfg.start_dirs[3] : fd;
+    return {fh, fd};
+}
+
+// the running totals a launch adds to, read at kernel entry like TronAcc's: my player's columns (pb), my game's (bb)
+struct TronLaneTotals { int ret; uint32_t wins, tc, ts, n_ep, len_sum, last_w; };
+__device__ __forceinline__ TronLaneTotals tron_lane_totals_load(const crl_tron_stats &st, const int64_t pb, const int64_t bb)
+{
+    // (unconditional, from a clamped index: under `pvalid ? load : 0` every load sits in its own branch with its own wait)
+    return {st.ret_sum[pb], st.win_count[pb], st.tcount[bb], st.tstep[bb], st.n_episodes[bb], st.len_sum[bb], st.last_winners[bb]};
+}
+
+// What a launch counts per lane, in two registers (pushed at every reset, by the kernels' own inline asm).  wn: episodes
+// finished << 16 | my wins.  marks: the latest reset in bits 15:0, the one before in 31:16, each (launch steps done at the
+// reset) << 1 | I was alive.  What they say after the launch's T steps, given the step counters the game came in with:
+struct TronMarks { uint32_t n_ep, wins, tc, ts, ts_at_entry; int last_alive, last_len; };
+__device__ __forceinline__ TronMarks tron_marks_decode(const uint32_t wn, const uint32_t marks, const uint32_t tc_in,
+                                                       const uint32_t ts_in, const int T)
+{
+    TronMarks o;
+    o.n_ep = wn >> 16; o.wins = wn & 0xffffu;
+    const int done_last = (int)((marks & 0xffffu) >> 1), done_prev = (int)(marks >> 17);
+    o.last_alive = (int)(marks & 1u);
+    o.tc = tc_in + (uint32_t)T; o.ts_at_entry = ts_in;
+    o.ts = o.n_ep ? (uint32_t)(T - done_last) : ts_in + (uint32_t)T;
+    o.last_len = (o.n_ep > 1u) ? done_last - done_prev : (int)ts_in + done_last;
+    return o;
+}
+
+// wave-cooperative new_state of the games whose quad / lane leader is set in `ending` (a ballot over the wave; game of
+// lane l = env0 + (l >> shift)): 16-byte stores between the board's unaligned ends
+template <int P>
+__device__ __forceinline__ void tron_wave_rewrite(const crl_tron_cfg &cfg, int8_t *board, const int64_t env0, const int NN,
+                                                  const int shift, const int lane, uint64_t ending)
+{
+    while (ending) {
+        const int l = (int)__builtin_ctzll(ending);
+        ending &= ending - 1;
+        uint8_t *eb = reinterpret_cast<uint8_t *>(board) + (env0 + (l >> shift)) * NN;
+        const int lead = min((int)((16u - (uint32_t)((uintptr_t)eb & 15u)) & 15u), NN);
+        const int chunks = (NN - lead) >> 4, tail0 = lead + (chunks << 4);
+        for (int c = lane; c < chunks; c += CRL_WAVE)
+            *reinterpret_cast<uint4 *>(eb + lead + (c << 4)) = tron_fresh_chunk16<P>(cfg, lead + (c << 4));
+        const int odd = lane < lead ? lane : (lane - lead < NN - tail0 ? tail0 + lane - lead : -1);   // (lead + tail < 31 bytes)
+        if (odd >= 0) {
+            int v = 0;
+#pragma unroll
+            for (int q = 0; q < P; ++q) v = (cfg.start_heads[q] == odd) ? q + 1 : v;
+            eb[odd] = (uint8_t)v;
+        }
+    }
+}
+
 // ---- diagnostic build only (-DCRL_QUAD_STAMPS): when each wave of the lane-per-player byte kernel passes its phases
 // (100 MHz wall clock: entry, boards in LDS, steps done, kernel end).  Leaves the kernel through g_quad_stamps alone; the
 // shipped build compiles none of it (tools/debug/quad_phases.py).
@@ -1185,11 +1266,8 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
     const int h_in = heads[pb];
     const int d_in = dirs[pb];
     int k = deaths[pb];
-    const int old_ret = st.ret_sum[pb];
-    const uint32_t old_wins = st.win_count[pb];
-    uint32_t tc = st.tcount[bb], ts = st.tstep[bb];
-    const uint32_t old_n_ep = st.n_episodes[bb], old_len_sum = st.len_sum[bb];
-    const uint32_t old_last_w = st.last_winners[bb];
+    const TronLaneTotals in = tron_lane_totals_load(st, pb, bb);
+    uint32_t tc = in.tc, ts = in.ts;
     k = pvalid ? k : 1;                                         // a seat without a player counts as dead for good
     if (rows20 || rowsN) {
         // the two wall rows and the junk dword of my game (three dwords per lane), then my rows of the wave's boards
@@ -1264,10 +1342,7 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
     }
     // ---- my player: head as an LDS address, the start layout for resets
     const int junk = mine + pad.junk + p;                       // four junk bytes per slab: one per lane of the quad
-    int fh = cfg.start_heads[0], fd = cfg.start_dirs[0];
-    fh = (p == 1) ? cfg.start_heads[1] : fh; fd = (p == 1) ? cfg.start_dirs[1] : fd;
-    fh = (p == 2) ? cfg.start_heads[2] : fh; fd = (p == 2) ? cfg.start_dirs[2] : fd;
-    fh = (p == 3) ? cfg.start_heads[3] : fh; fd = (p == 3) ? cfg.start_dirs[3] : fd;
+    const auto [fh, fd] = tron_seat_start(cfg, p);
     const int fy = (int)__umulhi((uint32_t)(fh < 0 ? 0 : fh), g.inv_n);
     const int fresh_h = (p < P) ? mine + (fy + 1) * RS + (fh - fy * N) : junk;
     const int fresh_d8 = fd << 3;
@@ -1367,17 +1442,18 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
             uint32_t stamp4[4];
             const int h0 = h_was;
             const int d0 = (run ? (dir8 - (int)(acts << 3)) >> 3 : d8 >> 3) & 3, dir = (dir8 >> 3) & 3, kk = run ? 0 : k;
-            s.h[0] = tron_quad<0x00>(h0); s.h[1] = tron_quad<0x55>(h0); s.h[2] = tron_quad<0xAA>(h0); s.h[3] = tron_quad<0xFF>(h0);
-            s.d[0] = tron_quad<0x00>(d0); s.d[1] = tron_quad<0x55>(d0); s.d[2] = tron_quad<0xAA>(d0); s.d[3] = tron_quad<0xFF>(d0);
-            s.k[0] = tron_quad<0x00>(kk); s.k[1] = tron_quad<0x55>(kk); s.k[2] = tron_quad<0xAA>(kk); s.k[3] = tron_quad<0xFF>(kk);
-            pr.tgt[0] = tron_quad<0x00>(tgt); pr.tgt[1] = tron_quad<0x55>(tgt); pr.tgt[2] = tron_quad<0xAA>(tgt); pr.tgt[3] = tron_quad<0xFF>(tgt);
-            pr.raw[0] = tron_quad<0x00>((int)raw); pr.raw[1] = tron_quad<0x55>((int)raw); pr.raw[2] = tron_quad<0xAA>((int)raw); pr.raw[3] = tron_quad<0xFF>((int)raw);
-            pr.ndir[0] = tron_quad<0x00>(dir); pr.ndir[1] = tron_quad<0x55>(dir); pr.ndir[2] = tron_quad<0xAA>(dir); pr.ndir[3] = tron_quad<0xFF>(dir);
+            tron_quad_all(h0, s.h);
+            tron_quad_all(d0, s.d);
+            tron_quad_all(kk, s.k);
+            tron_quad_all(tgt, pr.tgt);
+            tron_quad_all((int)raw, pr.raw);
+            tron_quad_all(dir, pr.ndir);
 #pragma unroll
             for (int q = 0; q < 4; ++q) stamp4[q] = tagbits | (uint32_t)(q + 1);
             LdsBoard<OB> bd{tagbits};
             bd.within(mine, mine + pad.stride);
             tron_resolve_lds<4>(bd, s, pr, stamp4, junk);       // trail writes of all four players from every lane: identical
+            // (restates tron_quad_mine, three arrays in one chain: one chain per array moves this kernel's registers)
             int hS = s.h[0], dS = s.d[0], kS = s.k[0];
             hS = (p == 1) ? s.h[1] : hS; dS = (p == 1) ? s.d[1] : dS; kS = (p == 1) ? s.k[1] : kS;
             hS = (p == 2) ? s.h[2] : hS; dS = (p == 2) ? s.d[2] : dS; kS = (p == 2) ? s.k[2] : kS;
@@ -1450,6 +1526,7 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
         for (int t = 0; t < T; ++t) one_step(std::false_type{});
     }
     QUAD_STAMP(2);
+    // (restates tron_marks_decode: through the helper the same instructions come out in another order, and this kernel's text must not move)
     const uint32_t n_ep = wn >> 16, wins = wn & 0xffffu;
     const int done_last = (int)((marks & 0xffffu) >> 1), done_prev = (int)(marks >> 17), last_alive = (int)(marks & 1u);
     tc = tc_in + (uint32_t)T;
@@ -1604,22 +1681,22 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
     lw |= tron_quad<0x4E>(lw);
     const int ret = 2 * (int)alive_steps - T + 9 * (int)wins;   // alive +1, dead -1, alive at a terminal step +10
     int32_t *row = st.results ? st.results + b * (3 + 2 * P) : nullptr;
-    uint16_t *pk = st.packed ? st.packed + b * ((4 + P + 1) & ~1) : nullptr;        // kTronPackedRow, P a run-time value here
+    uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow(P) : nullptr;
     if (pvalid) {
         const int rel = h - mine;
         const int rowi = rel / RS;                               // = y + 1
         heads[p * B + b] = (int16_t)((rowi - 1) * N + (rel - rowi * RS));
         dirs[p * B + b] = (int8_t)d;
         deaths[p * B + b] = (int8_t)k;
-        const int rs = old_ret + ret;
-        const uint32_t wc = old_wins + wins;
+        const int rs = in.ret + ret;
+        const uint32_t wc = in.wins + wins;
         st.ret_sum[p * B + b] = rs;
         st.win_count[p * B + b] = wc;
         if (row) { row[3 + p] = (int32_t)wc; row[3 + P + p] = rs; }
         if (pk) pk[4 + p] = (uint16_t)rs;
     }
     if (gvalid && p == 0) {
-        const uint32_t ne = old_n_ep + n_ep, ls = old_len_sum + (ts_at_entry + (uint32_t)T - ts);
+        const uint32_t ne = in.n_ep + n_ep, ls = in.len_sum + (ts_at_entry + (uint32_t)T - ts);
         st.tcount[b] = tc;
         st.tstep[b] = ts;
         st.n_episodes[b] = ne;
@@ -1628,8 +1705,8 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
             st.last_winners[b] = (uint8_t)lw;
             st.last_len[b] = (uint16_t)last_len;
         }
-        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = n_ep > 0 ? lw : (int32_t)old_last_w; }
-        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(n_ep > 0 ? (uint32_t)lw : old_last_w); pk[3] = (uint16_t)ts; }
+        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = n_ep > 0 ? lw : (int32_t)in.last_w; }
+        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(n_ep > 0 ? (uint32_t)lw : in.last_w); pk[3] = (uint16_t)ts; }
     }
 #ifdef CRL_QUAD_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the stores of this wave have left
@@ -1711,11 +1788,8 @@ tron_rollout_pair_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
     const int h_in = heads[pb];
     const int d_in = dirs[pb];
     int k = deaths[pb];
-    const int old_ret = st.ret_sum[pb];
-    const uint32_t old_wins = st.win_count[pb];
-    uint32_t tc = st.tcount[bb], ts = st.tstep[bb];
-    const uint32_t old_n_ep = st.n_episodes[bb], old_len_sum = st.len_sum[bb];
-    const uint32_t old_last_w = st.last_winners[bb];
+    const TronLaneTotals in = tron_lane_totals_load(st, pb, bb);
+    uint32_t tc = in.tc, ts = in.ts;
     k = pvalid ? k : 1;
     // walls everywhere (each lane half of its game's slab), then the cells
     for (int off = 4 * p; off < pad.stride; off += 8) *(lds_u32 *)(uintptr_t)(uint32_t)(mine + off) = 0xffffffffu;
@@ -1743,8 +1817,7 @@ tron_rollout_pair_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
     }
     // ---- my player: head as an LDS address, the start layout for resets
     const int junk = mine + pad.junk + p;
-    int fh = cfg.start_heads[0], fd = cfg.start_dirs[0];
-    fh = (p == 1) ? cfg.start_heads[1] : fh; fd = (p == 1) ? cfg.start_dirs[1] : fd;
+    const auto [fh, fd] = tron_seat_start(cfg, p);
     const int fy = (int)__umulhi((uint32_t)(fh < 0 ? 0 : fh), g.inv_n);
     const int fresh_h = (p < P) ? mine + (fy + 1) * RS + (fh - fy * N) : junk;
     const int fresh_d8 = fd << 3;
@@ -1849,12 +1922,7 @@ tron_rollout_pair_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
             neg2 = -32;
         }
     }
-    const uint32_t n_ep = wn >> 16, wins = wn & 0xffffu;
-    const int done_last = (int)((marks & 0xffffu) >> 1), done_prev = (int)(marks >> 17), last_alive = (int)(marks & 1u);
-    tc = tc_in + (uint32_t)T;
-    const uint32_t ts_at_entry = ts;
-    ts = n_ep ? (uint32_t)(T - done_last) : ts_at_entry + (uint32_t)T;
-    const int last_len = (n_ep > 1u) ? done_last - done_prev : (int)ts_at_entry + done_last;
+    const TronMarks fin = tron_marks_decode(wn, marks, tc_in, ts, T);
     k = a ? 0 : (k == 7 ? p + 1 : k);
     const int d = (d8 >> 3) & 3;
     // ---- epilogue: the junk dword hands this board's tag to its copier, boards LDS -> HBM without tags
@@ -1897,36 +1965,36 @@ tron_rollout_pair_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
         }
     }
     // ---- per-player state and statistics (my columns), per-game statistics (lane 0 of the pair)
-    int lw = (last_alive & 1) << p;
+    int lw = (fin.last_alive & 1) << p;
     lw |= tron_quad<0xB1>(lw);
-    const int ret = 2 * (int)alive_steps - T + 9 * (int)wins;
+    const int ret = 2 * (int)alive_steps - T + 9 * (int)fin.wins;
     int32_t *row = st.results ? st.results + b * (3 + 2 * P) : nullptr;
-    uint16_t *pk = st.packed ? st.packed + b * ((4 + P + 1) & ~1) : nullptr;
+    uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow(P) : nullptr;
     if (pvalid) {
         const int rel = h - mine;
         const int rowi = rel / RS;
         heads[p * B + b] = (int16_t)((rowi - 1) * N + (rel - rowi * RS));
         dirs[p * B + b] = (int8_t)d;
         deaths[p * B + b] = (int8_t)k;
-        const int rs = old_ret + ret;
-        const uint32_t wc = old_wins + wins;
+        const int rs = in.ret + ret;
+        const uint32_t wc = in.wins + fin.wins;
         st.ret_sum[p * B + b] = rs;
         st.win_count[p * B + b] = wc;
         if (row) { row[3 + p] = (int32_t)wc; row[3 + P + p] = rs; }
         if (pk) pk[4 + p] = (uint16_t)rs;
     }
     if (gvalid && p == 0) {
-        const uint32_t ne = old_n_ep + n_ep, ls = old_len_sum + (ts_at_entry + (uint32_t)T - ts);
-        st.tcount[b] = tc;
-        st.tstep[b] = ts;
+        const uint32_t ne = in.n_ep + fin.n_ep, ls = in.len_sum + (fin.ts_at_entry + (uint32_t)T - fin.ts);
+        st.tcount[b] = fin.tc;
+        st.tstep[b] = fin.ts;
         st.n_episodes[b] = ne;
         st.len_sum[b] = ls;
-        if (n_ep > 0) {
+        if (fin.n_ep > 0) {
             st.last_winners[b] = (uint8_t)lw;
-            st.last_len[b] = (uint16_t)last_len;
+            st.last_len[b] = (uint16_t)fin.last_len;
         }
-        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = n_ep > 0 ? lw : (int32_t)old_last_w; }
-        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(n_ep > 0 ? (uint32_t)lw : old_last_w); pk[3] = (uint16_t)ts; }
+        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = fin.n_ep > 0 ? lw : (int32_t)in.last_w; }
+        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(fin.n_ep > 0 ? (uint32_t)lw : in.last_w); pk[3] = (uint16_t)fin.ts; }
     }
 }
 
@@ -1971,6 +2039,7 @@ tron_rollout_gquad_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_
     const int h_in = heads[pb];
     const int d_in = dirs[pb];
     int k = deaths[pb];
+    // (restates tron_lane_totals_load and, below, tron_seat_start: through them this kernel's instances differ by up to 3 instructions)
     const int old_ret = st.ret_sum[pb];
     const uint32_t old_wins = st.win_count[pb];
     uint32_t tc = st.tcount[bb], ts = st.tstep[bb];
@@ -2028,25 +2097,24 @@ tron_rollout_gquad_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_
             TronRegs<4> s;
             TronProbe<4> pr;
             const int oobi = oob ? 1 : 0;
-            s.h[0] = tron_quad<0x00>(h0); s.h[1] = tron_quad<0x55>(h0); s.h[2] = tron_quad<0xAA>(h0); s.h[3] = tron_quad<0xFF>(h0);
-            s.x[0] = tron_quad<0x00>(hx0); s.x[1] = tron_quad<0x55>(hx0); s.x[2] = tron_quad<0xAA>(hx0); s.x[3] = tron_quad<0xFF>(hx0);
-            s.y[0] = tron_quad<0x00>(hy0); s.y[1] = tron_quad<0x55>(hy0); s.y[2] = tron_quad<0xAA>(hy0); s.y[3] = tron_quad<0xFF>(hy0);
-            s.d[0] = tron_quad<0x00>(d0); s.d[1] = tron_quad<0x55>(d0); s.d[2] = tron_quad<0xAA>(d0); s.d[3] = tron_quad<0xFF>(d0);
-            s.k[0] = tron_quad<0x00>(k0); s.k[1] = tron_quad<0x55>(k0); s.k[2] = tron_quad<0xAA>(k0); s.k[3] = tron_quad<0xFF>(k0);
-            pr.tgt[0] = tron_quad<0x00>(tgt); pr.tgt[1] = tron_quad<0x55>(tgt); pr.tgt[2] = tron_quad<0xAA>(tgt); pr.tgt[3] = tron_quad<0xFF>(tgt);
-            pr.raw[0] = tron_quad<0x00>(raw); pr.raw[1] = tron_quad<0x55>(raw); pr.raw[2] = tron_quad<0xAA>(raw); pr.raw[3] = tron_quad<0xFF>(raw);
-            pr.ndir[0] = tron_quad<0x00>(dir); pr.ndir[1] = tron_quad<0x55>(dir); pr.ndir[2] = tron_quad<0xAA>(dir); pr.ndir[3] = tron_quad<0xFF>(dir);
-            pr.nx[0] = tron_quad<0x00>(nx); pr.nx[1] = tron_quad<0x55>(nx); pr.nx[2] = tron_quad<0xAA>(nx); pr.nx[3] = tron_quad<0xFF>(nx);
-            pr.ny[0] = tron_quad<0x00>(ny); pr.ny[1] = tron_quad<0x55>(ny); pr.ny[2] = tron_quad<0xAA>(ny); pr.ny[3] = tron_quad<0xFF>(ny);
-            const int o0 = tron_quad<0x00>(oobi), o1 = tron_quad<0x55>(oobi), o2 = tron_quad<0xAA>(oobi), o3 = tron_quad<0xFF>(oobi);
-            pr.oob[0] = o0 != 0; pr.oob[1] = o1 != 0; pr.oob[2] = o2 != 0; pr.oob[3] = o3 != 0;
+            tron_quad_all(h0, s.h);
+            tron_quad_all(hx0, s.x);
+            tron_quad_all(hy0, s.y);
+            tron_quad_all(d0, s.d);
+            tron_quad_all(k0, s.k);
+            tron_quad_all(tgt, pr.tgt);
+            tron_quad_all(raw, pr.raw);
+            tron_quad_all(dir, pr.ndir);
+            tron_quad_all(nx, pr.nx);
+            tron_quad_all(ny, pr.ny);
+            int o4[4]; tron_quad_all(oobi, o4);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) pr.oob[q] = o4[q] != 0;
             int rew4[4], term4, wm4;
             const PlainBoard nowhere{nullptr CRL_CELLS_INIT(NN)};
             tron_resolve<4>(nowhere, false, s, pr, rew4, term4, wm4);   // valid = false: no stores here (below, with everybody's)
-            int hS = s.h[0], xS = s.x[0], yS = s.y[0], dS = s.d[0], kS = s.k[0];
-            hS = (p == 1) ? s.h[1] : hS; xS = (p == 1) ? s.x[1] : xS; yS = (p == 1) ? s.y[1] : yS; dS = (p == 1) ? s.d[1] : dS; kS = (p == 1) ? s.k[1] : kS;
-            hS = (p == 2) ? s.h[2] : hS; xS = (p == 2) ? s.x[2] : xS; yS = (p == 2) ? s.y[2] : yS; dS = (p == 2) ? s.d[2] : dS; kS = (p == 2) ? s.k[2] : kS;
-            hS = (p == 3) ? s.h[3] : hS; xS = (p == 3) ? s.x[3] : xS; yS = (p == 3) ? s.y[3] : yS; dS = (p == 3) ? s.d[3] : dS; kS = (p == 3) ? s.k[3] : kS;
+            const int hS = tron_quad_mine(p, s.h), xS = tron_quad_mine(p, s.x), yS = tron_quad_mine(p, s.y);
+            const int dS = tron_quad_mine(p, s.d), kS = tron_quad_mine(p, s.k);
             moved = hS != h0;                                   // (a head is never its owner's own target)
             h = hS; hx = xS; hy = yS; d = dS;
             k = kS;                                             // (also a dead player's entry, overwritten by a head-on killer: :56-57)
@@ -2071,6 +2139,7 @@ tron_rollout_gquad_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_
             a = fresh_a;
         }
         // new_state for the games of this wave that ended: the whole wave writes each one's start board
+        // (restates tron_wave_rewrite with shift = 2: through the helper the instances differ by 1-2 instructions)
         uint64_t ending = __builtin_amdgcn_ballot_w64(over && gvalid && p == 0);
         while (ending) {
             const int l = (int)__builtin_ctzll(ending);
@@ -2098,41 +2167,36 @@ tron_rollout_gquad_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_
         }
     }
     // ---- per-player state and statistics (my columns), per-game statistics (lane 0 of the quad)
-    const uint32_t n_ep = wn >> 16, wins = wn & 0xffffu;
-    const int done_last = (int)((marks & 0xffffu) >> 1), done_prev = (int)(marks >> 17), last_alive = (int)(marks & 1u);
-    tc = tc_in + (uint32_t)T;
-    const uint32_t ts_at_entry = ts;
-    ts = n_ep ? (uint32_t)(T - done_last) : ts_at_entry + (uint32_t)T;
-    const int last_len = (n_ep > 1u) ? done_last - done_prev : (int)ts_at_entry + done_last;
-    int lw = (last_alive & 1) << p;
+    const TronMarks fin = tron_marks_decode(wn, marks, tc_in, ts, T);
+    int lw = (fin.last_alive & 1) << p;
     lw |= tron_quad<0xB1>(lw);
     lw |= tron_quad<0x4E>(lw);
-    const int ret = 2 * (int)alive_steps - T + 9 * (int)wins;   // alive +1, dead -1, alive at a terminal step +10
+    const int ret = 2 * (int)alive_steps - T + 9 * (int)fin.wins;   // alive +1, dead -1, alive at a terminal step +10
     int32_t *row = st.results ? st.results + b * (3 + 2 * P) : nullptr;
-    uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow<P> : nullptr;
+    uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow(P) : nullptr;
     if (pvalid) {
         heads[p * B + b] = (int16_t)h;
         dirs[p * B + b] = (int8_t)d;
         deaths[p * B + b] = (int8_t)k;
         const int rs = old_ret + ret;
-        const uint32_t wc = old_wins + wins;
+        const uint32_t wc = old_wins + fin.wins;
         st.ret_sum[p * B + b] = rs;
         st.win_count[p * B + b] = wc;
         if (row) { row[3 + p] = (int32_t)wc; row[3 + P + p] = rs; }
         if (pk) pk[4 + p] = (uint16_t)rs;
     }
     if (gvalid && p == 0) {
-        const uint32_t ne = old_n_ep + n_ep, ls = old_len_sum + (ts_at_entry + (uint32_t)T - ts);
-        st.tcount[b] = tc;
-        st.tstep[b] = ts;
+        const uint32_t ne = old_n_ep + fin.n_ep, ls = old_len_sum + (fin.ts_at_entry + (uint32_t)T - fin.ts);
+        st.tcount[b] = fin.tc;
+        st.tstep[b] = fin.ts;
         st.n_episodes[b] = ne;
         st.len_sum[b] = ls;
-        if (n_ep > 0) {
+        if (fin.n_ep > 0) {
             st.last_winners[b] = (uint8_t)lw;
-            st.last_len[b] = (uint16_t)last_len;
+            st.last_len[b] = (uint16_t)fin.last_len;
         }
-        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = n_ep > 0 ? lw : (int32_t)old_last_w; }
-        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(n_ep > 0 ? (uint32_t)lw : old_last_w); pk[3] = (uint16_t)ts; }
+        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = fin.n_ep > 0 ? lw : (int32_t)old_last_w; }
+        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(fin.n_ep > 0 ? (uint32_t)lw : old_last_w); pk[3] = (uint16_t)fin.ts; }
     }
 }
 
@@ -2691,6 +2755,7 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
     const int h_in = heads[pb];
     const int d_in = dirs[pb];
     const int k_in = pvalid ? (int)deaths[pb] : 1;
+    // (restates tron_lane_totals_load and, below, tron_seat_start: through them this kernel's instances differ by up to 9 instructions)
     const int old_ret = st.ret_sum[pb];
     const uint32_t old_wins = st.win_count[pb];
     const uint32_t tc_in = st.tcount[bb], ts_at_entry = st.tstep[bb];
@@ -2904,12 +2969,12 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
                 const int entered = (tq == t1 ? m1 : 0) | (tq == t2 ? m2 : 0) | (tq == t3 ? m3 : 0);
                 oc = entered ? 0 : oc;
             }
-            int ps[4] = {tron_quad<0x00>(pos_was), tron_quad<0x55>(pos_was), tron_quad<0xAA>(pos_was), tron_quad<0xFF>(pos_was)};
-            int ds[4] = {tron_quad<0x00>(d), tron_quad<0x55>(d), tron_quad<0xAA>(d), tron_quad<0xFF>(d)};
-            int al4[4] = {tron_quad<0x00>(al), tron_quad<0x55>(al), tron_quad<0xAA>(al), tron_quad<0xFF>(al)};
-            const int tg[4] = {tron_quad<0x00>(tgt), tron_quad<0x55>(tgt), tron_quad<0xAA>(tgt), tron_quad<0xFF>(tgt)};
-            const int oq[4] = {tron_quad<0x00>(oc), tron_quad<0x55>(oc), tron_quad<0xAA>(oc), tron_quad<0xFF>(oc)};
-            const int nd[4] = {tron_quad<0x00>(dir), tron_quad<0x55>(dir), tron_quad<0xAA>(dir), tron_quad<0xFF>(dir)};
+            int ps[4]; tron_quad_all(pos_was, ps);
+            int ds[4]; tron_quad_all(d, ds);
+            int al4[4]; tron_quad_all(al, al4);
+            int tg[4]; tron_quad_all(tgt, tg);
+            int oq[4]; tron_quad_all(oc, oq);
+            int nd[4]; tron_quad_all(dir, nd);
             const int jbase = mine + 2 * kSlab;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {                       // CyTronGrid.pyx:15-62
@@ -2929,10 +2994,7 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
                 ps[i] = mv ? tg[i] : ps[i];
                 atomicOr((unsigned int *)(lds + ((mv ? ((tg[i] >> 3) & ~3) : jbase) - lds0)), 1u << (tg[i] & 31));
             }
-            int pS = ps[0], dS = ds[0], aS = al4[0];
-            pS = (p == 1) ? ps[1] : pS; dS = (p == 1) ? ds[1] : dS; aS = (p == 1) ? al4[1] : aS;
-            pS = (p == 2) ? ps[2] : pS; dS = (p == 2) ? ds[2] : dS; aS = (p == 2) ? al4[2] : aS;
-            pS = (p == 3) ? ps[3] : pS; dS = (p == 3) ? ds[3] : dS; aS = (p == 3) ? al4[3] : aS;
+            const int pS = tron_quad_mine(p, ps), dS = tron_quad_mine(p, ds), aS = tron_quad_mine(p, al4);
             pos = pS;
             d8 = dS << 3;
             alive_now = (p < P) && aS != 0;
@@ -3006,37 +3068,33 @@ tron_rollout_qbits_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPa
     }
     QUAD_STAMP(2);
     // ---- statistics (my player's columns; the game's by lane 0 of the quad)
-    const uint32_t n_ep = wn >> 16, wins = wn & 0xffffu;
-    const int done_last = (int)((marks & 0xffffu) >> 1), done_prev = (int)(marks >> 17), last_alive = (int)(marks & 1u);
-    const uint32_t tc = tc_in + (uint32_t)T;
-    const uint32_t ts = n_ep ? (uint32_t)(T - done_last) : ts_at_entry + (uint32_t)T;
-    const int last_len = (n_ep > 1u) ? done_last - done_prev : (int)ts_at_entry + done_last;
-    int lw = (last_alive & 1) << p;
+    const TronMarks fin = tron_marks_decode(wn, marks, tc_in, ts_at_entry, T);
+    int lw = (fin.last_alive & 1) << p;
     lw |= tron_quad<0xB1>(lw);
     lw |= tron_quad<0x4E>(lw);
-    const int ret = 2 * (int)alive_steps - T + 9 * (int)wins;
+    const int ret = 2 * (int)alive_steps - T + 9 * (int)fin.wins;
     int32_t *row = st.results ? st.results + b * (3 + 2 * P) : nullptr;
-    uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow<P> : nullptr;
+    uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow(P) : nullptr;
     if (pvalid) {
         const int rs = old_ret + ret;
-        const uint32_t wc = old_wins + wins;
+        const uint32_t wc = old_wins + fin.wins;
         st.ret_sum[p * B + b] = rs;
         st.win_count[p * B + b] = wc;
         if (row) { row[3 + p] = (int32_t)wc; row[3 + P + p] = rs; }
         if (pk) pk[4 + p] = (uint16_t)rs;
     }
     if (gvalid && p == 0) {
-        const uint32_t ne = old_n_ep + n_ep, ls = old_len_sum + (ts_at_entry + (uint32_t)T - ts);
-        st.tcount[b] = tc;
-        st.tstep[b] = ts;
+        const uint32_t ne = old_n_ep + fin.n_ep, ls = old_len_sum + (ts_at_entry + (uint32_t)T - fin.ts);
+        st.tcount[b] = fin.tc;
+        st.tstep[b] = fin.ts;
         st.n_episodes[b] = ne;
         st.len_sum[b] = ls;
-        if (n_ep > 0) {
+        if (fin.n_ep > 0) {
             st.last_winners[b] = (uint8_t)lw;
-            st.last_len[b] = (uint16_t)last_len;
+            st.last_len[b] = (uint16_t)fin.last_len;
         }
-        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = n_ep > 0 ? lw : (int32_t)old_last_w; }
-        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(n_ep > 0 ? (uint32_t)lw : old_last_w); pk[3] = (uint16_t)ts; }
+        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = fin.n_ep > 0 ? lw : (int32_t)old_last_w; }
+        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(fin.n_ep > 0 ? (uint32_t)lw : old_last_w); pk[3] = (uint16_t)fin.ts; }
     }
     QUAD_STAMP(3);
 }
@@ -3061,10 +3119,7 @@ __device__ __forceinline__ void tron_replay_quad(const crl_tron_cfg &cfg, const 
     const int junk = bmine + pad.junk + p;                      // four junk bytes per slab: one per lane of the quad
     const int64_t bbg = gvalid ? bg : 0;
     const int64_t pb = (int64_t)(seat ? p : 0) * B + bbg;
-    int fh = cfg.start_heads[0], fd = cfg.start_dirs[0];
-    fh = (p == 1) ? cfg.start_heads[1] : fh; fd = (p == 1) ? cfg.start_dirs[1] : fd;
-    fh = (p == 2) ? cfg.start_heads[2] : fh; fd = (p == 2) ? cfg.start_dirs[2] : fd;
-    fh = (p == 3) ? cfg.start_heads[3] : fh; fd = (p == 3) ? cfg.start_dirs[3] : fd;
+    const auto [fh, fd] = tron_seat_start(cfg, p);
     int hc = seat ? fh : 0, d = fd & 3, k = pvalid ? 0 : 1;
     if (!from_start) {                                          // (whole quads: a game's four lanes share from_start)
         hc = min(max((int)heads[pb], 0), NN - 1);
@@ -3109,22 +3164,19 @@ __device__ __forceinline__ void tron_replay_quad(const crl_tron_cfg &cfg, const 
             TronProbe<4> pr;
             uint32_t stamp4[4];
             const int kk = on ? k_was : 1;                      // a game that has not joined yet: nobody runs
-            s.h[0] = tron_quad<0x00>(h_was); s.h[1] = tron_quad<0x55>(h_was); s.h[2] = tron_quad<0xAA>(h_was); s.h[3] = tron_quad<0xFF>(h_was);
-            s.d[0] = tron_quad<0x00>(d_was); s.d[1] = tron_quad<0x55>(d_was); s.d[2] = tron_quad<0xAA>(d_was); s.d[3] = tron_quad<0xFF>(d_was);
-            s.k[0] = tron_quad<0x00>(kk); s.k[1] = tron_quad<0x55>(kk); s.k[2] = tron_quad<0xAA>(kk); s.k[3] = tron_quad<0xFF>(kk);
-            pr.tgt[0] = tron_quad<0x00>(tgt); pr.tgt[1] = tron_quad<0x55>(tgt); pr.tgt[2] = tron_quad<0xAA>(tgt); pr.tgt[3] = tron_quad<0xFF>(tgt);
-            pr.raw[0] = tron_quad<0x00>((int)raw); pr.raw[1] = tron_quad<0x55>((int)raw); pr.raw[2] = tron_quad<0xAA>((int)raw); pr.raw[3] = tron_quad<0xFF>((int)raw);
-            pr.ndir[0] = tron_quad<0x00>(dir); pr.ndir[1] = tron_quad<0x55>(dir); pr.ndir[2] = tron_quad<0xAA>(dir); pr.ndir[3] = tron_quad<0xFF>(dir);
+            tron_quad_all(h_was, s.h);
+            tron_quad_all(d_was, s.d);
+            tron_quad_all(kk, s.k);
+            tron_quad_all(tgt, pr.tgt);
+            tron_quad_all((int)raw, pr.raw);
+            tron_quad_all(dir, pr.ndir);
 #pragma unroll
             for (int q = 0; q < 4; ++q) stamp4[q] = (uint32_t)(q + 1);
             LdsBoard<3> bd{0u};
             bd.within(bmine, bmine + pad.stride);
             const int junk0 = bmine + pad.junk;
             tron_resolve_lds<4>(bd, s, pr, stamp4, junk0);      // trail writes of all four players from every lane: identical
-            int hS = s.h[0], dS = s.d[0], kS = s.k[0];
-            hS = (p == 1) ? s.h[1] : hS; dS = (p == 1) ? s.d[1] : dS; kS = (p == 1) ? s.k[1] : kS;
-            hS = (p == 2) ? s.h[2] : hS; dS = (p == 2) ? s.d[2] : dS; kS = (p == 2) ? s.k[2] : kS;
-            hS = (p == 3) ? s.h[3] : hS; dS = (p == 3) ? s.d[3] : dS; kS = (p == 3) ? s.k[3] : kS;
+            const int hS = tron_quad_mine(p, s.h), dS = tron_quad_mine(p, s.d), kS = tron_quad_mine(p, s.k);
             h = (on && seat) ? hS : h_was;
             d = on ? dS : d_was;
             k = on ? kS : k_was;
@@ -4381,30 +4433,6 @@ tron_sample_avoid_kernel(const TronGeom g, const int64_t B, const uint32_t seed_
     if (advance && p == 0) tcount[b] = c + 1u;
 }
 
-// wave-cooperative new_state of the games whose quad / lane leader is set in `ending` (a ballot over the wave; game of
-// lane l = env0 + (l >> shift)): 16-byte stores between the board's unaligned ends (as tron_rollout_gquad_kernel)
-template <int P>
-__device__ __forceinline__ void tron_avoid_rewrite(const crl_tron_cfg &cfg, int8_t *board, const int64_t env0, const int NN,
-                                                   const int shift, const int lane, uint64_t ending)
-{
-    while (ending) {
-        const int l = (int)__builtin_ctzll(ending);
-        ending &= ending - 1;
-        uint8_t *eb = reinterpret_cast<uint8_t *>(board) + (env0 + (l >> shift)) * NN;
-        const int lead = min((int)((16u - (uint32_t)((uintptr_t)eb & 15u)) & 15u), NN);
-        const int chunks = (NN - lead) >> 4, tail0 = lead + (chunks << 4);
-        for (int c = lane; c < chunks; c += CRL_WAVE)
-            *reinterpret_cast<uint4 *>(eb + lead + (c << 4)) = tron_fresh_chunk16<P>(cfg, lead + (c << 4));
-        const int odd = lane < lead ? lane : (lane - lead < NN - tail0 ? tail0 + lane - lead : -1);   // (lead + tail < 31 bytes)
-        if (odd >= 0) {
-            int v = 0;
-#pragma unroll
-            for (int q = 0; q < P; ++q) v = (cfg.start_heads[q] == odd) ? q + 1 : v;
-            eb[odd] = (uint8_t)v;
-        }
-    }
-}
-
 // T fused steps with every player on the avoid agent: tron_rollout_gquad_kernel with the agent in place of the random
 // stream -- one lane per player on boards in GLOBAL memory (any board size, at most 4 players), the quad sharing the alive
 // count and the reset, the reference's sequential order resolved on DPP-gathered copies only in wave-steps where players
@@ -4440,17 +4468,11 @@ tron_rollout_avoid_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_
     const int h_in = heads[pb];
     const int d_in = dirs[pb];
     int k = deaths[pb];
-    const int old_ret = st.ret_sum[pb];
-    const uint32_t old_wins = st.win_count[pb];
-    uint32_t tc = st.tcount[bb], ts = st.tstep[bb];
-    const uint32_t old_n_ep = st.n_episodes[bb], old_len_sum = st.len_sum[bb];
-    const uint32_t old_last_w = st.last_winners[bb];
+    const TronLaneTotals in = tron_lane_totals_load(st, pb, bb);
+    const uint32_t tc_in = in.tc;
     k = pvalid ? k : 1;                                         // a seat without a player counts as dead for good
-    int fh = cfg.start_heads[0], fd = cfg.start_dirs[0];
-    fh = (p == 1) ? cfg.start_heads[1] : fh; fd = (p == 1) ? cfg.start_dirs[1] : fd;
-    fh = (p == 2) ? cfg.start_heads[2] : fh; fd = (p == 2) ? cfg.start_dirs[2] : fd;
-    fh = (p == 3) ? cfg.start_heads[3] : fh; fd = (p == 3) ? cfg.start_dirs[3] : fd;
-    fh = seat ? fh : 0;
+    const TronSeatStart ss = tron_seat_start(cfg, p);
+    const int fh = seat ? ss.fh : 0, fd = ss.fd;
     const int fy = (int)__umulhi((uint32_t)fh, g.inv_n), fx = fh - fy * N;
     const int fresh_a = pvalid ? 1 : 0;
     // a head that is not a cell of the board never equals a target: seats without a player carry one of their own
@@ -4458,11 +4480,8 @@ tron_rollout_avoid_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_
     int h = seat ? min(max(h_in, 0), NN - 1) : no_head;
     int hy = seat ? (int)__umulhi((uint32_t)h, g.inv_n) : 0, hx = seat ? h - hy * N : 0;
     int d = d_in & 3;
-    // alive_steps: steps after which my player was alive; wn: episodes finished (high 16 bits) and my wins (low 16);
-    // marks: (steps into the launch << 1 | my player alive) at the last two terminal steps (low / high 16 bits)
-    uint32_t alive_steps = 0, wn = 0, marks = 0;
+    uint32_t alive_steps = 0, wn = 0, marks = 0;                // wn, marks: as tron_marks_decode reads them (plain C++ here)
     const uint32_t gid = (uint32_t)(first_env_id + (uint64_t)bb);
-    const uint32_t tc_in = tc;
     int a = (k == 0) ? 1 : 0;
     for (int t = 0; t < T; ++t) {
         const bool run = a != 0;
@@ -4501,25 +4520,24 @@ tron_rollout_avoid_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_
             TronRegs<4> s;
             TronProbe<4> pr;
             const int oobi = oob ? 1 : 0;
-            s.h[0] = tron_quad<0x00>(h0); s.h[1] = tron_quad<0x55>(h0); s.h[2] = tron_quad<0xAA>(h0); s.h[3] = tron_quad<0xFF>(h0);
-            s.x[0] = tron_quad<0x00>(hx0); s.x[1] = tron_quad<0x55>(hx0); s.x[2] = tron_quad<0xAA>(hx0); s.x[3] = tron_quad<0xFF>(hx0);
-            s.y[0] = tron_quad<0x00>(hy0); s.y[1] = tron_quad<0x55>(hy0); s.y[2] = tron_quad<0xAA>(hy0); s.y[3] = tron_quad<0xFF>(hy0);
-            s.d[0] = tron_quad<0x00>(d0); s.d[1] = tron_quad<0x55>(d0); s.d[2] = tron_quad<0xAA>(d0); s.d[3] = tron_quad<0xFF>(d0);
-            s.k[0] = tron_quad<0x00>(k0); s.k[1] = tron_quad<0x55>(k0); s.k[2] = tron_quad<0xAA>(k0); s.k[3] = tron_quad<0xFF>(k0);
-            pr.tgt[0] = tron_quad<0x00>(tgt); pr.tgt[1] = tron_quad<0x55>(tgt); pr.tgt[2] = tron_quad<0xAA>(tgt); pr.tgt[3] = tron_quad<0xFF>(tgt);
-            pr.raw[0] = tron_quad<0x00>(raw); pr.raw[1] = tron_quad<0x55>(raw); pr.raw[2] = tron_quad<0xAA>(raw); pr.raw[3] = tron_quad<0xFF>(raw);
-            pr.ndir[0] = tron_quad<0x00>(dir); pr.ndir[1] = tron_quad<0x55>(dir); pr.ndir[2] = tron_quad<0xAA>(dir); pr.ndir[3] = tron_quad<0xFF>(dir);
-            pr.nx[0] = tron_quad<0x00>(nx); pr.nx[1] = tron_quad<0x55>(nx); pr.nx[2] = tron_quad<0xAA>(nx); pr.nx[3] = tron_quad<0xFF>(nx);
-            pr.ny[0] = tron_quad<0x00>(ny); pr.ny[1] = tron_quad<0x55>(ny); pr.ny[2] = tron_quad<0xAA>(ny); pr.ny[3] = tron_quad<0xFF>(ny);
-            const int o0 = tron_quad<0x00>(oobi), o1 = tron_quad<0x55>(oobi), o2 = tron_quad<0xAA>(oobi), o3 = tron_quad<0xFF>(oobi);
-            pr.oob[0] = o0 != 0; pr.oob[1] = o1 != 0; pr.oob[2] = o2 != 0; pr.oob[3] = o3 != 0;
+            tron_quad_all(h0, s.h);
+            tron_quad_all(hx0, s.x);
+            tron_quad_all(hy0, s.y);
+            tron_quad_all(d0, s.d);
+            tron_quad_all(k0, s.k);
+            tron_quad_all(tgt, pr.tgt);
+            tron_quad_all(raw, pr.raw);
+            tron_quad_all(dir, pr.ndir);
+            tron_quad_all(nx, pr.nx);
+            tron_quad_all(ny, pr.ny);
+            int o4[4]; tron_quad_all(oobi, o4);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) pr.oob[q] = o4[q] != 0;
             int rew4[4], term4, wm4;
             const PlainBoard nowhere{nullptr CRL_CELLS_INIT(NN)};
             tron_resolve<4>(nowhere, false, s, pr, rew4, term4, wm4);   // valid = false: no stores here (below, with everybody's)
-            int hS = s.h[0], xS = s.x[0], yS = s.y[0], dS = s.d[0], kS = s.k[0];
-            hS = (p == 1) ? s.h[1] : hS; xS = (p == 1) ? s.x[1] : xS; yS = (p == 1) ? s.y[1] : yS; dS = (p == 1) ? s.d[1] : dS; kS = (p == 1) ? s.k[1] : kS;
-            hS = (p == 2) ? s.h[2] : hS; xS = (p == 2) ? s.x[2] : xS; yS = (p == 2) ? s.y[2] : yS; dS = (p == 2) ? s.d[2] : dS; kS = (p == 2) ? s.k[2] : kS;
-            hS = (p == 3) ? s.h[3] : hS; xS = (p == 3) ? s.x[3] : xS; yS = (p == 3) ? s.y[3] : yS; dS = (p == 3) ? s.d[3] : dS; kS = (p == 3) ? s.k[3] : kS;
+            const int hS = tron_quad_mine(p, s.h), xS = tron_quad_mine(p, s.x), yS = tron_quad_mine(p, s.y);
+            const int dS = tron_quad_mine(p, s.d), kS = tron_quad_mine(p, s.k);
             moved = hS != h0;                                   // (a head is never its owner's own target)
             h = hS; hx = xS; hy = yS; d = dS;
             k = kS;                                             // (also a dead player's entry, overwritten by a head-on killer: :56-57)
@@ -4543,46 +4561,41 @@ tron_rollout_avoid_kernel(const crl_tron_cfg cfg, const TronGeom g, const int64_
             a = fresh_a;
         }
         // new_state for the games of this wave that ended: the whole wave writes each one's start board
-        tron_avoid_rewrite<P>(cfg, board, env0, NN, 2, lane, __builtin_amdgcn_ballot_w64(over && gvalid && p == 0));
+        tron_wave_rewrite<P>(cfg, board, env0, NN, 2, lane, __builtin_amdgcn_ballot_w64(over && gvalid && p == 0));
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // this step's stores before the next step's probes
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     // ---- per-player state and statistics (my columns), per-game statistics (lane 0 of the quad); as tron_rollout_gquad_kernel
-    const uint32_t n_ep = wn >> 16, wins = wn & 0xffffu;
-    const int done_last = (int)((marks & 0xffffu) >> 1), done_prev = (int)(marks >> 17), last_alive = (int)(marks & 1u);
-    tc = tc_in + (uint32_t)T;
-    const uint32_t ts_at_entry = ts;
-    ts = n_ep ? (uint32_t)(T - done_last) : ts_at_entry + (uint32_t)T;
-    const int last_len = (n_ep > 1u) ? done_last - done_prev : (int)ts_at_entry + done_last;
-    int lw = (last_alive & 1) << p;
+    const TronMarks fin = tron_marks_decode(wn, marks, tc_in, in.ts, T);
+    int lw = (fin.last_alive & 1) << p;
     lw |= tron_quad<0xB1>(lw);
     lw |= tron_quad<0x4E>(lw);
-    const int ret = 2 * (int)alive_steps - T + 9 * (int)wins;   // alive +1, dead -1, alive at a terminal step +10
+    const int ret = 2 * (int)alive_steps - T + 9 * (int)fin.wins;   // alive +1, dead -1, alive at a terminal step +10
     int32_t *row = st.results ? st.results + b * (3 + 2 * P) : nullptr;
-    uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow<P> : nullptr;
+    uint16_t *pk = st.packed ? st.packed + b * kTronPackedRow(P) : nullptr;
     if (pvalid) {
         heads[p * B + b] = (int16_t)h;
         dirs[p * B + b] = (int8_t)d;
         deaths[p * B + b] = (int8_t)k;
-        const int rs = old_ret + ret;
-        const uint32_t wc = old_wins + wins;
+        const int rs = in.ret + ret;
+        const uint32_t wc = in.wins + fin.wins;
         st.ret_sum[p * B + b] = rs;
         st.win_count[p * B + b] = wc;
         if (row) { row[3 + p] = (int32_t)wc; row[3 + P + p] = rs; }
         if (pk) pk[4 + p] = (uint16_t)rs;
     }
     if (gvalid && p == 0) {
-        const uint32_t ne = old_n_ep + n_ep, ls = old_len_sum + (ts_at_entry + (uint32_t)T - ts);
-        st.tcount[b] = tc;
-        st.tstep[b] = ts;
+        const uint32_t ne = in.n_ep + fin.n_ep, ls = in.len_sum + (fin.ts_at_entry + (uint32_t)T - fin.ts);
+        st.tcount[b] = fin.tc;
+        st.tstep[b] = fin.ts;
         st.n_episodes[b] = ne;
         st.len_sum[b] = ls;
-        if (n_ep > 0) {
+        if (fin.n_ep > 0) {
             st.last_winners[b] = (uint8_t)lw;
-            st.last_len[b] = (uint16_t)last_len;
+            st.last_len[b] = (uint16_t)fin.last_len;
         }
-        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = n_ep > 0 ? lw : (int32_t)old_last_w; }
-        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(n_ep > 0 ? (uint32_t)lw : old_last_w); pk[3] = (uint16_t)ts; }
+        if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = fin.n_ep > 0 ? lw : (int32_t)in.last_w; }
+        if (pk) { pk[0] = (uint16_t)ne; pk[1] = (uint16_t)ls; pk[2] = (uint16_t)(fin.n_ep > 0 ? (uint32_t)lw : in.last_w); pk[3] = (uint16_t)fin.ts; }
     }
 }
 
@@ -4655,7 +4668,7 @@ tron_rollout_avoid_game_kernel(const crl_tron_cfg cfg, const TronGeom g, const i
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the trails before the rewrite of a board that ended
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        tron_avoid_rewrite<P>(cfg, board, env0, NN, 0, lane, __builtin_amdgcn_ballot_w64(ends));
+        tron_wave_rewrite<P>(cfg, board, env0, NN, 0, lane, __builtin_amdgcn_ballot_w64(ends));
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // this step's stores before the next step's probes
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
@@ -4963,6 +4976,10 @@ tron_playout_kernel(const TronGeom g, const int64_t B, const uint32_t seed_lo, c
         default: crl_set_error("tron: P=%d out of range 1..4", P_); return CRL_EINVAL; \
     }
 
+#define TRON_STATS_CHECK(fn)                                                                            \
+    CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.len_sum && st.ret_sum &&  \
+                st.last_winners && st.last_len, fn ": NULL stats pointer")
+
 int crl_tron_bounds(unsigned int *out4)
 {
     CRL_BOUNDS_READBACK(out4);
@@ -4981,6 +4998,9 @@ static int tron_opt_in_lds()
     if (dev >= 0 && dev < 64) opted_in[dev] = true;
     return CRL_OK;
 }
+
+template <auto Kernel> struct TronKernel { static constexpr auto kernel = Kernel; };   // a kernel instance as a value: named once, opted in and launched
+template <int V> using TronInt = std::integral_constant<int, V>;                 // ... and a template argument as one
 
 // ---- crl_tron_rollout: which of its seven kernels plays a call ---------------------------------------------------------
 enum class TronRollout { Global, Bytes, Bits, Quad, QBits, GQuad, Pair };
@@ -5141,8 +5161,7 @@ static int tron_rollout_impl(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
     };
     TRON_CTX_CHECK("crl_tron_rollout");
     CRL_REQUIRE(board && heads && dirs && deaths, "crl_tron_rollout: NULL state pointer");
-    CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.len_sum && st.ret_sum &&
-                st.last_winners && st.last_len, "crl_tron_rollout: NULL stats pointer");
+    TRON_STATS_CHECK("crl_tron_rollout");
     CRL_REQUIRE(T >= 0 && T <= (1 << 24), "crl_tron_rollout: T=%d out of range", T);
     CRL_REQUIRE((flags & ~(CRL_ROLLOUT_NO_LDS | CRL_ROLLOUT_BYTES | CRL_ROLLOUT_BITS | CRL_ROLLOUT_QUAD | CRL_ROLLOUT_QBITS | CRL_ROLLOUT_GQUAD | CRL_ROLLOUT_PAIR)) == 0, "crl_tron_rollout: unknown flags 0x%x", flags);
     const crl_tron_cfg &cfg = ctx->tron;
@@ -5184,17 +5203,14 @@ static int tron_rollout_impl(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
             break;
         case TronRollout::QBits:                                // + the replay as a kernel of its own
             TRON_DISPATCH_P4(cfg.P, {
-                if (small) {
-                    launch(tron_rollout_qbits_kernel<PP, false>, dim3(blocks_for(B, 64)), dim3(256), lds_q, false, cfg, g, pad, qb, B,
+                auto both = [&](auto large) {
+                    constexpr bool LARGE = decltype(large)::value;
+                    launch(tron_rollout_qbits_kernel<PP, LARGE>, dim3(blocks_for(B, 64)), dim3(256), lds_q, false, cfg, g, pad, qb, B,
                            seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
-                    launch(tron_replay_kernel<PP, false>, dim3(blocks_for(B, 16)), dim3(64), (size_t)16 * pad.stride, last, cfg, g, pad, B,
+                    launch(tron_replay_kernel<PP, LARGE>, dim3(blocks_for(B, 16)), dim3(64), (size_t)16 * pad.stride, last, cfg, g, pad, B,
                            seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
-                } else {
-                    launch(tron_rollout_qbits_kernel<PP, true>, dim3(blocks_for(B, 64)), dim3(256), lds_q, false, cfg, g, pad, qb, B,
-                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
-                    launch(tron_replay_kernel<PP, true>, dim3(blocks_for(B, 16)), dim3(64), (size_t)16 * pad.stride, last, cfg, g, pad, B,
-                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
-                }
+                };
+                if (small) both(std::false_type{}); else both(std::true_type{});
             });
             break;
         case TronRollout::Pair:
@@ -5213,24 +5229,19 @@ static int tron_rollout_impl(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
             const size_t lds_bytes = use_bits ? std::max(byte_slabs, (size_t)256 * bits.stride) : byte_slabs;
             CRL_REQUIRE(lds_bytes <= (size_t)kLdsDynamic, "crl_tron_rollout: internal: %zu bytes of LDS", lds_bytes);
             const dim3 grid(blocks_for(B, threads)), block(threads);
+            // opt in to the LDS, then launch: `mid` is what the kernel takes between pad and B (the bitboard geometry, or nothing)
+            auto go = [&](auto k, auto... mid) -> int {
+                if (const int rc = tron_opt_in_lds<decltype(k)::kernel>()) return rc;
+                launch(decltype(k)::kernel, grid, block, lds_bytes, last, cfg, g, pad, mid..., B,
+                       seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
+                return CRL_OK;
+            };
             TRON_DISPATCH_P(cfg.P, {
-                if (use_bits && small) {
-                    if (const int rc = tron_opt_in_lds<tron_rollout_bits_kernel<PP, false>>()) return rc;
-                    launch(tron_rollout_bits_kernel<PP, false>, grid, block, lds_bytes, last, cfg, g, pad, bits, B,
-                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
-                } else if (use_bits) {
-                    if (const int rc = tron_opt_in_lds<tron_rollout_bits_kernel<PP, true>>()) return rc;
-                    launch(tron_rollout_bits_kernel<PP, true>, grid, block, lds_bytes, last, cfg, g, pad, bits, B,
-                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
-                } else if (small) {
-                    if (const int rc = tron_opt_in_lds<tron_rollout_lds_kernel<PP, kRowBytesSmall>>()) return rc;
-                    launch(tron_rollout_lds_kernel<PP, kRowBytesSmall>, grid, block, lds_bytes, last, cfg, g, pad, B,
-                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
-                } else {
-                    if (const int rc = tron_opt_in_lds<tron_rollout_lds_kernel<PP, kRowBytesLarge>>()) return rc;
-                    launch(tron_rollout_lds_kernel<PP, kRowBytesLarge>, grid, block, lds_bytes, last, cfg, g, pad, B,
-                           seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
-                }
+                const int rc = (use_bits && small) ? go(TronKernel<tron_rollout_bits_kernel<PP, false>>{}, bits)
+                               : use_bits          ? go(TronKernel<tron_rollout_bits_kernel<PP, true>>{}, bits)
+                               : small             ? go(TronKernel<tron_rollout_lds_kernel<PP, kRowBytesSmall>>{})
+                                                   : go(TronKernel<tron_rollout_lds_kernel<PP, kRowBytesLarge>>{});
+                if (rc) return rc;
             });
             break;
         }
@@ -5321,8 +5332,7 @@ int crl_tron_rollout_avoid(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_
 {
     TRON_CTX_CHECK("crl_tron_rollout_avoid");
     CRL_REQUIRE(board && heads && dirs && deaths, "crl_tron_rollout_avoid: NULL state pointer");
-    CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.len_sum && st.ret_sum &&
-                st.last_winners && st.last_len, "crl_tron_rollout_avoid: NULL stats pointer");
+    TRON_STATS_CHECK("crl_tron_rollout_avoid");
     CRL_REQUIRE(T >= 0 && T <= (1 << 24), "crl_tron_rollout_avoid: T=%d out of range", T);
     CRL_REQUIRE(noise >= 0.0 && noise <= 1.0, "crl_tron_rollout_avoid: noise=%g not in [0, 1]", noise);
     CRL_REQUIRE(flags == 0u, "crl_tron_rollout_avoid: unknown flags 0x%x", flags);
@@ -5501,22 +5511,14 @@ int crl_tron_step_observe(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t
         const size_t lds_bytes = (size_t)G * slab + G;
         const dim3 grid(blocks_for(B, G));
         const uint32_t kflags = flags | (crl_stream_nt((int64_t)(cfg.P + 1) * NN * B, false) ? kStepObserveNT : 0u);
-        switch (cfg.P) {
-#define CRL_SO_CASE(P_)                                                                                                   \
-        case P_:                                                                                                          \
-            if (G == 64)                                                                                                  \
-                hipLaunchKernelGGL((tron_step_observe_kernel<P_, 64>), grid, dim3(256), lds_bytes, s, cfg, g, inv_cp, B,   \
-                                   (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, board, heads, dirs, deaths,     \
-                                   actions, tcount, rewards, terminal, winners, obs_board, obs_heads, obs_dirs, obs_deaths, kflags); \
-            else                                                                                                          \
-                hipLaunchKernelGGL((tron_step_observe_kernel<P_, 16>), grid, dim3(256), lds_bytes, s, cfg, g, inv_cp, B,   \
-                                   (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, board, heads, dirs, deaths,     \
-                                   actions, tcount, rewards, terminal, winners, obs_board, obs_heads, obs_dirs, obs_deaths, kflags); \
-            break;
-            CRL_SO_CASE(1) CRL_SO_CASE(2) CRL_SO_CASE(3) CRL_SO_CASE(4) CRL_SO_CASE(5) CRL_SO_CASE(6) CRL_SO_CASE(7) CRL_SO_CASE(8)
-#undef CRL_SO_CASE
-            default: crl_set_error("tron: P=%d out of range", cfg.P); return CRL_EINVAL;
-        }
+        auto fused = [&](auto pp, auto gg) {
+            hipLaunchKernelGGL((tron_step_observe_kernel<decltype(pp)::value, decltype(gg)::value>), grid, dim3(256), lds_bytes, s,
+                               cfg, g, inv_cp, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, board, heads, dirs, deaths,
+                               actions, tcount, rewards, terminal, winners, obs_board, obs_heads, obs_dirs, obs_deaths, kflags);
+        };
+        TRON_DISPATCH_P(cfg.P, {
+            if (G == 64) fused(TronInt<PP>{}, TronInt<64>{}); else fused(TronInt<PP>{}, TronInt<16>{});
+        });
         CRL_LAUNCH_CHECK();
         return CRL_OK;
     }
@@ -5530,21 +5532,16 @@ int crl_tron_step_observe(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t
             const size_t lds_bytes = (size_t)((Gf * NN + 15) & ~15) + Gf + 16;
             const dim3 grid(blocks_for(B, Gf));
             const uint32_t kflags = flags | (crl_stream_nt((int64_t)(cfg.P + 1) * NN * B, false) ? kStepObserveNT : 0u);
-            switch (cfg.P) {
-#define CRL_SOF_LAUNCH(P_, G_, R_)                                                                                        \
-                    hipLaunchKernelGGL((tron_step_observe_flat_kernel<P_, G_, R_>), grid, dim3(256), lds_bytes, s, cfg, g, inv_nn, B, \
-                                       (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, board, heads, dirs, deaths,   \
-                                       actions, tcount, rewards, terminal, winners, obs_board, obs_heads, obs_dirs, obs_deaths, kflags)
-#define CRL_SOF_CASE(P_)                                                                                                   \
-            case P_:                                                                                                      \
-                if (Gf == 64) { if (ragged) CRL_SOF_LAUNCH(P_, 64, true); else CRL_SOF_LAUNCH(P_, 64, false); }           \
-                else { if (ragged) CRL_SOF_LAUNCH(P_, 16, true); else CRL_SOF_LAUNCH(P_, 16, false); }                    \
-                break;
-                CRL_SOF_CASE(1) CRL_SOF_CASE(2) CRL_SOF_CASE(3) CRL_SOF_CASE(4) CRL_SOF_CASE(5) CRL_SOF_CASE(6) CRL_SOF_CASE(7) CRL_SOF_CASE(8)
-#undef CRL_SOF_CASE
-#undef CRL_SOF_LAUNCH
-                default: crl_set_error("tron: P=%d out of range", cfg.P); return CRL_EINVAL;
-            }
+            auto flat = [&](auto pp, auto gg, auto rr) {
+                hipLaunchKernelGGL((tron_step_observe_flat_kernel<decltype(pp)::value, decltype(gg)::value, decltype(rr)::value>),
+                                   grid, dim3(256), lds_bytes, s, cfg, g, inv_nn, B,
+                                   (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, board, heads, dirs, deaths,
+                                   actions, tcount, rewards, terminal, winners, obs_board, obs_heads, obs_dirs, obs_deaths, kflags);
+            };
+            TRON_DISPATCH_P(cfg.P, {
+                if (Gf == 64) { if (ragged) flat(TronInt<PP>{}, TronInt<64>{}, std::true_type{}); else flat(TronInt<PP>{}, TronInt<64>{}, std::false_type{}); }
+                else { if (ragged) flat(TronInt<PP>{}, TronInt<16>{}, std::true_type{}); else flat(TronInt<PP>{}, TronInt<16>{}, std::false_type{}); }
+            });
             CRL_LAUNCH_CHECK();
             return CRL_OK;
         }

@@ -359,6 +359,55 @@ def test_rollout_with_step_counters_that_differ_inside_a_wave(N, P, B, kernel):
         assert np.array_equal(getattr(hip.tb, k).cpu().numpy().view(want.dtype), want), k
 
 
+LANE_PER_PLAYER_SEED, LANE_PER_PLAYER_FIRST = 0x5EED0F5EA75, 4242
+
+
+@pytest.mark.parametrize("N,P,B,chunks,kernels", [(8, 3, 64 * 2 + 5, (1, 33, 2), ("quad", "qbits", "gquad")),
+                                                  (8, 2, 64 * 2 + 5, (1, 33, 2), ("quad", "qbits", "gquad", "pair")),
+                                                  (5, 4, 70, (20,), ("quad", "qbits", "gquad"))])
+def test_lane_per_player_kernels_agree(N, P, B, chunks, kernels):
+    """The lane-per-player kernels share their bookkeeping (totals in, start layout, the decode of a launch's counts, the
+    epilogue that writes the columns and both result rows): on ONE input every one of them must leave the same state, the
+    same statistics and the same rows as the others and as the oracle.  8x8 with three (two) players: an empty seat (two)
+    per quad, a ragged last workgroup, a one-step launch, a launch that crosses a 32-step refill of the actions, boards of
+    whole 16-byte chunks; 5x5: boards whose ends are not 16-byte aligned in the wave-cooperative rewrite.  Most games are
+    reset several times, so the rows carry this launch's winners; a one-step launch resets none and carries the incoming ones."""
+    import torch
+    COLS = ("board", "heads", "dirs", "deaths", "tcount", "tstep", "n_episodes", "win_count", "len_sum", "ret_sum",
+            "last_winners", "last_len")
+    i64 = lambda a: np.asarray(a).astype(np.int64)
+    sh, sd = O.tron_start_positions(N, P)
+    # the oracle's side once: columns and both rows (assembled from ITS columns) after every launch
+    ost = O.TronState(N, P, B)
+    O.tron_reset(ost, sh, sd)
+    want = []
+    for T in chunks:
+        O.tron_rollout(ost, LANE_PER_PLAYER_SEED, LANE_PER_PLAYER_FIRST, T, sh, sd, n_threads=1)
+        game = [i64(ost.n_episodes)[:, None], i64(ost.len_sum)[:, None], i64(ost.last_winners)[:, None]]
+        row = np.concatenate(game + [i64(ost.win_count).T, i64(ost.ret_sum).T], axis=1)
+        pk = np.concatenate(game + [i64(ost.tstep)[:, None], i64(ost.ret_sum).T], axis=1) & 0xffff
+        want.append(({k: getattr(ost, k).copy() for k in COLS}, row, pk))
+    assert ost.n_episodes.sum() > B                      # the n_ep > 0 branches of the epilogue run
+    rows, packed = [], []
+    for kernel in kernels:
+        hip = HipTron(N, P, B, sh, sd)
+        hip.tb.first_env_id = LANE_PER_PLAYER_FIRST
+        for T, (cols, row, pk) in zip(chunks, want):
+            hip.tb.rollout(T, LANE_PER_PLAYER_SEED, kernel=kernel)
+            for k in COLS:
+                assert np.array_equal(getattr(hip.tb, k).cpu().numpy().view(cols[k].dtype), cols[k]), (kernel, T, k)
+            assert np.array_equal(i64(hip.tb.results().cpu().numpy()), row), (kernel, T)
+            got_pk = i64(hip.tb.results_packed().cpu().numpy()) & 0xffff
+            assert np.array_equal(got_pk[:, :4 + P], pk) and not got_pk[:, 4 + P:].any(), (kernel, T)
+            assert torch.equal(hip.tb.results(), hip.tb.results_from_columns())
+            assert torch.equal(hip.tb.results_packed(), hip.tb.results_packed_from_columns())
+        assert hip.tb.packed_rows_exact()
+        rows.append(hip.tb.results())
+        packed.append(hip.tb.results_packed())
+    for r, pk in zip(rows[1:], packed[1:]):
+        assert torch.equal(r, rows[0]) and torch.equal(pk, packed[0])
+
+
 @pytest.mark.parametrize("N,T", [(20, 128), (40, 128), (40, 300)])
 def test_rollout_full_size_properties(N, T):
     """BASELINE config 2 (N=20, LDS byte slabs, a lane per player) and config 5 per-GPU shard (N=40: bitboards + replay,

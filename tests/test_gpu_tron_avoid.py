@@ -94,6 +94,8 @@ def _check_rollout_against_loops(N, P, B, T, seed, noise, first_env_id=0, host=T
         assert np.array_equal(a, b)
     assert np.array_equal(fused.tcount.cpu().numpy(), loop.tcount.cpu().numpy())
     assert torch.equal(fused.results(), fused.results_from_columns())
+    assert torch.equal(fused.results_packed(), fused.results_packed_from_columns())   # the 16-bit row the kernel packs, too
+    assert fused.packed_rows_exact()
     if not host:
         return fused
     ref = avoid_ref.HostLoop(N, P, B, fused.start_heads, fused.start_dirs)

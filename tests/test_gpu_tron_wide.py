@@ -82,6 +82,8 @@ def test_rollout_avoid_across_the_launch_split(P):
     assert np.array_equal(fused.tcount.cpu().numpy(), loop.tcount.cpu().numpy())
     assert (fused.tcount == T).all()
     assert torch.equal(fused.results(), fused.results_from_columns())
+    assert torch.equal(fused.results_packed(), fused.results_packed_from_columns())   # (the low 16 bits of totals that wrapped)
+    assert not fused.packed_rows_exact()
     # the statistics of the recorded loop: an episode ends at every terminal step
     rews, terms, wins = rews.cpu().numpy().astype(np.int64), terms.cpu().numpy() != 0, wins.cpu().numpy()
     steps = np.arange(1, T + 1)[:, None]

@@ -2146,18 +2146,15 @@ int crl_blokus_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t fi
     // (the pointer and argument checks come before the context's: they need no device)
     CRL_REQUIRE(occ && inv && score && round && to_move, "crl_blokus_playout: NULL state pointer");
     CRL_REQUIRE(wins && played && len_sum && score_sum, "crl_blokus_playout: NULL output pointer");
-    CRL_REQUIRE(R >= 1 && R <= 65535, "crl_blokus_playout: R=%d out of range 1..65535", R);
-    CRL_REQUIRE(A >= 1 && A <= 65535, "crl_blokus_playout: A=%d out of range 1..65535", A);
-    CRL_REQUIRE(cand != nullptr || A == 1, "crl_blokus_playout: A=%d with cand == NULL (must be 1)", A);
+    CRL_PLAYOUT_SHAPE_CHECK("crl_blokus_playout");
     CRL_REQUIRE(flags == 0, "crl_blokus_playout: unknown flags 0x%x", flags);
     BLK_CTX_CHECK("crl_blokus_playout");
-    const uint64_t rows = (uint64_t)B * (uint64_t)A, n_playouts = rows * (uint64_t)R;
+    const auto [rows, n_playouts] = crl_playout_shape_of(B, A, R);
     CRL_HIP(hipMemsetAsync(wins, 0, rows * 4 * sizeof(uint32_t), (hipStream_t)stream));   // the rows are sums of atomics
     CRL_HIP(hipMemsetAsync(played, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
     CRL_HIP(hipMemsetAsync(len_sum, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
     CRL_HIP(hipMemsetAsync(score_sum, 0, rows * 4 * sizeof(int32_t), (hipStream_t)stream));
-    const uint64_t want = (n_playouts + 3u) / 4u;           // a grid-stride loop past 2^20 workgroups
-    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));
+    const unsigned blocks = crl_playout_blocks(n_playouts, 4u);   // (a playout per wave)
     hipLaunchKernelGGL(blokus_playout_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        (const BlkTables *)ctx->blokus, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
                        occ, inv, score, round, to_move, tcount, cand, A, R, n_playouts, wins, played, len_sum, score_sum);

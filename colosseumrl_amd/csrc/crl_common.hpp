@@ -78,12 +78,33 @@ void crl_set_error(const char *fmt, ...);
     CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_TRON, fn ": ctx is not a tron context"); \
     CRL_REQUIRE(B > 0 && B <= ((int64_t)1 << 31), fn ": B=%lld out of range", (long long)B)
 
-// the avoid agent's noise threshold (also the territory agent's): W[0] < thr is "noisy", thr = min(2^32, ceil(noise * 2^32))
-// in 64 bits
-static inline uint64_t tron_avoid_threshold(const double noise)
+// the noise threshold of a scripted agent (Tron's avoid and territory agents, TicTacToe's tactical one): a 32-bit draw
+// below thr is "noisy", thr = min(2^32, ceil(noise * 2^32)) in 64 bits
+static inline uint64_t crl_noise_threshold(const double noise)
 {
     const double x = ceil(noise * 4294967296.0);
     return x >= 4294967296.0 ? ((uint64_t)1 << 32) : (uint64_t)x;
+}
+
+// ---------------------------------------------------------------- shared by the playout entries (crl_ttt_playout[_tactical],
+// crl_blokus_playout, crl_tron_playout): B positions x A candidates are the rows, R playouts each the lanes
+#define CRL_PLAYOUT_SHAPE_CHECK(fn)                                                             \
+    CRL_REQUIRE(R >= 1 && R <= 65535, "%s: R=%d out of range 1..65535", fn, R);                 \
+    CRL_REQUIRE(A >= 1 && A <= 65535, "%s: A=%d out of range 1..65535", fn, A);                 \
+    CRL_REQUIRE(cand != nullptr || A == 1, "%s: A=%d with cand == NULL (must be 1)", fn, A)
+
+struct crl_playout_shape { uint64_t rows, n_lanes; };
+static inline crl_playout_shape crl_playout_shape_of(const int64_t B, const int A, const int R)
+{
+    const uint64_t rows = (uint64_t)B * (uint64_t)A;
+    return {rows, rows * (uint64_t)R};
+}
+
+// workgroups for n_lanes playouts, per_block to a workgroup: a grid-stride loop past 2^20 workgroups
+static inline unsigned crl_playout_blocks(const uint64_t n_lanes, const uint64_t per_block)
+{
+    const uint64_t want = (n_lanes + per_block - 1) / per_block;
+    return (unsigned)(want < (1u << 20) ? want : (1u << 20));
 }
 
 // ---------------------------------------------------------------- bounds asserts (diagnostic build: -DCRL_BOUNDS)

@@ -5315,7 +5315,7 @@ int crl_tron_sample_avoid(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t
     const crl_tron_cfg &cfg = ctx->tron;
     CRL_REQUIRE((player_mask >> cfg.P) == 0u, "crl_tron_sample_avoid: player_mask 0x%x names players beyond P=%d", player_mask, cfg.P);
     const TronGeom g = geom_of(cfg);
-    const uint64_t thr = tron_avoid_threshold(noise);
+    const uint64_t thr = crl_noise_threshold(noise);
     const int lanes = cfg.P <= 1 ? 1 : cfg.P <= 2 ? 2 : cfg.P <= 4 ? 4 : 8;     // per game (tron_sample_avoid_kernel)
     TRON_DISPATCH_P(cfg.P, {
         hipLaunchKernelGGL((tron_sample_avoid_kernel<PP>), dim3(blocks_for(B * lanes, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -5339,7 +5339,7 @@ int crl_tron_rollout_avoid(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_
     const crl_tron_cfg &cfg = ctx->tron;
     if (T == 0) return CRL_OK;
     const TronGeom g = geom_of(cfg);
-    const uint64_t thr = tron_avoid_threshold(noise);
+    const uint64_t thr = crl_noise_threshold(noise);
     hipStream_t s = (hipStream_t)stream;
     for (int t0 = 0; t0 < T; t0 += kTronLaunchMaxT) {
         const int Tl = std::min(kTronLaunchMaxT, T - t0);
@@ -5386,30 +5386,26 @@ int crl_tron_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t firs
     TRON_CTX_CHECK("crl_tron_playout");
     CRL_REQUIRE(board && heads && dirs && deaths, "crl_tron_playout: NULL state pointer");
     CRL_REQUIRE(wins && played && len_sum && ret_sum, "crl_tron_playout: NULL output pointer");
-    CRL_REQUIRE(R >= 1 && R <= 65535, "crl_tron_playout: R=%d out of range 1..65535", R);
-    CRL_REQUIRE(A >= 1 && A <= 65535, "crl_tron_playout: A=%d out of range 1..65535", A);
-    CRL_REQUIRE(cand != nullptr || A == 1, "crl_tron_playout: A=%d with cand == NULL (must be 1)", A);
+    CRL_PLAYOUT_SHAPE_CHECK("crl_tron_playout");
     CRL_REQUIRE(noise >= 0.0 && noise <= 1.0, "crl_tron_playout: noise=%g not in [0, 1]", noise);
     CRL_REQUIRE(max_steps >= 0 && max_steps <= 65535, "crl_tron_playout: max_steps=%d out of range 0..65535", max_steps);
     CRL_REQUIRE((flags & ~(CRL_PLAYOUT_AVOID | CRL_PLAYOUT_UNTIL_SEAT_DONE)) == 0u, "crl_tron_playout: unknown flags 0x%x", flags);
     const crl_tron_cfg &cfg = ctx->tron;
     const TronGeom g = geom_of(cfg);
-    const uint64_t thr = tron_avoid_threshold(noise);
+    const uint64_t thr = crl_noise_threshold(noise);
     const int nwords = (g.NN + 31) >> 5;
     // lanes per wave and waves per workgroup: every lane's bitboard in LDS, at most 128 KB per workgroup (N <= 181)
     const int S = nwords <= 512 ? 64 : 32;
     const int threads = nwords <= 64 ? 256 : 64;
     const size_t lds = (size_t)(threads / 64) * S * nwords * sizeof(uint32_t);
-    const uint64_t rows = (uint64_t)B * (uint64_t)A, n_lanes = rows * (uint64_t)R;
+    const auto [rows, n_lanes] = crl_playout_shape_of(B, A, R);
     hipStream_t s = (hipStream_t)stream;
     // rows that span waves are summed by atomics: every output starts from zero
     CRL_HIP(hipMemsetAsync(wins, 0, rows * cfg.P * sizeof(uint32_t), s));
     CRL_HIP(hipMemsetAsync(played, 0, rows * sizeof(uint32_t), s));
     CRL_HIP(hipMemsetAsync(len_sum, 0, rows * sizeof(uint32_t), s));
     CRL_HIP(hipMemsetAsync(ret_sum, 0, rows * sizeof(int32_t), s));
-    const uint64_t per_block = (uint64_t)(threads / 64) * S;
-    const uint64_t want = (n_lanes + per_block - 1) / per_block;   // a grid-stride loop past 2^20 workgroups
-    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));
+    const unsigned blocks = crl_playout_blocks(n_lanes, (uint64_t)(threads / 64) * S);
     const int until = (flags & CRL_PLAYOUT_UNTIL_SEAT_DONE) ? 1 : 0;
 #define TRON_PLAYOUT_LAUNCH(AV_)                                                                                          \
     do {                                                                                                                  \

@@ -550,7 +550,7 @@ int crl_tron_sample_territory(const crl_ctx *ctx, int64_t B, uint64_t seed, uint
     const crl_tron_cfg &cfg = ctx->tron;
     CRL_REQUIRE((player_mask >> cfg.P) == 0u, "crl_tron_sample_territory: player_mask 0x%x names players beyond P=%d", player_mask, cfg.P);
     const TerrState s = terr_state(cfg, B, board, heads, dirs, deaths);
-    const uint64_t thr = tron_avoid_threshold(noise);
+    const uint64_t thr = crl_noise_threshold(noise);
     hipStream_t st = (hipStream_t)stream;
     if (cfg.N <= 64) {
         const uint64_t want = ((uint64_t)B + 3u) / 4u;

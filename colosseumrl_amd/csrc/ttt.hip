@@ -1361,12 +1361,125 @@ inline uint32_t ttt_inv_cells(const int cells) { return cells == 1 ? 0u : (uint3
 #define TTT_LAUNCH(kernel, blocks, ...) hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__)
 
 #define TTT_CTX_CHECK(fn)                                                                  \
-    CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_TTT, fn ": ctx is not a tictactoe context"); \
-    CRL_REQUIRE(B > 0 && B <= ((int64_t)1 << 31), fn ": B=%lld out of range", (long long)B)
+    CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_TTT, "%s: ctx is not a tictactoe context", fn); \
+    CRL_REQUIRE(B > 0 && B <= ((int64_t)1 << 31), "%s: B=%lld out of range", fn, (long long)B)
+// (a launcher that serves an agent's entry as well gets its noise by pointer, NULL from the random agent's entry, and
+// checks it where the tactical entry always did)
+#define TTT_NOISE_CHECK(fn) CRL_REQUIRE(noise == nullptr || (*noise >= 0.0 && *noise <= 1.0), "%s: noise=%g outside [0, 1]", fn, *noise)   /* (NaN fails too) */
 
 int crl_ttt_bounds(unsigned int *out4)
 {
     CRL_BOUNDS_READBACK(out4);
+    return CRL_OK;
+}
+
+// ---- one launcher per pair of entries (random agent / tactical agent): `fn` names the entry in the messages, `noise` is
+// NULL for the random agent's
+static int ttt_sample_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
+                             const int8_t *to_move, uint32_t *tcount, int advance, const double *noise, int8_t *action, void *stream)
+{
+    TTT_CTX_CHECK(fn);
+    CRL_REQUIRE(occ && (to_move || !noise) && tcount && action, "%s: NULL pointer", fn);
+    TTT_NOISE_CHECK(fn);
+    const ttt_dirs dd = dirs_of(ctx);
+    if (noise) {
+        TTT_DISPATCH_ND(ctx, TTT_LAUNCH((ttt_sample_tactical_kernel<PP, NDD>), blocks_for(B, 256), dd, B, (uint32_t)seed,
+                                        (uint32_t)(seed >> 32), first_env_id, crl_noise_threshold(*noise), occ, to_move, tcount,
+                                        advance, action));
+    } else {
+        TTT_LAUNCH(ttt_sample_kernel, blocks_for(B, 256), ctx->ttt.P, dd.full, B,
+                   (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, tcount, advance, action);
+    }
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+static int ttt_step_single_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *occ,
+                                  int8_t *winner, int8_t *to_move, const int8_t *seat, const int64_t *learner_action,
+                                  uint32_t *tcount, int8_t *reward, uint8_t *done, int8_t *winners, int8_t *obs_board,
+                                  uint32_t *valid, int rel_mod, const double *noise, uint32_t flags, void *stream)
+{
+    TTT_CTX_CHECK(fn);
+    CRL_REQUIRE(occ && winner && to_move, "%s: NULL state pointer", fn);
+    CRL_REQUIRE(seat && tcount, "%s: NULL seat / tcount pointer", fn);
+    CRL_REQUIRE(reward && done && winners && obs_board && valid, "%s: NULL output pointer", fn);
+    CRL_REQUIRE(rel_mod >= 1, "%s: rel_mod must be >= 1", fn);
+    TTT_NOISE_CHECK(fn);
+    CRL_REQUIRE(flags == 0, "%s: unknown flags 0x%x", fn, flags);
+    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "%s: a board of %d cells for %d players (%s)", fn, ctx->ttt.n_cells, ctx->ttt.P,
+                noise ? "as crl_ttt_step_single" : "a fresh game could end before the learner's turn");
+    CRL_REQUIRE((((uintptr_t)obs_board) & 3) == 0, "%s: obs_board must be 4-byte aligned", fn);
+    const ttt_dirs dd = dirs_of(ctx);
+    const uint32_t *win_tab = ttt_win_table_here(ctx);
+    if (noise) {
+        TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_step_single_tactical_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd,
+                                                    ttt_inv_cells(dd.n_cells), B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
+                                                    crl_noise_threshold(*noise), occ, winner, to_move, seat, learner_action, tcount,
+                                                    reward, done, winners, obs_board, valid, rel_mod, win_tab));
+    } else {
+        TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_step_single_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd,
+                                                    ttt_inv_cells(dd.n_cells), B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
+                                                    occ, winner, to_move, seat, learner_action, tcount, reward, done, winners,
+                                                    obs_board, valid, rel_mod, win_tab));
+    }
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+static int ttt_playout_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                              const uint32_t *occ, const int8_t *winner, const int8_t *to_move, const uint32_t *tcount,
+                              const int32_t *cand, int A, int R, uint32_t *wins, uint32_t *played, uint32_t *len_sum,
+                              const double *noise, uint32_t flags, void *stream)
+{
+    TTT_CTX_CHECK(fn);
+    CRL_REQUIRE(occ && winner && to_move, "%s: NULL state pointer", fn);
+    CRL_REQUIRE(wins && played && len_sum, "%s: NULL output pointer", fn);
+    CRL_PLAYOUT_SHAPE_CHECK(fn);
+    TTT_NOISE_CHECK(fn);
+    CRL_REQUIRE(flags == 0, "%s: unknown flags 0x%x", fn, flags);
+    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "%s: a board of %d cells for %d players (as crl_ttt_step_single)", fn,
+                ctx->ttt.n_cells, ctx->ttt.P);
+    const ttt_dirs dd = dirs_of(ctx);
+    const uint32_t *win_tab = ttt_win_table_here(ctx);
+    const auto [rows, n_lanes] = crl_playout_shape_of(B, A, R);
+    // rows that span waves are summed by atomics: every output starts from zero
+    CRL_HIP(hipMemsetAsync(wins, 0, rows * ctx->ttt.P * sizeof(uint32_t), (hipStream_t)stream));
+    CRL_HIP(hipMemsetAsync(played, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
+    CRL_HIP(hipMemsetAsync(len_sum, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
+    const unsigned blocks = crl_playout_blocks(n_lanes, 256u);
+    if (noise) {
+        TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_playout_tactical_kernel<PP, NDD, WTT>), blocks, dd, B, (uint32_t)seed,
+                                                    (uint32_t)(seed >> 32), first_env_id, crl_noise_threshold(*noise), occ, winner,
+                                                    to_move, tcount, cand, A, R, n_lanes, wins, played, len_sum, win_tab));
+    } else {
+        TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_playout_kernel<PP, NDD, WTT>), blocks, dd, B, (uint32_t)seed,
+                                                    (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, tcount, cand, A, R,
+                                                    n_lanes, wins, played, len_sum, win_tab));
+    }
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+static int ttt_rollout_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T,
+                              const double *noise, uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats st, void *stream)
+{
+    TTT_CTX_CHECK(fn);
+    CRL_REQUIRE(occ && winner && to_move, "%s: NULL state pointer", fn);
+    CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.draw_count && st.len_sum, "%s: NULL stats pointer", fn);
+    CRL_REQUIRE(T >= 0 && T <= (1 << 24), "%s: T=%d out of range", fn, T);
+    TTT_NOISE_CHECK(fn);
+    if (T == 0) return CRL_OK;
+    const ttt_dirs dd = dirs_of(ctx);
+    const uint32_t *win_tab = ttt_win_table_here(ctx);
+    if (noise) {
+        TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_rollout_tactical_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd, B,
+                                                    (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, crl_noise_threshold(*noise),
+                                                    T, occ, winner, to_move, st, win_tab));
+    } else {
+        TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_rollout_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd, B, (uint32_t)seed,
+                                                    (uint32_t)(seed >> 32), first_env_id, T, occ, winner, to_move, st, win_tab));
+    }
+    CRL_LAUNCH_CHECK();
     return CRL_OK;
 }
 
@@ -1471,16 +1584,10 @@ int crl_ttt_board(const crl_ctx *ctx, int64_t B, const uint32_t *occ, const int8
     return CRL_OK;
 }
 
-int crl_ttt_sample(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
-                   uint32_t *tcount, int advance, int8_t *action, void *stream)
+int crl_ttt_sample(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ, uint32_t *tcount,
+                   int advance, int8_t *action, void *stream)
 {
-    TTT_CTX_CHECK("crl_ttt_sample");
-    CRL_REQUIRE(occ && tcount && action, "crl_ttt_sample: NULL pointer");
-    const ttt_dirs dd = dirs_of(ctx);
-    TTT_LAUNCH(ttt_sample_kernel, blocks_for(B, 256), ctx->ttt.P, dd.full, B,
-               (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, occ, tcount, advance, action);
-    CRL_LAUNCH_CHECK();
-    return CRL_OK;
+    return ttt_sample_launch("crl_ttt_sample", ctx, B, seed, first_env_id, occ, nullptr, tcount, advance, nullptr, action, stream);
 }
 
 int crl_ttt_step_observe(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
@@ -1503,59 +1610,20 @@ int crl_ttt_step_observe(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t 
     return CRL_OK;
 }
 
-int crl_ttt_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
-                        uint32_t *occ, int8_t *winner, int8_t *to_move, const int8_t *seat,
-                        const int64_t *learner_action, uint32_t *tcount,
-                        int8_t *reward, uint8_t *done, int8_t *winners,
-                        int8_t *obs_board, uint32_t *valid, int rel_mod, uint32_t flags, void *stream)
+int crl_ttt_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *occ, int8_t *winner,
+                        int8_t *to_move, const int8_t *seat, const int64_t *learner_action, uint32_t *tcount, int8_t *reward,
+                        uint8_t *done, int8_t *winners, int8_t *obs_board, uint32_t *valid, int rel_mod, uint32_t flags, void *stream)
 {
-    TTT_CTX_CHECK("crl_ttt_step_single");
-    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_step_single: NULL state pointer");
-    CRL_REQUIRE(seat && tcount, "crl_ttt_step_single: NULL seat / tcount pointer");
-    CRL_REQUIRE(reward && done && winners && obs_board && valid, "crl_ttt_step_single: NULL output pointer");
-    CRL_REQUIRE(rel_mod >= 1, "crl_ttt_step_single: rel_mod must be >= 1");
-    CRL_REQUIRE(flags == 0, "crl_ttt_step_single: unknown flags 0x%x", flags);
-    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "crl_ttt_step_single: a board of %d cells for %d players (a fresh game could end "
-                "before the learner's turn)", ctx->ttt.n_cells, ctx->ttt.P);
-    CRL_REQUIRE((((uintptr_t)obs_board) & 3) == 0, "crl_ttt_step_single: obs_board must be 4-byte aligned");
-    const ttt_dirs dd = dirs_of(ctx);
-    const uint32_t *win_tab = ttt_win_table_here(ctx);
-    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_step_single_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd,
-                                                ttt_inv_cells(dd.n_cells), B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
-                                                occ, winner, to_move, seat, learner_action, tcount, reward, done, winners,
-                                                obs_board, valid, rel_mod, win_tab));
-    CRL_LAUNCH_CHECK();
-    return CRL_OK;
+    return ttt_step_single_launch("crl_ttt_step_single", ctx, B, seed, first_env_id, occ, winner, to_move, seat, learner_action, tcount,
+                                  reward, done, winners, obs_board, valid, rel_mod, nullptr, flags, stream);
 }
 
-int crl_ttt_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
-                    const uint32_t *occ, const int8_t *winner, const int8_t *to_move, const uint32_t *tcount,
-                    const int32_t *cand, int A, int R,
-                    uint32_t *wins, uint32_t *played, uint32_t *len_sum, uint32_t flags, void *stream)
+int crl_ttt_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ, const int8_t *winner,
+                    const int8_t *to_move, const uint32_t *tcount, const int32_t *cand, int A, int R, uint32_t *wins,
+                    uint32_t *played, uint32_t *len_sum, uint32_t flags, void *stream)
 {
-    TTT_CTX_CHECK("crl_ttt_playout");
-    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_playout: NULL state pointer");
-    CRL_REQUIRE(wins && played && len_sum, "crl_ttt_playout: NULL output pointer");
-    CRL_REQUIRE(R >= 1 && R <= 65535, "crl_ttt_playout: R=%d out of range 1..65535", R);
-    CRL_REQUIRE(A >= 1 && A <= 65535, "crl_ttt_playout: A=%d out of range 1..65535", A);
-    CRL_REQUIRE(cand != nullptr || A == 1, "crl_ttt_playout: A=%d with cand == NULL (must be 1)", A);
-    CRL_REQUIRE(flags == 0, "crl_ttt_playout: unknown flags 0x%x", flags);
-    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "crl_ttt_playout: a board of %d cells for %d players (as crl_ttt_step_single)",
-                ctx->ttt.n_cells, ctx->ttt.P);
-    const ttt_dirs dd = dirs_of(ctx);
-    const uint32_t *win_tab = ttt_win_table_here(ctx);
-    const uint64_t rows = (uint64_t)B * (uint64_t)A, n_lanes = rows * (uint64_t)R;
-    // rows that span waves are summed by atomics: every output starts from zero
-    CRL_HIP(hipMemsetAsync(wins, 0, rows * ctx->ttt.P * sizeof(uint32_t), (hipStream_t)stream));
-    CRL_HIP(hipMemsetAsync(played, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
-    CRL_HIP(hipMemsetAsync(len_sum, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
-    const uint64_t want = (n_lanes + 255u) / 256u;          // a grid-stride loop past 2^20 workgroups
-    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));
-    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_playout_kernel<PP, NDD, WTT>), blocks, dd, B, (uint32_t)seed,
-                                                (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, tcount, cand, A, R,
-                                                n_lanes, wins, played, len_sum, win_tab));
-    CRL_LAUNCH_CHECK();
-    return CRL_OK;
+    return ttt_playout_launch("crl_ttt_playout", ctx, B, seed, first_env_id, occ, winner, to_move, tcount, cand, A, R, wins, played,
+                              len_sum, nullptr, flags, stream);
 }
 
 static int ttt_step_board_launch(const char *fn, const crl_ctx *ctx, int64_t B, int8_t *board, int8_t *winner, int8_t *to_move,
@@ -1563,8 +1631,7 @@ static int ttt_step_board_launch(const char *fn, const crl_ctx *ctx, int64_t B, 
                                  int8_t *obs_board, int rel_mod, uint32_t flags, void *stream, const bool by_value, uint32_t *flag,
                                  const uint32_t seq)
 {
-    CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_TTT, "%s: ctx is not a tictactoe context", fn);
-    CRL_REQUIRE(B > 0 && B <= ((int64_t)1 << 31), "%s: B=%lld out of range", fn, (long long)B);
+    TTT_CTX_CHECK(fn);
     CRL_REQUIRE(board && winner && to_move, "%s: NULL state pointer", fn);
     CRL_REQUIRE(action && reward && terminal && winners, "%s: NULL action/output pointer", fn);
     CRL_REQUIRE(obs_board == nullptr || rel_mod >= 1, "%s: rel_mod must be >= 1 when obs_board is given", fn);
@@ -1617,25 +1684,13 @@ int crl_ttt_observe_board(const crl_ctx *ctx, int64_t B, const int8_t *board, co
     return CRL_OK;
 }
 
-int crl_ttt_rollout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T,
-                    uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats st, void *stream)
+int crl_ttt_rollout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, uint32_t *occ, int8_t *winner,
+                    int8_t *to_move, crl_ttt_stats st, void *stream)
 {
-    TTT_CTX_CHECK("crl_ttt_rollout");
-    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_rollout: NULL state pointer");
-    CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.draw_count && st.len_sum, "crl_ttt_rollout: NULL stats pointer");
-    CRL_REQUIRE(T >= 0 && T <= (1 << 24), "crl_ttt_rollout: T=%d out of range", T);
-    if (T == 0) return CRL_OK;
-    const ttt_dirs dd = dirs_of(ctx);
-    const uint32_t *win_tab = ttt_win_table_here(ctx);
-    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_rollout_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd, B, (uint32_t)seed,
-                                                (uint32_t)(seed >> 32), first_env_id, T, occ, winner, to_move, st, win_tab));
-    CRL_LAUNCH_CHECK();
-    return CRL_OK;
+    return ttt_rollout_launch("crl_ttt_rollout", ctx, B, seed, first_env_id, T, nullptr, occ, winner, to_move, st, stream);
 }
 
 // ---- the tactical agent's entries (the contract is in include/colosseum_hip.h)
-#define TTT_NOISE_CHECK(fn) CRL_REQUIRE(noise >= 0.0 && noise <= 1.0, fn ": noise=%g outside [0, 1]", noise)   /* (NaN fails too) */
-
 int crl_ttt_winning_cells(const crl_ctx *ctx, int64_t B, const uint32_t *occ, uint32_t *cells, void *stream)
 {
     TTT_CTX_CHECK("crl_ttt_winning_cells");
@@ -1649,91 +1704,31 @@ int crl_ttt_winning_cells(const crl_ctx *ctx, int64_t B, const uint32_t *occ, ui
 int crl_ttt_sample_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
                             const int8_t *to_move, uint32_t *tcount, int advance, double noise, int8_t *action, void *stream)
 {
-    TTT_CTX_CHECK("crl_ttt_sample_tactical");
-    CRL_REQUIRE(occ && to_move && tcount && action, "crl_ttt_sample_tactical: NULL pointer");
-    TTT_NOISE_CHECK("crl_ttt_sample_tactical");
-    const ttt_dirs dd = dirs_of(ctx);
-    TTT_DISPATCH_ND(ctx, TTT_LAUNCH((ttt_sample_tactical_kernel<PP, NDD>), blocks_for(B, 256), dd, B, (uint32_t)seed,
-                                    (uint32_t)(seed >> 32), first_env_id, tron_avoid_threshold(noise), occ, to_move, tcount,
-                                    advance, action));
-    CRL_LAUNCH_CHECK();
-    return CRL_OK;
+    return ttt_sample_launch("crl_ttt_sample_tactical", ctx, B, seed, first_env_id, occ, to_move, tcount, advance, &noise, action,
+                             stream);
 }
 
-int crl_ttt_rollout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, double noise,
-                             uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats st, void *stream)
+int crl_ttt_rollout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, double noise, uint32_t *occ,
+                             int8_t *winner, int8_t *to_move, crl_ttt_stats st, void *stream)
 {
-    TTT_CTX_CHECK("crl_ttt_rollout_tactical");
-    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_rollout_tactical: NULL state pointer");
-    CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.draw_count && st.len_sum,
-                "crl_ttt_rollout_tactical: NULL stats pointer");
-    CRL_REQUIRE(T >= 0 && T <= (1 << 24), "crl_ttt_rollout_tactical: T=%d out of range", T);
-    TTT_NOISE_CHECK("crl_ttt_rollout_tactical");
-    if (T == 0) return CRL_OK;
-    const ttt_dirs dd = dirs_of(ctx);
-    const uint32_t *win_tab = ttt_win_table_here(ctx);
-    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_rollout_tactical_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd, B, (uint32_t)seed,
-                                                (uint32_t)(seed >> 32), first_env_id, tron_avoid_threshold(noise), T, occ, winner,
-                                                to_move, st, win_tab));
-    CRL_LAUNCH_CHECK();
-    return CRL_OK;
+    return ttt_rollout_launch("crl_ttt_rollout_tactical", ctx, B, seed, first_env_id, T, &noise, occ, winner, to_move, st, stream);
 }
 
-int crl_ttt_step_single_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
-                                 uint32_t *occ, int8_t *winner, int8_t *to_move, const int8_t *seat,
-                                 const int64_t *learner_action, uint32_t *tcount,
-                                 int8_t *reward, uint8_t *done, int8_t *winners,
-                                 int8_t *obs_board, uint32_t *valid, int rel_mod, double noise, uint32_t flags, void *stream)
+int crl_ttt_step_single_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *occ, int8_t *winner,
+                                 int8_t *to_move, const int8_t *seat, const int64_t *learner_action, uint32_t *tcount, int8_t *reward,
+                                 uint8_t *done, int8_t *winners, int8_t *obs_board, uint32_t *valid, int rel_mod, double noise,
+                                 uint32_t flags, void *stream)
 {
-    TTT_CTX_CHECK("crl_ttt_step_single_tactical");
-    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_step_single_tactical: NULL state pointer");
-    CRL_REQUIRE(seat && tcount, "crl_ttt_step_single_tactical: NULL seat / tcount pointer");
-    CRL_REQUIRE(reward && done && winners && obs_board && valid, "crl_ttt_step_single_tactical: NULL output pointer");
-    CRL_REQUIRE(rel_mod >= 1, "crl_ttt_step_single_tactical: rel_mod must be >= 1");
-    TTT_NOISE_CHECK("crl_ttt_step_single_tactical");
-    CRL_REQUIRE(flags == 0, "crl_ttt_step_single_tactical: unknown flags 0x%x", flags);
-    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "crl_ttt_step_single_tactical: a board of %d cells for %d players (as "
-                "crl_ttt_step_single)", ctx->ttt.n_cells, ctx->ttt.P);
-    CRL_REQUIRE((((uintptr_t)obs_board) & 3) == 0, "crl_ttt_step_single_tactical: obs_board must be 4-byte aligned");
-    const ttt_dirs dd = dirs_of(ctx);
-    const uint32_t *win_tab = ttt_win_table_here(ctx);
-    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_step_single_tactical_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd,
-                                                ttt_inv_cells(dd.n_cells), B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
-                                                tron_avoid_threshold(noise), occ, winner, to_move, seat, learner_action, tcount,
-                                                reward, done, winners, obs_board, valid, rel_mod, win_tab));
-    CRL_LAUNCH_CHECK();
-    return CRL_OK;
+    return ttt_step_single_launch("crl_ttt_step_single_tactical", ctx, B, seed, first_env_id, occ, winner, to_move, seat,
+                                  learner_action, tcount, reward, done, winners, obs_board, valid, rel_mod, &noise, flags, stream);
 }
 
-int crl_ttt_playout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
-                             const uint32_t *occ, const int8_t *winner, const int8_t *to_move, const uint32_t *tcount,
-                             const int32_t *cand, int A, int R,
+int crl_ttt_playout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
+                             const int8_t *winner, const int8_t *to_move, const uint32_t *tcount, const int32_t *cand, int A, int R,
                              uint32_t *wins, uint32_t *played, uint32_t *len_sum, double noise, uint32_t flags, void *stream)
 {
-    TTT_CTX_CHECK("crl_ttt_playout_tactical");
-    CRL_REQUIRE(occ && winner && to_move, "crl_ttt_playout_tactical: NULL state pointer");
-    CRL_REQUIRE(wins && played && len_sum, "crl_ttt_playout_tactical: NULL output pointer");
-    CRL_REQUIRE(R >= 1 && R <= 65535, "crl_ttt_playout_tactical: R=%d out of range 1..65535", R);
-    CRL_REQUIRE(A >= 1 && A <= 65535, "crl_ttt_playout_tactical: A=%d out of range 1..65535", A);
-    CRL_REQUIRE(cand != nullptr || A == 1, "crl_ttt_playout_tactical: A=%d with cand == NULL (must be 1)", A);
-    TTT_NOISE_CHECK("crl_ttt_playout_tactical");
-    CRL_REQUIRE(flags == 0, "crl_ttt_playout_tactical: unknown flags 0x%x", flags);
-    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "crl_ttt_playout_tactical: a board of %d cells for %d players (as "
-                "crl_ttt_step_single)", ctx->ttt.n_cells, ctx->ttt.P);
-    const ttt_dirs dd = dirs_of(ctx);
-    const uint32_t *win_tab = ttt_win_table_here(ctx);
-    const uint64_t rows = (uint64_t)B * (uint64_t)A, n_lanes = rows * (uint64_t)R;
-    // rows that span waves are summed by atomics: every output starts from zero (as crl_ttt_playout)
-    CRL_HIP(hipMemsetAsync(wins, 0, rows * ctx->ttt.P * sizeof(uint32_t), (hipStream_t)stream));
-    CRL_HIP(hipMemsetAsync(played, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
-    CRL_HIP(hipMemsetAsync(len_sum, 0, rows * sizeof(uint32_t), (hipStream_t)stream));
-    const uint64_t want = (n_lanes + 255u) / 256u;
-    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));
-    TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_playout_tactical_kernel<PP, NDD, WTT>), blocks, dd, B, (uint32_t)seed,
-                                                (uint32_t)(seed >> 32), first_env_id, tron_avoid_threshold(noise), occ, winner,
-                                                to_move, tcount, cand, A, R, n_lanes, wins, played, len_sum, win_tab));
-    CRL_LAUNCH_CHECK();
-    return CRL_OK;
+    return ttt_playout_launch("crl_ttt_playout_tactical", ctx, B, seed, first_env_id, occ, winner, to_move, tcount, cand, A, R, wins,
+                              played, len_sum, &noise, flags, stream);
 }
 
 } // extern "C"

@@ -1,6 +1,6 @@
-"""Times TicTacToe's tactical (win-or-block) agent next to the random agent it stands beside, and the random agent of a
-PARENT build of the library next to both, so that the comparison is against the code before the tactical entries and not
-against this code.
+"""Times TicTacToe's tactical (win-or-block) agent next to the random agent it stands beside, and the same figures of a
+PARENT build of the library next to both, so that a change is held to the code before it and not to itself.  A parent that
+exports the tactical entries is measured with both agents; one from before them with the random agent alone.
 
 Per shape (3x3 P2, 3x5 K3 P3, 3x3x3 P4, 5x5 K4 P3) at B = 262,144 games, --noise 0.1, device-event times after a warm-up:
   * step_single_us    us per step_single call (one learner step, the opponents' plies included; the learner plays a uniform
@@ -8,7 +8,8 @@ Per shape (3x3 P2, 3x5 K3 P3, 3x3x3 P4, 5x5 K4 P3) at B = 262,144 games, --noise
   * playout_plies_per_s   plies/s of one playout call, 2^28 playouts (16,384 positions x 16,384) from the empty board
   * rollout_env_steps_per_s   env-steps/s of rollout / rollout_tactical, --roll-steps plies per game
   * winning_cells_us  us per winning_cells call (this build only)
-each for agent = random and tactical on this build and for random on the parent build (--parent-lib).  A library is
+each for agent = random and tactical on this build and on the parent build (--parent-lib; tactical: if it has the entries;
+winning_cells_us_parent likewise).  A library is
 loaded once per process, so every measurement round is a child process of its own -- this build, the parent, this build, ...
 (--rounds of each, alternating) -- and a row reports per figure the median over the rounds and [min, max] as its spread.
 Without --parent-lib the parent figures are null.  The parent build is the library of the commit before, e.g.
@@ -54,12 +55,20 @@ def _median_ms(fn, reps):
     return sorted(ts)[len(ts) // 2]
 
 
+def _exports(lib_path, names):
+    """whether the library exports every one of the entries"""
+    import ctypes
+    lib = ctypes.CDLL(lib_path)
+    return all(hasattr(lib, name) for name in names)
+
+
 def child(a):
     """one round: {shape: {figure_agent: value}} as a JSON line behind "ROUND " """
     import torch
     from colosseumrl_amd import _native
-    agents = ["random"] if a.parent else ["random", "tactical"]
-    if a.parent:                                            # a build from before the tactical entries exports none of them
+    tactical = not a.parent or _exports(_native.LIB_PATH, TACTICAL_ENTRIES)
+    agents = ["random", "tactical"] if tactical else ["random"]
+    if not tactical:                                        # a build from before the tactical entries exports none of them
         for name in TACTICAL_ENTRIES:
             _native.PROTOTYPES.pop(name)
     from colosseumrl_amd.batched import TTTBatch
@@ -77,8 +86,8 @@ def child(a):
         pb = TTTBatch(dims, k, p, a.playout_batch, device=DEV)
         R = a.playouts // a.playout_batch
         for agent in agents:
-            kw_single = {} if a.parent else {"opponent": agent, "noise": a.noise}
-            kw_playout = {} if a.parent else {"agent": agent, "noise": a.noise}
+            kw_single = {"opponent": agent, "noise": a.noise} if tactical else {}
+            kw_playout = {"agent": agent, "noise": a.noise} if tactical else {}
             bufs = {}
 
             def run_single():
@@ -93,7 +102,7 @@ def child(a):
             roll = (lambda: tb.rollout_tactical(a.roll_steps, 3, a.noise)) if agent == "tactical" else (lambda: tb.rollout(a.roll_steps, 3))
             tb.reset()
             row["rollout_env_steps_per_s_" + agent] = a.batch * a.roll_steps / (_median_ms(roll, a.reps) * 1e-3)
-        if not a.parent:
+        if tactical:
             row["winning_cells_us"] = _median_ms(tb.winning_cells, a.reps) * 1e3     # (the positions the rollouts left)
         out[shape_name(dims, k, p)] = row
         del tb, pb
@@ -161,7 +170,13 @@ def main():
                 row[fig + "_" + agent], row[fig + "_" + agent + "_spread"] = _summary([r[name][fig + "_" + agent] for r in here])
             row[fig + "_random_parent"], row[fig + "_random_parent_spread"] = \
                 _summary([r[name][fig + "_random"] for r in parent]) if parent else (None, None)
+            if parent and fig + "_tactical" in parent[0][name]:         # (a parent with the tactical entries)
+                row[fig + "_tactical_parent"], row[fig + "_tactical_parent_spread"] = \
+                    _summary([r[name][fig + "_tactical"] for r in parent])
         row["winning_cells_us"], row["winning_cells_us_spread"] = _summary([r[name]["winning_cells_us"] for r in here])
+        if parent and "winning_cells_us" in parent[0][name]:
+            row["winning_cells_us_parent"], row["winning_cells_us_parent_spread"] = \
+                _summary([r[name]["winning_cells_us"] for r in parent])
         row["step_single_tactical_over_random"] = row["step_single_us_tactical"] / row["step_single_us_random"]
         row["playout_random_over_tactical"] = row["playout_plies_per_s_random"] / row["playout_plies_per_s_tactical"]
         row["rollout_random_over_tactical"] = row["rollout_env_steps_per_s_random"] / row["rollout_env_steps_per_s_tactical"]

@@ -7,6 +7,7 @@ infrastructure and is never imported from this package.)
 import ctypes as C
 import os
 import subprocess
+import sys
 import threading
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -31,6 +32,7 @@ CRL_PLAYOUT_AVOID = 1
 CRL_PLAYOUT_UNTIL_SEAT_DONE = 2
 
 _lib = None
+_fast = None            # colosseumrl_amd._crl_fast (csrc/fastcall.cpp) once lib() has loaded it; stays None where it may not be used
 _lock = threading.Lock()
 
 
@@ -39,8 +41,9 @@ class NativeError(RuntimeError):
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/*.hip for gfx950 with hipcc into colosseumrl_amd/libcolosseum_hip.so (in-tree)."""
-    args = ["make", "-C", CSRC_DIR, "-j4"]
+    """Compile csrc/*.hip for gfx950 with hipcc into colosseumrl_amd/libcolosseum_hip.so (in-tree), and csrc/fastcall.cpp
+    with the host compiler into colosseumrl_amd/_crl_fast<EXT_SUFFIX> for the interpreter that runs this."""
+    args = ["make", "-C", CSRC_DIR, "-j4", "PYTHON=%s" % sys.executable]
     if force:
         args.append("-B")
     proc = subprocess.run(args, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -139,6 +142,11 @@ PROTOTYPES = {
     "crl_blokus_step_observe": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 15 + [_U32, _VP]),
     "crl_blokus_step_single": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 15 + [_U32, _VP]),
     "crl_blokus_playout": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 7 + [_I, _I] + [_VP] * 4 + [_U32, _VP]),
+    "crl_tron_rollout_bind": (_I, [_VP, _I64, _U64, _VP, _VP, _VP, _VP, TronStats, _U32, C.POINTER(_VP)]),
+    "crl_ttt_rollout_bind": (_I, [_VP, _I64, _U64, _VP, _VP, _VP, TTTStats, C.POINTER(_VP)]),
+    "crl_blokus_rollout_bind": (_I, [_VP, _I64, _U64, _VP, _VP, _VP, _VP, _VP, BlokusStats, C.POINTER(_VP)]),
+    "crl_rollout_launch": (_I, [_VP, _U64, _I, _VP]),
+    "crl_rollout_unbind": (_I, [_VP]),
 }
 
 
@@ -170,7 +178,33 @@ def lib():
                 raise NativeError("%s is ABI revision %d, this binding needs %d (include/colosseum_hip.h CRL_ABI_VERSION): "
                                   "rebuild it" % (LIB_PATH, got, CRL_ABI_VERSION))
             _lib = handle
+            _load_fast()
     return _lib
+
+
+def _load_fast():
+    """Import the C-API entry of the rollout region's two calls, behind the library it links against: the extension names
+    libcolosseum_hip.so as a dependency, and the loader must find the copy lib() just loaded (after torch, so that both share
+    torch's HIP runtime), never load one first.  Not used with CRL_NO_FASTCALL=1 (A/B runs and tests: the ctypes forms),
+    with a diagnostic library from CRL_LIB_PATH (the extension is linked to the shipped one), or where it was not built
+    (no Python.h at build time): the steppers then call crl_rollout_launch through ctypes."""
+    global _fast
+    if os.environ.get("CRL_LIB_PATH"):
+        return
+    try:
+        from . import _crl_fast
+    except ImportError:
+        return
+    if _crl_fast.ABI_VERSION == CRL_ABI_VERSION:
+        _fast = _crl_fast
+
+
+def fast():
+    """The module colosseumrl_amd._crl_fast (``rollout_launch``, ``stream_wait_mapped``), or None where the ctypes forms are
+    to be used (see `_load_fast`; CRL_NO_FASTCALL is read at every call, a stepper asks once, when it binds its first plan).
+    Loads the library first."""
+    lib()
+    return None if os.environ.get("CRL_NO_FASTCALL") == "1" else _fast
 
 
 def check(rc, what=""):

@@ -35,6 +35,22 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _stream_handle() -> int:
+    """`_stream()` as a plain int: what the plan launchers take (the C-API entry converts an int in a few nanoseconds; a
+    ctypes c_void_p argument accepts one too)"""
+    if _raw_stream is not None:
+        return _raw_stream(torch.cuda.current_device())
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _plan_launcher(lib):
+    """The callable `(plan, seed, T, stream) -> rc` that launches a bound rollout plan, handles as ints: the C-API entry
+    (colosseumrl_amd._crl_fast, csrc/fastcall.cpp) where it was built and imported, else ``crl_rollout_launch`` through
+    ctypes (also with CRL_NO_FASTCALL=1: A/B runs and tests)."""
+    fast = _native.fast()
+    return fast.rollout_launch if fast is not None else lib.crl_rollout_launch
+
+
 _ROLLOUT_KERNEL_FLAGS = {"auto": 0, "bits": _native.CRL_ROLLOUT_BITS, "bytes": _native.CRL_ROLLOUT_BYTES,
                          "global": _native.CRL_ROLLOUT_NO_LDS, "quad": _native.CRL_ROLLOUT_QUAD,
                          "qbits": _native.CRL_ROLLOUT_QBITS, "gquad": _native.CRL_ROLLOUT_GQUAD, "pair": _native.CRL_ROLLOUT_PAIR}
@@ -248,6 +264,51 @@ class _RolloutStepper(_Stepper, _Waitable):
     ``_results`` / ``_packed`` for those two), `_stats()` and `reset_stats()` all come from that table."""
     STATS_STRUCT = None
     STATS = {}
+    # Launch plans (include/colosseum_hip.h): `PLAN_BIND(ctx, B, first_env_id, *_state(), stats[, flags], &plan)` checks and
+    # stores everything of a plain `rollout()` that does not change from call to call -- the tensors are never reallocated
+    # --, so that a launch passes four scalars.  Bound at the first rollout (per kernel pin, for Tron), unbound with the
+    # stepper.
+    PLAN_BIND = None
+    _plans = None                # flags (None where the entry has none) -> plan handle
+    _launch = None               # `_plan_launcher`'s pick, made at the first bind
+
+    def _bind_plan(self, flags=None) -> int:
+        if self._plans is None:
+            self._plans, self._launch = {}, _plan_launcher(self._lib)
+        plan = C.c_void_p()
+        check(getattr(self._lib, self.PLAN_BIND)(self._ctx.handle, self.B, self.first_env_id, *self._state(), self._stats(),
+                                                 *(() if flags is None else (flags,)), C.byref(plan)), self.PLAN_BIND)
+        self._plans[flags] = plan.value
+        return plan.value
+
+    def _rollout_plan(self, steps: int, seed: int):
+        """`rollout` of the classes whose entry takes no flags: one launch through the plan"""
+        plan = (self._plans and self._plans.get(None)) or self._bind_plan()
+        with _DevGuard(self.device):
+            rc = self._launch(plan, seed, int(steps), _stream_handle())
+        if rc:
+            check(rc, "crl_rollout_launch")
+
+    def _unbind_plans(self):
+        plans, self._plans = self._plans, None
+        for plan in (plans or {}).values():
+            self._lib.crl_rollout_unbind(plan)
+
+    @property
+    def first_env_id(self) -> int:
+        return self._first_env_id
+
+    @first_env_id.setter
+    def first_env_id(self, value: int):
+        """(a plan holds the id it was bound with: the next rollout binds again)"""
+        self._first_env_id = int(value)
+        self._unbind_plans()
+
+    def __del__(self):
+        try:
+            self._unbind_plans()
+        except Exception:  # interpreter shutdown
+            pass
 
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
@@ -278,6 +339,7 @@ class TronBatch(_RolloutStepper):
       board  int8 [B, N*N]; heads int16 [P, B]; dirs int8 [P, B]; deaths int8 [P, B]
     """
     STATS_STRUCT = _native.TronStats
+    PLAN_BIND = "crl_tron_rollout_bind"
     STATS = {"tcount": (torch.int32, _per_game), "tstep": (torch.int32, _per_game), "n_episodes": (torch.int32, _per_game),
              "win_count": (torch.int32, _per_player), "len_sum": (torch.int32, _per_game), "ret_sum": (torch.int32, _per_player),
              "last_winners": (torch.uint8, _per_game), "last_len": (torch.int16, _per_game),
@@ -351,13 +413,16 @@ class TronBatch(_RolloutStepper):
         flags = _ROLLOUT_KERNEL_FLAGS[kernel]
         if not use_lds:
             flags = _native.CRL_ROLLOUT_NO_LDS
-        steps, args = int(steps), self._rollout_args or self._bind_rollout()
+        steps = int(steps)
         # `_call` written out: this launch is the benchmark's timed region, where one more Python frame per launch shows,
         # and the timed entry takes its events after the stream
+        if events is None:
+            plan = (self._plans and self._plans.get(flags)) or self._bind_plan(flags)
+        else:
+            args = self._rollout_args or self._bind_rollout()
         with _DevGuard(self.device):
-            if events is None:
-                rc = self._lib.crl_tron_rollout(self._ctx.handle, self.B, _seed(seed), self.first_env_id, steps, *args, flags,
-                                                _stream())
+            if events is None:                  # the plain launch: the bound plan, four scalars (the launcher masks the seed)
+                rc = self._launch(plan, seed, steps, _stream_handle())
             else:
                 if any(e is not None and not e.cuda_event for e in events):
                     raise ValueError("rollout(events=...): record() each event once before passing it (torch creates the "
@@ -366,7 +431,7 @@ class TronBatch(_RolloutStepper):
                 rc = self._lib.crl_tron_rollout_timed(self._ctx.handle, self.B, _seed(seed), self.first_env_id, steps, *args,
                                                       flags, _stream(), handles[0], handles[1])
         if rc:
-            check(rc, "crl_tron_rollout")
+            check(rc, "crl_rollout_launch" if events is None else "crl_tron_rollout_timed")
         self._stat_steps += steps
 
     def check_state(self) -> int:
@@ -621,6 +686,7 @@ class TTTBatch(_RolloutStepper):
     """
 
     STATS_STRUCT = _native.TTTStats
+    PLAN_BIND = "crl_ttt_rollout_bind"
     STATS = {"tcount": (torch.int32, _per_game), "tstep": (torch.int32, _per_game), "n_episodes": (torch.int32, _per_game),
              "win_count": (torch.int32, _per_player), "draw_count": (torch.int32, _per_game), "len_sum": (torch.int32, _per_game),
              "results": (torch.int32, lambda B, P: (B, 3 + P))}
@@ -642,6 +708,9 @@ class TTTBatch(_RolloutStepper):
             self.winners = torch.zeros((B,), dtype=torch.int8, device=dev)
             self.__dict__.update(_alloc(self._stat_spec(B, P), dev, torch.zeros))
         self._open_wait()
+
+    def _state(self):
+        return (_ptr(self.occ), _ptr(self.winner), _ptr(self.to_move))
 
     def lines(self):
         buf = (C.c_uint32 * 256)()
@@ -794,8 +863,7 @@ class TTTBatch(_RolloutStepper):
         return _flat_mc_pick(2 * mine + o["draws"], o["played"], cells)
 
     def rollout(self, steps: int, seed: int = 0):
-        self._call("crl_ttt_rollout", _seed(seed), self.first_env_id, int(steps), _ptr(self.occ), _ptr(self.winner),
-                   _ptr(self.to_move), self._stats())
+        self._rollout_plan(steps, seed)
 
     def results(self, copy: bool = True):
         """int32 [B, 3+P] = n_episodes, len_sum, draw_count, win_count[P]; written by the rollout kernel at the end of
@@ -855,6 +923,7 @@ class BlokusBatch(_RolloutStepper):
     """
     MASK_WORDS = 10500
     STATS_STRUCT = _native.BlokusStats
+    PLAN_BIND = "crl_blokus_rollout_bind"
     STATS = {"tcount": (torch.int32, _per_game), "tstep": (torch.int32, _per_game), "n_episodes": (torch.int32, _per_game),
              "win_count": (torch.int32, _per_player), "len_sum": (torch.int32, _per_game), "score_sum": (torch.int32, _per_player),
              "results": (torch.int32, lambda B, P: (B, 10))}
@@ -1049,7 +1118,7 @@ class BlokusBatch(_RolloutStepper):
         return out
 
     def rollout(self, steps: int, seed: int = 0):
-        self._call("crl_blokus_rollout", _seed(seed), self.first_env_id, int(steps), *self._state(), self._stats())
+        self._rollout_plan(steps, seed)
 
     def results(self, copy: bool = True):
         """int32 [B, 10] = n_episodes, len_sum, win_count[4], score_sum[4]; written by the rollout kernel at the end of

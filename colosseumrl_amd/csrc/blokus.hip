@@ -1889,6 +1889,43 @@ int crl_blokus_bounds(unsigned int *out4)
     return CRL_OK;
 }
 
+// The arguments of crl_blokus_rollout that stay the same from launch to launch (include/colosseum_hip.h, "launch plans"), checked.
+struct blokus_plan : crl_plan {
+    const crl_ctx *ctx;
+    int64_t B;
+    uint64_t first_env_id;
+    uint32_t *occ, *inv;
+    int32_t *score, *round, *to_move;
+    crl_blokus_stats st;
+
+    int run(const char *fn, uint64_t seed, int T, void *stream) const;
+    int launch(uint64_t seed, int T, void *stream) const override { return run("crl_rollout_launch", seed, T, stream); }
+};
+
+static int blokus_plan_bind(blokus_plan &p, const char *fn, const crl_ctx *ctx, int64_t B, uint64_t first_env_id, uint32_t *occ,
+                            uint32_t *inv, int32_t *score, int32_t *round, int32_t *to_move, const crl_blokus_stats &st)
+{
+    CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_BLOKUS && ctx->blokus, "%s: ctx is not a blokus context", fn);
+    CRL_REQUIRE(B > 0 && B <= ((int64_t)1 << 28), "%s: B=%lld out of range", fn, (long long)B);
+    CRL_REQUIRE(occ && inv && score && round && to_move, "%s: NULL state pointer", fn);
+    CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.len_sum && st.score_sum, "%s: NULL stats pointer", fn);
+    p.ctx = ctx; p.B = B; p.first_env_id = first_env_id;
+    p.occ = occ; p.inv = inv; p.score = score; p.round = round; p.to_move = to_move;
+    p.st = st;
+    return CRL_OK;
+}
+
+int blokus_plan::run(const char *fn, const uint64_t seed, const int T, void *stream) const
+{
+    CRL_REQUIRE(T >= 0 && T <= (1 << 24), "%s: T=%d out of range", fn, T);
+    if (T == 0) return CRL_OK;
+    hipLaunchKernelGGL(blokus_rollout_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const BlkTables *)ctx->blokus, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, T,
+                       occ, inv, score, round, to_move, st);
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
 extern "C" {
 
 int crl_blokus_create(crl_ctx **out)
@@ -2166,15 +2203,22 @@ int crl_blokus_rollout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t fi
                        uint32_t *occ, uint32_t *inv, int32_t *score, int32_t *round, int32_t *to_move,
                        crl_blokus_stats st, void *stream)
 {
-    BLK_CTX_CHECK("crl_blokus_rollout");
-    CRL_REQUIRE(occ && inv && score && round && to_move, "crl_blokus_rollout: NULL state pointer");
-    CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.len_sum && st.score_sum, "crl_blokus_rollout: NULL stats pointer");
-    CRL_REQUIRE(T >= 0 && T <= (1 << 24), "crl_blokus_rollout: T=%d out of range", T);
-    if (T == 0) return CRL_OK;
-    hipLaunchKernelGGL(blokus_rollout_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const BlkTables *)ctx->blokus, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, T,
-                       occ, inv, score, round, to_move, st);
-    CRL_LAUNCH_CHECK();
+    blokus_plan plan;
+    if (const int rc = blokus_plan_bind(plan, "crl_blokus_rollout", ctx, B, first_env_id, occ, inv, score, round, to_move, st)) return rc;
+    return plan.run("crl_blokus_rollout", seed, T, stream);
+}
+
+int crl_blokus_rollout_bind(const crl_ctx *ctx, int64_t B, uint64_t first_env_id, uint32_t *occ, uint32_t *inv, int32_t *score,
+                            int32_t *round, int32_t *to_move, crl_blokus_stats st, crl_plan **out)
+{
+    CRL_REQUIRE(out != nullptr, "crl_blokus_rollout_bind: plan is NULL");
+    *out = nullptr;
+    blokus_plan *plan = new blokus_plan();
+    if (const int rc = blokus_plan_bind(*plan, "crl_blokus_rollout_bind", ctx, B, first_env_id, occ, inv, score, round, to_move, st)) {
+        delete plan;
+        return rc;
+    }
+    *out = plan;
     return CRL_OK;
 }
 

@@ -168,6 +168,19 @@ int crl_stream_wait_mapped(void *stream, uint32_t *flag_device, const volatile u
     return crl_spin_mapped(stream, flag_host, seq, timeout_s, "crl_stream_wait_mapped");
 }
 
+// ---- launch plans: the game's own bind entry made the plan; launching and freeing are the same for all three
+int crl_rollout_launch(const crl_plan *plan, uint64_t seed, int T, void *stream)
+{
+    CRL_REQUIRE(plan != nullptr, "crl_rollout_launch: plan is NULL");
+    return plan->launch(seed, T, stream);
+}
+
+int crl_rollout_unbind(crl_plan *plan)
+{
+    delete plan;
+    return CRL_OK;
+}
+
 int crl_diag_bounds(uint32_t *out12)
 {
     CRL_REQUIRE(out12 != nullptr, "crl_diag_bounds: out12 is NULL");

@@ -44,6 +44,14 @@ struct crl_ctx {
 
 void crl_set_error(const char *fmt, ...);
 
+// a launch plan (include/colosseum_hip.h, "launch plans"): the arguments of a rollout entry that stay the same from call to
+// call, checked once, with the geometry that does not depend on T.  Each game derives its own (tron.hip, ttt.hip,
+// blokus.hip); nothing changes after bind, so `launch` is const and safe from several threads.
+struct crl_plan {
+    virtual ~crl_plan() {}
+    virtual int launch(uint64_t seed, int T, void *stream) const = 0;
+};
+
 #define CRL_REQUIRE(cond, ...)                                   \
     do {                                                         \
         if (!(cond)) { crl_set_error(__VA_ARGS__); return CRL_EINVAL; } \

@@ -5146,37 +5146,52 @@ int crl_tron_step(const crl_ctx *ctx, int64_t B,
     return CRL_OK;
 }
 
-static int tron_rollout_impl(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T,
-                             int8_t *board, int16_t *heads, int8_t *dirs, int8_t *deaths,
-                             crl_tron_stats st, uint32_t flags, void *stream, hipEvent_t ev_start, hipEvent_t ev_stop)
+// The arguments of crl_tron_rollout that stay the same from launch to launch (include/colosseum_hip.h, "launch plans"),
+// checked, with every piece of launch geometry that does not depend on T.  crl_tron_rollout / _timed make one on the stack
+// per call; crl_tron_rollout_bind keeps one on the heap for crl_rollout_launch.
+struct tron_plan : crl_plan {
+    const crl_ctx *ctx;
+    int64_t B;
+    uint64_t first_env_id;
+    int8_t *board;
+    int16_t *heads;
+    int8_t *dirs, *deaths;
+    crl_tron_stats st;
+    uint32_t flags;
+    bool aligned16, small;
+    TronGeom g;
+    TronPad pad;
+    TronBits bits, qb;
+    size_t lds_q;
+
+    int bind(const char *fn, const crl_ctx *ctx_, int64_t B_, uint64_t first_env_id_, int8_t *board_, int16_t *heads_,
+             int8_t *dirs_, int8_t *deaths_, const crl_tron_stats &st_, uint32_t flags_);
+    int run(const char *fn, uint64_t seed, int T, void *stream, hipEvent_t ev_start, hipEvent_t ev_stop) const;
+    int launch(uint64_t seed, int T, void *stream) const override { return run("crl_rollout_launch", seed, T, stream, nullptr, nullptr); }
+};
+
+int tron_plan::bind(const char *fn, const crl_ctx *ctx_, int64_t B_, uint64_t first_env_id_, int8_t *board_, int16_t *heads_,
+                    int8_t *dirs_, int8_t *deaths_, const crl_tron_stats &st_, uint32_t flags_)
 {
-    // every launch of the rollout goes through here: with events, the FIRST launch carries the start event and the LAST one
-    // the stop event in the dispatch itself (hipExtLaunchKernelGGL) -- no marker packets around the kernels
-    bool first_launch = true;
-    auto launch = [&](auto kernel, const dim3 grid, const dim3 block, const size_t lds_bytes, const bool last, auto... args) {
-        hipEvent_t e0 = first_launch ? ev_start : nullptr, e1 = last ? ev_stop : nullptr;
-        first_launch = false;
-        if (e0 || e1) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds_bytes, (hipStream_t)stream, e0, e1, 0u, args...);
-        else hipLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t)stream, args...);
-    };
-    TRON_CTX_CHECK("crl_tron_rollout");
-    CRL_REQUIRE(board && heads && dirs && deaths, "crl_tron_rollout: NULL state pointer");
-    TRON_STATS_CHECK("crl_tron_rollout");
-    CRL_REQUIRE(T >= 0 && T <= (1 << 24), "crl_tron_rollout: T=%d out of range", T);
-    CRL_REQUIRE((flags & ~(CRL_ROLLOUT_NO_LDS | CRL_ROLLOUT_BYTES | CRL_ROLLOUT_BITS | CRL_ROLLOUT_QUAD | CRL_ROLLOUT_QBITS | CRL_ROLLOUT_GQUAD | CRL_ROLLOUT_PAIR)) == 0, "crl_tron_rollout: unknown flags 0x%x", flags);
-    const crl_tron_cfg &cfg = ctx->tron;
+    CRL_REQUIRE(ctx_ != nullptr && ctx_->game == CRL_GAME_TRON, "%s: ctx is not a tron context", fn);
+    CRL_REQUIRE(B_ > 0 && B_ <= ((int64_t)1 << 31), "%s: B=%lld out of range", fn, (long long)B_);
+    CRL_REQUIRE(board_ && heads_ && dirs_ && deaths_, "%s: NULL state pointer", fn);
+    CRL_REQUIRE(st_.tcount && st_.tstep && st_.n_episodes && st_.win_count && st_.len_sum && st_.ret_sum &&
+                st_.last_winners && st_.last_len, "%s: NULL stats pointer", fn);
+    CRL_REQUIRE((flags_ & ~(CRL_ROLLOUT_NO_LDS | CRL_ROLLOUT_BYTES | CRL_ROLLOUT_BITS | CRL_ROLLOUT_QUAD | CRL_ROLLOUT_QBITS | CRL_ROLLOUT_GQUAD | CRL_ROLLOUT_PAIR)) == 0, "%s: unknown flags 0x%x", fn, flags_);
+    const crl_tron_cfg &cfg = ctx_->tron;
     const int NN = cfg.N * cfg.N;
-    CRL_REQUIRE((NN % 16 != 0) || (((uintptr_t)board & 15) == 0), "crl_tron_rollout: board must be 16-byte aligned");
-    if (T == 0) return CRL_OK;
-    const TronRollout kernel = tron_pick_rollout(cfg, B, T, flags, ((uintptr_t)board & 15) == 0);
-    const TronGeom g = geom_of(cfg);
-    const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
+    CRL_REQUIRE((NN % 16 != 0) || (((uintptr_t)board_ & 15) == 0), "%s: board must be 16-byte aligned", fn);
+    ctx = ctx_; B = B_; first_env_id = first_env_id_;
+    board = board_; heads = heads_; dirs = dirs_; deaths = deaths_;
+    st = st_; flags = flags_;
+    aligned16 = ((uintptr_t)board_ & 15) == 0;
+    g = geom_of(cfg);
     // LDS-resident kernels.  Byte slabs: 256 games per workgroup on boards up to 20x20, 64 (one wave) up to 40x40.
     // Bitboards (T >= 256): 256 games per workgroup either way; the replay takes the byte slabs one wave at a time
     // on the larger boards.
-    const bool small = cfg.N <= kLdsMaxNSmall;
-    const TronPad pad = pad_of(cfg, small ? kRowBytesSmall : kRowBytesLarge);
-    TronBits bits;
+    small = cfg.N <= kLdsMaxNSmall;
+    pad = pad_of(cfg, small ? kRowBytesSmall : kRowBytesLarge);
     {
         const int max_n = small ? kLdsMaxNSmall : kLdsMaxNLarge;
         const int max_w = (((max_n + 2) * (max_n + 1) + 31) / 32 + 3) & ~3;
@@ -5187,9 +5202,28 @@ static int tron_rollout_impl(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
     // the LDS serves eight lanes (two games) at a time: a game stride of 16 dwords mod 32 banks keeps the two games on
     // different banks (the lane-per-game kernel's 4 mod 32 would overlap them)
     constexpr int kQBitsPad = 64;                               // bytes behind a game's two slabs: the four junk words + bank padding
-    TronBits qb = bits;
+    qb = bits;
     qb.stride = bits.stride - 16 + kQBitsPad;
-    const size_t lds_q = std::max((size_t)64 * qb.stride, (size_t)16 * pad.stride);
+    lds_q = std::max((size_t)64 * qb.stride, (size_t)16 * pad.stride);
+    return CRL_OK;
+}
+
+int tron_plan::run(const char *fn, const uint64_t seed, const int T, void *stream, hipEvent_t ev_start, hipEvent_t ev_stop) const
+{
+    // every launch of the rollout goes through here: with events, the FIRST launch carries the start event and the LAST one
+    // the stop event in the dispatch itself (hipExtLaunchKernelGGL) -- no marker packets around the kernels
+    bool first_launch = true;
+    auto launch = [&](auto kernel, const dim3 grid, const dim3 block, const size_t lds_bytes, const bool last, auto... args) {
+        hipEvent_t e0 = first_launch ? ev_start : nullptr, e1 = last ? ev_stop : nullptr;
+        first_launch = false;
+        if (e0 || e1) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds_bytes, (hipStream_t)stream, e0, e1, 0u, args...);
+        else hipLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t)stream, args...);
+    };
+    CRL_REQUIRE(T >= 0 && T <= (1 << 24), "%s: T=%d out of range", fn, T);
+    if (T == 0) return CRL_OK;
+    const crl_tron_cfg &cfg = ctx->tron;
+    const TronRollout kernel = tron_pick_rollout(cfg, B, T, flags, aligned16);
+    const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
     // the lane-per-game kernels take all T steps in one launch, the lane-per-player ones at most kTronLaunchMaxT
     const bool per_game = kernel == TronRollout::Global || kernel == TronRollout::Bytes || kernel == TronRollout::Bits;
     const int chunk = per_game ? T : kTronLaunchMaxT;
@@ -5227,7 +5261,7 @@ static int tron_rollout_impl(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
             const int threads = (use_bits || small) ? 256 : 64;
             const size_t byte_slabs = (size_t)(small ? 256 : 64) * pad.stride;
             const size_t lds_bytes = use_bits ? std::max(byte_slabs, (size_t)256 * bits.stride) : byte_slabs;
-            CRL_REQUIRE(lds_bytes <= (size_t)kLdsDynamic, "crl_tron_rollout: internal: %zu bytes of LDS", lds_bytes);
+            CRL_REQUIRE(lds_bytes <= (size_t)kLdsDynamic, "%s: internal: %zu bytes of LDS", fn, lds_bytes);
             const dim3 grid(blocks_for(B, threads)), block(threads);
             // opt in to the LDS, then launch: `mid` is what the kernel takes between pad and B (the bitboard geometry, or nothing)
             auto go = [&](auto k, auto... mid) -> int {
@@ -5259,7 +5293,9 @@ int crl_tron_rollout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t firs
                      int8_t *board, int16_t *heads, int8_t *dirs, int8_t *deaths,
                      crl_tron_stats st, uint32_t flags, void *stream)
 {
-    return tron_rollout_impl(ctx, B, seed, first_env_id, T, board, heads, dirs, deaths, st, flags, stream, nullptr, nullptr);
+    tron_plan plan;
+    if (const int rc = plan.bind("crl_tron_rollout", ctx, B, first_env_id, board, heads, dirs, deaths, st, flags)) return rc;
+    return plan.run("crl_tron_rollout", seed, T, stream, nullptr, nullptr);
 }
 
 int crl_tron_rollout_timed(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T,
@@ -5267,8 +5303,23 @@ int crl_tron_rollout_timed(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_
                            crl_tron_stats st, uint32_t flags, void *stream, void *start_event, void *stop_event)
 {
     CRL_REQUIRE(T > 0 || (!start_event && !stop_event), "crl_tron_rollout_timed: no launch to attach the events to (T = 0)");
-    return tron_rollout_impl(ctx, B, seed, first_env_id, T, board, heads, dirs, deaths, st, flags, stream,
-                             (hipEvent_t)start_event, (hipEvent_t)stop_event);
+    tron_plan plan;
+    if (const int rc = plan.bind("crl_tron_rollout", ctx, B, first_env_id, board, heads, dirs, deaths, st, flags)) return rc;
+    return plan.run("crl_tron_rollout", seed, T, stream, (hipEvent_t)start_event, (hipEvent_t)stop_event);
+}
+
+int crl_tron_rollout_bind(const crl_ctx *ctx, int64_t B, uint64_t first_env_id, int8_t *board, int16_t *heads, int8_t *dirs,
+                          int8_t *deaths, crl_tron_stats st, uint32_t flags, crl_plan **out)
+{
+    CRL_REQUIRE(out != nullptr, "crl_tron_rollout_bind: plan is NULL");
+    *out = nullptr;
+    tron_plan *plan = new tron_plan();
+    if (const int rc = plan->bind("crl_tron_rollout_bind", ctx, B, first_env_id, board, heads, dirs, deaths, st, flags)) {
+        delete plan;
+        return rc;
+    }
+    *out = plan;
+    return CRL_OK;
 }
 
 #ifdef CRL_QUAD_STAMPS

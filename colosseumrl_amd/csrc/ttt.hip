@@ -1460,16 +1460,39 @@ static int ttt_playout_launch(const char *fn, const crl_ctx *ctx, int64_t B, uin
     return CRL_OK;
 }
 
-static int ttt_rollout_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T,
-                              const double *noise, uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats st, void *stream)
+// The arguments of crl_ttt_rollout that stay the same from launch to launch (include/colosseum_hip.h, "launch plans"), checked.
+// The win table is looked up per launch: it depends on the device that is current then.
+struct ttt_plan : crl_plan {
+    const crl_ctx *ctx;
+    int64_t B;
+    uint64_t first_env_id;
+    uint32_t *occ;
+    int8_t *winner, *to_move;
+    crl_ttt_stats st;
+    ttt_dirs dd;
+
+    int run(const char *fn, uint64_t seed, int T, const double *noise, void *stream) const;
+    int launch(uint64_t seed, int T, void *stream) const override { return run("crl_rollout_launch", seed, T, nullptr, stream); }
+};
+
+static int ttt_plan_bind(ttt_plan &p, const char *fn, const crl_ctx *ctx, int64_t B, uint64_t first_env_id, uint32_t *occ,
+                         int8_t *winner, int8_t *to_move, const crl_ttt_stats &st)
 {
     TTT_CTX_CHECK(fn);
     CRL_REQUIRE(occ && winner && to_move, "%s: NULL state pointer", fn);
     CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.draw_count && st.len_sum, "%s: NULL stats pointer", fn);
+    p.ctx = ctx; p.B = B; p.first_env_id = first_env_id;
+    p.occ = occ; p.winner = winner; p.to_move = to_move;
+    p.st = st;
+    p.dd = dirs_of(ctx);
+    return CRL_OK;
+}
+
+int ttt_plan::run(const char *fn, const uint64_t seed, const int T, const double *noise, void *stream) const
+{
     CRL_REQUIRE(T >= 0 && T <= (1 << 24), "%s: T=%d out of range", fn, T);
     TTT_NOISE_CHECK(fn);
     if (T == 0) return CRL_OK;
-    const ttt_dirs dd = dirs_of(ctx);
     const uint32_t *win_tab = ttt_win_table_here(ctx);
     if (noise) {
         TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_rollout_tactical_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd, B,
@@ -1481,6 +1504,14 @@ static int ttt_rollout_launch(const char *fn, const crl_ctx *ctx, int64_t B, uin
     }
     CRL_LAUNCH_CHECK();
     return CRL_OK;
+}
+
+static int ttt_rollout_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T,
+                              const double *noise, uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats st, void *stream)
+{
+    ttt_plan plan;
+    if (const int rc = ttt_plan_bind(plan, fn, ctx, B, first_env_id, occ, winner, to_move, st)) return rc;
+    return plan.run(fn, seed, T, noise, stream);
 }
 
 extern "C" {
@@ -1688,6 +1719,20 @@ int crl_ttt_rollout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first
                     int8_t *to_move, crl_ttt_stats st, void *stream)
 {
     return ttt_rollout_launch("crl_ttt_rollout", ctx, B, seed, first_env_id, T, nullptr, occ, winner, to_move, st, stream);
+}
+
+int crl_ttt_rollout_bind(const crl_ctx *ctx, int64_t B, uint64_t first_env_id, uint32_t *occ, int8_t *winner, int8_t *to_move,
+                         crl_ttt_stats st, crl_plan **out)
+{
+    CRL_REQUIRE(out != nullptr, "crl_ttt_rollout_bind: plan is NULL");
+    *out = nullptr;
+    ttt_plan *plan = new ttt_plan();
+    if (const int rc = ttt_plan_bind(*plan, "crl_ttt_rollout_bind", ctx, B, first_env_id, occ, winner, to_move, st)) {
+        delete plan;
+        return rc;
+    }
+    *out = plan;
+    return CRL_OK;
 }
 
 // ---- the tactical agent's entries (the contract is in include/colosseum_hip.h)

@@ -811,6 +811,32 @@ int crl_ttt_playout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
                              const int32_t *cand, int A, int R,
                              uint32_t *wins, uint32_t *played, uint32_t *len_sum, double noise, uint32_t flags, void *stream);
 
+/* ------------------------------------------------------------------ launch plans: bind a rollout's arguments once
+ * A caller that launches short rollouts in a loop passes the same context, batch, state and statistics pointers and flags
+ * every time; only the seed, the number of steps and the stream change.  A plan holds the constant part: a bind entry runs
+ * every check of its rollout entry (context, B, NULL pointers, alignment, flags, statistics -- same codes, messages under the
+ * bind entry's name, nothing touches the device) and stores the arguments with the launch geometry that does not depend on
+ * T.  crl_rollout_launch then checks T (0 .. 2^24; T = 0 returns CRL_OK and launches nothing) and issues exactly the
+ * launches the rollout entry issues for the same arguments -- the same kernel choice per T, the same split of long Tron
+ * rollouts -- so the results are bit-identical and the call is as asynchronous and graph-capturable as that entry.
+ * Added under revision 113: new entries only, no existing struct, argument list or RNG contract changed.
+ * Lifetime: a plan refers to its context and to the caller's buffers; unbind it before crl_destroy of the context, and bind
+ * a new one when a buffer moves.  A plan is immutable after bind: any number of host threads may launch one plan
+ * concurrently (on different streams, or ordered by the stream they share).  crl_rollout_unbind frees a plan once no
+ * launch call on it is in progress (launches already queued on a stream keep nothing of the plan); NULL is harmless.
+ * Errors of crl_rollout_launch (CRL_EINVAL): a NULL plan, T outside the range; CRL_EHIP as the rollout entries. */
+typedef struct crl_plan crl_plan;   /* opaque, immutable after bind */
+int crl_tron_rollout_bind(const crl_ctx *ctx, int64_t B, uint64_t first_env_id,
+                          int8_t *board, int16_t *heads, int8_t *dirs, int8_t *deaths,
+                          crl_tron_stats stats, uint32_t flags, crl_plan **plan);
+int crl_ttt_rollout_bind(const crl_ctx *ctx, int64_t B, uint64_t first_env_id,
+                         uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats stats, crl_plan **plan);
+int crl_blokus_rollout_bind(const crl_ctx *ctx, int64_t B, uint64_t first_env_id,
+                            uint32_t *occ, uint32_t *inv, int32_t *score, int32_t *round, int32_t *to_move,
+                            crl_blokus_stats stats, crl_plan **plan);
+int crl_rollout_launch(const crl_plan *plan, uint64_t seed, int T, void *stream);
+int crl_rollout_unbind(crl_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

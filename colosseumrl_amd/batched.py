@@ -105,6 +105,13 @@ def _unit(name: str, v) -> float:
     return float(v)
 
 
+def _exploration(name: str, v) -> int:
+    """cexp of crl_ttt_mcts: round(256 * v), in [0, 65535]"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) * 256.0 <= 65535.0:   # (NaN fails too)
+        raise ValueError("%s must be a number in [0, %g], got %r" % (name, 65535 / 256, v))
+    return int(round(256.0 * float(v)))
+
+
 def _one_of(name: str, v, choices):
     if v not in choices:
         raise ValueError("%s must be %s, got %r" % (name, " or ".join(repr(c) for c in choices), v))
@@ -861,6 +868,41 @@ class TTTBatch(_RolloutStepper):
         mover = self.to_move.to(torch.int64).clamp(0, self.P - 1)       # (other values: the position skips every row)
         mine = torch.gather(o["wins"], 2, mover.view(-1, 1, 1).expand(self.B, self.n_cells, 1)).squeeze(2)
         return _flat_mc_pick(2 * mine + o["draws"], o["played"], cells)
+
+    # -- Monte Carlo tree search; the contract is with crl_ttt_mcts in include/colosseum_hip.h
+    @functools.cached_property
+    def mcts_max_simulations(self) -> int:
+        """the most simulations ``mcts`` takes on this board (``crl_ttt_mcts_max_simulations``: the tree stays in LDS)"""
+        rc = self._lib.crl_ttt_mcts_max_simulations(self._ctx.handle)
+        if rc < 0:
+            check(rc, "crl_ttt_mcts_max_simulations")
+        return int(rc)
+
+    def mcts(self, simulations: int, playouts: int = 16, seed: int = 0, exploration: float = 1.0, out: Optional[dict] = None):
+        """A tree search (UCT) for the player to move in every game, ONE launch (``crl_ttt_mcts``): each game builds a tree
+        of its own by ``simulations`` descents (at most ``mcts_max_simulations``), each new leaf valued by ``playouts`` (1 ..
+        1024) random games to their end; ``exploration`` (0 .. 65535 / 256; 0 = pure exploitation) multiplies
+        sqrt(log2 n_parent / n_child) on a value scale of 0 .. 1.  Finished positions are skipped.  The draws are keyed by
+        ``seed``, the game ids and ``tcount`` as the counter base (the call reads the state and writes none of it).
+        Returns {'visits', 'value' int32 [B, cells]: simulations through the root's child at each cell and its half-points
+        (2 per won playout, 1 per drawn one) for the mover, 'nodes' int32 [B], 'best' int32 [B]: the most visited cell (ties:
+        the larger value, then the lowest cell; -1 for a skipped position)}; ``out`` reuses such a dict.  The visit counts
+        are the policy target of an AlphaZero-style trainer.  No host synchronisation; capturable into a graph."""
+        S = _int_in("simulations", simulations, 1, self.mcts_max_simulations)
+        R = _int_in("playouts", playouts, 1, 1024)
+        cexp = _exploration("exploration", exploration)
+        i32 = torch.int32
+        out = _out_dict(out, {"visits": (i32, (self.B, self.n_cells)), "value": (i32, (self.B, self.n_cells)),
+                              "nodes": (i32, (self.B,)), "best": (i32, (self.B,))}, self.device)
+        self._call("crl_ttt_mcts", _seed(seed), self.first_env_id, _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move),
+                   _ptr(self.tcount), S, R, cexp, _ptr(out["visits"]), _ptr(out["value"]), _ptr(out["nodes"]), _ptr(out["best"]), 0)
+        return out
+
+    def mcts_action(self, simulations: int, playouts: int = 16, seed: int = 0, exploration: float = 1.0,
+                    out: Optional[dict] = None) -> torch.Tensor:
+        """``mcts``'s most visited cell as an int64 [B] action for ``step_single`` (-1 where the game is over): the arg-max
+        is the kernel's own ``best``, only widened here.  No host synchronisation; capturable."""
+        return self.mcts(simulations, playouts, seed, exploration, out)["best"].to(torch.int64)
 
     def rollout(self, steps: int, seed: int = 0):
         self._rollout_plan(steps, seed)

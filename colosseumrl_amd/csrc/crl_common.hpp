@@ -201,6 +201,7 @@ __device__ __forceinline__ philox_out philox4x32_10(uint32_t c0, uint32_t c1, ui
 #define CRL_TAG_TTT_PLAYOUT    0x54500000u   /* random playouts (crl_ttt_playout) */
 #define CRL_TAG_TTT_TACTICAL         0x54630000u   /* the tactical agent's draws (crl_ttt_sample_tactical) */
 #define CRL_TAG_TTT_TACTICAL_PLAYOUT 0x54430000u   /* playouts, tactical agent (crl_ttt_playout_tactical) */
+#define CRL_TAG_TTT_MCTS       0x544D0000u   /* the playouts of the tree search (crl_ttt_mcts) */
 #define CRL_TAG_BLOKUS_PLAYOUT 0x42500000u   /* random playouts (crl_blokus_playout) */
 #define CRL_TAG_TRON_PLAYOUT       0x54700000u   /* playouts, random agent (crl_tron_playout) */
 #define CRL_TAG_TRON_AVOID_PLAYOUT 0x54610000u   /* playouts, avoid agent (crl_tron_playout with CRL_PLAYOUT_AVOID) */

@@ -127,9 +127,8 @@ __device__ __forceinline__ int nth_set_bit(const uint32_t m, int r)
 // 2 KB of LDS filled by the 256 threads of the workgroup (ttt_fill_rank_table; the caller puts a __syncthreads behind it).
 // Two levels by arithmetic find the byte, one LDS read the bit in it: 15 vector instructions + 1 LDS read where the
 // five-level search takes 26 (in the rollout's ply, where this chain is a third of the instructions).
-__device__ __forceinline__ void ttt_fill_rank_table(uint8_t (&tab)[256 * 8])
+__device__ __forceinline__ uint2 ttt_rank_row(const uint32_t t)      // the eight bytes of row t (a byte value)
 {
-    const uint32_t t = threadIdx.x & 255u;
     uint32_t lo = 0, hi = 0, n = 0;
 #pragma unroll
     for (uint32_t bit = 0; bit < 8; ++bit) {
@@ -139,7 +138,13 @@ __device__ __forceinline__ void ttt_fill_rank_table(uint8_t (&tab)[256 * 8])
         hi |= (n < 4u) ? 0u : v;
         n += set ? 1u : 0u;
     }
-    *reinterpret_cast<uint2 *>(&tab[t * 8]) = make_uint2(lo, hi);
+    return make_uint2(lo, hi);
+}
+
+__device__ __forceinline__ void ttt_fill_rank_table(uint8_t (&tab)[256 * 8])
+{
+    const uint32_t t = threadIdx.x & 255u;
+    *reinterpret_cast<uint2 *>(&tab[t * 8]) = ttt_rank_row(t);
 }
 
 // SMALL: the board has at most 16 cells (3x3, 3x5): the first level falls away.
@@ -1139,6 +1144,250 @@ ttt_playout_tactical_kernel(const ttt_dirs dd, const int64_t B, const uint32_t s
     }
 }
 
+// ---- batched Monte Carlo tree search (crl_ttt_mcts; the contract is in include/colosseum_hip.h).  One wave per tree, the
+// tree in LDS: n[S + 1] and w[S + 1] as dwords, then the child slots as uint16 [S + 1][cells] with 0 = none (the root is
+// nobody's child) -- (S + 1) (8 + 2 cells) bytes, which is what bounds S.  A node's slots are cleared when it is made, so
+// nothing but the root is initialised up front.  The descent is wave-uniform: the position is P words every lane holds
+// alike, the branches are on ballots and on v_readlane results.  While the wave selects, lane e is cell e; while it
+// evaluates, lane r is playout r; while it backs up, lane i is entry i of the path.  The lanes hand values to each other
+// through LDS only across ttt_wave_sync (a compiler fence; the LDS itself executes a wave's accesses in order).
+
+__device__ __forceinline__ void ttt_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the maximum of v over the 64 lanes, in every lane: a running maximum inside each row of 16 lanes by DPP row shifts, the
+// rows joined by the two row broadcasts, lane 63 read back.  A lane without a source (or outside the row mask) sees 0.
+// Every lane of the wave must run it (no lane may sit out a divergent branch around the call).
+__device__ __forceinline__ uint32_t ttt_wave_max(uint32_t v)
+{
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));   // row_shr:1
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));   // row_shr:2
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false));   // row_shr:4
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false));   // row_shr:8
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1, 3
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2, 3
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// a wave-uniform word in a vector register: the descent keeps its copy of the position there, alike in every lane, so
+// that its plies run on the vector unit beside the playouts' and leave the scalar registers to the kernel's arguments
+// (with the position and the line test's temporaries in scalar registers the 13-direction instances spilled them)
+__device__ __forceinline__ uint32_t ttt_in_vgpr(const uint32_t x)
+{
+    uint32_t v;
+    asm("v_mov_b32 %0, %1" : "=v"(v) : "s"(x));
+    return v;
+}
+
+template <class T>
+__device__ __forceinline__ T *ttt_in_vgpr(T *const p)
+{
+    const uint64_t v = (uint64_t)p;
+    return (T *)((uint64_t)ttt_in_vgpr((uint32_t)v) | ((uint64_t)ttt_in_vgpr((uint32_t)(v >> 32)) << 32));
+}
+
+// floor(num / den) for num < 2^52 and 1 <= den < 2^32: the double quotient is within one of it, the remainder decides
+// (the generic 64-bit division is a loop of some hundred instructions, and a selection makes two per cell)
+__device__ __forceinline__ uint64_t ttt_mcts_div(const uint64_t num, const uint32_t den)
+{
+    uint64_t q = (uint64_t)((double)num / (double)den);
+    const int64_t r = (int64_t)(num - q * (uint64_t)den);
+    q = r < 0 ? q - 1u : (r >= (int64_t)den ? q + 1u : q);
+    return q;
+}
+
+// the exact floor square root of x < 2^52
+__device__ __forceinline__ uint64_t ttt_mcts_isqrt(const uint64_t x)
+{
+    uint64_t s = (uint64_t)sqrt((double)x);
+    s = s * s > x ? s - 1u : ((s + 1u) * (s + 1u) <= x ? s + 1u : s);
+    return s;
+}
+
+// the contract's piecewise-linear log2 with 8 fraction bits, n >= 1
+__device__ __forceinline__ uint32_t ttt_mcts_lg(const uint32_t n)
+{
+    const uint32_t m = 31u - (uint32_t)__clz((int)n);
+    return 256u * m + (((n << (31u - m)) >> 23) & 255u);
+}
+
+// LDS, in dwords: [the win-mask table, 2048, if WT][the rank table, 512, if use_rank][a tree of tree_words per wave]
+template <int P, int ND, bool WT>
+__global__ void __launch_bounds__(256)
+ttt_mcts_kernel(const ttt_dirs dd_arg, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi, const uint64_t first_env_id,
+                const uint32_t *occ_arg, const int8_t *winner_arg, const int8_t *to_move_arg, const uint32_t *tcount_arg,
+                const int S, const int R, const uint32_t cexp, const uint32_t tree_words, const int use_rank,
+                uint32_t *visits_arg, uint32_t *value_arg, uint32_t *nodes_arg, int32_t *best_arg,
+                const uint32_t *__restrict__ win_tab)
+{
+    // What the loops branch on stays in scalar registers; the eight pointers (read or written once per position) and the
+    // strides and start masks of the line test move into vector registers, alike in every lane: left where the arguments
+    // arrive, these 16 + 2 ND words are live through every loop and the compiler spilled scalar registers around them.
+    const uint32_t *occ = ttt_in_vgpr(occ_arg), *tcount = ttt_in_vgpr(tcount_arg);
+    const int8_t *winner = ttt_in_vgpr(winner_arg), *to_move = ttt_in_vgpr(to_move_arg);
+    uint32_t *visits = ttt_in_vgpr(visits_arg), *value = ttt_in_vgpr(value_arg), *nodes = ttt_in_vgpr(nodes_arg);
+    int32_t *best = ttt_in_vgpr(best_arg);
+    const bool has_tcount = tcount_arg != nullptr;
+    ttt_dirs dd = dd_arg;
+    if (!WT) {
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            dd.stride[d] = (int32_t)ttt_in_vgpr((uint32_t)dd_arg.stride[d]);
+            dd.start[d] = ttt_in_vgpr(dd_arg.start[d]);
+        }
+    }
+    extern __shared__ __attribute__((aligned(16))) uint32_t mcts_lds[];
+    uint32_t *win_bits = mcts_lds;
+    uint32_t *rank_words = mcts_lds + (WT ? 2048 : 0);
+    const uint8_t (&rank_tab)[256 * 8] = *reinterpret_cast<const uint8_t (*)[256 * 8]>(rank_words);
+    uint32_t *trees = rank_words + (use_rank ? 512 : 0);
+    if (WT) {
+        for (uint32_t i = threadIdx.x; i < 512u; i += blockDim.x)
+            reinterpret_cast<uint4 *>(win_bits)[i] = reinterpret_cast<const uint4 *>(win_tab)[i];
+    }
+    if (use_rank) {                                              // ttt_fill_rank_table, for a workgroup of any size
+        for (uint32_t t = threadIdx.x; t < 256u; t += blockDim.x) reinterpret_cast<uint2 *>(rank_words)[t] = ttt_rank_row(t);
+    }
+    __syncthreads();
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), n_waves = (int)(blockDim.x >> 6);
+    const int cells = dd.n_cells;
+    uint32_t *n_arr = trees + (uint32_t)wave * tree_words, *w_arr = n_arr + (S + 1);
+    uint16_t *child = reinterpret_cast<uint16_t *>(w_arr + (S + 1));
+    const bool cell_lane = lane < cells;
+    for (int64_t b = (int64_t)blockIdx.x * n_waves + wave; b < B; b += (int64_t)gridDim.x * n_waves) {
+        uint32_t o0[P];                                          // (the same words in every lane)
+#pragma unroll
+        for (int p = 0; p < P; ++p) o0[p] = ttt_in_vgpr((uint32_t)__builtin_amdgcn_readfirstlane((int)occ[p * B + b]));
+        const int w0 = __builtin_amdgcn_readfirstlane((int)winner[b]), tm0 = __builtin_amdgcn_readfirstlane((int)to_move[b]);
+        const uint32_t tc = has_tcount ? (uint32_t)__builtin_amdgcn_readfirstlane((int)tcount[b]) : 0u;
+        const uint32_t g = (uint32_t)(first_env_id + (uint64_t)b);
+        if (w0 >= 0 || ttt_union<P>(o0) == dd.full || (unsigned)tm0 >= (unsigned)P) {   // a skipped position: zeros
+            if (cell_lane) { visits[b * cells + lane] = 0u; value[b * cells + lane] = 0u; }
+            if (lane == 0) { nodes[b] = 0u; best[b] = -1; }
+            continue;
+        }
+        if (lane == 0) { n_arr[0] = 0u; w_arr[0] = 0u; }
+        if (cell_lane) child[lane] = 0;
+        ttt_wave_sync();
+        int nn = 1;                                              // nodes so far
+        for (int s = 0; s < S; ++s) {
+            uint32_t o[P];
+#pragma unroll
+            for (int p = 0; p < P; ++p) o[p] = o0[p];
+            int w = -1, tm = (int)ttt_in_vgpr((uint32_t)tm0), v = 0, d = 0, term = 0, ws = -1, rw;   // (the mover: with the position)
+            uint32_t path = 0;                                   // lane i: the node at depth i of this simulation's path
+            for (;;) {
+                const uint32_t E = dd.full & ~ttt_union<P>(o);
+                const bool in_e = lane < 32 && ((E >> (lane & 31)) & 1u);
+                CRL_BOUNDS_LT(in_e ? v * cells + lane : 0, (S + 1) * cells, 210);
+                const uint32_t cu = in_e ? child[v * cells + lane] : 0u;
+                CRL_BOUNDS_LT(cu, S + 1, 211);
+                const unsigned long long fresh = __ballot(in_e && cu == 0u);
+                int e, u;
+                if (fresh) {                                     // expand: the lowest cell without a child
+                    e = (int)__builtin_ctzll(fresh);
+                    u = nn++;
+                    CRL_BOUNDS_LT(u, S + 1, 212);
+                    if (lane == e) child[v * cells + e] = (uint16_t)u;
+                    if (cell_lane) child[u * cells + lane] = 0;
+                    if (lane == 0) { n_arr[u] = 0u; w_arr[u] = 0u; }
+                } else {                                         // select: lane e scores the child at cell e
+                    const uint32_t lgv = ttt_mcts_lg(n_arr[v]);
+                    uint32_t key = 0;
+                    if (in_e) {
+                        const uint32_t nu = n_arr[cu], wu = w_arr[cu];
+                        const uint64_t exploit = ttt_mcts_div((uint64_t)wu << 15, nu * (uint32_t)R);
+                        const uint64_t X = ttt_mcts_div((uint64_t)lgv << 24, nu);
+                        const uint64_t score = exploit + (((uint64_t)cexp * ttt_mcts_isqrt(X)) >> 8);   // < 2^26
+                        key = (((uint32_t)score << 5) | (uint32_t)(31 - lane)) + 1u;     // ties: the lowest cell
+                    }
+                    const uint32_t top = ttt_wave_max(key);      // (all lanes: outside the branch above)
+                    e = 31 - (int)((top - 1u) & 31u);
+                    u = __builtin_amdgcn_readlane((int)cu, e);
+                }
+                d += 1;
+                path = lane == d ? (uint32_t)u : path;
+                ttt_step_core<P, ND, WT>(dd, o, w, tm, e, rw, term, ws, win_bits);
+                term = __builtin_amdgcn_readfirstlane(term);     // (every lane played the same ply)
+                ws = __builtin_amdgcn_readfirstlane(ws);
+                if (fresh || term || d >= 32) break;             // (d >= 32: never, a ply that fills the board is terminal)
+                v = u;
+            }
+            // ---- evaluate the leaf: the outcome of the ply into it, or R random playouts, lane r playout r
+            uint32_t cnt[P], draws;                              // (wave-uniform sums, kept in vector registers)
+#pragma unroll
+            for (int p = 0; p < P; ++p) cnt[p] = ttt_in_vgpr(term && ws == p ? (uint32_t)R : 0u);
+            draws = ttt_in_vgpr(term && ws < 0 ? (uint32_t)R : 0u);
+            if (!term) {
+                for (int r0 = 0; r0 < R; r0 += 64) {
+                    const uint32_t r = (uint32_t)(r0 + lane);
+                    const bool live = r < (uint32_t)R;
+                    int wn = -1;
+                    if (live) {
+                        uint32_t po[P];
+#pragma unroll
+                        for (int p = 0; p < P; ++p) po[p] = o[p];
+                        int pw = w, ptm = tm, pterm = 0, prw, pws = -1;
+                        const uint32_t c2 = ((uint32_t)s << 16) | r;
+                        uint32_t c = tc + (uint32_t)d;
+                        philox_out rnd = philox4x32_10<true>(g, c >> 3, c2, CRL_TAG_TTT_MCTS, seed_lo, seed_hi);
+                        for (int left = 33; !pterm && left > 0; --left) {   // ttt_playout_kernel's random ply (left: never runs out)
+                            const uint32_t empty = dd.full & ~ttt_union<P>(po);
+                            const uint32_t n_empty = (uint32_t)__popc(empty);       // (not 0: the game is running)
+                            const uint32_t sel = (c >> 1) & 3u;
+                            uint32_t word = rnd.w[0];
+                            word = (sel == 1) ? rnd.w[1] : word;
+                            word = (sel == 2) ? rnd.w[2] : word;
+                            word = (sel == 3) ? rnd.w[3] : word;
+                            word = (c & 1u) ? word * (n_empty + 1u) : word;
+                            const uint32_t rank = __umulhi(word, n_empty);
+                            const int act = use_rank ? (int)nth_set_bit_tab<WT>(rank_tab, empty, rank) : nth_set_bit(empty, (int)rank);
+                            ttt_step_core<P, ND, WT>(dd, po, pw, ptm, act, prw, pterm, pws, win_bits);
+                            c += 1u;
+                            if ((c & 7u) == 0u && !pterm) rnd = philox4x32_10<true>(g, c >> 3, c2, CRL_TAG_TTT_MCTS, seed_lo, seed_hi);
+                        }
+                        wn = pws;
+                    }
+#pragma unroll
+                    for (int p = 0; p < P; ++p) cnt[p] += ttt_in_vgpr((uint32_t)__builtin_popcountll(__ballot(live && wn == p)));
+                    draws += ttt_in_vgpr((uint32_t)__builtin_popcountll(__ballot(live && wn < 0)));
+                }
+            }
+            // ---- back up: lane i adds to the node at depth i (distinct nodes: no atomics), q = who moved into it
+            ttt_wave_sync();
+            if (lane <= d) {
+                uint32_t add = 0;
+                if (lane > 0) {
+                    const int q = (tm0 + lane - 1) % P;
+                    uint32_t mine = 0;
+#pragma unroll
+                    for (int p = 0; p < P; ++p) mine = (p == q) ? cnt[p] : mine;
+                    add = 2u * mine + draws;
+                }
+                CRL_BOUNDS_LT(path, S + 1, 213);
+                n_arr[path] += 1u;
+                w_arr[path] += add;
+            }
+            ttt_wave_sync();
+        }
+        // ---- the root's children: visits, value, the most visited (then the larger w, then the lowest cell)
+        const uint32_t cu = cell_lane ? child[lane] : 0u;
+        const uint32_t vis = cu ? n_arr[cu] : 0u, val = cu ? w_arr[cu] : 0u;
+        if (cell_lane) { visits[b * cells + lane] = vis; value[b * cells + lane] = val; }
+        const uint32_t top_n = ttt_wave_max(vis);                // (a child has n >= 1)
+        const bool most = cu != 0u && vis == top_n;
+        const uint32_t top_w = ttt_wave_max(most ? val + 1u : 0u);
+        const unsigned long long pick = __ballot(most && val + 1u == top_w);
+        if (lane == 0) { nodes[b] = (uint32_t)nn; best[b] = pick ? (int32_t)__builtin_ctzll(pick) : -1; }
+        ttt_wave_sync();                                         // the next tree starts behind these reads
+    }
+}
+
 __global__ void __launch_bounds__(256)
 ttt_reset_kernel(const int P, const int64_t B, const uint8_t *__restrict__ mask, uint32_t *__restrict__ occ,
                  int8_t *__restrict__ winner, int8_t *__restrict__ to_move)
@@ -1460,6 +1709,48 @@ static int ttt_playout_launch(const char *fn, const crl_ctx *ctx, int64_t B, uin
     return CRL_OK;
 }
 
+// S_max of crl_ttt_mcts (include/colosseum_hip.h): a tree of S + 1 nodes of 8 + 2 cells bytes within 64 KB, s in 12 bits
+static int ttt_mcts_max_simulations(const int cells)
+{
+    const int s = 65536 / (8 + 2 * cells) - 1;
+    return s < 4095 ? s : 4095;
+}
+
+static int ttt_mcts_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
+                           const int8_t *winner, const int8_t *to_move, const uint32_t *tcount, int S, int R, uint32_t cexp,
+                           uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best, uint32_t flags, void *stream)
+{
+    TTT_CTX_CHECK(fn);
+    CRL_REQUIRE(occ && winner && to_move, "%s: NULL state pointer", fn);
+    CRL_REQUIRE(visits && value && nodes && best, "%s: NULL output pointer", fn);
+    const int cells = ctx->ttt.n_cells, s_max = ttt_mcts_max_simulations(cells);
+    CRL_REQUIRE(S >= 1 && S <= s_max, "%s: S=%d out of range 1..%d (a board of %d cells)", fn, S, s_max, cells);
+    CRL_REQUIRE(R >= 1 && R <= 1024, "%s: R=%d out of range 1..1024", fn, R);
+    CRL_REQUIRE(cexp <= 65535u, "%s: cexp=%u out of range 0..65535", fn, cexp);
+    CRL_REQUIRE(flags == 0, "%s: unknown flags 0x%x", fn, flags);
+    CRL_REQUIRE(cells >= ctx->ttt.P, "%s: a board of %d cells for %d players (as crl_ttt_playout)", fn, cells, ctx->ttt.P);
+    const ttt_dirs dd = dirs_of(ctx);
+    // LDS of a workgroup, at most 64 KB: the trees of its waves (one to four, as many as fit) behind the two tables.  A tree
+    // that leaves no room for a table does without it: the win test is then computed, the cell found by arithmetic.
+    constexpr uint32_t kLds = 65536u, kWinTab = 8192u, kRankTab = 2048u;
+    const uint32_t tree_bytes = (((uint32_t)(S + 1) * (uint32_t)(8 + 2 * cells)) + 3u) & ~3u;
+    const uint32_t *win_tab = ttt_win_table_here(ctx);
+    if (cells > 16 || dd.n_dirs > 4 || tree_bytes + kWinTab + kRankTab > kLds) win_tab = nullptr;
+    const int use_rank = tree_bytes + (win_tab ? kWinTab : 0u) + kRankTab <= kLds;
+    const uint32_t tables = (win_tab ? kWinTab : 0u) + (use_rank ? kRankTab : 0u);
+    uint32_t waves = (kLds - tables) / tree_bytes;
+    waves = waves > 4u ? 4u : waves;
+    waves = (int64_t)waves > B ? (uint32_t)B : waves;
+    const uint64_t want = ((uint64_t)B + waves - 1u) / waves;
+    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));      // (a grid-stride loop past that)
+    TTT_DISPATCH_ND_WT(ctx, win_tab, hipLaunchKernelGGL((ttt_mcts_kernel<PP, NDD, WTT>), dim3(blocks), dim3(64u * waves),
+                                                        tables + waves * tree_bytes, (hipStream_t)stream, dd, B, (uint32_t)seed,
+                                                        (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, tcount, S, R,
+                                                        cexp, tree_bytes / 4u, use_rank, visits, value, nodes, best, win_tab));
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
 // The arguments of crl_ttt_rollout that stay the same from launch to launch (include/colosseum_hip.h, "launch plans"), checked.
 // The win table is looked up per launch: it depends on the device that is current then.
 struct ttt_plan : crl_plan {
@@ -1655,6 +1946,20 @@ int crl_ttt_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first
 {
     return ttt_playout_launch("crl_ttt_playout", ctx, B, seed, first_env_id, occ, winner, to_move, tcount, cand, A, R, wins, played,
                               len_sum, nullptr, flags, stream);
+}
+
+int crl_ttt_mcts_max_simulations(const crl_ctx *ctx)
+{
+    CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_TTT, "crl_ttt_mcts_max_simulations: ctx is not a tictactoe context");
+    return ttt_mcts_max_simulations(ctx->ttt.n_cells);
+}
+
+int crl_ttt_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ, const int8_t *winner,
+                 const int8_t *to_move, const uint32_t *tcount, int S, int R, uint32_t cexp, uint32_t *visits, uint32_t *value,
+                 uint32_t *nodes, int32_t *best, uint32_t flags, void *stream)
+{
+    return ttt_mcts_launch("crl_ttt_mcts", ctx, B, seed, first_env_id, occ, winner, to_move, tcount, S, R, cexp, visits, value, nodes,
+                           best, flags, stream);
 }
 
 static int ttt_step_board_launch(const char *fn, const crl_ctx *ctx, int64_t B, int8_t *board, int8_t *winner, int8_t *to_move,

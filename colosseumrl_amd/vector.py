@@ -234,6 +234,14 @@ class TicTacToeSinglePlayerVectorEnv:
         _want(action, torch.int64, (self.num_envs,), self.batch.device, "action")
         return self._step(action)
 
+    def mcts_action(self, simulations: int, playouts: int = 16, seed: int = 1, exploration: float = 1.0,
+                    out: Optional[dict] = None) -> torch.Tensor:
+        """A tree search for the learner on the env's own games (``TTTBatch.mcts_action``): int64 [B] actions for ``step``,
+        one launch, no host synchronisation.  It is the learner's turn in every game after ``reset`` / ``step``, so the
+        search is the learner's; the tree values every reply, the opponents' included, by random playouts.  ``out``: the
+        ``TTTBatch.mcts`` dict to reuse (its 'visits' are a policy target)."""
+        return self.batch.mcts_action(simulations, playouts, seed, exploration, out)
+
 
 class BlokusSinglePlayerVectorEnv:
     """B Blokus games of one learner against the random agent in the other three seats: the turn-based counterpart of

@@ -87,7 +87,8 @@ const char *crl_last_error(void);
  *      CRL_PLAYOUT_AVOID / CRL_PLAYOUT_UNTIL_SEAT_DONE), on the same terms, and so were crl_tron_territory /
  *      crl_tron_sample_territory (Voronoi territory and the territory-greedy agent: two new entries, one new Philox tag).
  *      So were crl_ttt_winning_cells and crl_ttt_sample_tactical / _rollout_tactical / _step_single_tactical /
- *      _playout_tactical (the win-or-block agent of TicTacToe: five new entries, two new Philox tags). */
+ *      _playout_tactical (the win-or-block agent of TicTacToe: five new entries, two new Philox tags), and
+ *      crl_ttt_mcts / crl_ttt_mcts_max_simulations (batched tree search: two new entries, one new Philox tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -810,6 +811,60 @@ int crl_ttt_playout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
                              const uint32_t *occ, const int8_t *winner, const int8_t *to_move, const uint32_t *tcount,
                              const int32_t *cand, int A, int R,
                              uint32_t *wins, uint32_t *played, uint32_t *len_sum, double noise, uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------ batched Monte Carlo tree search (UCT), TicTacToe
+ * crl_ttt_mcts: from each of B positions build a search tree of its own by S simulations s = 0 .. S-1, in order, each
+ * evaluated by R random playouts, and report the root's children.  One launch, no host sync.  Added under revision 113: new
+ * entries and one new Philox tag, no existing struct, argument list or RNG contract changed.
+ * The state is read only, in the layouts of crl_ttt_playout; tcount uint32 [B] may be NULL, which means 0.
+ *
+ * Nodes.  Node 0 is the root, position b.  A node holds n, the number of simulations that passed through it; w, the
+ * half-points of the player who made the move INTO it (a won playout counts 2, a drawn one 1; the root's w stays 0); and
+ * one child slot per cell, empty ("none") at first.
+ * Descent.  A simulation starts at the root with a private copy of the position.  At node v with the empty cells E of the
+ * position there, in ascending order:
+ *   expand: if some cell of E has no child, take the lowest such cell e; a new node with the next free index becomes v's
+ *           child at e, ply e is played as crl_ttt_step plays it, and the new node is the leaf (also when that ply is
+ *           terminal);
+ *   select: else take the child u at the cell of E that maximises score(v, u), ties to the lowest cell, and play that cell;
+ *           if crl_ttt_step reports the ply terminal u is the leaf, else the descent continues at u.
+ * Score, in 64-bit integers with floor divisions:
+ *   exploit = (w_u << 15) / (n_u * R)                                        in [0, 65536]
+ *   lg(n), n >= 1: m = the index of n's leading one, f = ((n << (31 - m)) >> 23) & 255 (the 8 bits below it, zero-filled),
+ *           lg(n) = 256 m + f: a piecewise-linear log2 with 8 fraction bits
+ *   X = (lg(n_v) << 24) / n_u
+ *   score = exploit + ((cexp * isqrt(X)) >> 8),  isqrt the exact floor square root
+ * so cexp / 256 multiplies sqrt(log2 n_v / n_u) on a value scale of 0 .. 1: cexp = 256 is the usual choice, 0 pure
+ * exploitation.
+ * Evaluation of the leaf L at depth d (plies from the root).  If the ply into L ended the game, all R playouts have that
+ * outcome and no draw is made.  Else R playouts r = 0 .. R-1 start from L's position, each the random agent of
+ * crl_ttt_rollout played to the first terminal ply: random ply k has step counter c = tcount[b] + d + k (uint32 arithmetic),
+ * game id g = first_env_id + b (low 32 bits) and
+ *   w = Philox4x32-10(ctr = {g, c >> 3, (s << 16) | r, 0x544D0000}, key = {seed lo, seed hi})[(c >> 1) & 3],
+ * with the rollout's even / odd mixed-radix rule and r' = mulhi32(draw, n_empty).  The tag 0x544D0000 is used nowhere else.
+ * Backup.  Every node on the path from the root to L: n += 1; every one but the root, q the player who moved into it:
+ * w += 2 * (playouts q won) + (playouts drawn).
+ * Outputs, every word overwritten:
+ *   visits uint32 [B][cells], value uint32 [B][cells]   n and w of the root's child at each cell, 0 where there is none;
+ *   nodes  uint32 [B]                                   the node count, root included;
+ *   best   int32  [B]                                   the cell whose root child has the most visits; ties go to the larger
+ *                                                       w, then to the lowest cell.
+ * A position that is over (winner[b] >= 0, or no empty cell) or whose to_move[b] is outside [0, P) is skipped: zeros,
+ * nodes 0, best -1.
+ * Limits (CRL_EINVAL, with a crl_last_error message, before any device work): NULL state or output pointers, B out of range
+ * (as the siblings), S outside [1, S_max], R outside [1, 1024], cexp > 65535, flags != 0, a context with cells < P (as
+ * crl_ttt_playout).  S_max = min(4095, 65536 / (8 + 2 * cells) - 1): a tree of S + 1 nodes of 8 + 2 * cells bytes fits one
+ * workgroup's 64 KB of LDS, and s fits its counter word -- 2,519 on 3x3, 1,723 on 3x5, 1,128 on 5x5, 1,056 on 3x3x3, 909 on
+ * 32 cells.  crl_ttt_mcts_max_simulations returns S_max of the context (a negative code on a bad context).
+ * One wave per tree, the tree in LDS: the wave's lanes are the cells while it selects (the arg-max is a cross-lane
+ * reduction, the tie rule part of the reduced key), the playouts while it evaluates (R > 64 in passes) and the path
+ * entries while it backs up.  Nothing is shared between waves, so the results do not depend on their order. */
+int crl_ttt_mcts_max_simulations(const crl_ctx *ctx);
+int crl_ttt_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                 const uint32_t *occ, const int8_t *winner, const int8_t *to_move, const uint32_t *tcount,
+                 int S, int R, uint32_t cexp,
+                 uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best,
+                 uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ launch plans: bind a rollout's arguments once
  * A caller that launches short rollouts in a loop passes the same context, batch, state and statistics pointers and flags

@@ -2,17 +2,16 @@
 header's words: a tree is plain lists, the integers are Python ints, isqrt is math.isqrt.  No code is shared with the kernel.
 
 It sits over the CPU oracle: positions are the oracle's TTTState, the win lines are oracle.ttt_lines.  For speed (a search
-is some thousand playouts) the plies are stepped with masks of its own (`Game.step`) and the draws come from a Philox of its
-own (`philox`); tests/test_ttt_mcts_host.py holds both to oracle.ttt_step on whole random games and to oracle.philox4x32.
+is some thousand playouts) the plies are stepped with masks of its own (`Game.step`) and the draws come from the integer
+Philox of tests/rng_ref.py; tests/test_ttt_mcts_host.py holds both to oracle.ttt_step on whole random games and to
+oracle.philox4x32.
 `ttt_mcts(..., stepper="oracle")` runs the same search through oracle.ttt_step and oracle.philox4x32 themselves."""
 import math
 
 import numpy as np
 
 from oracle import oracle as O
-
-TAG_TTT_MCTS = 0x544D0000
-M32 = 0xFFFFFFFF
+from tests.rng_ref import CRL_TAG_TTT_MCTS as TAG_TTT_MCTS, M32, philox_int as philox
 
 
 def max_simulations(cells):
@@ -35,15 +34,6 @@ def score(n_v, n_u, w_u, R, cexp):
     exploit = (w_u << 15) // (n_u * R)
     X = (lg(n_v) << 24) // n_u
     return exploit + ((cexp * math.isqrt(X)) >> 8)
-
-
-def philox(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 (Salmon et al., SC'11) on Python ints"""
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
-        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & M32, (p0 >> 32) ^ c3 ^ k1, p0 & M32
-        k0, k1 = (k0 + 0x9E3779B9) & M32, (k1 + 0xBB67AE85) & M32
-    return c0, c1, c2, c3
 
 
 def _philox_oracle(c0, c1, c2, c3, k0, k1):
@@ -107,7 +97,7 @@ def playout(game, occ, tm, seed, g, c, c2, tag=TAG_TTT_MCTS, step=None, rng=phil
         if block != c >> 3:
             block = c >> 3
             words = rng(g & M32, block, c2, tag, k0, k1)
-        w = words[(c >> 1) & 3]
+        w = words[(c >> 1) & 3]                                  # the draw rule of ttt_ref.random_agent, on ints
         if c & 1:
             w = (w * (n + 1)) & M32
         term, ws = step(occ, tm, cells[(w * n) >> 32])

@@ -6,14 +6,15 @@ seat):
   (i)  ``areas_by_distance``: one full breadth-first search per player through ALL free cells, then the strict-minimum
        comparison of the definition;
   (ii) ``areas_by_levels``: the level-synchronous flood through unclaimed cells only (what the kernels do).
-Test infrastructure: the stepping is the CPU oracle's; ``avoid_ref.philox`` is the vectorised Philox4x32-10 the host tests
+Test infrastructure: the stepping is the CPU oracle's; ``rng_ref.philox`` is the vectorised Philox4x32-10 the host tests
 check against the oracle's.
 """
 import numpy as np
 
-from tests import avoid_ref
+from tests import rng_ref as RNG
+from tests import tron_ref
 
-TAG_TERRITORY = 0x54760000
+TAG_TERRITORY = RNG.CRL_TAG_TRON_TERRITORY
 FATAL_SCORE = -(1 << 30)
 _DX = np.array([0, 1, 0, -1])
 _DY = np.array([-1, 0, 1, 0])
@@ -154,12 +155,12 @@ def decide(N, board, heads, dirs, deaths, g, c, seed, noise, players=None):
     dead players are 0.  g, c: the games' global ids and step counters [B]."""
     P, B = heads.shape
     act = np.zeros((P, B), dtype=np.int8)
-    thr = avoid_ref.threshold(noise)
+    thr = RNG.threshold(noise)
     code = np.array([0, 1, -1], dtype=np.int8)
     for p in (range(P) if players is None else players):
-        w = avoid_ref.philox(np.asarray(g, np.uint64), np.asarray(c, np.uint64), p, TAG_TERRITORY, seed)
+        w = RNG.philox(np.asarray(g, np.uint64), np.asarray(c, np.uint64), p, TAG_TERRITORY, seed)
         noisy = w[0].astype(np.uint64) < np.uint64(thr)
-        a = ((w[1].astype(np.uint64) * np.uint64(3)) >> np.uint64(32)).astype(np.int64)
+        a = RNG.mulhi(w[1], 3)
         live = deaths[p] == 0
         idx = np.nonzero(live & ~noisy)[0]
         if idx.size:
@@ -190,7 +191,7 @@ def positions(N, P, B, seed, avoid, start=None):
     stop = rng.integers(0, 2 * N, size=B)
     for t in range(int(stop.max())):
         if avoid:
-            act = avoid_ref.decide(N, st.board, st.heads, st.dirs, st.deaths, np.arange(B), np.full(B, t), seed, 0.1)
+            act = tron_ref.decide(N, st.board, st.heads, st.dirs, st.deaths, np.arange(B), np.full(B, t), seed, 0.1)
         else:
             act = rng.integers(-1, 2, size=(P, B)).astype(np.int8)
         nxt = st.copy()

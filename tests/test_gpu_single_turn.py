@@ -1,23 +1,20 @@
 """One learner against the random agent on the GPU (crl_ttt_step_single / crl_blokus_step_single): bit-exact against the
-numpy restatement of the header's contract (tests/single_ref.py), a learner that plays the random agent's own draw
-against the oracle's rollout of each game, ragged and large batches, both vector envs replayed from a HIP graph, and the
+numpy restatement of the header's contract (tests/ttt_ref.py, tests/blokus_ref.py), a learner that plays the random agent's
+own draw against the oracle's rollout of each game, ragged and large batches, both vector envs replayed from a HIP graph, and the
 outcome rates of a uniformly random TicTacToe learner."""
 import numpy as np
 import pytest
 import torch
 
-from tests import single_ref as R
+from tests import blokus_ref as R
+from tests import ttt_ref
 from tests import ttt_probes as TP
+from tests.gpu_util import DEV, np_of as _np, same_ttt_state as _ttt_same_state
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 TTT_CONFIGS = TP.INSTANCE_ROWS              # every <P, win table / 4 directions / 13 directions> instance of the kernel
 TTT_IDS = TP.INSTANCE_IDS
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 def _ttt_pair(dims, K, P, B):
@@ -26,16 +23,10 @@ def _ttt_pair(dims, K, P, B):
     return TTTBatch(dims, K, P, B, device=DEV), O.TTTState(dims, K, P, B)
 
 
-def _ttt_same_state(tb, st):
-    assert np.array_equal(_np(tb.occ).view(np.uint32), st.occ)
-    assert np.array_equal(_np(tb.winner), st.winner) and np.array_equal(_np(tb.to_move), st.to_move)
-    assert np.array_equal(_np(tb.tcount).view(np.uint32), st.tcount)
-
-
 def _ttt_compare(tb, st, seat, act, seed):
     seat_t = torch.from_numpy(seat).to(DEV)
     out = tb.step_single(seat_t, None if act is None else torch.from_numpy(act).to(DEV), seed)
-    reward, done, winners, obs, valid = R.ttt_step_single(st, seat, act, seed)
+    reward, done, winners, obs, valid = ttt_ref.step_single(st, seat, act, seed, ttt_ref.random_agent)
     torch.cuda.synchronize()
     _ttt_same_state(tb, st)
     assert np.array_equal(_np(out["reward"]), reward) and np.array_equal(_np(out["done"]), done)
@@ -152,7 +143,7 @@ def test_blokus_against_restatement(rank):
     for _ in range(60):
         act = np.empty(B, np.int64)
         for b in range(B):
-            one = R._blk_one(st, b)
+            one = R.blokus_one(st, b)
             n = int(O.blokus_valid(one, player=np.array([seat[b]], np.int8))[0][0])
             kind = rng.integers(0, 10)
             if rank:

@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests import avoid_ref
+from tests import tron_ref
+from tests.gpu_util import first_episodes, tron_put, tron_state as _state
 from tests import territory_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -18,14 +19,7 @@ def _tb(N, P, B, **kw):
 
 
 def _put(tb, st):
-    tb.board.copy_(torch.from_numpy(np.ascontiguousarray(st.board)))
-    tb.heads.copy_(torch.from_numpy(np.ascontiguousarray(st.heads)))
-    tb.dirs.copy_(torch.from_numpy(np.ascontiguousarray(st.dirs)))
-    tb.deaths.copy_(torch.from_numpy(np.ascontiguousarray(st.deaths)))
-
-
-def _state(tb):
-    return [t.cpu().numpy() for t in (tb.board, tb.heads, tb.dirs, tb.deaths)]
+    tron_put(tb, st.board, st.heads, st.dirs, st.deaths)
 
 
 def _midgame(N, P, B, seed):
@@ -156,7 +150,7 @@ class _HostSingle:
     """Host replay of TronSinglePlayerVectorEnv(opponent="territory"): learner = player 0, done resets."""
 
     def __init__(self, N, P, B, sh, sd, seed, noise):
-        self.loop = avoid_ref.HostLoop(N, P, B, sh, sd)
+        self.loop = tron_ref.HostLoop(N, P, B, sh, sd)
         self.seed, self.noise = seed, noise
 
     def step(self, action):
@@ -244,17 +238,9 @@ def _first_episode_win_rate(policy, batch, seed, max_t=400):
     from colosseumrl_amd.vector import TronSinglePlayerVectorEnv
     env = TronSinglePlayerVectorEnv(15, 4, batch, noise=0.1, seed=seed, device="cuda:0")
     env.reset()
-    won = torch.zeros(batch, dtype=torch.bool, device="cuda:0")
-    live = torch.ones(batch, dtype=torch.bool, device="cuda:0")
     gen = torch.Generator(device="cuda:0").manual_seed(seed)
-    for t in range(max_t):
-        _, reward, done, _ = env.step(policy(env, gen))
-        won |= live & (reward == 10)
-        live &= done == 0
-        if t % 20 == 19 and not bool(live.any()):
-            break
-    assert not bool(live.any())
-    return won.double().mean().item()
+    reward, _, _ = first_episodes(env, lambda env, t: policy(env, gen), max_t)
+    return (reward == 10).double().mean().item()           # +10: the surviving winner, on the step that ends the game
 
 
 def test_territory_learner_beats_avoid_and_random_learners():

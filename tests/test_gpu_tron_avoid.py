@@ -8,13 +8,13 @@ import numpy as np
 import pytest
 import torch
 
-from tests import avoid_ref
+from tests import tron_ref
+from tests.gpu_util import TRON_STATS as STATS, tron_put as _put, tron_state as _state, tron_stats as _stats
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "tron_avoid_*.npz")))
-STATS = ("tcount", "tstep", "n_episodes", "win_count", "len_sum", "ret_sum", "last_winners", "last_len")
 
 
 def _tb(N, P, B, **kw):
@@ -25,21 +25,6 @@ def _tb(N, P, B, **kw):
 def _load(path):
     with np.load(path) as z:
         return {k: z[k] for k in z.files}
-
-
-def _put(tb, board, heads, dirs, deaths):
-    tb.board.copy_(torch.from_numpy(np.ascontiguousarray(board)))
-    tb.heads.copy_(torch.from_numpy(np.ascontiguousarray(heads)))
-    tb.dirs.copy_(torch.from_numpy(np.ascontiguousarray(dirs)))
-    tb.deaths.copy_(torch.from_numpy(np.ascontiguousarray(deaths)))
-
-
-def _state(tb):
-    return [t.cpu().numpy() for t in (tb.board, tb.heads, tb.dirs, tb.deaths)]
-
-
-def _stats(tb):
-    return {k: getattr(tb, k).cpu().numpy() for k in STATS}
 
 
 @pytest.mark.parametrize("path", GOLDEN, ids=[os.path.basename(p) for p in GOLDEN])
@@ -98,7 +83,7 @@ def _check_rollout_against_loops(N, P, B, T, seed, noise, first_env_id=0, host=T
     assert fused.packed_rows_exact()
     if not host:
         return fused
-    ref = avoid_ref.HostLoop(N, P, B, fused.start_heads, fused.start_dirs)
+    ref = tron_ref.HostLoop(N, P, B, fused.start_heads, fused.start_dirs)
     ref.run(T, seed, noise, first_env_id)
     for a, b in zip(fs, (ref.st.board, ref.st.heads, ref.st.dirs, ref.st.deaths)):
         assert np.array_equal(a, b)
@@ -162,13 +147,13 @@ class _HostSingle:
     """Host replay of TronSinglePlayerVectorEnv: learner = player 0, opponents on the avoid contract, done resets."""
 
     def __init__(self, N, P, B, sh, sd, seed, noise):
-        self.loop = avoid_ref.HostLoop(N, P, B, sh, sd)
+        self.loop = tron_ref.HostLoop(N, P, B, sh, sd)
         self.seed, self.noise = seed, noise
 
     def step(self, action):
         from oracle import oracle as O
         st = self.loop.st
-        act = avoid_ref.decide(st.N, st.board, st.heads, st.dirs, st.deaths, np.arange(st.B), st.tcount, self.seed, self.noise)
+        act = tron_ref.decide(st.N, st.board, st.heads, st.dirs, st.deaths, np.arange(st.B), st.tcount, self.seed, self.noise)
         st.tcount += 1
         act[0] = np.array([0, 1, -1], np.int8)[action]
         rew, term, _ = O.tron_step(st, act)

@@ -1,5 +1,5 @@
 """Batched Tron playouts on the GPU (crl_tron_playout): bit-exact against the numpy restatement of the header's contract
-(tests/tron_playout_ref.py) on ragged batches of mid-game positions over board sizes, player counts, both agents, both
+(tests/tron_ref.py) on ragged batches of mid-game positions over board sizes, player counts, both agents, both
 stop modes and step caps; outcome counts of a tiny board against exact probabilities; read-only inputs, overwritten
 outputs, determinism, graph replay, lane indices past 2^31; flat Monte Carlo in TronSinglePlayerVectorEnv against a
 random and an avoid learner; and a smoke run of tools/tron_playout_rate.py."""
@@ -14,16 +14,12 @@ import pytest
 import torch
 
 from tests import test_tron_playout_host as H
-from tests import tron_playout_ref as TR
+from tests import tron_ref as TR
+from tests.gpu_util import DEV, first_episodes, np_of as _np, tron_put
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 def _positions(N, P, B, seed):
@@ -45,10 +41,7 @@ def _positions(N, P, B, seed):
 
 
 def _upload(tb, st, tcount, first_env_id):
-    tb.board.copy_(torch.from_numpy(st.board))
-    tb.heads.copy_(torch.from_numpy(st.heads))
-    tb.dirs.copy_(torch.from_numpy(st.dirs))
-    tb.deaths.copy_(torch.from_numpy(st.deaths))
+    tron_put(tb, st.board, st.heads, st.dirs, st.deaths)
     tb.tcount.copy_(torch.from_numpy(tcount.view(np.int32)))
     tb.first_env_id = first_env_id
 
@@ -234,21 +227,9 @@ def _first_episode(policy, B=1024, seed=5, max_t=300):
     from colosseumrl_amd.vector import TronSinglePlayerVectorEnv
     env = TronSinglePlayerVectorEnv(15, 4, B, noise=0.1, seed=seed, device=DEV)
     env.reset()
-    ret = torch.zeros(B, dtype=torch.int64, device=DEV)
-    steps = torch.zeros(B, dtype=torch.int64, device=DEV)
-    won = torch.zeros(B, dtype=torch.bool, device=DEV)
-    live = torch.ones(B, dtype=torch.bool, device=DEV)
     gen = torch.Generator(device=DEV).manual_seed(seed)
-    for t in range(max_t):
-        a = policy(env, t, gen)
-        _, reward, done, info = env.step(a)
-        ret += torch.where(live, reward.to(torch.int64), 0)
-        steps += live.to(torch.int64)
-        won |= live & (reward == 10)
-        live &= done == 0
-        if t % 20 == 19 and not bool(live.any()):
-            break
-    assert not bool(live.any())
+    reward, ret, steps = first_episodes(env, lambda env, t: policy(env, t, gen), max_t)
+    won = reward == 10                                     # +10: the surviving winner, on the step that ends the game
     return ret.double().mean().item(), steps.double().mean().item(), won.double().mean().item()
 
 

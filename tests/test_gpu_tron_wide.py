@@ -11,7 +11,7 @@ import torch
 from test_gpu_tron import _rollout_pair
 from test_gpu_tron_avoid import STATS, _check_rollout_against_loops, _state, _stats, _tb
 from test_gpu_tron_playout import _check_against_restatement
-from tests import avoid_ref
+from tests import tron_ref
 from tests import tron_wide_shapes as S
 
 pytestmark = pytest.mark.gpu
@@ -51,7 +51,7 @@ def test_rollout_avoid_small_boards(N, P, B):
 def test_rollout_avoid_wide_boards(N, P, B):
     """Boards above 40x40, at a noise at which the host loop finishes at least B episodes."""
     from oracle import oracle as O
-    ref = avoid_ref.HostLoop(N, P, B, *O.tron_start_positions(N, P))
+    ref = tron_ref.HostLoop(N, P, B, *O.tron_start_positions(N, P))
     ref.run(S.AVOID_T, S.avoid_seed(N, P), S.AVOID_NOISE_WIDE, S.AVOID_FIRST)
     assert ref.st.n_episodes.sum() >= B
     _check_rollout_against_loops(N, P, B, S.AVOID_T, seed=S.avoid_seed(N, P), noise=S.AVOID_NOISE_WIDE, first_env_id=S.AVOID_FIRST)

@@ -10,10 +10,10 @@ import pytest
 import torch
 
 from tests import mcts_ref as M
+from tests.gpu_util import DEV, first_episodes, np_of as _np, ttt_batch
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 # (dims, K, P, built without the win-mask table)
 INSTANCES = [((3, 3), 3, 2, False), ((3, 5), 3, 3, False), ((3, 3, 3), 3, 4, False), ((5, 5), 4, 3, False), ((4, 8), 4, 2, False),
              ((3, 3), 3, 2, True)]
@@ -22,19 +22,8 @@ inst = pytest.mark.parametrize("dims,K,P,no_table", INSTANCES, ids=IDS)
 FIRST_ENV_ID = 77
 
 
-def _np(t):
-    return t.cpu().numpy()
-
-
 def _batch(st, first_env_id=FIRST_ENV_ID):
-    """a TTTBatch holding the oracle state `st` (tcount included)"""
-    from colosseumrl_amd.batched import TTTBatch
-    tb = TTTBatch(st.dims, st.K, st.P, st.B, device=DEV, first_env_id=first_env_id)
-    tb.occ.copy_(torch.from_numpy(st.occ.view(np.int32)))
-    tb.winner.copy_(torch.from_numpy(st.winner))
-    tb.to_move.copy_(torch.from_numpy(st.to_move))
-    tb.tcount.copy_(torch.from_numpy(st.tcount.view(np.int32)))
-    return tb
+    return ttt_batch(st, first_env_id)
 
 
 def _same(got, want, what=""):
@@ -205,15 +194,8 @@ def _first_episode_losses(learner, games, seed):
     from colosseumrl_amd.vector import TicTacToeSinglePlayerVectorEnv
     env = TicTacToeSinglePlayerVectorEnv((3, 3), 3, 2, games, seat=1, seed=seed, device=DEV, opponent="tactical", noise=0.0)
     env.reset()
-    over = torch.zeros((games,), dtype=torch.bool, device=DEV)
-    lost = torch.zeros((games,), dtype=torch.bool, device=DEV)
-    for step in range(5):                                                # the learner has at most four plies in a game
-        _, reward, done, _ = env.step(learner(env, step))
-        first = (done != 0) & ~over
-        lost |= first & (reward < 0)
-        over |= first
-    assert bool(over.all())
-    return float(lost.float().mean())
+    reward, _, _ = first_episodes(env, learner, 5)                       # the learner has at most four plies in a game
+    return float((reward < 0).float().mean())
 
 
 def test_search_learner_loses_at_most_half_as_often_as_flat_monte_carlo():

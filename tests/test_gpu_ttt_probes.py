@@ -9,27 +9,14 @@ import numpy as np
 import pytest
 import torch
 
-from tests import playout_ref
+from tests import ttt_ref
 from tests import ttt_probes as TP
+from tests.gpu_util import DEV, np_of as _np, to_dev as _dev, ttt_batch, u32_of as _u32
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 SMALL = [(d, k, p, dens) for d, k, p, dens in TP.PROBE_SHAPES if TP.n_cells_of(d) <= 16]
 SMALL_IDS = [TP.shape_id(d, k, p) for d, k, p, _ in SMALL]
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _u32(t):
-    return _np(t).view(np.uint32)
-
-
-def _dev(a):
-    a = np.array(a)                                                          # (a copy: the shared probe arrays are read-only)
-    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(DEV)
 
 
 def _batch(dims, K, P, pr):
@@ -129,7 +116,6 @@ def test_playout_row_shapes(Rn, A):
     two waves and two lanes (130).  B is the smallest with a lane in a second 256-lane workgroup, so that rows lie inside
     a wave, across waves and -- where R does not divide 256 -- across workgroups; positions that are over and candidates
     that are not empty cells leave skipped rows among the played ones."""
-    from colosseumrl_amd.batched import TTTBatch
     dims, K, P = (3, 3), 3, 2
     B = 256 // (Rn * A) + 1
     assert B * A * Rn > 256 and (B - 1) * A * Rn <= 256
@@ -141,18 +127,14 @@ def test_playout_row_shapes(Rn, A):
     tcount = rng.integers(0, 1000, size=B).astype(np.uint32)
     cand = rng.integers(-1, 10, size=(B, A))
     cand[0, 0] = 4
-    tb = TTTBatch(dims, K, P, B, device=DEV, first_env_id=first_env_id)
-    tb.occ.copy_(_dev(st.occ))
-    tb.winner.copy_(_dev(st.winner))
-    tb.to_move.copy_(_dev(st.to_move))
-    tb.tcount.copy_(_dev(tcount))
+    tb = ttt_batch(st, first_env_id, tcount)
     out = tb.playout(Rn, _dev(cand.astype(np.int32)), seed)
-    wins, played, len_sum = playout_ref.ttt_playout(st, seed, Rn, cand=cand, A=A, first_env_id=first_env_id, tcount=tcount)
+    wins, played, len_sum = ttt_ref.playout(st, seed, Rn, ttt_ref.random_agent, cand=cand, A=A, first_env_id=first_env_id, tcount=tcount)
     assert played.any()
     assert np.array_equal(_u32(out["played"]), played) and np.array_equal(_u32(out["wins"]), wins)
     assert np.array_equal(_u32(out["len_sum"]), len_sum)
     if A == 1:                                                               # and without candidates
         out = tb.playout(Rn, None, seed)
-        wins, played, len_sum = playout_ref.ttt_playout(st, seed, Rn, first_env_id=first_env_id, tcount=tcount)
+        wins, played, len_sum = ttt_ref.playout(st, seed, Rn, ttt_ref.random_agent, first_env_id=first_env_id, tcount=tcount)
         assert np.array_equal(_u32(out["played"]), played) and np.array_equal(_u32(out["wins"]), wins)
         assert np.array_equal(_u32(out["len_sum"]), len_sum)

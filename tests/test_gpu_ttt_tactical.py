@@ -1,6 +1,6 @@
 """TicTacToe's tactical (win-or-block) agent on the GPU: crl_ttt_winning_cells and crl_ttt_sample_tactical /
 _rollout_tactical / _step_single_tactical / _playout_tactical, bit-exact against the numpy restatement of the header's
-contract (tests/tactical_ref.py) on its generated positions (planted threats at every turn distance, so that no case
+contract (tests/ttt_ref.py) on its generated positions (planted threats at every turn distance, so that no case
 only exercises the fallback: tests/test_ttt_tactical_host.py asserts that on the restatement alone), the identities of
 the contract, the random defaults against today's calls, the vector env replayed from a HIP graph, and the strength of
 the agent against a uniformly random learner."""
@@ -10,39 +10,14 @@ import numpy as np
 import pytest
 import torch
 
-from tests import tactical_ref as TR
+from tests import ttt_ref as TR
 from tests import ttt_probes as TP
+from tests.gpu_util import DEV, np_of as _np, same_ttt_state as _same_state, ttt_batch as _batch, u32_of as _u32
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 ROWS, IDS = TP.INSTANCE_ROWS, TP.INSTANCE_IDS
 NOISE = 0.1
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _u32(t):
-    return _np(t).view(np.uint32)
-
-
-def _batch(st, first_env_id=0):
-    """a TTTBatch holding the oracle state `st` (tcount included)"""
-    from colosseumrl_amd.batched import TTTBatch
-    tb = TTTBatch(st.dims, st.K, st.P, st.B, device=DEV, first_env_id=first_env_id)
-    tb.occ.copy_(torch.from_numpy(st.occ.view(np.int32)))
-    tb.winner.copy_(torch.from_numpy(st.winner))
-    tb.to_move.copy_(torch.from_numpy(st.to_move))
-    tb.tcount.copy_(torch.from_numpy(st.tcount.view(np.int32)))
-    return tb
-
-
-def _same_state(tb, st):
-    assert np.array_equal(_u32(tb.occ), st.occ)
-    assert np.array_equal(_np(tb.winner), st.winner) and np.array_equal(_np(tb.to_move), st.to_move)
-    assert np.array_equal(_u32(tb.tcount), st.tcount)
 
 
 def _same_stats(tb, st):
@@ -128,13 +103,13 @@ def test_sample(cfg, noise):
     got = tb.sample_tactical(seed, noise, advance=False)
     torch.cuda.synchronize()
     _same_state(tb, st)                                              # advance=False leaves tcount alone
-    want = TR.sample(st, seed, noise, first, advance=False)
+    want = TR.sample(st, seed, TR.tactical_agent(noise), first, advance=False)
     assert np.array_equal(_np(got), want)
     got = tb.sample_tactical(seed, noise)                            # the same draw, and the counter moves on (2^32 - 1 wraps)
-    assert np.array_equal(_np(got), TR.sample(st, seed, noise, first))
+    assert np.array_equal(_np(got), TR.sample(st, seed, TR.tactical_agent(noise), first))
     assert 0 in st.tcount[TR.positions(cfg)["tcount"] == 2 ** 32 - 1]
     _same_state(tb, st)
-    assert np.array_equal(_np(tb.sample_tactical(seed, noise)), TR.sample(st, seed, noise, first))     # the other parity
+    assert np.array_equal(_np(tb.sample_tactical(seed, noise)), TR.sample(st, seed, TR.tactical_agent(noise), first))     # the other parity
     _same_state(tb, st)
 
 
@@ -146,7 +121,7 @@ def test_sample_passes_without_a_mover_or_a_cell():
     assert full.sum() >= 2 and not full[:6].all()
     got = _np(_batch(st).sample_tactical(7, 0.5))
     assert (got[:6] == -1).all() and (got[full] == -1).all() and (got[6:][~full[6:]] >= 0).all()
-    assert np.array_equal(got, TR.sample(st, 7, 0.5))
+    assert np.array_equal(got, TR.sample(st, 7, TR.tactical_agent(0.5)))
 
 
 # ------------------------------------------------------------------ 3. fused rollouts
@@ -160,7 +135,7 @@ def _rollout_ref(cfg):
     st = TR.state_of(cfg, 37)
     snaps = []
     for T in LAUNCHES:
-        TR.rollout(st, seed, NOISE, T, first)
+        TR.rollout(st, seed, TR.tactical_agent(NOISE), T, first)
         snaps.append({k: getattr(st, k).copy() for k in ("occ", "winner", "to_move", "tcount", "tstep", "n_episodes",
                                                        "win_count", "draw_count", "len_sum")})
     return seed, first, snaps
@@ -201,7 +176,7 @@ def test_rollout_is_sample_then_step(cfg):
 def _single_compare(tb, st, seat, act, seed):
     out = tb.step_single(torch.from_numpy(seat).to(DEV), None if act is None else torch.from_numpy(act).to(DEV), seed,
                          opponent="tactical", noise=NOISE)
-    reward, done, winners, obs, valid = TR.step_single(st, seat, act, seed, NOISE)
+    reward, done, winners, obs, valid = TR.step_single(st, seat, act, seed, TR.tactical_agent(NOISE))
     torch.cuda.synchronize()
     _same_state(tb, st)
     assert np.array_equal(_np(out["reward"]), reward) and np.array_equal(_np(out["done"]), done)
@@ -239,7 +214,7 @@ def _check_games_against_rollout(tb, cfg, seed, games, board=None):
     tc, occ, winner, to_move = _u32(tb.tcount), _u32(tb.occ), _np(tb.winner), _np(tb.to_move)
     for g in games:
         ref = O.TTTState(*cfg, 1)
-        TR.rollout(ref, seed, NOISE, int(tc[g]), first_env_id=int(g))
+        TR.rollout(ref, seed, TR.tactical_agent(NOISE), int(tc[g]), first_env_id=int(g))
         assert np.array_equal(ref.occ[:, 0], occ[:, g]) and ref.winner[0] == winner[g] and ref.to_move[0] == to_move[g], g
         if board is not None:
             bd = ref.board()[0].astype(np.int16)
@@ -271,7 +246,7 @@ def _playout_check(tb, st, tcount, Rn, cand, seed, first_env_id, noise=NOISE):
     snap = [t.clone() for t in (tb.occ, tb.winner, tb.to_move, tb.tcount)]
     out = tb.playout(Rn, None if cand is None else torch.from_numpy(cand.astype(np.int32)).to(DEV), seed, agent="tactical",
                      noise=noise)
-    wins, played, len_sum = TR.playout(st, seed, Rn, noise, cand=cand, A=A, first_env_id=first_env_id, tcount=tcount)
+    wins, played, len_sum = TR.playout(st, seed, Rn, TR.tactical_agent(noise), cand=cand, A=A, first_env_id=first_env_id, tcount=tcount)
     torch.cuda.synchronize()
     assert np.array_equal(_u32(out["played"]), played)
     assert np.array_equal(_u32(out["wins"]), wins)
@@ -314,7 +289,7 @@ def test_flat_mc_action():
     cfg = ((3, 3), 3, 2)
     st, tcount, rng, first_env_id, seed, tb = _playout_inputs(cfg)
     cells = np.tile(np.arange(9), (st.B, 1))
-    wins, played, _ = TR.playout(st, seed, 6, NOISE, cand=cells, A=9, first_env_id=first_env_id, tcount=tcount)
+    wins, played, _ = TR.playout(st, seed, 6, TR.tactical_agent(NOISE), cand=cells, A=9, first_env_id=first_env_id, tcount=tcount)
     want = TR.flat_mc_pick(st, wins, played, cells)
     got = _np(tb.flat_mc_action(6, seed, agent="tactical", noise=NOISE))
     assert np.array_equal(got, want) and (want >= 0).any() and (want < 0).any()
@@ -354,7 +329,7 @@ def test_vector_env_graph_replay():
                                               opponent="tactical", noise=NOISE)
     eager, graphed = make(), make()
     st = O.TTTState(*cfg, B)
-    _, _, _, obs, _ = TR.step_single(st, seat, None, seed, NOISE)
+    _, _, _, obs, _ = TR.step_single(st, seat, None, seed, TR.tactical_agent(NOISE))
     assert np.array_equal(_np(eager.reset()["board"]), obs) and np.array_equal(_np(graphed.reset()["board"]), obs)
     rng = np.random.default_rng(11)
     action = torch.zeros((B,), dtype=torch.int64, device=DEV)
@@ -364,7 +339,7 @@ def test_vector_env_graph_replay():
         action.copy_(torch.from_numpy(a))
         e_obs, e_rew, e_done, e_info = eager.step(torch.from_numpy(a).to(DEV))
         res = replay()
-        reward, done, winners, obs, valid = TR.step_single(st, seat, a, seed, NOISE)
+        reward, done, winners, obs, valid = TR.step_single(st, seat, a, seed, TR.tactical_agent(NOISE))
         torch.cuda.synchronize()
         for o, rew, dn, info in ((e_obs, e_rew, e_done, e_info), res):
             assert np.array_equal(_np(o["board"]), obs) and np.array_equal(_np(rew), reward) and np.array_equal(_np(dn), done)

@@ -8,14 +8,9 @@ import os
 import pytest
 
 from colosseumrl_amd import _native
+from tests.host_util import D, refused as _refused, tron_context, ttt_context
 
-D = C.c_void_p(64)                         # 16-byte aligned, never dereferenced: every launch below is refused or has T = 0
 TRON_FLAGS = 2 | 4 | 8 | 16 | 32 | 64 | 128
-
-
-def _refused(lib, rc, *words):
-    msg = lib.crl_last_error()
-    assert rc == -1 and all(w in msg for w in words), (rc, msg)
 
 
 def _tron_stats(null=None):
@@ -25,10 +20,8 @@ def _tron_stats(null=None):
 
 @pytest.fixture
 def tron():
-    lib, h = _native.lib(), C.c_void_p()
-    assert lib.crl_tron_create(20, 4, (C.c_int16 * 4)(21, 38, 361, 378), (C.c_int8 * 4)(1, 2, 0, 3), C.byref(h)) == 0
-    yield lib, h
-    lib.crl_destroy(h)
+    with tron_context(20, 4, (21, 38, 361, 378), (1, 2, 0, 3)) as h:
+        yield _native.lib(), h
 
 
 def _bind_tron(lib, h, B=67, first=2 ** 32 + 3, state=(D, D, D, D), stats=None, flags=0):
@@ -130,14 +123,10 @@ def test_tron_bind_refuses_what_the_rollout_refuses(tron):
         rc, plan = _bind_tron(lib, h, flags=flags)
         assert rc == 0 and plan.value
         assert lib.crl_rollout_unbind(plan) == 0
-    h19 = C.c_void_p()
-    assert lib.crl_tron_create(19, 4, (C.c_int16 * 4)(20, 36, 324, 340), (C.c_int8 * 4)(1, 2, 0, 3), C.byref(h19)) == 0
-    try:
+    with tron_context(19, 4, (20, 36, 324, 340), (1, 2, 0, 3)) as h19:
         rc, plan = _bind_tron(lib, h19, state=(C.c_void_p(72), D, D, D))
         assert rc == 0
         assert lib.crl_rollout_unbind(plan) == 0
-    finally:
-        lib.crl_destroy(h19)
 
 
 def test_the_old_entry_still_names_itself(tron):
@@ -165,9 +154,7 @@ def test_launch_checks_t_and_the_plan(tron):
 
 def test_ttt_and_blokus_bind_checks():
     lib = _native.lib()
-    h = C.c_void_p()
-    assert lib.crl_ttt_create(1, 3, 5, 3, 3, C.byref(h)) == 0
-    try:
+    with ttt_context(1, 3, 5, 3, 3) as h:
         def bind(ctx=h, B=131, state=(D, D, D), null=None):
             stats = _native.TTTStats(*[None if n == null else 64 for n, _ in _native.TTTStats._fields_])
             plan = C.c_void_p()
@@ -192,8 +179,6 @@ def test_ttt_and_blokus_bind_checks():
                  b"not a blokus context")
         _refused(lib, lib.crl_tron_rollout_bind(h, 33, 0, D, D, D, D, _tron_stats(), 0, C.byref(plan)), b"crl_tron_rollout_bind",
                  b"not a tron context")
-    finally:
-        lib.crl_destroy(h)
 
 
 def test_no_fastcall_selects_the_ctypes_form(monkeypatch):

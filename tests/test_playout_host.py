@@ -1,6 +1,6 @@
 """Batched random playouts (crl_ttt_playout / crl_blokus_playout) on the host: the argument checks of the two C entry
 points (every CRL_EINVAL case is rejected before any device work), the argument checks of the Python wrappers, and the
-numpy restatement of the header's contract (tests/playout_ref.py) against exact outcome probabilities of 3x3 positions
+numpy restatement of the header's contract (tests/ttt_ref.py) against exact outcome probabilities of 3x3 positions
 under uniform random play, computed here by recursion over the game tree."""
 import ctypes as C
 import math
@@ -8,15 +8,8 @@ import math
 import numpy as np
 import pytest
 
-from tests import playout_ref as R
-
-
-def _lib():
-    from colosseumrl_amd import _native
-    return _native.lib()
-
-
-D = C.c_void_p(64)                         # never dereferenced: every call below is rejected by its checks
+from tests import ttt_ref as R
+from tests.host_util import D, fake as _fake, lib as _lib, ttt_context
 
 
 def _ttt_call(lib, ctx, B=4, ptrs=None, cand=D, A=1, Rn=1, outs=None, flags=0):
@@ -27,9 +20,7 @@ def _ttt_call(lib, ctx, B=4, ptrs=None, cand=D, A=1, Rn=1, outs=None, flags=0):
 
 def test_ttt_playout_argument_checks():
     lib = _lib()
-    h = C.c_void_p()
-    assert lib.crl_ttt_create(1, 3, 3, 3, 2, C.byref(h)) == 0
-    try:
+    with ttt_context() as h:
         for i in range(3):                 # occ, winner, to_move (tcount may be NULL)
             ptrs = [D] * 4
             ptrs[i] = None
@@ -48,24 +39,16 @@ def test_ttt_playout_argument_checks():
         for flags in (1, 8, 0x80000000):
             assert _ttt_call(lib, h, flags=flags) == -1 and b"flags" in lib.crl_last_error()
         assert _ttt_call(lib, None) == -1 and b"tictactoe" in lib.crl_last_error()
-    finally:
-        lib.crl_destroy(h)
-    small = C.c_void_p()                   # fewer cells than players: refused as by crl_ttt_step_single
-    assert lib.crl_ttt_create(1, 1, 2, 2, 3, C.byref(small)) == 0
-    try:
+    with ttt_context(1, 1, 2, 2, 3) as small:  # fewer cells than players: refused as by crl_ttt_step_single
         assert _ttt_call(lib, small) == -1 and b"cells" in lib.crl_last_error()
-    finally:
-        lib.crl_destroy(small)
 
 
 def test_blokus_playout_argument_checks():
     lib = _lib()
-    tt = C.c_void_p()
-    assert lib.crl_ttt_create(1, 3, 3, 3, 2, C.byref(tt)) == 0
 
     def call(state=(D,) * 6, cand=D, A=1, Rn=1, outs=(D,) * 4, flags=0, ctx=None, B=4):
         return lib.crl_blokus_playout(ctx, B, 1, 0, *state, cand, A, Rn, *outs, flags, None)
-    try:
+    with ttt_context() as tt:
         for i in range(5):                 # occ, inv, score, round, to_move (tcount may be NULL)
             st = [D] * 6
             st[i] = None
@@ -84,8 +67,6 @@ def test_blokus_playout_argument_checks():
         # every argument right but the context: none, or one of another game
         assert call() == -1 and b"blokus context" in lib.crl_last_error()
         assert call(ctx=tt) == -1 and b"blokus context" in lib.crl_last_error()
-    finally:
-        lib.crl_destroy(tt)
 
 
 def test_playout_prototypes():
@@ -95,15 +76,6 @@ def test_playout_prototypes():
 
 
 # ---- the Python wrappers refuse bad arguments before they reach the library (no device needed to get there)
-def _fake(cls, **attrs):
-    import torch
-    obj = cls.__new__(cls)
-    obj.device = torch.device("cpu")
-    for k, v in attrs.items():
-        setattr(obj, k, v)
-    return obj
-
-
 def test_ttt_wrapper_argument_checks():
     import torch
     from colosseumrl_amd.batched import TTTBatch
@@ -166,7 +138,7 @@ def test_restatement_matches_exact_probabilities():
     Rn, seed = 1500, 0xC0FFEE
     st = _ttt_state(POSITIONS)
     before = (st.occ.copy(), st.winner.copy(), st.to_move.copy())
-    wins, played, len_sum = R.ttt_playout(st, seed, Rn, first_env_id=11, tcount=np.array([0, 5, 9, 2, 7], np.uint32))
+    wins, played, len_sum = R.playout(st, seed, Rn, R.random_agent, first_env_id=11, tcount=np.array([0, 5, 9, 2, 7], np.uint32))
     assert np.array_equal(st.occ, before[0]) and np.array_equal(st.to_move, before[2])   # inputs are read only
     assert (played[:, 0] == Rn).all()
     for b, (x, o, m) in enumerate(POSITIONS):
@@ -184,12 +156,12 @@ def test_restatement_candidates_and_skips():
     st = _ttt_state([(0b000000011, 0b000011000, 0), (0b000000111, 0b000011000, 1)])   # b = 1: X has won
     st.winner[1] = 0
     cand = np.array([[2, 0, -1, 9, 8], [5, 6, 7, 8, -1]], np.int64)
-    wins, played, len_sum = R.ttt_playout(st, 3, 40, cand=cand, A=5)
+    wins, played, len_sum = R.playout(st, 3, 40, R.random_agent, cand=cand, A=5)
     assert list(played[0]) == [40, 0, 0, 0, 40] and (played[1] == 0).all()
     assert wins[0, 0, 0] == 40 and len_sum[0, 0] == 40          # cell 2 completes X's row: one ply, always won
     assert (wins[1] == 0).all() and (len_sum[1] == 0).all()
     # the candidate ply is a move of the mover, the random plies follow it
-    one = R._ttt_copy(st, 0)
+    one = R.one_game(st, 0)
     O.ttt_step(one, np.array([8], np.int8))
     p = R.exact_3x3(int(one.occ[0, 0]), int(one.occ[1, 0]), 1)
     sigma = math.sqrt(40 * p[0] * (1 - p[0]))

@@ -7,16 +7,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests import avoid_ref
+from tests import rng_ref
 from tests import territory_ref as R
-
-
-def _lib():
-    from colosseumrl_amd import _native
-    return _native.lib()
-
-
-D = C.c_void_p(64)                         # never dereferenced: every call below is rejected by its checks
+from tests.host_util import D, fake as _fake, lib as _lib, tron_context, ttt_context
 
 
 def _terr(lib, ctx, B=4, state=(D,) * 4, seat=D, cand=D, A=1, outs=(D, D)):
@@ -29,15 +22,8 @@ def _agent(lib, ctx, B=4, tcount=D, noise=0.1, mask=3, state=(D,) * 4, actions=D
 
 @pytest.fixture
 def contexts():
-    lib = _lib()
-    h = C.c_void_p()
-    sh, sd = (C.c_int16 * 2)(0, 24), (C.c_int8 * 2)(0, 2)
-    assert lib.crl_tron_create(5, 2, sh, sd, C.byref(h)) == 0
-    tt = C.c_void_p()
-    assert lib.crl_ttt_create(1, 3, 3, 3, 2, C.byref(tt)) == 0
-    yield lib, h, tt
-    lib.crl_destroy(h)
-    lib.crl_destroy(tt)
+    with tron_context() as h, ttt_context() as tt:
+        yield _lib(), h, tt
 
 
 def test_territory_argument_checks(contexts):
@@ -85,22 +71,13 @@ def test_prototypes_and_revision():
 
 def test_territory_tag_words_match_the_oracle_philox():
     from oracle import oracle as O
-    w = avoid_ref.philox(np.array([7, 8]), np.array([3, 0xFFFFFFFF]), 2, R.TAG_TERRITORY, 0x1234567890ABCDEF)
+    w = rng_ref.philox(np.array([7, 8]), np.array([3, 0xFFFFFFFF]), 2, R.TAG_TERRITORY, 0x1234567890ABCDEF)
     for i, (g, c) in enumerate(((7, 3), (8, 0xFFFFFFFF))):
-        want = O.philox4x32([g, c, 2, 0x54760000], [0x90ABCDEF, 0x12345678])
+        want = O.philox4x32([g, c, 2, rng_ref.CRL_TAG_TRON_TERRITORY], [0x90ABCDEF, 0x12345678])
         assert [int(x[i]) for x in w] == want.tolist()
 
 
 # ---- the Python wrappers refuse bad arguments before they reach the library (no device needed to get there)
-def _fake(cls, **attrs):
-    import torch
-    obj = cls.__new__(cls)
-    obj.device = torch.device("cpu")
-    for k, v in attrs.items():
-        setattr(obj, k, v)
-    return obj
-
-
 def test_wrapper_argument_checks():
     import torch
     from colosseumrl_amd.batched import TronBatch
@@ -221,7 +198,7 @@ def test_agent_restatement_noise_extremes():
         assert np.array_equal(greedy[p][live], want[live]) and (greedy[p][~live] == 0).all()
     noisy = R.decide(13, st.board, st.heads, st.dirs, st.deaths, g, c, 77, 1.0)
     for p in range(3):
-        w = avoid_ref.philox(g, c, p, R.TAG_TERRITORY, 77)
+        w = rng_ref.philox(g, c, p, R.TAG_TERRITORY, 77)
         want = code[(w[1].astype(np.uint64) * np.uint64(3)) >> np.uint64(32)]
         assert np.array_equal(noisy[p], np.where(st.deaths[p] == 0, want, 0))
     only = R.decide(13, st.board, st.heads, st.dirs, st.deaths, g, c, 77, 0.0, players=[1])

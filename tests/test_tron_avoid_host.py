@@ -10,7 +10,8 @@ import sys
 import numpy as np
 import pytest
 
-from tests import avoid_ref
+from tests import rng_ref, tron_ref
+from tests.host_util import D, lib as _lib, tron_context
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "tron_avoid_*.npz")))
@@ -41,15 +42,15 @@ def test_philox_matches_oracle():
         ctr = rng.integers(0, 2 ** 32, size=4, dtype=np.uint64)
         seed = int(rng.integers(0, 2 ** 63))
         want = O.philox4x32(ctr.astype(np.uint32), [seed & 0xFFFFFFFF, seed >> 32])
-        got = avoid_ref.philox(*[np.uint64(c) for c in ctr], seed)
+        got = rng_ref.philox(*[np.uint64(c) for c in ctr], seed)
         assert [int(x) for x in got] == [int(x) for x in want]
 
 
 def test_threshold():
-    assert avoid_ref.threshold(0.0) == 0
-    assert avoid_ref.threshold(1.0) == 1 << 32
-    assert avoid_ref.threshold(0.5) == 1 << 31
-    assert avoid_ref.threshold(1e-12) == 1
+    assert rng_ref.threshold(0.0) == 0
+    assert rng_ref.threshold(1.0) == 1 << 32
+    assert rng_ref.threshold(0.5) == 1 << 31
+    assert rng_ref.threshold(1e-12) == 1
 
 
 @pytest.mark.parametrize("path", GOLDEN, ids=[os.path.basename(p) for p in GOLDEN])
@@ -59,9 +60,9 @@ def test_numpy_contract_reproduces_reference_actions(path):
     noise = int(r["noise_num"]) / int(r["noise_den"])
     S = len(r["c"])
     g = np.arange(S, dtype=np.uint64)
-    w = np.stack(avoid_ref.words(g[None, :], r["c"].astype(np.uint64)[None, :], np.arange(P, dtype=np.uint64)[:, None], seed), -1)
+    w = np.stack(tron_ref.words(g[None, :], r["c"].astype(np.uint64)[None, :], np.arange(P, dtype=np.uint64)[:, None], seed), -1)
     assert np.array_equal(w.transpose(1, 0, 2), r["words"])
-    act = avoid_ref.decide(N, r["board"], r["heads"].T.copy(), r["dirs"].T.copy(), r["deaths"].T.copy(), g, r["c"], seed, noise)
+    act = tron_ref.decide(N, r["board"], r["heads"].T.copy(), r["dirs"].T.copy(), r["deaths"].T.copy(), g, r["c"], seed, noise)
     assert np.array_equal(act.T, r["actions"])
     # ... and the CPU oracle's step of those actions is the reference's next_state
     from oracle import oracle as O
@@ -97,7 +98,7 @@ def test_generator_contract_random():
         sys.path.pop(0)
     fake = G.ContractRandom()
     for noise in (0.0, 0.1, 1.0):
-        fake.noise, fake.thr = noise, avoid_ref.threshold(noise)
+        fake.noise, fake.thr = noise, rng_ref.threshold(noise)
         for w0 in (0, 1, fake.thr - 1, fake.thr, 2 ** 32 - 1):
             if not 0 <= w0 < 2 ** 32:
                 continue
@@ -114,21 +115,15 @@ def test_generator_contract_random():
 
 # ---- argument checks of the C entry points (rejected before anything touches a device)
 def _ctx(N=9, P=4):
-    from colosseumrl_amd import _native
     from oracle import oracle as O
-    lib = _native.lib()
-    sh, sd = O.tron_start_positions(N, P)
-    h = C.c_void_p()
-    assert lib.crl_tron_create(N, P, sh.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), C.byref(h)) == 0
-    return lib, h
+    return tron_context(N, P, *O.tron_start_positions(N, P))
 
 
 def test_sample_avoid_argument_checks():
     from colosseumrl_amd import _native
-    lib, h = _ctx()
-    d = C.c_void_p(64)                    # never dereferenced: every call below is rejected by its checks
-    try:
-        def call(noise=0.1, mask=0xF, ptrs=(d,) * 6):
+    lib = _lib()
+    with _ctx() as h:
+        def call(noise=0.1, mask=0xF, ptrs=(D,) * 6):
             tc, board, heads, dirs, deaths, acts = ptrs
             return lib.crl_tron_sample_avoid(h, 4, 1, 0, tc, 1, noise, mask, board, heads, dirs, deaths, acts, None)
         for noise in (-0.01, 1.01, float("nan"), float("inf")):
@@ -137,30 +132,27 @@ def test_sample_avoid_argument_checks():
         assert call(mask=0x10) == -1 and b"player_mask" in lib.crl_last_error()
         assert call(mask=0x80000000) == -1
         for i in range(6):
-            ptrs = [d] * 6
+            ptrs = [D] * 6
             ptrs[i] = None
             assert call(ptrs=tuple(ptrs)) == -1 and b"NULL" in lib.crl_last_error()
-        assert lib.crl_tron_sample_avoid(None, 4, 1, 0, d, 1, 0.1, 1, d, d, d, d, d, None) == -1
-        assert lib.crl_tron_sample_avoid(h, 0, 1, 0, d, 1, 0.1, 1, d, d, d, d, d, None) == -1
-    finally:
-        lib.crl_destroy(h)
+        assert lib.crl_tron_sample_avoid(None, 4, 1, 0, D, 1, 0.1, 1, D, D, D, D, D, None) == -1
+        assert lib.crl_tron_sample_avoid(h, 0, 1, 0, D, 1, 0.1, 1, D, D, D, D, D, None) == -1
     assert _native.PROTOTYPES["crl_tron_sample_avoid"][1][6] is C.c_double
 
 
 def test_rollout_avoid_argument_checks():
     from colosseumrl_amd._native import TronStats
-    lib, h = _ctx()
-    d = C.c_void_p(64)
+    lib = _lib()
     full = TronStats(*([64] * 8 + [None, None]))
-    try:
-        def call(noise=0.1, T=4, flags=0, stats=full, state=(d,) * 4):
+    with _ctx() as h:
+        def call(noise=0.1, T=4, flags=0, stats=full, state=(D,) * 4):
             return lib.crl_tron_rollout_avoid(h, 4, 1, 0, T, noise, *state, stats, flags, None)
         for noise in (-1.0, 2.0, float("nan")):
             assert call(noise=noise) == -1 and b"noise" in lib.crl_last_error()
         assert call(T=-1) == -1
         assert call(flags=1) == -1 and b"flags" in lib.crl_last_error()
         for i in range(4):
-            st = [d] * 4
+            st = [D] * 4
             st[i] = None
             assert call(state=tuple(st)) == -1 and b"NULL" in lib.crl_last_error()
         for i in range(8):
@@ -168,17 +160,12 @@ def test_rollout_avoid_argument_checks():
             vals[i] = None
             assert call(stats=TronStats(*vals)) == -1 and b"NULL" in lib.crl_last_error()
         assert call(T=0) == 0                                      # nothing to do: no launch
-    finally:
-        lib.crl_destroy(h)
 
 
 def test_step_single_argument_checks():
-    lib, h = _ctx()
-    d = C.c_void_p(64)
-    try:
+    lib = _lib()
+    with _ctx() as h:
         for i in range(9):
-            ptrs = [d] * 9
+            ptrs = [D] * 9
             ptrs[i] = None
             assert lib.crl_tron_step_single(h, 4, *ptrs, None) == -1 and b"NULL" in lib.crl_last_error()
-    finally:
-        lib.crl_destroy(h)

@@ -1,6 +1,6 @@
 """Batched Tron playouts (crl_tron_playout) on the host: every CRL_EINVAL case of the C entry (rejected before any device
 work), the argument checks of the Python wrappers, the prototype, and the numpy restatement of the header's contract
-(tests/tron_playout_ref.py) against exact outcome probabilities of tiny boards under uniform random play, computed here
+(tests/tron_ref.py) against exact outcome probabilities of tiny boards under uniform random play, computed here
 by memoised recursion over the 3^alive joint actions."""
 import ctypes as C
 import functools
@@ -9,15 +9,8 @@ import math
 import numpy as np
 import pytest
 
-from tests import tron_playout_ref as TR
-
-
-def _lib():
-    from colosseumrl_amd import _native
-    return _native.lib()
-
-
-D = C.c_void_p(64)                         # never dereferenced: every call below is rejected by its checks
+from tests import tron_ref as TR
+from tests.host_util import D, fake as _fake, lib as _lib, tron_context, ttt_context
 
 
 def _call(lib, ctx, B=4, state=(D,) * 4, tcount=D, seat=D, cand=D, A=1, Rn=1, noise=0.1, max_steps=0, outs=(D,) * 4,
@@ -27,12 +20,7 @@ def _call(lib, ctx, B=4, state=(D,) * 4, tcount=D, seat=D, cand=D, A=1, Rn=1, no
 
 def test_tron_playout_argument_checks():
     lib = _lib()
-    h = C.c_void_p()
-    sh, sd = (C.c_int16 * 2)(0, 24), (C.c_int8 * 2)(0, 2)
-    assert lib.crl_tron_create(5, 2, sh, sd, C.byref(h)) == 0
-    tt = C.c_void_p()
-    assert lib.crl_ttt_create(1, 3, 3, 3, 2, C.byref(tt)) == 0
-    try:
+    with tron_context() as h, ttt_context() as tt:
         for i in range(4):                 # board, heads, dirs, deaths (tcount and seat may be NULL)
             st = [D] * 4
             st[i] = None
@@ -56,9 +44,6 @@ def test_tron_playout_argument_checks():
             assert _call(lib, h, flags=flags) == -1 and b"flags" in lib.crl_last_error()
         assert _call(lib, None) == -1 and b"tron context" in lib.crl_last_error()
         assert _call(lib, tt) == -1 and b"tron context" in lib.crl_last_error()
-    finally:
-        lib.crl_destroy(h)
-        lib.crl_destroy(tt)
 
 
 def test_tron_playout_prototype():
@@ -69,15 +54,6 @@ def test_tron_playout_prototype():
 
 
 # ---- the Python wrappers refuse bad arguments before they reach the library (no device needed to get there)
-def _fake(cls, **attrs):
-    import torch
-    obj = cls.__new__(cls)
-    obj.device = torch.device("cpu")
-    for k, v in attrs.items():
-        setattr(obj, k, v)
-    return obj
-
-
 def test_tron_wrapper_argument_checks():
     import torch
     from colosseumrl_amd.batched import TronBatch

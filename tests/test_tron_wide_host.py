@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from tests import avoid_ref
+from tests import tron_ref
 from tests import tron_wide_shapes as S
 
 
@@ -57,7 +57,7 @@ def test_avoid_host_loop_finishes_episodes(N, P, B):
     """At the table's noise the numpy + oracle loop finishes at least B episodes in AVOID_T steps, on the wide boards too."""
     noise = S.AVOID_NOISE_WIDE if N > 40 else S.AVOID_NOISE_SMALL
     sh, sd = O.tron_start_positions(N, P)
-    ref = avoid_ref.HostLoop(N, P, B, sh, sd)
+    ref = tron_ref.HostLoop(N, P, B, sh, sd)
     ref.run(S.AVOID_T, S.avoid_seed(N, P), noise, S.AVOID_FIRST)
     assert ref.st.n_episodes.sum() >= B
     assert np.array_equal(ref.st.tcount, np.full(B, S.AVOID_T, ref.st.tcount.dtype))

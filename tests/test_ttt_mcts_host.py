@@ -10,17 +10,11 @@ import numpy as np
 import pytest
 
 from tests import mcts_ref as M
+from tests import rng_ref as RNG
+from tests.host_util import D, fake as _fake, lib as _lib, tron_context, ttt_context
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOARDS = [((1, 3, 3), 3, 2, 2519), ((1, 3, 5), 3, 3, 1723), ((3, 3, 3), 3, 4, 1056), ((1, 5, 5), 4, 3, 1128), ((1, 4, 8), 4, 2, 909)]
-
-
-def _lib():
-    from colosseumrl_amd import _native
-    return _native.lib()
-
-
-D = C.c_void_p(64)                         # never dereferenced: every call below is refused by its checks
 
 
 def _call(lib, ctx, B=4, state=None, S=8, Rn=4, cexp=256, outs=None, flags=0):
@@ -29,16 +23,9 @@ def _call(lib, ctx, B=4, state=None, S=8, Rn=4, cexp=256, outs=None, flags=0):
     return lib.crl_ttt_mcts(ctx, B, 1, 0, occ, winner, to_move, tcount, S, Rn, cexp, visits, value, nodes, best, flags, None)
 
 
-def _ctx(lib, d, k, p):
-    h = C.c_void_p()
-    assert lib.crl_ttt_create(d[0], d[1], d[2], k, p, C.byref(h)) == 0
-    return h
-
-
 def test_mcts_argument_checks():
     lib = _lib()
-    h = _ctx(lib, (1, 3, 3), 3, 2)
-    try:
+    with ttt_context() as h:
         for i in range(3):                 # occ, winner, to_move (tcount may be NULL)
             st = [D] * 4
             st[i] = None
@@ -59,21 +46,11 @@ def test_mcts_argument_checks():
             assert _call(lib, h, flags=flags) == -1 and b"flags" in lib.crl_last_error()
         assert _call(lib, None) == -1 and b"tictactoe" in lib.crl_last_error()
         assert lib.crl_ttt_mcts_max_simulations(None) == -1 and b"tictactoe" in lib.crl_last_error()
-    finally:
-        lib.crl_destroy(h)
-    tron = C.c_void_p()                    # a context of another game
-    sh, sd = (C.c_int16 * 2)(0, 24), (C.c_int8 * 2)(0, 2)
-    assert lib.crl_tron_create(5, 2, sh, sd, C.byref(tron)) == 0
-    try:
+    with tron_context() as tron:           # a context of another game
         assert _call(lib, tron) == -1 and b"tictactoe" in lib.crl_last_error()
         assert lib.crl_ttt_mcts_max_simulations(tron) == -1 and b"tictactoe" in lib.crl_last_error()
-    finally:
-        lib.crl_destroy(tron)
-    small = _ctx(lib, (1, 1, 2), 2, 3)     # fewer cells than players: refused as by crl_ttt_playout
-    try:
+    with ttt_context(1, 1, 2, 2, 3) as small:   # fewer cells than players: refused as by crl_ttt_playout
         assert _call(lib, small) == -1 and b"cells" in lib.crl_last_error()
-    finally:
-        lib.crl_destroy(small)
 
 
 @pytest.mark.parametrize("d, k, p, s_max", BOARDS, ids=["3x3", "3x5", "3x3x3", "5x5", "4x8"])
@@ -84,22 +61,16 @@ def test_max_simulations(d, k, p, s_max):
     cells = d[0] * d[1] * d[2]
     assert M.max_simulations(cells) == s_max == min(4095, 65536 // (8 + 2 * cells) - 1)
     assert (s_max + 1) * (8 + 2 * cells) <= 65536 < (s_max + 2) * (8 + 2 * cells) or s_max == 4095
-    h = _ctx(lib, d, k, p)
-    try:
+    with ttt_context(*d, k, p) as h:
         assert lib.crl_ttt_mcts_max_simulations(h) == s_max
         assert _call(lib, h, S=s_max, flags=1) == -1 and b"flags" in lib.crl_last_error()
         assert _call(lib, h, S=s_max + 1, flags=1) == -1 and b"S=" in lib.crl_last_error()
-    finally:
-        lib.crl_destroy(h)
 
 
 def test_max_simulations_small_board():
     lib = _lib()                           # the 12 bits of s in the counter word bound S on small boards
-    h = _ctx(lib, (1, 1, 3), 2, 2)
-    try:
+    with ttt_context(1, 1, 3, 2, 2) as h:
         assert lib.crl_ttt_mcts_max_simulations(h) == 4095 == M.max_simulations(3)
-    finally:
-        lib.crl_destroy(h)
 
 
 def test_mcts_prototypes_and_tag():
@@ -108,21 +79,12 @@ def test_mcts_prototypes_and_tag():
     assert "crl_ttt_mcts" in _native.PROTOTYPES and "crl_ttt_mcts_max_simulations" in _native.PROTOTYPES
     common = open(os.path.join(ROOT, "colosseumrl_amd", "csrc", "crl_common.hpp")).read()
     tags = re.findall(r"#define\s+(CRL_TAG_\w+)\s+(0x[0-9a-fA-F]+)u", common)
-    assert ("CRL_TAG_TTT_MCTS", "0x544D0000") in tags
+    assert ("CRL_TAG_TTT_MCTS", RNG.tag_hex("CRL_TAG_TTT_MCTS")) in tags
     values = [int(v, 16) for _, v in tags]
     assert len(set(values)) == len(values) and values.count(M.TAG_TTT_MCTS) == 1     # used nowhere else
 
 
 # ---- the Python wrappers refuse bad arguments before they reach the library (no device needed to get there)
-def _fake(cls, **attrs):
-    import torch
-    obj = cls.__new__(cls)
-    obj.device = torch.device("cpu")
-    for k, v in attrs.items():
-        setattr(obj, k, v)
-    return obj
-
-
 def test_wrapper_argument_checks():
     import torch
     from colosseumrl_amd.batched import TTTBatch, _exploration
@@ -284,7 +246,7 @@ def _flat_mc(game, occ, tm, budget, seed, g, c):
         else:
             v = 0
             for r in range(Rn):
-                ws = M.playout(game, o, (tm + 1) % game.P, seed, g, c + 1, (cell << 16) | r, tag=0x54500000)
+                ws = M.playout(game, o, (tm + 1) % game.P, seed, g, c + 1, (cell << 16) | r, tag=RNG.CRL_TAG_TTT_PLAYOUT)
                 v += 2 if ws == tm else (1 if ws < 0 else 0)
         if v > best_v:
             best, best_v = cell, v

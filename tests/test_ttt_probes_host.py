@@ -5,7 +5,7 @@ of the instance table, at the sizes of the GPU tests, for the episode conditions
 import numpy as np
 import pytest
 
-from tests import playout_ref, single_ref
+from tests import ttt_ref
 from tests import ttt_probes as TP
 
 TRAJ = ["ttt_traj_%dp_%s" % (p, r) for p in (2, 3, 4) for r in ("reset", "noreset")]
@@ -163,11 +163,11 @@ def test_step_single_restatement_on_the_instance_table(dims, K, P, mixed):
     st = O.TTTState(dims, K, P, B)
     rng = np.random.default_rng(P * 10 + mixed)
     seat = (rng.integers(0, P, size=B) if mixed else np.full(B, P - 1)).astype(np.int8)
-    single_ref.ttt_step_single(st, seat, None, seed)
+    ttt_ref.step_single(st, seat, None, seed, ttt_ref.random_agent)
     n_done = 0
     for _ in range(18):
         act = TP.single_turn_actions(st, rng)
-        reward, done, winners, obs, valid = single_ref.ttt_step_single(st, seat, act, seed)
+        reward, done, winners, obs, valid = ttt_ref.step_single(st, seat, act, seed, ttt_ref.random_agent)
         n_done += int(done.sum())
         assert valid.dtype == np.uint32 and valid.tolist() == _valid_by_hand(st)
         assert all(int(st.to_move[b]) == seat[b] for b in range(B))
@@ -183,7 +183,7 @@ def test_playout_restatement_on_the_instance_table(cfg, r_cand, r_none, n_cand):
     n = st.n_cells
     cand = TP.playout_candidates(n, st.B, rng, n_cand)
     assert cand.shape[1] == (n if n_cand is None else n_cand) + 4
-    wins, played, len_sum = playout_ref.ttt_playout(st, seed, r_cand, cand=cand, A=cand.shape[1], first_env_id=first_env_id,
+    wins, played, len_sum = ttt_ref.playout(st, seed, r_cand, ttt_ref.random_agent, cand=cand, A=cand.shape[1], first_env_id=first_env_id,
                                                     tcount=tcount)
     assert played.any() and not played.all() and set(np.unique(played)) == {0, r_cand}
     empty = np.array(_valid_by_hand(st), np.uint64)
@@ -193,7 +193,7 @@ def test_playout_restatement_on_the_instance_table(cfg, r_cand, r_none, n_cand):
     assert (wins.sum(axis=2) <= played).all() and (len_sum >= played).all()  # running game
     if n == 32:
         assert (played[cand == 31] > 0).any()
-    wins, played, len_sum = playout_ref.ttt_playout(st, seed, r_none, first_env_id=first_env_id, tcount=tcount)
+    wins, played, len_sum = ttt_ref.playout(st, seed, r_none, ttt_ref.random_agent, first_env_id=first_env_id, tcount=tcount)
     assert played.any() and not played.all()
     assert np.array_equal(played[:, 0] > 0, running)
     assert (len_sum[played > 0] <= r_none * np.array([bin(int(e)).count("1") for e in empty])[played[:, 0] > 0]).all()

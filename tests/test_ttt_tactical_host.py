@@ -1,6 +1,6 @@
 """TicTacToe's tactical (win-or-block) agent on the host: every argument check of the five C entries (rejected before any
 device work), their prototypes and declarations, the Python wrappers' validation and defaults over a stub library, and the
-numpy restatement of the contract (tests/tactical_ref.py) on its own -- that the generated positions hold every decision
+numpy restatement of the contract (tests/ttt_ref.py) on its own -- that the generated positions hold every decision
 kind in every row (so the GPU tests cannot be vacuous), the winning cells against a brute force over the line list, the
 identities of the contract, and the agent's strength against a uniformly random learner."""
 import collections
@@ -14,33 +14,21 @@ import numpy as np
 import pytest
 import torch
 
-from tests import single_ref
-from tests import tactical_ref as TR
+from tests import rng_ref as RNG
+from tests import ttt_ref as TR
 from tests import ttt_probes as TP
+from tests.host_util import D, lib as _lib, refused as _refused, ttt_context
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("crl_ttt_winning_cells", "crl_ttt_sample_tactical", "crl_ttt_rollout_tactical", "crl_ttt_step_single_tactical",
            "crl_ttt_playout_tactical")
-D = C.c_void_p(64)                         # never dereferenced: every call below is rejected by its checks
 BAD_NOISE = (-1e-9, math.nextafter(1.0, 2.0), math.nan, math.inf, -math.inf)
-
-
-def _lib():
-    from colosseumrl_amd import _native
-    return _native.lib()
 
 
 @pytest.fixture
 def ctx():
-    lib, h = _lib(), C.c_void_p()
-    assert lib.crl_ttt_create(1, 3, 3, 3, 2, C.byref(h)) == 0
-    yield lib, h
-    lib.crl_destroy(h)
-
-
-def _refused(lib, rc, word):
-    msg = lib.crl_last_error()
-    assert rc == -1 and word in msg, (rc, msg)
+    with ttt_context() as h:
+        yield _lib(), h
 
 
 def _common(lib, h, call, name, n_ptr):
@@ -61,12 +49,8 @@ def _noise(lib, call):
 
 
 def _small_board(lib, call):
-    small = C.c_void_p()                   # fewer cells than players: refused as by crl_ttt_step_single
-    assert lib.crl_ttt_create(1, 1, 2, 2, 3, C.byref(small)) == 0
-    try:
+    with ttt_context(1, 1, 2, 2, 3) as small:   # fewer cells than players: refused as by crl_ttt_step_single
         _refused(lib, call(ctx=small), b"cells")
-    finally:
-        lib.crl_destroy(small)
 
 
 def test_winning_cells_argument_checks(ctx):
@@ -144,8 +128,9 @@ def test_prototypes_and_declarations():
     assert _native.CRL_ABI_VERSION == 113 and _lib().crl_version() == 113
     header = open(os.path.join(ROOT, "include", "colosseum_hip.h")).read()
     common = open(os.path.join(ROOT, "colosseumrl_amd", "csrc", "crl_common.hpp")).read()
-    assert "CRL_TAG_TTT_TACTICAL         0x54630000u" in common and "CRL_TAG_TTT_TACTICAL_PLAYOUT 0x54430000u" in common
-    assert "0x54630000" in header and "0x54430000" in header
+    tag, playout_tag = RNG.tag_hex("CRL_TAG_TTT_TACTICAL"), RNG.tag_hex("CRL_TAG_TTT_TACTICAL_PLAYOUT")
+    assert "CRL_TAG_TTT_TACTICAL         %su" % tag in common and "CRL_TAG_TTT_TACTICAL_PLAYOUT %su" % playout_tag in common
+    assert tag in header and playout_tag in header
     for name in ENTRIES:
         res, args = _native.PROTOTYPES[name]
         assert res is C.c_int and hasattr(_lib(), name)
@@ -330,8 +315,8 @@ def test_winning_cells_against_the_line_list(cfg):
 
 
 def test_threshold():
-    assert TR.threshold(0.0) == 0 and TR.threshold(1.0) == 1 << 32 and TR.threshold(0.5) == 1 << 31
-    assert TR.threshold(2.0 ** -33) == 1 and TR.threshold(1.0 - 2.0 ** -40) == 1 << 32
+    assert RNG.threshold(0.0) == 0 and RNG.threshold(1.0) == 1 << 32 and RNG.threshold(0.5) == 1 << 31
+    assert RNG.threshold(2.0 ** -33) == 1 and RNG.threshold(1.0 - 2.0 ** -40) == 1 << 32
 
 
 @pytest.mark.parametrize("cfg", [((3, 5), 3, 3), ((4, 4), 4, 4), ((2, 2, 8), 2, 5)], ids=["3x5k3p3", "4x4k4p4", "2x2x8k2p5"])
@@ -340,8 +325,8 @@ def test_the_move_follows_the_contract(cfg):
     st = TR.state_of(cfg)
     W = TR.winning_cells(st)
     E = TR.empties(dims, st.occ)
-    quiet, loud = TR.sample(st, 5, 0.0, advance=False), TR.sample(st, 5, 1.0, advance=False)
-    some = TR.sample(st, 5, 0.1, advance=False)
+    quiet, loud = TR.sample(st, 5, TR.tactical_agent(0.0), advance=False), TR.sample(st, 5, TR.tactical_agent(1.0), advance=False)
+    some = TR.sample(st, 5, TR.tactical_agent(0.1), advance=False)
     assert (st.tcount == TR.positions(cfg)["tcount"]).all()        # advance=False
     n_noisy = 0
     for b in range(st.B):
@@ -357,7 +342,7 @@ def test_the_move_follows_the_contract(cfg):
         n_noisy += some[b] != quiet[b]
     assert 0 < n_noisy < 60                                      # about a tenth of the plies, fewer where the sets agree
     before = st.tcount.copy()
-    TR.sample(st, 5, 0.1)
+    TR.sample(st, 5, TR.tactical_agent(0.1))
     assert (st.tcount == before + np.uint32(1)).all()              # advance (2^32 - 1 wraps to 0)
 
 
@@ -370,15 +355,15 @@ def test_a_learner_that_plays_the_agents_move_is_the_rollout(cfg):
     seat = (np.arange(B) % P).astype(np.int8)
 
     def policy(s):
-        return TR.sample(s, seed, noise, advance=False).astype(np.int64)
-    TR.step_single(st, seat, None, seed, noise)
+        return TR.sample(s, seed, TR.tactical_agent(noise), advance=False).astype(np.int64)
+    TR.step_single(st, seat, None, seed, TR.tactical_agent(noise))
     n_done = 0
     for _ in range(8):
-        n_done += int(TR.step_single(st, seat, None, seed, noise, policy=policy)[1].sum())
+        n_done += int(TR.step_single(st, seat, None, seed, TR.tactical_agent(noise), policy=policy)[1].sum())
     assert n_done > 0 and (st.to_move == seat).all()
     for g in range(B):
         ref = O.TTTState(dims, K, P, 1)
-        TR.rollout(ref, seed, noise, int(st.tcount[g]), first_env_id=g)
+        TR.rollout(ref, seed, TR.tactical_agent(noise), int(st.tcount[g]), first_env_id=g)
         assert np.array_equal(ref.occ[:, 0], st.occ[:, g]) and ref.winner[0] == st.winner[g] and ref.to_move[0] == st.to_move[g], g
 
 
@@ -388,7 +373,7 @@ def test_playout_without_a_candidate_is_the_rollouts_first_episode():
     from oracle import oracle as O
     cfg = ((3, 5), 3, 3)
     st = TR.state_of(cfg, 37)
-    wins, played, len_sum = TR.playout(st, 9, 3, 0.1, first_env_id=100, tcount=st.tcount)
+    wins, played, len_sum = TR.playout(st, 9, 3, TR.tactical_agent(0.1), first_env_id=100, tcount=st.tcount)
     over = (st.winner >= 0) | (TR.empties(cfg[0], st.occ) == 0)
     assert (played[~over, 0] == 3).all() and not played[over].any() and not len_sum[over].any() and not wins[over].any()
     for b in np.flatnonzero(~over)[:10]:
@@ -397,7 +382,7 @@ def test_playout_without_a_candidate_is_the_rollouts_first_episode():
             one.occ[:, 0], one.to_move[0] = st.occ[:, b], st.to_move[b]
             c, plies = int(st.tcount[b]), 0
             while True:
-                u, v = TR.draws(9, [100 + b], [c], [r], TR.TAG_PLAYOUT)
+                u, v = TR.draws(9, [100 + b], [c], [r], RNG.CRL_TAG_TTT_TACTICAL_PLAYOUT)
                 act, _, _ = TR.moves(cfg[0], cfg[1], cfg[2], one.occ, one.to_move, u, v, 0.1)
                 _, term, ws = O.ttt_step(one, act)
                 plies, c = plies + 1, (c + 1) & 0xFFFFFFFF
@@ -434,13 +419,13 @@ def test_strength_on_the_restatement():
     st = O.TTTState((3, 3), 3, 2, B)
 
     def against_random(act):
-        reward, done, _, _, valid = single_ref.ttt_step_single(st, seat, act, 2024)
+        reward, done, _, _, valid = TR.step_single(st, seat, act, 2024, TR.random_agent)
         return reward, done, valid
     rnd = _uniform_learner_share(against_random, B, np.random.default_rng(1))
     st = O.TTTState((3, 3), 3, 2, B)
 
     def against_tactical(act):
-        reward, done, _, _, valid = TR.step_single(st, seat, act, 2024, 0.0)
+        reward, done, _, _, valid = TR.step_single(st, seat, act, 2024, TR.tactical_agent(0.0))
         return reward, done, valid
     tac = _uniform_learner_share(against_tactical, B, np.random.default_rng(1))
     assert rnd >= 0.45 and tac <= 0.15, (rnd, tac)

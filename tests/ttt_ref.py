@@ -1,51 +1,76 @@
-"""numpy restatement of TicTacToe's tactical (win-or-block) agent -- crl_ttt_winning_cells and crl_ttt_sample_tactical /
-_rollout_tactical / _step_single_tactical / _playout_tactical (include/colosseum_hip.h) -- written from the header's words:
-the winning cells come from tests.ttt_probes.has_line on o[q] | 1 << e (one call per (game, player) over all its empty
-cells; many games at once are the same call on the concatenated masks), the draws from oracle.philox4x32, the plies from
-oracle.ttt_step.  No code is shared with the kernels.
+"""numpy restatement of every TicTacToe contract of include/colosseum_hip.h but the tree search (tests/mcts_ref.py):
+crl_ttt_sample / _rollout / _step_single / _playout with the random agent, crl_ttt_winning_cells and the same four calls
+with the tactical (win-or-block) agent.  Written from the header's words over the CPU oracle's own bindings: the plies are
+oracle.ttt_step's, the winning cells come from tests.ttt_probes.has_line on o[q] | 1 << e, the draws from rng_ref.philox.
+No code is shared with the kernels.
 
-Also the positions the host and the GPU tests share (`positions`): random ones, boards with planted threats at every turn
-distance from the mover, empty and full boards.
+An agent is a function ``agent(dims, K, P, occ, to_move, seed, g, c, c2, tag) -> int8 [N]`` of N games (occ uint32 [P, N],
+to_move [N]) with game ids g, step counters c, third counter words c2 (None = 0) and a Philox tag; ``agent.tag`` and
+``agent.playout_tag`` are the tags of its per-step calls and of its playouts.  Each frame (`sample`, `rollout`,
+`step_single`, `playout`) is written once, steps all its games in lockstep and takes the agent as a parameter.
+
+Also the positions the host and the GPU tests of the tactical agent share (`positions`): random ones, boards with planted
+threats at every turn distance from the mover, empty and full boards; and the exact outcome probabilities of 3x3 positions
+under uniform random play.
 
 States are the oracle's TTTState (``tcount`` is the step counter of the draws)."""
 import functools
-import math
 
 import numpy as np
 
 from oracle import oracle as O
+from tests import rng_ref as RNG
 from tests import ttt_probes as TP
 
-TAG = 0x54630000                           # CRL_TAG_TTT_TACTICAL
-TAG_PLAYOUT = 0x54430000                   # CRL_TAG_TTT_TACTICAL_PLAYOUT
-M32 = 0xFFFFFFFF
 N_POSITIONS = 203
 
-# decision kinds of a noise-free ply (`kinds`)
+# decision kinds of a noise-free tactical ply (`kinds`)
 OVER, OWN, NEXT, LATER, NONE = "over", "own", "next", "later", "none"
 
 
-def threshold(noise):
-    """thr of the header's step 3: min(2^32, ceil(noise * 2^32))"""
-    return min(1 << 32, math.ceil(noise * 4294967296.0))
-
-
-def _key(seed):
-    return [seed & M32, (seed >> 32) & M32]
-
-
-def _u32(a):
+def _as_u32(a):
     return np.asarray(a).astype(np.uint32)
 
 
 def empties(dims, occ):
     """uint32 [N]: E of every game (occ uint32 [P, N])"""
-    return np.uint32(TP.full_mask(dims)) & ~np.bitwise_or.reduce(_u32(occ), axis=0)
+    return np.uint32(TP.full_mask(dims)) & ~np.bitwise_or.reduce(_as_u32(occ), axis=0)
 
 
+def _popcount(S):
+    return np.array([bin(int(s)).count("1") for s in S], np.uint64)
+
+
+def _nth_set_bit(S, r):
+    """the r[i]-th set bit of S[i], ascending"""
+    bits = ((S[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & np.uint32(1)).astype(np.int64)
+    return ((np.cumsum(bits, axis=1) == (r[:, None] + 1)) & (bits == 1)).argmax(axis=1)
+
+
+def _counters(g, c, c2):
+    g, c = np.asarray(g, np.uint64), np.asarray(c, np.uint64) & np.uint64(RNG.M32)
+    return g, c, (np.zeros(len(g), np.uint64) if c2 is None else np.asarray(c2, np.uint64))
+
+
+# ------------------------------------------------------------------ the random agent
+def random_agent(dims, K, P, occ, to_move, seed, g, c, c2, tag):
+    """crl_ttt_sample's rule: word (c >> 1) & 3 of block c >> 3, on odd counters multiplied by n + 1 (mod 2^32), picks the
+    mulhi32-th of the n empty cells; -1 on a full board"""
+    g, c, c2 = _counters(g, c, c2)
+    E = empties(dims, occ)
+    n = _popcount(E)
+    w = np.choose(((c >> np.uint64(1)) & np.uint64(3)).astype(np.int64), RNG.philox(g, c >> np.uint64(3), c2, tag, seed))
+    w = np.where((c & np.uint64(1)) != 0, (w.astype(np.uint64) * (n + np.uint64(1))) & np.uint64(RNG.M32), w)
+    return np.where(n == 0, -1, _nth_set_bit(E, RNG.mulhi(w, n))).astype(np.int8)
+
+
+random_agent.tag, random_agent.playout_tag = RNG.CRL_TAG_TTT, RNG.CRL_TAG_TTT_PLAYOUT
+
+
+# ------------------------------------------------------------------ the tactical agent
 def winning_cells_of(dims, K, marks, E):
     """uint32 [N]: W = {e in E[i] : has_line(marks[i] | 1 << e)} for each pair (marks[i], E[i])"""
-    marks, E = _u32(marks), _u32(E)
+    marks, E = _as_u32(marks), _as_u32(E)
     n = TP.n_cells_of(dims)
     game, cell = np.nonzero((E[:, None] >> np.arange(n, dtype=np.uint32)[None, :]) & np.uint32(1))
     W = np.zeros(len(marks), np.uint32)
@@ -62,35 +87,25 @@ def winning_cells(st):
     return np.stack([winning_cells_of(st.dims, st.K, st.occ[q], E) for q in range(st.P)])
 
 
-def draws(seed, g, c, c2=None, tag=TAG):
-    """(u, v) uint64 [N] of the header's step 2 for games g at step counters c (third counter word c2, default 0)"""
-    g, c = np.asarray(g, np.uint64), np.asarray(c, np.uint64)
-    c2 = np.zeros(len(g), np.uint64) if c2 is None else np.asarray(c2, np.uint64)
-    u, v = np.zeros(len(g), np.uint64), np.zeros(len(g), np.uint64)
-    key = _key(seed)
-    for i in range(len(g)):
-        w = O.philox4x32([int(g[i]) & M32, (int(c[i]) & M32) >> 1, int(c2[i]) & M32, tag], key)
-        k = 2 * (int(c[i]) & 1)
-        u[i], v[i] = int(w[k]), int(w[k + 1])
-    return u, v
-
-
-def _nth_set_bit(S, r):
-    """the r[i]-th set bit of S[i], ascending"""
-    bits = ((S[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & np.uint32(1)).astype(np.int64)
-    return ((np.cumsum(bits, axis=1) == (r[:, None] + 1)) & (bits == 1)).argmax(axis=1)
+def draws(seed, g, c, c2=None, tag=RNG.CRL_TAG_TTT_TACTICAL):
+    """(u, v) uint64 [N] of the header's step 2 for games g at step counters c (third counter word c2, default 0): words
+    2 * (c & 1) and 2 * (c & 1) + 1 of block c >> 1"""
+    g, c, c2 = _counters(g, c, c2)
+    w = RNG.philox(g, c >> np.uint64(1), c2, tag, seed)
+    k = 2 * (c & np.uint64(1)).astype(np.int64)
+    return np.choose(k, w).astype(np.uint64), np.choose(k + 1, w).astype(np.uint64)
 
 
 def moves(dims, K, P, occ, to_move, u, v, noise):
     """The tactical move (steps 1, 3, 4, 5) of N games with draws (u, v): (action int8 [N], distance int [N], S uint32 [N]).
     distance: -2 pass, -1 noisy, i = the set of player (mover + i) mod P was chosen, P = nobody has a winning cell."""
-    occ, tm = _u32(occ), np.asarray(to_move).astype(np.int64)
+    occ, tm = _as_u32(occ), np.asarray(to_move).astype(np.int64)
     N = occ.shape[1]
     E = empties(dims, occ)
     S = E.copy()
     dist = np.full(N, P, np.int64)
     passing = (tm < 0) | (tm >= P) | (E == 0)
-    noisy = ~passing & (u < np.uint64(threshold(noise)))
+    noisy = ~passing & (u < np.uint64(RNG.threshold(noise)))
     dist[noisy], dist[passing] = -1, -2
     pending = ~passing & ~noisy
     for i in range(P):
@@ -101,23 +116,32 @@ def moves(dims, K, P, occ, to_move, u, v, noise):
         W = winning_cells_of(dims, K, occ[q, idx], E[idx])
         hit = idx[W != 0]
         S[hit], dist[hit], pending[hit] = W[W != 0], i, False
-    count = np.array([bin(int(s)).count("1") for s in S], np.uint64)
-    action = _nth_set_bit(S, ((v * count) >> np.uint64(32)).astype(np.int64))
+    action = _nth_set_bit(S, RNG.mulhi(v, _popcount(S)))
     return np.where(passing, -1, action).astype(np.int8), dist, S
 
 
+def tactical_agent(noise):
+    """the win-or-block agent at noise level `noise`"""
+    def agent(dims, K, P, occ, to_move, seed, g, c, c2, tag):
+        u, v = draws(seed, g, c, c2, tag)
+        return moves(dims, K, P, occ, to_move, u, v, noise)[0]
+    agent.tag, agent.playout_tag = RNG.CRL_TAG_TTT_TACTICAL, RNG.CRL_TAG_TTT_TACTICAL_PLAYOUT
+    return agent
+
+
 def kinds(st):
-    """the decision kind of a noise-free ply on every game of `st`, and the chosen sets: (list of str, S uint32 [B], E)"""
+    """the decision kind of a noise-free tactical ply on every game of `st`, and the chosen sets: (list of str, S uint32
+    [B], E)"""
     zero = np.zeros(st.B, np.uint64)
     _, dist, S = moves(st.dims, st.K, st.P, st.occ, st.to_move, zero, zero, 0.0)
     name = {-2: OVER, 0: OWN, 1: NEXT, st.P: NONE}
     return [name.get(int(d), LATER) for d in dist], S, empties(st.dims, st.occ)
 
 
-def sample(st, seed, noise, first_env_id=0, advance=True):
-    """crl_ttt_sample_tactical on every game of `st`: int8 [B]; `advance` moves st.tcount on"""
-    u, v = draws(seed, first_env_id + np.arange(st.B), st.tcount)
-    act, _, _ = moves(st.dims, st.K, st.P, st.occ, st.to_move, u, v, noise)
+# ------------------------------------------------------------------ the frames
+def sample(st, seed, agent, first_env_id=0, advance=True):
+    """crl_ttt_sample / _sample_tactical on every game of `st`: int8 [B]; `advance` moves st.tcount on"""
+    act = agent(st.dims, st.K, st.P, st.occ, st.to_move, seed, first_env_id + np.arange(st.B), st.tcount, None, agent.tag)
     if advance:
         st.tcount += np.uint32(1)
     return act
@@ -138,10 +162,10 @@ def step_auto_reset(st, act):
     return reward, term, ws
 
 
-def rollout(st, seed, noise, T, first_env_id=0):
-    """crl_ttt_rollout_tactical(T) on `st` (mutated, statistics included)"""
+def rollout(st, seed, agent, T, first_env_id=0):
+    """crl_ttt_rollout / _rollout_tactical (T) on `st` (mutated, statistics included)"""
     for _ in range(T):
-        step_auto_reset(st, sample(st, seed, noise, first_env_id))
+        step_auto_reset(st, sample(st, seed, agent, first_env_id))
 
 
 def results(st):
@@ -149,8 +173,8 @@ def results(st):
     return np.stack([st.n_episodes, st.len_sum, st.draw_count] + [st.win_count[p] for p in range(st.P)], axis=1).astype(np.int32)
 
 
-def step_single(st, seat, learner_action, seed, noise, first_env_id=0, rel_mod=None, policy=None):
-    """crl_ttt_step_single_tactical on every game of `st` (mutated, tcount included), the games in lockstep.
+def step_single(st, seat, learner_action, seed, agent, first_env_id=0, rel_mod=None, policy=None):
+    """crl_ttt_step_single / _step_single_tactical on every game of `st` (mutated, tcount included), the games in lockstep.
     learner_action int64 [B] or None; `policy(st)` (instead) returns int64 [B] learner actions for the current states.
     Returns (reward int8, done uint8, winners int8, obs int8 [B, cells], valid uint32)."""
     P, B, n = st.P, st.B, st.n_cells
@@ -168,11 +192,9 @@ def step_single(st, seat, learner_action, seed, noise, first_env_id=0, rel_mod=N
         if learner.any():
             v = np.asarray(policy(st) if policy is not None else learner_action, np.int64)
             act[learner] = np.where((v >= -1) & (v < n), v, -1)[learner]
-        agent = active & ~learner
-        idx = np.flatnonzero(agent)
+        idx = np.flatnonzero(active & ~learner)
         if len(idx):
-            u, w = draws(seed, g[idx], st.tcount[idx])
-            act[idx], _, _ = moves(st.dims, st.K, P, st.occ[:, idx], st.to_move[idx], u, w, noise)
+            act[idx] = agent(st.dims, st.K, P, st.occ[:, idx], st.to_move[idx], seed, g[idx], st.tcount[idx], None, agent.tag)
             opp[idx] += 1
         learner[:] = False
         before = (st.occ.copy(), st.winner.copy(), st.to_move.copy())
@@ -190,27 +212,32 @@ def step_single(st, seat, learner_action, seed, noise, first_env_id=0, rel_mod=N
     return reward, done, winners, obs, empties(st.dims, st.occ)
 
 
-def playout(st, seed, R, noise, cand=None, A=1, first_env_id=0, tcount=None):
-    """crl_ttt_playout_tactical on the oracle state `st` (never written), all playouts in lockstep: (wins uint32 [B, A, P],
-    played uint32 [B, A], len_sum uint32 [B, A])."""
+def playout(st, seed, R, agent, cand=None, A=1, first_env_id=0, tcount=None, rows=None):
+    """crl_ttt_playout / _playout_tactical on the oracle state `st` (never written), all playouts in lockstep: (wins uint32
+    [B, A, P], played uint32 [B, A], len_sum uint32 [B, A]).  rows: optional iterable of (b, a) to compute (the others stay
+    0)."""
     B, P, n = st.B, st.P, st.n_cells
+    if cand is None:
+        assert A == 1
+    else:
+        cand = np.asarray(cand, np.int64)
+        assert cand.shape == (B, A)
     E = empties(st.dims, st.occ)
-    rows = []                                                    # (b, a, first or -1) of the rows that play
-    for b in range(B):
+    todo = []                                                    # (b, a, first or -1) of the rows that play
+    for b, a in (rows if rows is not None else [(b, a) for b in range(B) for a in range(A)]):
         if int(st.winner[b]) >= 0 or int(E[b]) == 0 or not 0 <= int(st.to_move[b]) < P:
             continue                                             # a position that is over skips every row
-        for a in range(A):
-            first = -1
-            if cand is not None:
-                first = int(cand[b][a])
-                if not (0 <= first < n and (int(E[b]) >> first) & 1):
-                    continue                                     # not an empty cell: the row is skipped
-            rows.append((b, a, first))
+        first = -1
+        if cand is not None:
+            first = int(cand[b, a])
+            if not (0 <= first < n and (int(E[b]) >> first) & 1):
+                continue                                         # not an empty cell: the row is skipped
+        todo.append((b, a, first))
     wins, played, len_sum = np.zeros((B, A, P), np.uint32), np.zeros((B, A), np.uint32), np.zeros((B, A), np.uint32)
-    if not rows:
+    if not todo:
         return wins, played, len_sum
-    rb, ra, rf = (np.repeat(np.array(col, np.int64), R) for col in zip(*rows))
-    rr = np.tile(np.arange(R, dtype=np.int64), len(rows))
+    rb, ra, rf = (np.repeat(np.array(col, np.int64), R) for col in zip(*todo))
+    rr = np.tile(np.arange(R, dtype=np.int64), len(todo))
     N = len(rb)
     one = O.TTTState(st.dims, st.K, P, N)
     one.occ[:], one.winner[:], one.to_move[:] = st.occ[:, rb], st.winner[rb], st.to_move[rb]
@@ -224,9 +251,9 @@ def playout(st, seed, R, noise, cand=None, A=1, first_env_id=0, tcount=None):
         if first_ply:                                            # the candidate ply: no draw
             act[:] = rf
         else:
-            u, v = draws(seed, first_env_id + rb[idx], c[idx], (ra[idx] << 16) | rr[idx], TAG_PLAYOUT)
-            act[idx], _, _ = moves(st.dims, st.K, P, one.occ[:, idx], one.to_move[idx], u, v, noise)
-            c[idx] = (c[idx] + np.uint64(1)) & np.uint64(M32)
+            act[idx] = agent(st.dims, st.K, P, one.occ[:, idx], one.to_move[idx], seed, first_env_id + rb[idx], c[idx],
+                             (ra[idx] << 16) | rr[idx], agent.playout_tag)
+            c[idx] = (c[idx] + np.uint64(1)) & np.uint64(RNG.M32)
         _, term, ws = O.ttt_step(one, act.astype(np.int8))       # (a finished playout's further plies are never read)
         plies[idx] += 1
         ended = alive & (term != 0)
@@ -250,6 +277,14 @@ def flat_mc_pick(st, wins, played, cells):
     best = value.argmax(axis=1)
     pick = np.take_along_axis(np.asarray(cells, np.int64), best[:, None], axis=1)[:, 0]
     return np.where(played.max(axis=1) > 0, pick, -1)
+
+
+def one_game(st, b):
+    """a one-game oracle state holding game b of `st`"""
+    one = O.TTTState(st.dims, st.K, st.P, 1)
+    one.occ[:, 0] = st.occ[:, b]
+    one.winner[0], one.to_move[0] = st.winner[b], st.to_move[b]
+    return one
 
 
 # ------------------------------------------------------------------ the positions the host and GPU tests share
@@ -331,3 +366,52 @@ def state_of(cfg, B=N_POSITIONS):
     st = O.TTTState(dims, K, P, B)
     st.occ[:], st.winner[:], st.to_move[:], st.tcount[:] = pos["occ"][:, pick], pos["winner"][pick], pos["to_move"][pick], pos["tcount"][pick]
     return st
+
+
+# ------------------------------------------------------------------ exact values (3x3, two players, uniform random play)
+_LINES_3X3 = [0b000000111, 0b000111000, 0b111000000, 0b001001001, 0b010010010, 0b100100100, 0b100010001, 0b001010100]
+
+
+def exact_3x3(x, o, mover, memo=None):
+    """(P(player 0 wins), P(player 1 wins)) of a running 3x3 position (marks x of player 0, o of player 1) under uniform
+    random play to the end, by recursion over the game tree."""
+    memo = {} if memo is None else memo
+    key = (x, o, mover)
+    if key in memo:
+        return memo[key]
+    empty = [i for i in range(9) if not ((x | o) >> i) & 1]
+    p0 = p1 = 0.0
+    for cell in empty:
+        nx, no = (x | (1 << cell), o) if mover == 0 else (x, o | (1 << cell))
+        mine = nx if mover == 0 else no
+        if any((mine & ln) == ln for ln in _LINES_3X3):
+            w = (1.0, 0.0) if mover == 0 else (0.0, 1.0)
+        elif (nx | no) == 0x1FF:
+            w = (0.0, 0.0)
+        else:
+            w = exact_3x3(nx, no, 1 - mover, memo)
+        p0 += w[0] / len(empty)
+        p1 += w[1] / len(empty)
+    memo[key] = (p0, p1)
+    return memo[key]
+
+
+def reachable_3x3():
+    """every running (non-terminal) position reachable from the empty 3x3 board: [(x, o, mover)] (4,520)"""
+    seen, frontier = set(), [(0, 0, 0)]
+    while frontier:
+        nxt = []
+        for x, o, m in frontier:
+            if (x, o, m) in seen:
+                continue
+            seen.add((x, o, m))
+            for cell in range(9):
+                if ((x | o) >> cell) & 1:
+                    continue
+                nx, no = (x | (1 << cell), o) if m == 0 else (x, o | (1 << cell))
+                mine = nx if m == 0 else no
+                if any((mine & ln) == ln for ln in _LINES_3X3) or (nx | no) == 0x1FF:
+                    continue
+                nxt.append((nx, no, 1 - m))
+        frontier = nxt
+    return sorted(seen)

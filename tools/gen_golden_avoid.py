@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from tests import avoid_ref  # noqa: E402
+from tests import rng_ref, tron_ref  # noqa: E402
 
 SEED = 0x5EED_A701
 # (N, P, noise as num / den, games, step cap per game)
@@ -102,7 +102,7 @@ def load_reference_agent():
 def play(ref, mod, N, P, noise, games, cap, seed=SEED):
     fake = ContractRandom()
     fake.noise = noise
-    fake.thr = avoid_ref.threshold(noise)
+    fake.thr = rng_ref.threshold(noise)
     mod.random = fake
     agent = mod.SimpleAvoidAgent(noise=noise)
     env = ref["tron"].create(board_size=N, num_players=P)
@@ -113,7 +113,7 @@ def play(ref, mod, N, P, noise, games, cap, seed=SEED):
         for c in range(cap):
             board, heads, dirs, deaths = state
             g = len(rec["c"])
-            w = np.stack(avoid_ref.words(np.uint64(g), np.uint64(c), np.arange(P, dtype=np.uint64), seed), axis=1)
+            w = np.stack(tron_ref.words(np.uint64(g), np.uint64(c), np.arange(P, dtype=np.uint64), seed), axis=1)
             acts = np.zeros(P, np.int8)
             names = []
             for p in players:
@@ -145,7 +145,7 @@ def situations(N, rec):
     and both sides occupied on the clamped probes)."""
     heads, dirs, deaths, board = rec["heads"].T, rec["dirs"].T, rec["deaths"].T, rec["board"]
     rows = np.arange(board.shape[0])[None, :]
-    cell = lambda off: avoid_ref.clamped_cell(N, heads, dirs.astype(np.int64) + off)
+    cell = lambda off: tron_ref.clamped_cell(N, heads, dirs.astype(np.int64) + off)
     alive = deaths == 0
     wall = alive & (cell(0) == heads)
     boxed = alive & (board[rows, cell(0)] != 0) & (board[rows, cell(1)] != 0) & (board[rows, cell(3)] != 0)

@@ -126,6 +126,9 @@ PROTOTYPES = {
     "crl_ttt_playout_tactical": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 5 + [_I, _I] + [_VP] * 3 + [C.c_double, _U32, _VP]),
     "crl_ttt_mcts_max_simulations": (_I, [_VP]),
     "crl_ttt_mcts": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 4 + [_I, _I, _U32] + [_VP] * 4 + [_U32, _VP]),
+    "crl_ttt_sample_mcts": (_I, [_VP, _I64, _U64, _U64, _VP, _VP, _VP, _I, _I, _I, _U32, C.c_double, _VP, _VP]),
+    "crl_ttt_rollout_mcts": (_I, [_VP, _I64, _U64, _U64, _I, _I, _I, _U32, C.c_double, _VP, _VP, _VP, TTTStats, _VP]),
+    "crl_ttt_step_single_mcts": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 11 + [_I, _I, _I, _U32, C.c_double, _U32, _VP]),
     "crl_blokus_create": (_I, [C.POINTER(_VP)]),
     "crl_blokus_placement": (_I, [_I, _I, _I, _VP]),
     "crl_blokus_stamps": (_I, [_VP, _I]),

@@ -807,7 +807,8 @@ class TTTBatch(_RolloutStepper):
         return out
 
     def step_single(self, seat: torch.Tensor, learner_action: Optional[torch.Tensor] = None, seed: int = 0,
-                    rel_mod: Optional[int] = None, out: Optional[dict] = None, opponent: str = "random", noise: float = 0.1):
+                    rel_mod: Optional[int] = None, out: Optional[dict] = None, opponent: str = "random", noise: float = 0.1,
+                    simulations: Optional[int] = None, playouts: int = 16, exploration: float = 1.0):
         """One step of "learner at seat[b] against the random agent" in every game, ONE launch (``crl_ttt_step_single``):
         the learner plays ``learner_action`` (int64 [B]: a cell in [-1, cells), anything else passes) when it is its turn,
         the random agent plays every other seat until it is the learner's turn again, finished games restart on the way.
@@ -815,17 +816,25 @@ class TTTBatch(_RolloutStepper):
         {'board' int8 [B, cells] relative to the learner, 'valid' int32 [B] empties mask, 'reward' int8 [B] (+1 the learner
         won, -1 another player, 0 draw or not over), 'done' uint8 [B], 'winners' int8 [B]}; every ply, the learner's
         included, advances ``tcount`` (the draws are ``sample``'s).  ``opponent="tactical"``: every other seat plays the
-        tactical agent with ``noise`` instead (``crl_ttt_step_single_tactical``; the draws are ``sample_tactical``'s)."""
+        tactical agent with ``noise`` instead (``crl_ttt_step_single_tactical``; the draws are ``sample_tactical``'s).
+        ``opponent="mcts"``: every other seat plays the search agent (``crl_ttt_step_single_mcts``; ``sample_mcts``'s moves) with
+        ``simulations`` (required), ``playouts``, ``exploration`` and ``noise``; still one launch."""
         _want(seat, torch.int8, (self.B,), self.device, "seat")
         if learner_action is not None:
             _want(learner_action, torch.int64, (self.B,), self.device, "learner_action")
-        tactical = _one_of("opponent", opponent, self.AGENTS) == "tactical"
+        opponent = _one_of("opponent", opponent, self.OPPONENTS)
         noise = _unit("noise", noise)
+        if opponent == "mcts":
+            if simulations is None:
+                raise ValueError("opponent='mcts' needs simulations")
+            name, tail = "crl_ttt_step_single_mcts", self._search_args(simulations, playouts, exploration) + (noise, 0)
+        else:
+            name, tail = ("crl_ttt_step_single_tactical", (noise, 0)) if opponent == "tactical" else ("crl_ttt_step_single", (0,))
         out = out or _alloc(dict(self._obs_spec(), done=(torch.uint8, (self.B,))), self.device)
-        self._call("crl_ttt_step_single_tactical" if tactical else "crl_ttt_step_single", _seed(seed), self.first_env_id,
+        self._call(name, _seed(seed), self.first_env_id,
                    _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move), _ptr(seat), _ptr(learner_action), _ptr(self.tcount),
                    _ptr(self.reward), _ptr(out["done"]), _ptr(self.winners), _ptr(out["board"]), _ptr(out["valid"]),
-                   int(rel_mod if rel_mod else self.P), *((noise, 0) if tactical else (0,)))
+                   int(rel_mod if rel_mod else self.P), *tail)
         out["reward"], out["winners"] = self.reward, self.winners
         return out
 
@@ -888,9 +897,7 @@ class TTTBatch(_RolloutStepper):
         (2 per won playout, 1 per drawn one) for the mover, 'nodes' int32 [B], 'best' int32 [B]: the most visited cell (ties:
         the larger value, then the lowest cell; -1 for a skipped position)}; ``out`` reuses such a dict.  The visit counts
         are the policy target of an AlphaZero-style trainer.  No host synchronisation; capturable into a graph."""
-        S = _int_in("simulations", simulations, 1, self.mcts_max_simulations)
-        R = _int_in("playouts", playouts, 1, 1024)
-        cexp = _exploration("exploration", exploration)
+        S, R, cexp = self._search_args(simulations, playouts, exploration)
         i32 = torch.int32
         out = _out_dict(out, {"visits": (i32, (self.B, self.n_cells)), "value": (i32, (self.B, self.n_cells)),
                               "nodes": (i32, (self.B,)), "best": (i32, (self.B,))}, self.device)
@@ -898,11 +905,42 @@ class TTTBatch(_RolloutStepper):
                    _ptr(self.tcount), S, R, cexp, _ptr(out["visits"]), _ptr(out["value"]), _ptr(out["nodes"]), _ptr(out["best"]), 0)
         return out
 
+    def _search_args(self, simulations, playouts, exploration):
+        """(S, R, cexp) of a search as the C entries take them, checked"""
+        return (_int_in("simulations", simulations, 1, self.mcts_max_simulations), _int_in("playouts", playouts, 1, 1024),
+                _exploration("exploration", exploration))
+
     def mcts_action(self, simulations: int, playouts: int = 16, seed: int = 0, exploration: float = 1.0,
                     out: Optional[dict] = None) -> torch.Tensor:
         """``mcts``'s most visited cell as an int64 [B] action for ``step_single`` (-1 where the game is over): the arg-max
         is the kernel's own ``best``, only widened here.  No host synchronisation; capturable."""
         return self.mcts(simulations, playouts, seed, exploration, out)["best"].to(torch.int64)
+
+    # -- the search as a seated agent; the contract is with crl_ttt_sample_mcts in include/colosseum_hip.h
+    OPPONENTS = AGENTS + ("mcts",)          # who `step_single` seats (`playout` takes AGENTS only)
+
+    def sample_mcts(self, simulations: int, playouts: int = 16, seed: int = 0, exploration: float = 1.0, noise: float = 0.0,
+                    advance: bool = True):
+        """The search agent for one step (``crl_ttt_sample_mcts``): int8 [B] flat cell at each game's step counter -- with
+        probability ``noise`` a uniform empty cell (``sample_tactical``'s draw: at ``noise=1`` the same move), else ``best`` of
+        ``mcts(simulations, playouts, seed, exploration)`` on the position with the counter as its base; -1 on a full board.
+        ``step(sample_mcts(...), auto_reset=True)`` T times == ``rollout_mcts(T, ...)``.  One launch, a wave per game; no host
+        synchronisation, capturable into a graph."""
+        S, R, cexp = self._search_args(simulations, playouts, exploration)
+        noise = _unit("noise", noise)
+        act = torch.empty((self.B,), dtype=torch.int8, device=self.device)
+        self._call("crl_ttt_sample_mcts", _seed(seed), self.first_env_id, _ptr(self.occ), _ptr(self.to_move), _ptr(self.tcount),
+                   int(advance), S, R, cexp, noise, _ptr(act))
+        return act
+
+    def rollout_mcts(self, steps: int, simulations: int, playouts: int = 16, seed: int = 0, exploration: float = 1.0,
+                     noise: float = 0.0):
+        """``rollout`` with every seat on the search agent (``crl_ttt_rollout_mcts``): self-play of the search in one launch,
+        with the same statistics tensors, ``results()`` rows and step counter."""
+        S, R, cexp = self._search_args(simulations, playouts, exploration)
+        noise = _unit("noise", noise)
+        self._call("crl_ttt_rollout_mcts", _seed(seed), self.first_env_id, int(steps), S, R, cexp, noise, _ptr(self.occ),
+                   _ptr(self.winner), _ptr(self.to_move), self._stats())
 
     def rollout(self, steps: int, seed: int = 0):
         self._rollout_plan(steps, seed)

@@ -1388,6 +1388,329 @@ ttt_mcts_kernel(const ttt_dirs dd_arg, const int64_t B, const uint32_t seed_lo, 
     }
 }
 
+// ---- the search as a seated agent (crl_ttt_sample_mcts / _rollout_mcts / _step_single_mcts; the contract is in
+// include/colosseum_hip.h).  One wave per game and ttt_mcts_kernel's LDS layout; outside the search the wave holds the
+// game's position as P words every lane holds alike, and what it branches on goes through v_readfirstlane.
+//
+// One search of the running position (o0, mover tm0) at step counter tc of game g, winner taken as -1: the root's most
+// visited cell (ties: the larger w, then the lowest cell).  The text is ttt_mcts_kernel's tree loop and root scan, side by
+// side with it: that kernel's instances keep their registers this way.  Every lane of the wave must call it.
+template <int P, int ND, bool WT>
+__device__ __forceinline__ int ttt_search_best(const ttt_dirs &dd, const uint32_t (&o0)[P], const int tm0, const uint32_t tc, const uint32_t g,
+                                               const uint32_t seed_lo, const uint32_t seed_hi, const int S, const int R, const uint32_t cexp,
+                                               const int use_rank, const uint32_t *win_bits, const uint8_t (&rank_tab)[256 * 8],
+                                               uint32_t *n_arr, uint32_t *w_arr, uint16_t *child, const int lane)
+{
+    const int cells = dd.n_cells;
+    const bool cell_lane = lane < cells;
+    if (lane == 0) { n_arr[0] = 0u; w_arr[0] = 0u; }
+    if (cell_lane) child[lane] = 0;
+    ttt_wave_sync();
+    int nn = 1;                                                  // nodes so far
+    for (int s = 0; s < S; ++s) {
+        uint32_t o[P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) o[p] = o0[p];
+        int w = -1, tm = (int)ttt_in_vgpr((uint32_t)tm0), v = 0, d = 0, term = 0, ws = -1, rw;
+        uint32_t path = 0;                                       // lane i: the node at depth i of this simulation's path
+        for (;;) {
+            const uint32_t E = dd.full & ~ttt_union<P>(o);
+            const bool in_e = lane < 32 && ((E >> (lane & 31)) & 1u);
+            CRL_BOUNDS_LT(in_e ? v * cells + lane : 0, (S + 1) * cells, 220);
+            const uint32_t cu = in_e ? child[v * cells + lane] : 0u;
+            CRL_BOUNDS_LT(cu, S + 1, 221);
+            const unsigned long long fresh = __ballot(in_e && cu == 0u);
+            int e, u;
+            if (fresh) {                                         // expand: the lowest cell without a child
+                e = (int)__builtin_ctzll(fresh);
+                u = nn++;
+                CRL_BOUNDS_LT(u, S + 1, 222);
+                if (lane == e) child[v * cells + e] = (uint16_t)u;
+                if (cell_lane) child[u * cells + lane] = 0;
+                if (lane == 0) { n_arr[u] = 0u; w_arr[u] = 0u; }
+            } else {                                             // select: lane e scores the child at cell e
+                const uint32_t lgv = ttt_mcts_lg(n_arr[v]);
+                uint32_t key = 0;
+                if (in_e) {
+                    const uint32_t nu = n_arr[cu], wu = w_arr[cu];
+                    const uint64_t exploit = ttt_mcts_div((uint64_t)wu << 15, nu * (uint32_t)R);
+                    const uint64_t X = ttt_mcts_div((uint64_t)lgv << 24, nu);
+                    const uint64_t score = exploit + (((uint64_t)cexp * ttt_mcts_isqrt(X)) >> 8);   // < 2^26
+                    key = (((uint32_t)score << 5) | (uint32_t)(31 - lane)) + 1u;     // ties: the lowest cell
+                }
+                const uint32_t top = ttt_wave_max(key);          // (all lanes: outside the branch above)
+                e = 31 - (int)((top - 1u) & 31u);
+                u = __builtin_amdgcn_readlane((int)cu, e);
+            }
+            d += 1;
+            path = lane == d ? (uint32_t)u : path;
+            ttt_step_core<P, ND, WT>(dd, o, w, tm, e, rw, term, ws, win_bits);
+            term = __builtin_amdgcn_readfirstlane(term);         // (every lane played the same ply)
+            ws = __builtin_amdgcn_readfirstlane(ws);
+            if (fresh || term || d >= 32) break;                 // (d >= 32: never, a ply that fills the board is terminal)
+            v = u;
+        }
+        // ---- evaluate the leaf: the outcome of the ply into it, or R random playouts, lane r playout r
+        uint32_t cnt[P], draws;                                  // (wave-uniform sums, kept in vector registers)
+#pragma unroll
+        for (int p = 0; p < P; ++p) cnt[p] = ttt_in_vgpr(term && ws == p ? (uint32_t)R : 0u);
+        draws = ttt_in_vgpr(term && ws < 0 ? (uint32_t)R : 0u);
+        if (!term) {
+            for (int r0 = 0; r0 < R; r0 += 64) {
+                const uint32_t r = (uint32_t)(r0 + lane);
+                const bool live = r < (uint32_t)R;
+                int wn = -1;
+                if (live) {
+                    uint32_t po[P];
+#pragma unroll
+                    for (int p = 0; p < P; ++p) po[p] = o[p];
+                    int pw = w, ptm = tm, pterm = 0, prw, pws = -1;
+                    const uint32_t c2 = ((uint32_t)s << 16) | r;
+                    uint32_t c = tc + (uint32_t)d;
+                    philox_out rnd = philox4x32_10<true>(g, c >> 3, c2, CRL_TAG_TTT_MCTS, seed_lo, seed_hi);
+                    for (int left = 33; !pterm && left > 0; --left) {   // ttt_playout_kernel's random ply (left: never runs out)
+                        const uint32_t empty = dd.full & ~ttt_union<P>(po);
+                        const uint32_t n_empty = (uint32_t)__popc(empty);       // (not 0: the game is running)
+                        const uint32_t sel = (c >> 1) & 3u;
+                        uint32_t word = rnd.w[0];
+                        word = (sel == 1) ? rnd.w[1] : word;
+                        word = (sel == 2) ? rnd.w[2] : word;
+                        word = (sel == 3) ? rnd.w[3] : word;
+                        word = (c & 1u) ? word * (n_empty + 1u) : word;
+                        const uint32_t rank = __umulhi(word, n_empty);
+                        const int act = use_rank ? (int)nth_set_bit_tab<WT>(rank_tab, empty, rank) : nth_set_bit(empty, (int)rank);
+                        ttt_step_core<P, ND, WT>(dd, po, pw, ptm, act, prw, pterm, pws, win_bits);
+                        c += 1u;
+                        if ((c & 7u) == 0u && !pterm) rnd = philox4x32_10<true>(g, c >> 3, c2, CRL_TAG_TTT_MCTS, seed_lo, seed_hi);
+                    }
+                    wn = pws;
+                }
+#pragma unroll
+                for (int p = 0; p < P; ++p) cnt[p] += ttt_in_vgpr((uint32_t)__builtin_popcountll(__ballot(live && wn == p)));
+                draws += ttt_in_vgpr((uint32_t)__builtin_popcountll(__ballot(live && wn < 0)));
+            }
+        }
+        // ---- back up: lane i adds to the node at depth i (distinct nodes: no atomics), q = who moved into it
+        ttt_wave_sync();
+        if (lane <= d) {
+            uint32_t add = 0;
+            if (lane > 0) {
+                const int q = (tm0 + lane - 1) % P;
+                uint32_t mine = 0;
+#pragma unroll
+                for (int p = 0; p < P; ++p) mine = (p == q) ? cnt[p] : mine;
+                add = 2u * mine + draws;
+            }
+            CRL_BOUNDS_LT(path, S + 1, 223);
+            n_arr[path] += 1u;
+            w_arr[path] += add;
+        }
+        ttt_wave_sync();
+    }
+    // ---- the root's most visited child (then the larger w, then the lowest cell)
+    const uint32_t cu = cell_lane ? child[lane] : 0u;
+    CRL_BOUNDS_LT(cu, S + 1, 224);
+    const uint32_t vis = cu ? n_arr[cu] : 0u, val = cu ? w_arr[cu] : 0u;
+    const uint32_t top_n = ttt_wave_max(vis);                    // (a child has n >= 1)
+    const bool most = cu != 0u && vis == top_n;
+    const uint32_t top_w = ttt_wave_max(most ? val + 1u : 0u);
+    const unsigned long long pick = __ballot(most && val + 1u == top_w);
+    ttt_wave_sync();                                             // the next tree starts behind these reads
+    return pick ? (int)__builtin_ctzll(pick) : -1;
+}
+
+// the three frames around the agent's move, one kernel text: which one is a template parameter
+enum { TTT_FRAME_SAMPLE = 0, TTT_FRAME_ROLLOUT = 1, TTT_FRAME_SINGLE = 2 };
+
+// what the frames read and write besides the state (each frame its own part; the rest is NULL / 0)
+struct ttt_agent_io {
+    uint32_t *tcount;                                            // sample, step_single (the rollout's is st.tcount)
+    int8_t *action;                                              // sample
+    int advance;
+    int T;                                                       // rollout
+    crl_ttt_stats st;
+    const int8_t *seat;                                          // step_single
+    const int64_t *learner_action;
+    int8_t *reward;
+    uint8_t *done;
+    int8_t *winners, *obs;
+    uint32_t *valid;
+    int rel_mod;
+};
+
+// LDS as ttt_mcts_kernel: [the win-mask table, 2048, if WT][the rank table, 512, if use_rank][a tree of tree_words per wave]
+template <int P, int ND, bool WT, int FRAME>
+__global__ void __launch_bounds__(256)
+ttt_mcts_agent_kernel(const ttt_dirs dd_arg, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi, const uint64_t first_env_id,
+                      const uint64_t thr, const int S, const int R, const uint32_t cexp, const uint32_t tree_words, const int use_rank,
+                      uint32_t *occ_arg, int8_t *winner_arg, int8_t *to_move_arg, const ttt_agent_io io,
+                      const uint32_t *__restrict__ win_tab)
+{
+    // (the pointers and the line test's strides and start masks in vector registers, as ttt_mcts_kernel has them)
+    uint32_t *occ = ttt_in_vgpr(occ_arg);
+    int8_t *winner = ttt_in_vgpr(winner_arg), *to_move = ttt_in_vgpr(to_move_arg);
+    ttt_dirs dd = dd_arg;
+    if (!WT) {
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            dd.stride[d] = (int32_t)ttt_in_vgpr((uint32_t)dd_arg.stride[d]);
+            dd.start[d] = ttt_in_vgpr(dd_arg.start[d]);
+        }
+    }
+    extern __shared__ __attribute__((aligned(16))) uint32_t mcts_lds[];
+    uint32_t *win_bits = mcts_lds;
+    uint32_t *rank_words = mcts_lds + (WT ? 2048 : 0);
+    const uint8_t (&rank_tab)[256 * 8] = *reinterpret_cast<const uint8_t (*)[256 * 8]>(rank_words);
+    uint32_t *trees = rank_words + (use_rank ? 512 : 0);
+    if (WT) {
+        for (uint32_t i = threadIdx.x; i < 512u; i += blockDim.x)
+            reinterpret_cast<uint4 *>(win_bits)[i] = reinterpret_cast<const uint4 *>(win_tab)[i];
+    }
+    if (use_rank) {
+        for (uint32_t t = threadIdx.x; t < 256u; t += blockDim.x) reinterpret_cast<uint2 *>(rank_words)[t] = ttt_rank_row(t);
+    }
+    __syncthreads();
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), n_waves = (int)(blockDim.x >> 6);
+    const int cells = dd.n_cells;
+    uint32_t *n_arr = trees + (uint32_t)wave * tree_words, *w_arr = n_arr + (S + 1);
+    uint16_t *child = reinterpret_cast<uint16_t *>(w_arr + (S + 1));
+    // the agent's move for the mover tm on the position o at step counter c of game g (rules 1 to 5 of the contract)
+    auto agent_move = [&](const uint32_t (&o)[P], const int tm, const uint32_t c, const uint32_t g) -> int {
+        const uint32_t E = (uint32_t)__builtin_amdgcn_readfirstlane((int)(dd.full & ~ttt_union<P>(o)));
+        if ((unsigned)tm >= (unsigned)P || E == 0u) return -1;
+        const philox_out rnd = ttt_tactical_block(g, c, 0u, CRL_TAG_TTT_TACTICAL, seed_lo, seed_hi);
+        const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)((c & 1u) ? rnd.w[2] : rnd.w[0]));
+        if ((uint64_t)u < thr) {                                 // a noisy ply: a uniform empty cell, no search
+            const uint32_t v = (c & 1u) ? rnd.w[3] : rnd.w[1];
+            return __builtin_amdgcn_readfirstlane(nth_set_bit(E, (int)__umulhi(v, (uint32_t)__popc(E))));
+        }
+        return ttt_search_best<P, ND, WT>(dd, o, tm, c, g, seed_lo, seed_hi, S, R, cexp, use_rank, win_bits, rank_tab, n_arr, w_arr,
+                                          child, lane);
+    };
+    // a ply of the wave's game, every lane alike: what the frames branch on comes back wave-uniform
+    auto play = [&](uint32_t (&o)[P], int &w, int &tm, const int action, int &term, int &ws) {
+        int r;
+        ttt_step_core<P, ND, WT>(dd, o, w, tm, action, r, term, ws, win_bits);
+        w = __builtin_amdgcn_readfirstlane(w);
+        tm = __builtin_amdgcn_readfirstlane(tm);
+        term = __builtin_amdgcn_readfirstlane(term);
+        ws = __builtin_amdgcn_readfirstlane(ws);
+    };
+    for (int64_t b = (int64_t)blockIdx.x * n_waves + wave; b < B; b += (int64_t)gridDim.x * n_waves) {
+        uint32_t o[P];                                           // (the same words in every lane)
+#pragma unroll
+        for (int p = 0; p < P; ++p) o[p] = ttt_in_vgpr((uint32_t)__builtin_amdgcn_readfirstlane((int)occ[p * B + b]));
+        int tm = __builtin_amdgcn_readfirstlane((int)to_move[b]);
+        const uint32_t g = (uint32_t)(first_env_id + (uint64_t)b);
+        if constexpr (FRAME == TTT_FRAME_SAMPLE) {
+            uint32_t *tcount = ttt_in_vgpr(io.tcount);
+            const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)tcount[b]);
+            const int act = agent_move(o, tm, c, g);
+            if (lane == 0) {
+                ttt_in_vgpr(io.action)[b] = (int8_t)act;
+                if (io.advance) tcount[b] = c + 1u;
+            }
+        } else if constexpr (FRAME == TTT_FRAME_ROLLOUT) {
+            // crl_ttt_rollout_tactical's ply (ttt_step_core, the restart, the statistics) with the search agent's move; position,
+            // counters and statistics stay in registers over the T plies
+            const crl_ttt_stats &st = io.st;
+            int w = __builtin_amdgcn_readfirstlane((int)winner[b]);
+            uint32_t tc = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.tcount[b]);
+            uint32_t ts = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.tstep[b]), n_ep = 0, draws = 0, len_sum = 0, wins[P];
+#pragma unroll
+            for (int p = 0; p < P; ++p) wins[p] = 0;
+            for (int t = 0; t < io.T; ++t) {
+                const int action = agent_move(o, tm, tc, g);
+                int term, ws;
+                play(o, w, tm, action, term, ws);
+                ts += 1;
+                tc += 1;
+                if (term) {
+                    n_ep += 1;
+                    len_sum += ts;
+                    draws += (ws < 0);
+#pragma unroll
+                    for (int p = 0; p < P; ++p) { wins[p] += (ws == p); o[p] = 0; }
+                    w = -1; tm = 0; ts = 0;
+                }
+            }
+            if (lane == 0) {
+                int32_t *row = st.results ? st.results + b * (3 + P) : nullptr;    // packed result row, as crl_ttt_rollout writes it
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    occ[p * B + b] = o[p];
+                    const uint32_t wc = st.win_count[p * B + b] + wins[p];
+                    st.win_count[p * B + b] = wc;
+                    if (row) row[3 + p] = (int32_t)wc;
+                }
+                winner[b] = (int8_t)w;
+                to_move[b] = (int8_t)tm;
+                st.tcount[b] = tc;
+                st.tstep[b] = ts;
+                const uint32_t ne = st.n_episodes[b] + n_ep, dr = st.draw_count[b] + draws, ls = st.len_sum[b] + len_sum;
+                st.n_episodes[b] = ne;
+                st.draw_count[b] = dr;
+                st.len_sum[b] = ls;
+                if (row) { row[0] = (int32_t)ne; row[1] = (int32_t)ls; row[2] = (int32_t)dr; }
+            }
+        } else {
+            // ttt_step_single_kernel's loop, wave-uniform, with the opponents' plies from the search agent
+            uint32_t *tcount = ttt_in_vgpr(io.tcount);
+            int w = __builtin_amdgcn_readfirstlane((int)winner[b]);
+            int s = (int)io.seat[b] % P;
+            s += s < 0 ? P : 0;
+            s = __builtin_amdgcn_readfirstlane(s);
+            uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)tcount[b]);
+            int rew = 0, dn = 0, wout = -1;
+            bool learner = io.learner_action != nullptr && tm == s;
+            for (int opp = 0; learner || (tm != s && opp < 2 * (P - 1)); ) {
+                int act;
+                if (learner) {                          // crl_ttt_step's int8 action for v in [-1, cells), else the pass
+                    const int64_t v = io.learner_action[b];
+                    act = __builtin_amdgcn_readfirstlane((v >= -1 && v < cells) ? (int)v : -1);
+                } else {                                // crl_ttt_sample_mcts at this game's step counter
+                    act = agent_move(o, tm, c, g);
+                    ++opp;
+                }
+                c += 1u;
+                learner = false;
+                int t, ws;
+                play(o, w, tm, act, t, ws);
+                if (t) {                                // the learner's outcome, restart (as ttt_step_single_kernel)
+                    dn = 1;
+                    wout = ws;
+                    rew = ws < 0 ? 0 : (ws == s ? 1 : -1);
+#pragma unroll
+                    for (int p = 0; p < P; ++p) o[p] = 0;
+                    w = -1; tm = 0;
+                }
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int p = 0; p < P; ++p) occ[p * B + b] = o[p];
+                winner[b] = (int8_t)w;
+                to_move[b] = (int8_t)tm;
+                tcount[b] = c;
+                io.reward[b] = (int8_t)rew;
+                io.done[b] = (uint8_t)dn;
+                io.winners[b] = (int8_t)wout;
+                io.valid[b] = dd.full & ~ttt_union<P>(o);
+            }
+            if (lane < cells) {                          // the learner's observation, lane = cell (ttt_write_boards' rule)
+                int v = -1;
+#pragma unroll
+                for (int p = 0; p < P; ++p) v = ((o[p] >> lane) & 1u) ? p : v;
+                if (v >= 0) {
+                    const int rr = (v - s) % io.rel_mod;
+                    v = rr < 0 ? rr + io.rel_mod : rr;
+                }
+                io.obs[b * cells + lane] = (int8_t)v;
+            }
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256)
 ttt_reset_kernel(const int P, const int64_t B, const uint8_t *__restrict__ mask, uint32_t *__restrict__ occ,
                  int8_t *__restrict__ winner, int8_t *__restrict__ to_move)
@@ -1622,15 +1945,106 @@ int crl_ttt_bounds(unsigned int *out4)
     return CRL_OK;
 }
 
-// ---- one launcher per pair of entries (random agent / tactical agent): `fn` names the entry in the messages, `noise` is
-// NULL for the random agent's
+// S_max of crl_ttt_mcts (include/colosseum_hip.h): a tree of S + 1 nodes of 8 + 2 cells bytes within 64 KB, s in 12 bits
+static int ttt_mcts_max_simulations(const int cells)
+{
+    const int s = 65536 / (8 + 2 * cells) - 1;
+    return s < 4095 ? s : 4095;
+}
+
+// the parameters of a search, crl_ttt_mcts's own or a search agent's (NULL in a launcher that serves the other agents too):
+// the limits of include/colosseum_hip.h, stated here and nowhere else
+struct ttt_search { int S, R; uint32_t cexp; };
+#define TTT_SEARCH_CHECK(fn)                                                                                          \
+    if (search) {                                                                                                     \
+        const int cells_ = ctx->ttt.n_cells, s_max_ = ttt_mcts_max_simulations(cells_);                               \
+        CRL_REQUIRE(search->S >= 1 && search->S <= s_max_, "%s: S=%d out of range 1..%d (a board of %d cells)", fn, search->S, s_max_, cells_); \
+        CRL_REQUIRE(search->R >= 1 && search->R <= 1024, "%s: R=%d out of range 1..1024", fn, search->R);             \
+        CRL_REQUIRE(search->cexp <= 65535u, "%s: cexp=%u out of range 0..65535", fn, search->cexp);                   \
+    }
+
+// LDS of a workgroup of the search kernels, at most 64 KB: the trees of its waves (one to four, as many as fit) behind the
+// two tables.  A tree that leaves no room for a table does without it: the win test is then computed, the cell found by
+// arithmetic.  win_tab: the table on this device or NULL (ttt_win_table_here); NULL comes back where it is not used.
+struct ttt_mcts_geometry {
+    const uint32_t *win_tab;
+    int use_rank;
+    uint32_t tree_words, waves, lds_bytes;
+    unsigned blocks;
+};
+static ttt_mcts_geometry ttt_mcts_geometry_of(const crl_ctx *ctx, const int64_t B, const int S, const uint32_t *win_tab)
+{
+    constexpr uint32_t kLds = 65536u, kWinTab = 8192u, kRankTab = 2048u;
+    const int cells = ctx->ttt.n_cells;
+    const uint32_t tree_bytes = (((uint32_t)(S + 1) * (uint32_t)(8 + 2 * cells)) + 3u) & ~3u;
+    if (cells > 16 || ctx->ttt_dd.n_dirs > 4 || tree_bytes + kWinTab + kRankTab > kLds) win_tab = nullptr;
+    const int use_rank = tree_bytes + (win_tab ? kWinTab : 0u) + kRankTab <= kLds;
+    const uint32_t tables = (win_tab ? kWinTab : 0u) + (use_rank ? kRankTab : 0u);
+    uint32_t waves = (kLds - tables) / tree_bytes;
+    waves = waves > 4u ? 4u : waves;
+    waves = (int64_t)waves > B ? (uint32_t)B : waves;
+    const uint64_t want = ((uint64_t)B + waves - 1u) / waves;
+    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));      // (a grid-stride loop past that)
+    return {win_tab, use_rank, tree_bytes / 4u, waves, tables + waves * tree_bytes, blocks};
+}
+
+static int ttt_mcts_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
+                           const int8_t *winner, const int8_t *to_move, const uint32_t *tcount, int S, int R, uint32_t cexp,
+                           uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best, uint32_t flags, void *stream)
+{
+    TTT_CTX_CHECK(fn);
+    CRL_REQUIRE(occ && winner && to_move, "%s: NULL state pointer", fn);
+    CRL_REQUIRE(visits && value && nodes && best, "%s: NULL output pointer", fn);
+    const ttt_search params = {S, R, cexp}, *search = &params;
+    TTT_SEARCH_CHECK(fn);
+    CRL_REQUIRE(flags == 0, "%s: unknown flags 0x%x", fn, flags);
+    CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "%s: a board of %d cells for %d players (as crl_ttt_playout)", fn, ctx->ttt.n_cells,
+                ctx->ttt.P);
+    const ttt_dirs dd = dirs_of(ctx);
+    const ttt_mcts_geometry geo = ttt_mcts_geometry_of(ctx, B, S, ttt_win_table_here(ctx));
+    const uint32_t *win_tab = geo.win_tab;
+    TTT_DISPATCH_ND_WT(ctx, win_tab, hipLaunchKernelGGL((ttt_mcts_kernel<PP, NDD, WTT>), dim3(geo.blocks), dim3(64u * geo.waves),
+                                                        geo.lds_bytes, (hipStream_t)stream, dd, B, (uint32_t)seed,
+                                                        (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, tcount, S, R,
+                                                        cexp, geo.tree_words, geo.use_rank, visits, value, nodes, best, win_tab));
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+// the search agent's kernel in one of its three frames (the entries' checks are done): ttt_mcts_launch's geometry
+template <int FRAME>
+static int ttt_agent_launch(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, double noise, const ttt_search &search,
+                            uint32_t *occ, int8_t *winner, int8_t *to_move, const ttt_agent_io &io, void *stream)
+{
+    const ttt_dirs dd = dirs_of(ctx);
+    const ttt_mcts_geometry geo = ttt_mcts_geometry_of(ctx, B, search.S, ttt_win_table_here(ctx));
+    const uint32_t *win_tab = geo.win_tab;
+    TTT_DISPATCH_ND_WT(ctx, win_tab, hipLaunchKernelGGL((ttt_mcts_agent_kernel<PP, NDD, WTT, FRAME>), dim3(geo.blocks),
+                                                        dim3(64u * geo.waves), geo.lds_bytes, (hipStream_t)stream, dd, B,
+                                                        (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
+                                                        crl_noise_threshold(noise), search.S, search.R, search.cexp, geo.tree_words,
+                                                        geo.use_rank, occ, winner, to_move, io, win_tab));
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+// ---- one launcher per family of entries (random agent / tactical agent / search agent): `fn` names the entry in the
+// messages, `noise` is NULL for the random agent's, `search` is NULL but for the search agent's
 static int ttt_sample_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
-                             const int8_t *to_move, uint32_t *tcount, int advance, const double *noise, int8_t *action, void *stream)
+                             const int8_t *to_move, uint32_t *tcount, int advance, const double *noise, const ttt_search *search,
+                             int8_t *action, void *stream)
 {
     TTT_CTX_CHECK(fn);
     CRL_REQUIRE(occ && (to_move || !noise) && tcount && action, "%s: NULL pointer", fn);
+    TTT_SEARCH_CHECK(fn);
     TTT_NOISE_CHECK(fn);
     const ttt_dirs dd = dirs_of(ctx);
+    if (search) {
+        ttt_agent_io io = {};
+        io.tcount = tcount; io.action = action; io.advance = advance;
+        return ttt_agent_launch<TTT_FRAME_SAMPLE>(ctx, B, seed, first_env_id, *noise, *search, const_cast<uint32_t *>(occ), nullptr,
+                                                  const_cast<int8_t *>(to_move), io, stream);
+    }
     if (noise) {
         TTT_DISPATCH_ND(ctx, TTT_LAUNCH((ttt_sample_tactical_kernel<PP, NDD>), blocks_for(B, 256), dd, B, (uint32_t)seed,
                                         (uint32_t)(seed >> 32), first_env_id, crl_noise_threshold(*noise), occ, to_move, tcount,
@@ -1646,13 +2060,15 @@ static int ttt_sample_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint
 static int ttt_step_single_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *occ,
                                   int8_t *winner, int8_t *to_move, const int8_t *seat, const int64_t *learner_action,
                                   uint32_t *tcount, int8_t *reward, uint8_t *done, int8_t *winners, int8_t *obs_board,
-                                  uint32_t *valid, int rel_mod, const double *noise, uint32_t flags, void *stream)
+                                  uint32_t *valid, int rel_mod, const double *noise, const ttt_search *search, uint32_t flags,
+                                  void *stream)
 {
     TTT_CTX_CHECK(fn);
     CRL_REQUIRE(occ && winner && to_move, "%s: NULL state pointer", fn);
     CRL_REQUIRE(seat && tcount, "%s: NULL seat / tcount pointer", fn);
     CRL_REQUIRE(reward && done && winners && obs_board && valid, "%s: NULL output pointer", fn);
     CRL_REQUIRE(rel_mod >= 1, "%s: rel_mod must be >= 1", fn);
+    TTT_SEARCH_CHECK(fn);
     TTT_NOISE_CHECK(fn);
     CRL_REQUIRE(flags == 0, "%s: unknown flags 0x%x", fn, flags);
     CRL_REQUIRE(ctx->ttt.n_cells >= ctx->ttt.P, "%s: a board of %d cells for %d players (%s)", fn, ctx->ttt.n_cells, ctx->ttt.P,
@@ -1660,6 +2076,12 @@ static int ttt_step_single_launch(const char *fn, const crl_ctx *ctx, int64_t B,
     CRL_REQUIRE((((uintptr_t)obs_board) & 3) == 0, "%s: obs_board must be 4-byte aligned", fn);
     const ttt_dirs dd = dirs_of(ctx);
     const uint32_t *win_tab = ttt_win_table_here(ctx);
+    if (search) {
+        ttt_agent_io io = {};
+        io.tcount = tcount; io.seat = seat; io.learner_action = learner_action; io.reward = reward; io.done = done;
+        io.winners = winners; io.obs = obs_board; io.valid = valid; io.rel_mod = rel_mod;
+        return ttt_agent_launch<TTT_FRAME_SINGLE>(ctx, B, seed, first_env_id, *noise, *search, occ, winner, to_move, io, stream);
+    }
     if (noise) {
         TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_step_single_tactical_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd,
                                                     ttt_inv_cells(dd.n_cells), B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id,
@@ -1709,48 +2131,6 @@ static int ttt_playout_launch(const char *fn, const crl_ctx *ctx, int64_t B, uin
     return CRL_OK;
 }
 
-// S_max of crl_ttt_mcts (include/colosseum_hip.h): a tree of S + 1 nodes of 8 + 2 cells bytes within 64 KB, s in 12 bits
-static int ttt_mcts_max_simulations(const int cells)
-{
-    const int s = 65536 / (8 + 2 * cells) - 1;
-    return s < 4095 ? s : 4095;
-}
-
-static int ttt_mcts_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
-                           const int8_t *winner, const int8_t *to_move, const uint32_t *tcount, int S, int R, uint32_t cexp,
-                           uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best, uint32_t flags, void *stream)
-{
-    TTT_CTX_CHECK(fn);
-    CRL_REQUIRE(occ && winner && to_move, "%s: NULL state pointer", fn);
-    CRL_REQUIRE(visits && value && nodes && best, "%s: NULL output pointer", fn);
-    const int cells = ctx->ttt.n_cells, s_max = ttt_mcts_max_simulations(cells);
-    CRL_REQUIRE(S >= 1 && S <= s_max, "%s: S=%d out of range 1..%d (a board of %d cells)", fn, S, s_max, cells);
-    CRL_REQUIRE(R >= 1 && R <= 1024, "%s: R=%d out of range 1..1024", fn, R);
-    CRL_REQUIRE(cexp <= 65535u, "%s: cexp=%u out of range 0..65535", fn, cexp);
-    CRL_REQUIRE(flags == 0, "%s: unknown flags 0x%x", fn, flags);
-    CRL_REQUIRE(cells >= ctx->ttt.P, "%s: a board of %d cells for %d players (as crl_ttt_playout)", fn, cells, ctx->ttt.P);
-    const ttt_dirs dd = dirs_of(ctx);
-    // LDS of a workgroup, at most 64 KB: the trees of its waves (one to four, as many as fit) behind the two tables.  A tree
-    // that leaves no room for a table does without it: the win test is then computed, the cell found by arithmetic.
-    constexpr uint32_t kLds = 65536u, kWinTab = 8192u, kRankTab = 2048u;
-    const uint32_t tree_bytes = (((uint32_t)(S + 1) * (uint32_t)(8 + 2 * cells)) + 3u) & ~3u;
-    const uint32_t *win_tab = ttt_win_table_here(ctx);
-    if (cells > 16 || dd.n_dirs > 4 || tree_bytes + kWinTab + kRankTab > kLds) win_tab = nullptr;
-    const int use_rank = tree_bytes + (win_tab ? kWinTab : 0u) + kRankTab <= kLds;
-    const uint32_t tables = (win_tab ? kWinTab : 0u) + (use_rank ? kRankTab : 0u);
-    uint32_t waves = (kLds - tables) / tree_bytes;
-    waves = waves > 4u ? 4u : waves;
-    waves = (int64_t)waves > B ? (uint32_t)B : waves;
-    const uint64_t want = ((uint64_t)B + waves - 1u) / waves;
-    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));      // (a grid-stride loop past that)
-    TTT_DISPATCH_ND_WT(ctx, win_tab, hipLaunchKernelGGL((ttt_mcts_kernel<PP, NDD, WTT>), dim3(blocks), dim3(64u * waves),
-                                                        tables + waves * tree_bytes, (hipStream_t)stream, dd, B, (uint32_t)seed,
-                                                        (uint32_t)(seed >> 32), first_env_id, occ, winner, to_move, tcount, S, R,
-                                                        cexp, tree_bytes / 4u, use_rank, visits, value, nodes, best, win_tab));
-    CRL_LAUNCH_CHECK();
-    return CRL_OK;
-}
-
 // The arguments of crl_ttt_rollout that stay the same from launch to launch (include/colosseum_hip.h, "launch plans"), checked.
 // The win table is looked up per launch: it depends on the device that is current then.
 struct ttt_plan : crl_plan {
@@ -1762,8 +2142,8 @@ struct ttt_plan : crl_plan {
     crl_ttt_stats st;
     ttt_dirs dd;
 
-    int run(const char *fn, uint64_t seed, int T, const double *noise, void *stream) const;
-    int launch(uint64_t seed, int T, void *stream) const override { return run("crl_rollout_launch", seed, T, nullptr, stream); }
+    int run(const char *fn, uint64_t seed, int T, const double *noise, const ttt_search *search, void *stream) const;
+    int launch(uint64_t seed, int T, void *stream) const override { return run("crl_rollout_launch", seed, T, nullptr, nullptr, stream); }
 };
 
 static int ttt_plan_bind(ttt_plan &p, const char *fn, const crl_ctx *ctx, int64_t B, uint64_t first_env_id, uint32_t *occ,
@@ -1779,12 +2159,18 @@ static int ttt_plan_bind(ttt_plan &p, const char *fn, const crl_ctx *ctx, int64_
     return CRL_OK;
 }
 
-int ttt_plan::run(const char *fn, const uint64_t seed, const int T, const double *noise, void *stream) const
+int ttt_plan::run(const char *fn, const uint64_t seed, const int T, const double *noise, const ttt_search *search, void *stream) const
 {
     CRL_REQUIRE(T >= 0 && T <= (1 << 24), "%s: T=%d out of range", fn, T);
+    TTT_SEARCH_CHECK(fn);
     TTT_NOISE_CHECK(fn);
     if (T == 0) return CRL_OK;
     const uint32_t *win_tab = ttt_win_table_here(ctx);
+    if (search) {
+        ttt_agent_io io = {};
+        io.T = T; io.st = st;
+        return ttt_agent_launch<TTT_FRAME_ROLLOUT>(ctx, B, seed, first_env_id, *noise, *search, occ, winner, to_move, io, stream);
+    }
     if (noise) {
         TTT_DISPATCH_ND_WT(ctx, win_tab, TTT_LAUNCH((ttt_rollout_tactical_kernel<PP, NDD, WTT>), blocks_for(B, 256), dd, B,
                                                     (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, crl_noise_threshold(*noise),
@@ -1798,11 +2184,12 @@ int ttt_plan::run(const char *fn, const uint64_t seed, const int T, const double
 }
 
 static int ttt_rollout_launch(const char *fn, const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T,
-                              const double *noise, uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats st, void *stream)
+                              const double *noise, const ttt_search *search, uint32_t *occ, int8_t *winner, int8_t *to_move,
+                              crl_ttt_stats st, void *stream)
 {
     ttt_plan plan;
     if (const int rc = ttt_plan_bind(plan, fn, ctx, B, first_env_id, occ, winner, to_move, st)) return rc;
-    return plan.run(fn, seed, T, noise, stream);
+    return plan.run(fn, seed, T, noise, search, stream);
 }
 
 extern "C" {
@@ -1909,7 +2296,7 @@ int crl_ttt_board(const crl_ctx *ctx, int64_t B, const uint32_t *occ, const int8
 int crl_ttt_sample(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ, uint32_t *tcount,
                    int advance, int8_t *action, void *stream)
 {
-    return ttt_sample_launch("crl_ttt_sample", ctx, B, seed, first_env_id, occ, nullptr, tcount, advance, nullptr, action, stream);
+    return ttt_sample_launch("crl_ttt_sample", ctx, B, seed, first_env_id, occ, nullptr, tcount, advance, nullptr, nullptr, action, stream);
 }
 
 int crl_ttt_step_observe(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
@@ -1937,7 +2324,7 @@ int crl_ttt_step_single(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t f
                         uint8_t *done, int8_t *winners, int8_t *obs_board, uint32_t *valid, int rel_mod, uint32_t flags, void *stream)
 {
     return ttt_step_single_launch("crl_ttt_step_single", ctx, B, seed, first_env_id, occ, winner, to_move, seat, learner_action, tcount,
-                                  reward, done, winners, obs_board, valid, rel_mod, nullptr, flags, stream);
+                                  reward, done, winners, obs_board, valid, rel_mod, nullptr, nullptr, flags, stream);
 }
 
 int crl_ttt_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ, const int8_t *winner,
@@ -2023,7 +2410,7 @@ int crl_ttt_observe_board(const crl_ctx *ctx, int64_t B, const int8_t *board, co
 int crl_ttt_rollout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, uint32_t *occ, int8_t *winner,
                     int8_t *to_move, crl_ttt_stats st, void *stream)
 {
-    return ttt_rollout_launch("crl_ttt_rollout", ctx, B, seed, first_env_id, T, nullptr, occ, winner, to_move, st, stream);
+    return ttt_rollout_launch("crl_ttt_rollout", ctx, B, seed, first_env_id, T, nullptr, nullptr, occ, winner, to_move, st, stream);
 }
 
 int crl_ttt_rollout_bind(const crl_ctx *ctx, int64_t B, uint64_t first_env_id, uint32_t *occ, int8_t *winner, int8_t *to_move,
@@ -2054,14 +2441,14 @@ int crl_ttt_winning_cells(const crl_ctx *ctx, int64_t B, const uint32_t *occ, ui
 int crl_ttt_sample_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
                             const int8_t *to_move, uint32_t *tcount, int advance, double noise, int8_t *action, void *stream)
 {
-    return ttt_sample_launch("crl_ttt_sample_tactical", ctx, B, seed, first_env_id, occ, to_move, tcount, advance, &noise, action,
-                             stream);
+    return ttt_sample_launch("crl_ttt_sample_tactical", ctx, B, seed, first_env_id, occ, to_move, tcount, advance, &noise, nullptr,
+                             action, stream);
 }
 
 int crl_ttt_rollout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, double noise, uint32_t *occ,
                              int8_t *winner, int8_t *to_move, crl_ttt_stats st, void *stream)
 {
-    return ttt_rollout_launch("crl_ttt_rollout_tactical", ctx, B, seed, first_env_id, T, &noise, occ, winner, to_move, st, stream);
+    return ttt_rollout_launch("crl_ttt_rollout_tactical", ctx, B, seed, first_env_id, T, &noise, nullptr, occ, winner, to_move, st, stream);
 }
 
 int crl_ttt_step_single_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *occ, int8_t *winner,
@@ -2070,7 +2457,8 @@ int crl_ttt_step_single_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, u
                                  uint32_t flags, void *stream)
 {
     return ttt_step_single_launch("crl_ttt_step_single_tactical", ctx, B, seed, first_env_id, occ, winner, to_move, seat,
-                                  learner_action, tcount, reward, done, winners, obs_board, valid, rel_mod, &noise, flags, stream);
+                                  learner_action, tcount, reward, done, winners, obs_board, valid, rel_mod, &noise, nullptr, flags,
+                                  stream);
 }
 
 int crl_ttt_playout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
@@ -2079,6 +2467,33 @@ int crl_ttt_playout_tactical(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
 {
     return ttt_playout_launch("crl_ttt_playout_tactical", ctx, B, seed, first_env_id, occ, winner, to_move, tcount, cand, A, R, wins,
                               played, len_sum, &noise, flags, stream);
+}
+
+// ---- the search agent's entries (the contract is in include/colosseum_hip.h)
+int crl_ttt_sample_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
+                        const int8_t *to_move, uint32_t *tcount, int advance, int S, int R, uint32_t cexp, double noise,
+                        int8_t *action, void *stream)
+{
+    const ttt_search search = {S, R, cexp};
+    return ttt_sample_launch("crl_ttt_sample_mcts", ctx, B, seed, first_env_id, occ, to_move, tcount, advance, &noise, &search, action,
+                             stream);
+}
+
+int crl_ttt_rollout_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, int S, int R, uint32_t cexp,
+                         double noise, uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats st, void *stream)
+{
+    const ttt_search search = {S, R, cexp};
+    return ttt_rollout_launch("crl_ttt_rollout_mcts", ctx, B, seed, first_env_id, T, &noise, &search, occ, winner, to_move, st, stream);
+}
+
+int crl_ttt_step_single_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *occ, int8_t *winner,
+                             int8_t *to_move, const int8_t *seat, const int64_t *learner_action, uint32_t *tcount, int8_t *reward,
+                             uint8_t *done, int8_t *winners, int8_t *obs_board, uint32_t *valid, int rel_mod, int S, int R,
+                             uint32_t cexp, double noise, uint32_t flags, void *stream)
+{
+    const ttt_search search = {S, R, cexp};
+    return ttt_step_single_launch("crl_ttt_step_single_mcts", ctx, B, seed, first_env_id, occ, winner, to_move, seat, learner_action,
+                                  tcount, reward, done, winners, obs_board, valid, rel_mod, &noise, &search, flags, stream);
 }
 
 } // extern "C"

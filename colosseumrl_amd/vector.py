@@ -6,11 +6,12 @@ The reference exposes single games to RL libraries through ``RllibWrapper`` / ``
 reset/step contract for B games at once, with tensors instead of dicts of Python objects: actions in,
 observations / rewards / dones out, everything staying on the GPU, games auto-resetting when they end.
 """
+import math
 from typing import Dict, Optional, Tuple
 
 import torch
 
-from .batched import BlokusBatch, TronBatch, TTTBatch, _unit, _want
+from .batched import BlokusBatch, TronBatch, TTTBatch, _exploration, _int_in, _unit, _want
 
 
 class TronVectorEnv:
@@ -209,20 +210,30 @@ class TicTacToeSinglePlayerVectorEnv:
     A step is ONE launch (``crl_ttt_step_single``) with no host synchronisation, and can be captured into a HIP graph
     (``torch.cuda.graph``).  The opponents' draws are ``crl_ttt_sample``'s at each game's step counter, keyed by ``seed``;
     the learner's ply advances the counter as well.  ``opponent="tactical"`` seats the win-or-block agent with ``noise``
-    instead (``crl_ttt_step_single_tactical``, ``TTTBatch.sample_tactical``'s draws): still one launch per step."""
+    instead (``crl_ttt_step_single_tactical``, ``TTTBatch.sample_tactical``'s draws): still one launch per step.
+    ``opponent="mcts"`` seats the tree search (``crl_ttt_step_single_mcts``, ``TTTBatch.sample_mcts``'s moves) with
+    ``simulations`` x ``playouts`` per move, ``exploration`` and ``noise``: one launch per step as well."""
 
     def __init__(self, dims=(3, 3), k: int = 3, num_players: int = 2, batch: int = 1024, seat=0, seed: int = 0,
-                 device="cuda", opponent: str = "random", noise: float = 0.1):
-        if opponent not in TTTBatch.AGENTS:
-            raise ValueError("opponent must be 'random' or 'tactical', got %r" % (opponent,))
+                 device="cuda", opponent: str = "random", noise: float = 0.1, simulations: int = 64, playouts: int = 16,
+                 exploration: float = 1.0):
+        if opponent not in TTTBatch.OPPONENTS:
+            raise ValueError("opponent must be 'random', 'tactical' or 'mcts', got %r" % (opponent,))
         self.opponent, self.noise = opponent, _unit("noise", noise)
+        self._search = {}
+        if opponent == "mcts":
+            s_max = min(4095, 65536 // (8 + 2 * max(1, math.prod(int(d) for d in dims))) - 1)      # S_max of crl_ttt_mcts
+            _exploration("exploration", exploration)
+            self._search = dict(simulations=_int_in("simulations", simulations, 1, s_max),
+                                playouts=_int_in("playouts", playouts, 1, 1024), exploration=exploration)
         self.batch = TTTBatch(dims, k, num_players, batch, device=device)
         self.num_players, self.num_envs, self.seed = num_players, batch, int(seed)
         self.seat = _seat_tensor(seat, num_players, batch, self.batch.device)
         self._out = None
 
     def _step(self, action):
-        self._out = self.batch.step_single(self.seat, action, self.seed, out=self._out, opponent=self.opponent, noise=self.noise)
+        self._out = self.batch.step_single(self.seat, action, self.seed, out=self._out, opponent=self.opponent, noise=self.noise,
+                                           **self._search)
         o = self._out
         return {"board": o["board"]}, o["reward"], o["done"], {"valid": o["valid"], "winners": o["winners"]}
 

@@ -88,7 +88,8 @@ const char *crl_last_error(void);
  *      crl_tron_sample_territory (Voronoi territory and the territory-greedy agent: two new entries, one new Philox tag).
  *      So were crl_ttt_winning_cells and crl_ttt_sample_tactical / _rollout_tactical / _step_single_tactical /
  *      _playout_tactical (the win-or-block agent of TicTacToe: five new entries, two new Philox tags), and
- *      crl_ttt_mcts / crl_ttt_mcts_max_simulations (batched tree search: two new entries, one new Philox tag). */
+ *      crl_ttt_mcts / crl_ttt_mcts_max_simulations (batched tree search: two new entries, one new Philox tag), and
+ *      crl_ttt_sample_mcts / _rollout_mcts / _step_single_mcts (the search as a seated agent: three new entries, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -865,6 +866,52 @@ int crl_ttt_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_en
                  int S, int R, uint32_t cexp,
                  uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best,
                  uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------ the tree search as a seated agent of TicTacToe
+ * The search of crl_ttt_mcts in the three forms the random and the tactical agent have: one step, a fused rollout with
+ * every seat on it, and the opponents of the single-player step.  Added under revision 113: new entries only, no new Philox
+ * tag, no existing struct, argument list or RNG contract changed.
+ * The search agent has the parameters S, R, cexp (crl_ttt_mcts's) and noise.  Its move for the mover p = to_move[b] at step
+ * counter c of global game g = first_env_id + b, E the empty cells:
+ *   1. p outside [0, P) or E == 0: the action is -1 (pass) and no draw is made (the tactical agent's rule 1).
+ *   2. (u, v) are the tactical agent's two words at that counter, exactly its rule 2 for the entries that are no playouts:
+ *      w = Philox4x32-10(ctr = {g, c >> 1, 0, 0x54630000}, key = {seed lo, seed hi}), u = w[2 (c & 1)], v = w[2 (c & 1) + 1].
+ *      Only one agent moves at a given counter of a game, so the stream is shared at no cost.
+ *   3. noisy  iff  u < thr,  thr = min(2^32, ceil(noise * 2^32)) as the tactical agent's rule 3: noise = 0 is never noisy,
+ *      noise = 1 always.
+ *   4. noisy: the action is the mulhi32(v, popcount(E))-th set bit of E, ascending -- with noise = 1 bit for bit the tactical
+ *      agent at noise 1.
+ *   5. else the action is `best` of crl_ttt_mcts(S, R, cexp) on this position with tcount[b] taken as c and winner[b] as -1
+ *      (like crl_ttt_sample and the tactical agent, the agent reads occ and to_move only).  The playouts of that search draw
+ *      as crl_ttt_mcts says: tag 0x544D0000, counter c + depth + k, third word (s << 16) | r.  With E != 0 and S >= 1 the
+ *      root has a child, so `best` is an empty cell.
+ * Errors (CRL_EINVAL, with a crl_last_error message, before any device work): everything the tactical sibling of each entry
+ * refuses, S outside [1, S_max] (crl_ttt_mcts_max_simulations), R outside [1, 1024], cexp > 65535, noise outside [0, 1] or
+ * NaN.
+ * One wave per game, the tree in LDS with crl_ttt_mcts's layout (win-mask table, rank table, one tree per wave, one to four
+ * waves per workgroup); outside the search the wave holds the game's position alike in every lane, and a noisy ply does not
+ * search.  Games are walked in a grid-stride loop with 64-bit indices.
+ *
+ * action[b] = the search agent's move at step counter tcount[b]; advance != 0 also increments tcount (passes included). */
+int crl_ttt_sample_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
+                        const int8_t *to_move, uint32_t *tcount, int advance, int S, int R, uint32_t cexp, double noise,
+                        int8_t *action, void *stream);
+/* crl_ttt_rollout_tactical with EVERY seat on the search agent: the same auto-reset, crl_ttt_stats bookkeeping and results
+ * row, the same checks of T.
+ * T x (crl_ttt_sample_mcts(advance = 1); crl_ttt_step with CRL_STEP_AUTO_RESET) == crl_ttt_rollout_mcts(T). */
+int crl_ttt_rollout_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, int S, int R,
+                         uint32_t cexp, double noise, uint32_t *occ, int8_t *winner, int8_t *to_move, crl_ttt_stats stats,
+                         void *stream);
+/* crl_ttt_step_single word for word, except that in its step 2 the opponents' action is what
+ * crl_ttt_sample_mcts(advance = 1) returns on that state -- the opponents who open a game that was reset inside the call
+ * included: they search from the empty board.  The learner's ply still consumes one counter value.  The learner's
+ * observation is written with the wave's lanes as the cells. */
+int crl_ttt_step_single_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                             uint32_t *occ, int8_t *winner, int8_t *to_move, const int8_t *seat,
+                             const int64_t *learner_action, uint32_t *tcount,
+                             int8_t *reward, uint8_t *done, int8_t *winners,
+                             int8_t *obs_board, uint32_t *valid, int rel_mod, int S, int R, uint32_t cexp, double noise,
+                             uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ launch plans: bind a rollout's arguments once
  * A caller that launches short rollouts in a loop passes the same context, batch, state and statistics pointers and flags

@@ -86,6 +86,7 @@ PROTOTYPES = {
     "crl_diag_bounds": (_I, [_VP]),
     "crl_philox4x32": (_I, [_VP, _U32, _U32, _VP, _I64, _VP]),
     "crl_tron_create": (_I, [_I, _I, _VP, _VP, C.POINTER(_VP)]),
+    "crl_tron_lane_table": (_I, [_VP, _VP, _I]),
     "crl_tron_reset": (_I, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "crl_tron_step": (_I, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _VP]),
     "crl_tron_rollout": (_I, [_VP, _I64, _U64, _U64, _I, _VP, _VP, _VP, _VP, TronStats, _U32, _VP]),

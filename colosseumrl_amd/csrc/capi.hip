@@ -15,6 +15,7 @@ void crl_set_error(const char *fmt, ...)
 }
 
 void crl_blokus_free(void *tables);   // blokus.hip
+void crl_tron_lanes_free(void *tables);   // tron.hip
 
 namespace {
 __global__ void __launch_bounds__(256)
@@ -111,6 +112,7 @@ void crl_destroy(crl_ctx *ctx)
     if (ctx->ttt_lines_dev) (void)hipFree(ctx->ttt_lines_dev);
     if (ctx->ttt_win_dev) (void)hipFree(ctx->ttt_win_dev);
     if (ctx->blokus) crl_blokus_free(ctx->blokus);
+    if (ctx->tron_lanes) crl_tron_lanes_free(ctx->tron_lanes);
     delete ctx;
 }
 

@@ -40,6 +40,7 @@ struct crl_ctx {
     uint32_t *ttt_win_dev;     // boards of <= 16 cells: DEVICE bit table, bit m = "the mask m holds a K-line" (8 KB), or NULL
     int ttt_win_device;        // the device that table lives on
     void *blokus;              // blokus tables (blokus.hip)
+    void *tron_lanes;          // lane constants of the byte-slab lane-per-player rollout kernel, host + device copies (tron.hip), or NULL
 };
 
 void crl_set_error(const char *fmt, ...);

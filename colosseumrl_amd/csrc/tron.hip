@@ -36,7 +36,9 @@
 // new_state in global memory).  A kernel that keeps its own text of one says so at the place and why (docs/history.md).
 // plus crl_tron_ranking (compute_ranking, TronGridEnvironment.py:483-508), one wave per game.
 #include "crl_common.hpp"
+#include "tron_lane_table.hpp"
 #include <hip/hip_ext.h>
+#include <mutex>
 // Observation boards are written once and not read again by the kernel that writes them; whether their 16-byte stores should
 // be NONTEMPORAL depends on where they land (round-5 A/B on one box, tools/debug/stream_ab.py -> profiles/r5_stream_ab.txt;
 // Tron 20x20 P4, GPU us per call, plain / nontemporal):
@@ -46,6 +48,7 @@
 // observe_all: nontemporal always.  step_observe: nontemporal once the call's boards in + out (131 MB at 65,536 games,
 // where plain stores are absorbed by the 256 MiB Infinity Cache) exceed 192 MiB.
 typedef uint32_t crl_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t crl_u32x3 __attribute__((ext_vector_type(3), aligned(4)));
 __device__ __forceinline__ void crl_stream_store16(void *ptr, const uint4 v, const bool nt)
 {
     if (nt) __builtin_nontemporal_store(crl_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<crl_u32x4 *>(ptr));
@@ -193,6 +196,7 @@ __device__ __forceinline__ void tron_outcome(const TronRegs<P> &s, int (&rew)[P]
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes of global memory at a dword boundary
+typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));   // 8 bytes of global memory at a dword boundary
 
 // phases 2+3: the reference's sequential resolution on registers (CyTronGrid.pyx:15-62), trail writes, and the
 // reward / terminal / winners tail (TronGridEnvironment.py:309-321).  Straight-line code: every decision is a
@@ -1054,8 +1058,18 @@ __device__ __forceinline__ int tron_quad(const int v)          // v of the lane 
 // swaps), so that byte p' holds player p''s four actions, and the quad exchanges them with DPP broadcasts: lane p ends up
 // with its player's 32 actions of group `group` = c >> 5 in two registers (steps 0-15 / 16-31 of the group).
 // Every lane of the quad must call this together (the broadcasts read all four lanes).
-__device__ __forceinline__ void tron_quad_actions(const uint32_t gid, const uint32_t group, const int p, const uint32_t seed_lo,
-                                                  const uint32_t seed_hi, const uint8_t *act_lut, uint32_t &a_lo, uint32_t &a_hi)
+// In two halves: the draw needs the step counter, the seed and the game id alone; the codes need the action table (LDS).  A
+// kernel's prologue can run the draw before its boards are in and its action table is up (tron_rollout_quad_kernel does).
+__device__ __forceinline__ philox_out tron_quad_draw(const uint32_t gid, const uint32_t group, const int p, const uint32_t seed_lo,
+                                                     const uint32_t seed_hi)
+{
+    // (the seed through an opaque copy: the ten rounds' keys are then derived here, every 32 steps, instead of living in
+    //  20 scalar registers across the caller's step loop)
+    uint32_t k0 = seed_lo, k1 = seed_hi;
+    asm volatile("" : "+s"(k0), "+s"(k1));
+    return philox4x32_10<true>(gid, 4u * group + (uint32_t)p, 0u, CRL_TAG_TRON, k0, k1);
+}
+__device__ __forceinline__ void tron_quad_codes(const philox_out &r, const int p, const uint8_t *act_lut, uint32_t &a_lo, uint32_t &a_hi)
 {
     auto transpose2 = [](uint32_t x) -> uint32_t {              // 4x4 transpose of the 2-bit fields of x (bit 8r + 2c)
         uint32_t t = (x ^ (x >> 6)) & 0x00CC00CCu;
@@ -1064,11 +1078,6 @@ __device__ __forceinline__ void tron_quad_actions(const uint32_t gid, const uint
         x ^= t ^ (t << 12);
         return x;
     };
-    // (the seed through an opaque copy: the ten rounds' keys are then derived here, every 32 steps, instead of living in
-    //  20 scalar registers across the caller's step loop)
-    uint32_t k0 = seed_lo, k1 = seed_hi;
-    asm volatile("" : "+s"(k0), "+s"(k1));
-    const philox_out r = philox4x32_10<true>(gid, 4u * group + (uint32_t)p, 0u, CRL_TAG_TRON, k0, k1);
     uint32_t code[8];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -1091,6 +1100,11 @@ __device__ __forceinline__ void tron_quad_actions(const uint32_t gid, const uint
     for (int q = 0; q < 4; ++q) s16[q] = ((uint32_t)(p < 2 ? b01[q] : b23[q]) >> sh) & 0xffffu;
     a_lo = s16[0] | s16[1] << 16;
     a_hi = s16[2] | s16[3] << 16;
+}
+__device__ __forceinline__ void tron_quad_actions(const uint32_t gid, const uint32_t group, const int p, const uint32_t seed_lo,
+                                                  const uint32_t seed_hi, const uint8_t *act_lut, uint32_t &a_lo, uint32_t &a_hi)
+{
+    tron_quad_codes(tron_quad_draw(gid, group, p, seed_lo, seed_hi), p, act_lut, a_lo, a_hi);
 }
 
 // ---- what the lane-per-player rollout kernels share (quad, pair, gquad, qbits, avoid; the replay takes the first three) ------
@@ -1189,20 +1203,30 @@ __global__ void __launch_bounds__(256, 4)
 tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad pad, const int64_t B,
                          const uint32_t seed_lo, const uint32_t seed_hi, const uint64_t first_env_id, const int T,
                          int8_t *__restrict__ board, int16_t *__restrict__ heads, int8_t *__restrict__ dirs,
-                         int8_t *__restrict__ deaths, const crl_tron_stats st)
+                         int8_t *__restrict__ deaths, const crl_tron_stats st, const uint32_t *__restrict__ ltab)
 {
     constexpr int kGames = 64, kWaveGames = 16;
     constexpr int kRowDwords = RS / 4;
     constexpr uint32_t step4 = (uint32_t)((-RS) & 0xff) | (1u << 8) | ((uint32_t)RS << 16) | (0xffu << 24);
     constexpr int OB = 3;                                       // P <= 4: owners 1..4, 5 tag bits
     constexpr uint32_t kTags = (1u << (8 - OB)) - 1u;           // the all-ones tag is never used: 0xff stays "wall"
+    static_assert(RS == kTronLaneRowBytes, "the lane table is laid out for this kernel's slabs");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    __shared__ uint8_t act_lut[84];
+    __shared__ __attribute__((aligned(4))) uint8_t act_lut[4 * kTronLaneLutWords];
     QUAD_STAMP(0);
-    tron_fill_action_lut(act_lut);
+    // ---- what depends on the context and my place in the workgroup alone comes out of the context's lane table
+    // (tron_lane_table.hpp): three loads (16 + 16 + 12 bytes), issued ahead of everything else; nothing of them is looked at
+    // before the path's own loads are out
+    const crl_u32x4 *ltab_mine = reinterpret_cast<const crl_u32x4 *>(ltab) + 3u * threadIdx.x;
+    const crl_u32x4 lt_rows = ltab_mine[0], lt_seat = ltab_mine[1];
+    const crl_u32x3 lt_fresh = *reinterpret_cast<const crl_u32x3 *>(ltab_mine + 2);
+    const uint32_t lut_word = ltab[kTronLaneLutWord + min((int)threadIdx.x, kTronLaneLutWords - 1)];
     const int N = g.N, NN = g.NN, P = cfg.P;
     const int lane = threadIdx.x & (CRL_WAVE - 1);
-    const int wave = threadIdx.x >> 6;
+    // (as a scalar: what follows from it -- the wave's first game, how many it has, which copy path it takes -- is then
+    //  scalar arithmetic and real branches; as a vector value every path choice below is an exec mask, and the waits of
+    //  all paths are merged into each)
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int p = lane & 3;                                     // my player
     const int slot = threadIdx.x >> 2;                          // my game's slab in this workgroup
     const int64_t b = (int64_t)blockIdx.x * kGames + slot;
@@ -1216,7 +1240,17 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
     const int slab0 = lds0 + wave * kWaveGames * pad.stride;    // first slab of this wave
     const bool wide = (N & 3) == 0 && N >= 8;
     // ---- prologue: every global load in flight together (the wave's boards, my player's state, the running totals)
-    constexpr int kCopyBatch = 7;                               // 16 boards of <= 400 bytes = <= 6.25 KiB per wave
+    // My step counter and my player's state go out AHEAD of the boards (loads come back in order): the first draw of actions
+    // waits for the counter alone and the seat set-up for the head, both while the boards are still on their way.
+    // (unconditional, from a clamped index: under `pvalid ? load : 0` every load sits in its own branch with its own wait)
+    const int64_t pb = (int64_t)(p < P ? p : 0) * B + bb;
+    uint32_t tc = st.tcount[bb];
+    // (kept in their own width up to their first use: widened here, the extension waits for the load here)
+    const int16_t h_in = heads[pb];
+    const int8_t d_in = dirs[pb];
+    const uint8_t k_in = reinterpret_cast<const uint8_t *>(deaths)[pb];     // 0 or a 1-based id
+    int k;
+    constexpr int kCopyBatch = 7;                           // 16 boards of <= 400 bytes = <= 6.25 KiB per wave
     const int8_t *gslab_in = board + (n_env > 0 ? env0 : 0) * NN;   // (a wave wholly beyond the batch still issues its loads: from game 0)
     const int bytes_in = n_env * NN;
     // 20x20 boards (the headline shape) move by ROWS: a row is 20 bytes = five dwords in HBM and six in the slab (its four
@@ -1226,9 +1260,13 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
     constexpr int kRowsPerLane = (kWaveGames * 20) / CRL_WAVE;  // 5
     const bool rows20 = N == 20;
     const int rows_in = n_env * 20;
-    uint4 cin[kCopyBatch];
-    u32x4_a4 rin4[kRowsPerLane];
+    // the boards on their way from HBM to the slabs.  Every copy path loads 16-byte pieces first of all: ONE set of registers
+    // for them, whichever path the wave takes (as arrays of their own, three paths' worth are live side by side up to the
+    // stores); what a row has beyond 16 bytes -- one dword at 20x20, two on the any-alignment path -- has its own.
+    crl_u32x4 cin[kCopyBatch];
     uint32_t rin1[kRowsPerLane];
+    u32x2_a4 rin2[kRowsPerLane];
+    static_assert(kRowsPerLane <= kCopyBatch, "the 16-byte registers hold every path's loads");
     // Boards whose width is not a multiple of four (19 x 19, the reference's default; round 5) move by rows as well: row R of the
     // wave's 16 * N starts at byte R * N of its run -- any alignment --, so a lane loads the six dwords around it and funnels
     // them to the row's start (v_alignbyte); the copy back stores a row as leading bytes, aligned dwords, trailing bytes.  Not
@@ -1236,48 +1274,99 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
     const bool rowsN = !rows20 && !wide && N >= 4 && N <= 20 && (((uintptr_t)board & 3) == 0) &&
                        !(env0 + kWaveGames >= B && ((B * (int64_t)NN) & 3) != 0);
     const int rows_inN = n_env * N;
-    uint32_t rwN[kRowsPerLane][6];
+    // ---- what every path does between issuing its loads and storing its boards (stated once, run inside each path: the
+    // wait in front of it then counts that path's loads alone).  The running totals are not looked at before the epilogue:
+    // their loads go out behind the boards.  Then, in the shadow of the loads: the first block of actions as far as it goes
+    // without the action table, and my player -- head as an LDS address, the start layout for resets (the table's offsets
+    // count from the first slab).
+    TronLaneTotals in;
+    uint32_t ts;
+    const uint32_t gid = (uint32_t)(first_env_id + (uint64_t)bb);
+    philox_out draw0;
+    // (nothing of the table is touched before the path's loads are out: unpacked up here, the first board load would wait
+    //  for the table)
+    int junk;                                                   // four junk bytes per slab: one per lane of the quad
+    int fresh_h, fresh_d8, fresh_a;                             // (fresh_h of a seat without a player: its junk byte)
+    int h, d8;                                                  // directions live pre-scaled (the bit offset into step4),
+                                                                // bits above 4:3 are garbage
+    // my share of a fresh row: dwords p and p + 2 of its six (dwords 2 and 3 are stored twice, with the same value)
+    static_assert(kRowDwords == 6, "the row rewrite of the quad kernel shares out six dwords");
+    const uint32_t rp[2] = {lt_fresh.x, lt_fresh.y};
+    int sweep_first, sweep, sweep_end;                          // my first dword of the row the next reset rewrites
+    const uint32_t lt_row[kRowsPerLane] = {lt_rows.x, lt_rows.y, lt_rows.z, lt_rows.w, lt_seat.x};
+    auto in_flight = [&]() {
+        junk = lds0 + (int)(lt_seat.z & 0xffffu);
+        fresh_h = lds0 + (int)(lt_seat.y & 0xffffu);
+        fresh_d8 = (int)(lt_fresh.z & 0xffu);
+        fresh_a = (int)(lt_fresh.z >> 8);
+        sweep_first = lds0 + (int)(lt_seat.y >> 16);
+        sweep = sweep_first;
+        sweep_end = sweep_first + N * RS;
+        in = {st.ret_sum[pb], st.win_count[pb], tc, st.tstep[bb], st.n_episodes[bb], st.len_sum[bb], st.last_winners[bb]};
+        ts = in.ts;
+        k = pvalid ? (int)k_in : 1;                             // a seat without a player counts as dead for good
+        draw0 = tron_quad_draw(gid, tc >> 5, p, seed_lo, seed_hi);
+        d8 = (d_in & 3) << 3;
+        const int hc = min(max((int)h_in, 0), NN - 1);
+        const int y = (int)__umulhi((uint32_t)hc, g.inv_n);
+        h = pvalid ? mine + (y + 1) * RS + (hc - y * N) : junk;   // a seat without a player never matches a target
+        if (threadIdx.x < (unsigned)kTronLaneLutWords) *(lds_u32 *)(uintptr_t)(uint32_t)((int)(uint32_t)(uintptr_t)(lds_u8 *)act_lut + 4 * (int)threadIdx.x) = lut_word;
+    };
+    // the two wall rows and the junk dword of my game (three dwords per lane)
+    auto wall_rows = [&]() {
+        *(lds_u32 *)(uintptr_t)(uint32_t)(lds0 + (int)(lt_seat.z >> 16)) = 0xffffffffu;
+        *(lds_u32 *)(uintptr_t)(uint32_t)(lds0 + (int)(lt_seat.w & 0xffffu)) = 0xffffffffu;
+        *(lds_u32 *)(uintptr_t)(uint32_t)(lds0 + (int)(lt_seat.w >> 16)) = 0xffffffffu;
+        if (p == 0) *(lds_u32 *)(uintptr_t)(uint32_t)(mine + pad.junk) = 0xffffffffu;
+    };
+    // A wave with all its 16 games on 20x20 boards (one scalar, decided once): every row exists and every lane has its five, so
+    // the copies need no clamp and no select, and a row's place in the slabs comes from the table.  Any other wave -- ragged,
+    // beyond the batch, other board sizes -- keeps the general code.
+    const bool whole = rows20 && n_env == kWaveGames;
+    if (whole) {
+        const int8_t *src = gslab_in + lane * 20;
+#pragma unroll
+        for (int k = 0; k < kRowsPerLane; ++k) {
+            cin[k] = *reinterpret_cast<const u32x4_a4 *>(src + k * (CRL_WAVE * 20));
+            rin1[k] = *reinterpret_cast<const uint32_t *>(src + k * (CRL_WAVE * 20) + 16);
+        }
+        in_flight();
+        wall_rows();
+#pragma unroll
+        for (int k2 = 0; k2 < kRowsPerLane; ++k2) {
+            // (indexed off ONE pointer: the dwords' offsets then ride in the instructions, not in an add each)
+            lds_u32 *row = (lds_u32 *)(uintptr_t)(uint32_t)(lds0 + (int)(lt_row[k2] & 0xffffu));
+            row[0] = cin[k2].x; row[1] = cin[k2].y; row[2] = cin[k2].z; row[3] = cin[k2].w;
+            row[4] = rin1[k2];
+            row[5] = 0xffffffffu;
+        }
+    } else {
     if (rowsN) {
 #pragma unroll
         for (int k = 0; k < kRowsPerLane; ++k) {
             const int R = lane + k * CRL_WAVE;
             const uint32_t boff = (uint32_t)((R < rows_inN ? R : 0) * N);
             const int8_t *src = gslab_in + (boff & ~3u);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) rwN[k][i] = *reinterpret_cast<const uint32_t *>(src + 4 * i);
+            cin[k] = *reinterpret_cast<const u32x4_a4 *>(src);
+            rin2[k] = *reinterpret_cast<const u32x2_a4 *>(src + 16);
         }
     } else if (rows20) {
 #pragma unroll
         for (int k = 0; k < kRowsPerLane; ++k) {
             const int R = lane + k * CRL_WAVE;
             const int8_t *src = gslab_in + (R < rows_in ? R * 20 : 0);
-            rin4[k] = *reinterpret_cast<const u32x4_a4 *>(src);
+            cin[k] = *reinterpret_cast<const u32x4_a4 *>(src);
             rin1[k] = *reinterpret_cast<const uint32_t *>(src + 16);
         }
     } else if (wide) {
 #pragma unroll
         for (int k = 0; k < kCopyBatch; ++k) {
             const int off = lane * 16 + k * (CRL_WAVE * 16);
-            cin[k] = *reinterpret_cast<const uint4 *>(gslab_in + (off < bytes_in ? off : 0));
+            cin[k] = *reinterpret_cast<const crl_u32x4 *>(gslab_in + (off < bytes_in ? off : 0));
         }
     }
-    // (unconditional, from a clamped index: under `pvalid ? load : 0` every load sits in its own branch with its own wait)
-    const int64_t pb = (int64_t)(p < P ? p : 0) * B + bb;
-    const int h_in = heads[pb];
-    const int d_in = dirs[pb];
-    int k = deaths[pb];
-    const TronLaneTotals in = tron_lane_totals_load(st, pb, bb);
-    uint32_t tc = in.tc, ts = in.ts;
-    k = pvalid ? k : 1;                                         // a seat without a player counts as dead for good
-    if (rows20 || rowsN) {
-        // the two wall rows and the junk dword of my game (three dwords per lane), then my rows of the wave's boards
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int dw = 3 * p + i;
-            *(lds_u32 *)(uintptr_t)(uint32_t)(mine + (dw < 6 ? 4 * dw : (N + 1) * RS + 4 * (dw - 6))) = 0xffffffffu;
-        }
-        if (p == 0) *(lds_u32 *)(uintptr_t)(uint32_t)(mine + pad.junk) = 0xffffffffu;
-    }
+    in_flight();
+    if (rows20 || rowsN) wall_rows();                           // ... then my rows of the wave's boards
     if (rows20) {
 #pragma unroll
         for (int k2 = 0; k2 < kRowsPerLane; ++k2) {
@@ -1285,10 +1374,10 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
             const bool have = R < rows_in;                      // rows of games beyond the batch: empty
             const int e = (int)__umulhi((uint32_t)R, g.inv_n);  // R = 20 e + r
             const int a = slab0 + e * pad.stride + (R - 20 * e + 1) * RS;
-            *(lds_u32 *)(uintptr_t)(uint32_t)(a) = have ? rin4[k2].x : 0u;
-            *(lds_u32 *)(uintptr_t)(uint32_t)(a + 4) = have ? rin4[k2].y : 0u;
-            *(lds_u32 *)(uintptr_t)(uint32_t)(a + 8) = have ? rin4[k2].z : 0u;
-            *(lds_u32 *)(uintptr_t)(uint32_t)(a + 12) = have ? rin4[k2].w : 0u;
+            *(lds_u32 *)(uintptr_t)(uint32_t)(a) = have ? cin[k2].x : 0u;
+            *(lds_u32 *)(uintptr_t)(uint32_t)(a + 4) = have ? cin[k2].y : 0u;
+            *(lds_u32 *)(uintptr_t)(uint32_t)(a + 8) = have ? cin[k2].z : 0u;
+            *(lds_u32 *)(uintptr_t)(uint32_t)(a + 12) = have ? cin[k2].w : 0u;
             *(lds_u32 *)(uintptr_t)(uint32_t)(a + 16) = have ? rin1[k2] : 0u;
             *(lds_u32 *)(uintptr_t)(uint32_t)(a + 20) = 0xffffffffu;
         }
@@ -1308,9 +1397,10 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
                 const uint32_t m8 = ((uint32_t)((have ? R : 0) * N) & 3u);
                 const int e = (int)__umulhi((uint32_t)R, g.inv_n);      // R = N e + y
                 const int a = slab0 + e * pad.stride + (R - N * e + 1) * RS;
+                const uint32_t rw[6] = {cin[k2].x, cin[k2].y, cin[k2].z, cin[k2].w, rin2[k2].x, rin2[k2].y};
 #pragma unroll
                 for (int q = 0; q < 5; ++q) {
-                    uint32_t d = __builtin_amdgcn_alignbyte(rwN[k2][q + 1], rwN[k2][q], m8);
+                    uint32_t d = __builtin_amdgcn_alignbyte(rw[q + 1], rw[q], m8);
                     d = have ? d : 0u;
                     const int keep = N - 4 * q;                 // cells of this dword that are on the board; the rest is wall
                     d = keep >= 4 ? d : (keep <= 0 ? 0xffffffffu : (d | (0xffffffffu << (8 * keep))));
@@ -1340,43 +1430,17 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
                 *(lds_u8 *)(uintptr_t)(uint32_t)(slab0 + e * pad.stride + (y + 1) * RS + (c - y * N)) = (uint8_t)gslab_in[(int64_t)e * NN + c];
             }
     }
-    // ---- my player: head as an LDS address, the start layout for resets
-    const int junk = mine + pad.junk + p;                       // four junk bytes per slab: one per lane of the quad
-    const auto [fh, fd] = tron_seat_start(cfg, p);
-    const int fy = (int)__umulhi((uint32_t)(fh < 0 ? 0 : fh), g.inv_n);
-    const int fresh_h = (p < P) ? mine + (fy + 1) * RS + (fh - fy * N) : junk;
-    const int fresh_d8 = fd << 3;
-    const int fresh_a = (p < P) ? 1 : 0;
-    int h, d8 = (d_in & 3) << 3;                                // directions live pre-scaled (the bit offset into step4),
-    {                                                           // bits above 4:3 are garbage
-        const int hc = min(max(h_in, 0), NN - 1);
-        const int y = (int)__umulhi((uint32_t)hc, g.inv_n);
-        h = pvalid ? mine + (y + 1) * RS + (hc - y * N) : junk;   // a seat without a player never matches a target
-    }
-    // my share of a fresh row: dwords p and p + 2 of its six (dwords 2 and 3 are stored twice, with the same value)
-    static_assert(kRowDwords == 6, "the row rewrite of the quad kernel shares out six dwords");
-    uint32_t rp[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int j = p + 2 * i;
-        uint32_t w = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) w |= (4 * j + c < N) ? 0u : (0xffu << (8 * c));
-        rp[i] = w;
-    }
-    int sweep = mine + RS + 4 * p;                              // my first dword of the row the next reset rewrites
-    const int sweep_end = mine + (N + 1) * RS + 4 * p, sweep_first = mine + RS + 4 * p;
+    }                                                           // (the general paths)
     uint32_t tagbits = 0, stamp = (uint32_t)(p + 1);
     uint32_t alive_steps = 0, wn = 0;                           // wn: episodes << 16 | my wins
     uint32_t marks = 0;                                         // the latest reset in bits 15:0, the one before in 31:16:
                                                                 // (launch steps done at the reset) << 1 | I was alive
     if (!gvalid) k = 1;
-    const uint32_t gid = (uint32_t)(first_env_id + (uint64_t)bb);
     __syncthreads();                                            // action table; (non-wide) slabs written by other lanes
     QUAD_STAMP(1);
     uint32_t a_lo = 0, a_hi = 0;                                // my player's actions of steps 0-15 / 16-31 of the group
     auto refill = [&](const uint32_t group) { tron_quad_actions(gid, group, p, seed_lo, seed_hi, act_lut, a_lo, a_hi); };
-    refill(tc >> 5);
+    tron_quad_codes(draw0, p, act_lut, a_lo, a_hi);             // the rest of refill(tc >> 5)
     uint32_t acts = ((tc & 16u) ? a_hi : a_lo) >> ((tc & 15u) * 2u);   // bits 1:0 = this step's action code (0, 1, 3)
     // `acts` runs dry after dry2 / 2 steps of this launch; neg2 = 2 (launch steps done) - dry2 counts up to zero
     uint32_t dry2 = 32u - 2u * (tc & 15u);
@@ -1618,6 +1682,31 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
             for (int i = lane; i < NN; i += CRL_WAVE)           // 16 boards = N * N chunks of 16 bytes
                 *reinterpret_cast<crl_u32x4 *>(gslab + 16 * i) = *(const __attribute__((address_space(3))) crl_u32x4 *)(uintptr_t)(uint32_t)(slab0 + 16 * i);
         }
+    } else if (whole) {
+        // (the prologue's whole wave: the rows' slab addresses and their games' junk bytes are the table's, kept since then;
+        //  every row goes back, to where it came from)
+        uint32_t c[kRowsPerLane][5], trep[kRowsPerLane];
+#pragma unroll
+        for (int k2 = 0; k2 < kRowsPerLane; ++k2) {             // all LDS reads in flight, then the arithmetic
+            const lds_u32 *row = (const lds_u32 *)(uintptr_t)(uint32_t)(lds0 + (int)(lt_row[k2] & 0xffffu));
+            trep[k2] = (uint32_t)*(const lds_u8 *)(uintptr_t)(uint32_t)(lds0 + (int)(lt_row[k2] >> 16));
+#pragma unroll
+            for (int q = 0; q < 5; ++q) c[k2][q] = row[q];
+        }
+        int8_t *dst = gslab + lane * 20;
+#pragma unroll
+        for (int k2 = 0; k2 < kRowsPerLane; ++k2) {
+            const uint32_t tr = trep[k2] * 0x01010101u;
+            uint32_t w[5];
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                const uint32_t diff = ((c[k2][q] >> OB) & TM) ^ tr;
+                const uint32_t stale = ((diff + 0x7f7f7f7fu) >> 7) & 0x01010101u;
+                w[q] = c[k2][q] & OM & ~((stale << 8) - stale);  // (stale * 0xff without the quarter-rate multiply)
+            }
+            *reinterpret_cast<u32x4_a4 *>(dst + k2 * (CRL_WAVE * 20)) = (u32x4_a4){w[0], w[1], w[2], w[3]};
+            *reinterpret_cast<uint32_t *>(dst + k2 * (CRL_WAVE * 20) + 16) = w[4];
+        }
     } else if (rows20) {
         uint32_t c[kRowsPerLane][5], trep[kRowsPerLane];
 #pragma unroll
@@ -1685,13 +1774,14 @@ tron_rollout_quad_kernel(const crl_tron_cfg cfg, const TronGeom g, const TronPad
     if (pvalid) {
         const int rel = h - mine;
         const int rowi = rel / RS;                               // = y + 1
-        heads[p * B + b] = (int16_t)((rowi - 1) * N + (rel - rowi * RS));
-        dirs[p * B + b] = (int8_t)d;
-        deaths[p * B + b] = (int8_t)k;
+        const int64_t po = (int64_t)p * B + b;                   // my column's element, formed once: every array below is base + po
+        heads[po] = (int16_t)((rowi - 1) * N + (rel - rowi * RS));
+        dirs[po] = (int8_t)d;
+        deaths[po] = (int8_t)k;
         const int rs = in.ret + ret;
         const uint32_t wc = in.wins + wins;
-        st.ret_sum[p * B + b] = rs;
-        st.win_count[p * B + b] = wc;
+        st.ret_sum[po] = rs;
+        st.win_count[po] = wc;
         if (row) { row[3 + p] = (int32_t)wc; row[3 + P + p] = rs; }
         if (pk) pk[4 + p] = (uint16_t)rs;
     }
@@ -4980,6 +5070,48 @@ tron_playout_kernel(const TronGeom g, const int64_t B, const uint32_t seed_lo, c
     CRL_REQUIRE(st.tcount && st.tstep && st.n_episodes && st.win_count && st.len_sum && st.ret_sum &&  \
                 st.last_winners && st.last_len, fn ": NULL stats pointer")
 
+// ---- the lane table of tron_rollout_quad_kernel (tron_lane_table.hpp): built by crl_tron_create, owned by the context, one
+// device copy per device a rollout of the context runs on (uploaded by the first bind there), all freed by crl_destroy
+struct tron_lane_tables {
+    static constexpr int kMaxDev = 64;
+    uint32_t host[kTronLaneTableWords];
+    std::mutex mu;
+    uint32_t *dev[kMaxDev] = {};
+};
+
+// the copy on the current device
+static int tron_lane_table_here(const crl_ctx *ctx, const uint32_t **out)
+{
+    tron_lane_tables *lt = static_cast<tron_lane_tables *>(ctx->tron_lanes);
+    CRL_REQUIRE(lt != nullptr, "tron: internal: a context without a lane table reached the lane-per-player byte kernel");
+    int dev = 0;
+    CRL_HIP(hipGetDevice(&dev));
+    CRL_REQUIRE(dev >= 0 && dev < tron_lane_tables::kMaxDev, "tron: device %d is beyond the %d a context keeps tables for", dev, tron_lane_tables::kMaxDev);
+    std::lock_guard<std::mutex> lock(lt->mu);
+    if (!lt->dev[dev]) {
+        void *d = nullptr;
+        CRL_HIP(hipMalloc(&d, sizeof(lt->host)));
+        const hipError_t e = hipMemcpy(d, lt->host, sizeof(lt->host), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            crl_set_error("tron: uploading the lane table failed: %s", hipGetErrorString(e));
+            return CRL_EHIP;
+        }
+        lt->dev[dev] = static_cast<uint32_t *>(d);
+    }
+    *out = lt->dev[dev];
+    return CRL_OK;
+}
+
+void crl_tron_lanes_free(void *tables)                          // crl_destroy
+{
+    tron_lane_tables *lt = static_cast<tron_lane_tables *>(tables);
+    if (!lt) return;
+    for (uint32_t *d : lt->dev)
+        if (d) (void)hipFree(d);
+    delete lt;
+}
+
 int crl_tron_bounds(unsigned int *out4)
 {
     CRL_BOUNDS_READBACK(out4);
@@ -5094,8 +5226,23 @@ int crl_tron_create(int N, int P, const int16_t *start_heads, const int8_t *star
     c->tron.P = P;
     for (int p = 0; p < P; ++p) { c->tron.start_heads[p] = start_heads[p]; c->tron.start_dirs[p] = start_dirs[p]; }
     for (int p = P; p < CRL_TRON_MAX_P; ++p) { c->tron.start_heads[p] = -1; c->tron.start_dirs[p] = 0; }
+    if (N <= kTronLaneMaxN && P <= kTronLaneMaxP) {             // the shapes tron_rollout_quad_kernel plays
+        tron_lane_tables *lt = new tron_lane_tables();
+        crl_tron_lane_table_build(N, P, start_heads, start_dirs, lt->host);
+        c->tron_lanes = lt;
+    }
     *out = c;
     return CRL_OK;
+}
+
+int crl_tron_lane_table(const crl_ctx *ctx, uint32_t *table, int cap)
+{
+    CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_TRON, "crl_tron_lane_table: ctx is not a tron context");
+    CRL_REQUIRE(cap >= 0, "crl_tron_lane_table: cap=%d is negative", cap);
+    if (!ctx->tron_lanes) return 0;
+    const tron_lane_tables *lt = static_cast<const tron_lane_tables *>(ctx->tron_lanes);
+    if (table) memcpy(table, lt->host, sizeof(uint32_t) * (size_t)std::min(cap, kTronLaneTableWords));
+    return kTronLaneTableWords;
 }
 
 int crl_tron_reset(const crl_ctx *ctx, int64_t B, const uint8_t *mask,
@@ -5163,6 +5310,7 @@ struct tron_plan : crl_plan {
     TronPad pad;
     TronBits bits, qb;
     size_t lds_q;
+    mutable const uint32_t *lanes = nullptr;    // the context's lane table on this plan's device: looked up by the first launch that needs it
 
     int bind(const char *fn, const crl_ctx *ctx_, int64_t B_, uint64_t first_env_id_, int8_t *board_, int16_t *heads_,
              int8_t *dirs_, int8_t *deaths_, const crl_tron_stats &st_, uint32_t flags_);
@@ -5252,8 +5400,12 @@ int tron_plan::run(const char *fn, const uint64_t seed, const int T, void *strea
                    cfg, g, pad, B, seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
             break;
         case TronRollout::Quad:
+            if (!lanes) {
+                CRL_REQUIRE(pad.stride == crl_tron_lane_stride(cfg.N), "%s: internal: slab stride %d, the lane table's is %d", fn, pad.stride, crl_tron_lane_stride(cfg.N));
+                if (const int rc = tron_lane_table_here(ctx, &lanes)) return rc;
+            }
             launch(tron_rollout_quad_kernel<kRowBytesSmall>, dim3(blocks_for(B, 64)), dim3(256), (size_t)64 * pad.stride, last,
-                   cfg, g, pad, B, seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st);
+                   cfg, g, pad, B, seed_lo, seed_hi, first_env_id, tt, board, heads, dirs, deaths, st, lanes);
             break;
         case TronRollout::Bits:
         case TronRollout::Bytes: {

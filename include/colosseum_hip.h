@@ -154,6 +154,12 @@ int crl_philox4x32(const uint32_t *ctr, uint32_t key0, uint32_t key1, uint32_t *
 /* replaces the per-instance set-up of TronGridEnvironment.__init__/generate_start_positions
  * (TronGridEnvironment.py:92-118,183-226); start_* are HOST arrays of length P */
 int crl_tron_create(int N, int P, const int16_t *start_heads, const int8_t *start_dirs, crl_ctx **out);
+/* Boards up to 20x20 with at most 4 players: crl_tron_create also builds, on the host, the table of per-lane constants of
+ * the byte-slab lane-per-player rollout kernel (slab offsets of the rows a lane copies, its seat's start cell, its share of
+ * the walls and of a rewritten row, the action table; layout: csrc/tron_lane_table.hpp).  The context owns it; the first
+ * rollout on a device uploads it there once, crl_destroy frees every copy.  This call copies the HOST table out (for
+ * tests): returns its length in dwords, or 0 for a context without one; table may be NULL, at most cap dwords are written. */
+int crl_tron_lane_table(const crl_ctx *ctx, uint32_t *table, int cap);
 
 /* replaces TronGridEnvironment.new_state (TronGridEnvironment.py:228-263) for B envs.
  * mask (DEVICE, uint8 [B]) may be NULL = reset all; else only envs with mask[b] != 0 */

@@ -12,7 +12,7 @@ make -s -C "$ROOT/colosseumrl_amd/csrc" -j4 >/dev/null
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function "$@" \
     -c "$ROOT/colosseumrl_amd/csrc/$SRC.hip" -o "$OUT/$SRC.o"
 OBJS=""
-for f in capi tron ttt blokus; do
+for f in capi tron tron_territory ttt blokus; do
   if [ "$f" = "$SRC" ]; then OBJS="$OBJS $OUT/$f.o"; else OBJS="$OBJS $ROOT/colosseumrl_amd/csrc/$f.o"; fi
 done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o "$OUT/libcolosseum_hip.so" $OBJS

@@ -5,7 +5,8 @@ Full random games through ``BlokusEnvironment.valid_actions`` / ``next_state`` o
 processes).  Stored per step: the chosen action (encoded), the number of legal actions, a 64-bit
 hash of the ordered legal-action id list, the full ordered list for every 4th step, and the state
 after the step (board, inventories, scores, round, next player, reward, terminal, winners).
-Plus scripted inventory-exhaustion states for the +15 / +20 bonuses (ai.py:49-52).
+Plus scripted inventory-exhaustion states for the +15 / +20 bonuses (ai.py:49-52), and (`endgame`) 24 whole games from
+crafted endgame states: inventories of one or two pieces, players who hold nothing, corners taken in round 0.
 """
 import os
 import sys
@@ -415,6 +416,107 @@ def gen_illegal(R, out_dir):
           "| corner cells true", int(grids.sum()), "of them occupied", int(sum((grids[k, c] & (bases[k][0][0].board_contents != 0)).sum() for k in range(len(bases)) for c in range(4))))
 
 
+ENDGAME_FAMILIES = (("tiny_inventories", 6), ("all_out", 6), ("empty_handed", 6), ("round0_blocked", 6))
+ENDGAME_LIST_BELOW = 6
+
+
+def endgame_starts():
+    """The crafted start states of the `endgame` games, from tests/blokus_positions.py (built on the CPU oracle): six games
+    each of tiny_inventories, all_out, empty_handed and the short games of round0_blocked.
+    -> (board int8 [G,20,20], inv uint32 [G,4], score int32 [G,4], round int32 [G], player int32 [G], family int8 [G])"""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tests import blokus_positions as P
+    parts, family = [], []
+    for k, (name, n) in enumerate(ENDGAME_FAMILIES):
+        st = P.FAMILIES[name](64)
+        idx = P.round0_short(64)[:n] if name == "round0_blocked" else np.arange(n)
+        parts.append(P.clone(st, idx))
+        family += [k] * n
+    st = P.concat(parts)
+    return st.board, st.inv.copy(), st.score.copy(), st.round.copy(), st.to_move.copy(), np.array(family, np.int8)
+
+
+def _endgame_game(args):
+    """game k of `endgame_starts` (its board, inventories, scores, round and mover), written into the reference's (Board,
+    round, [AI]) as `bonus_cases` writes its states and played through valid_actions / next_state until it is terminal"""
+    k, board0, inv0, score0, round0, player0 = args
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from oracle import ref_loader
+    R = ref_loader.load()
+    env = R["blokus"]()
+    state, _ = env.new_state()
+    board, _, ais = state
+    board.board_contents[:] = board0
+    for q in range(4):
+        ais[q].current_pieces = [PIECES[i] for i in range(21) if (int(inv0[q]) >> i) & 1]
+        ais[q].player_score = int(score0[q])
+    state, pl = (board, int(round0), ais), int(player0)
+    rng = np.random.default_rng(1000 + k)
+    rec = dict(action=[], n_valid=[], valid_hash=[], board=[], inv=[], score=[], round=[], next_player=[], reward=[],
+               terminal=[], winners=[], lists=[], list_step=[])
+    with np.errstate(over="ignore"):
+        for t in range(MAX_STEPS):
+            va = env.valid_actions(state, pl)
+            ids = [encode(s) for s in va if s != ""]
+            assert ids == sorted(ids), "reference order is ascending in the dense id"
+            a = ids[int(rng.integers(0, len(ids)))] if ids else -1
+            astr = va[ids.index(a)] if ids else ""
+            state, players, rewards, terminal, winners = env.next_state(state, [pl], [astr])
+            pl = players[0]
+            rec["action"].append(a)
+            rec["n_valid"].append(len(ids))
+            rec["valid_hash"].append(list_hash(ids))
+            if len(ids) < ENDGAME_LIST_BELOW:
+                rec["lists"].append(ids + [-1] * (ENDGAME_LIST_BELOW - len(ids)))
+                rec["list_step"].append(t)
+            rec["board"].append(state[0].board_contents.astype(np.int8).copy())
+            rec["inv"].append([inv_mask(p) for p in state[2]])
+            rec["score"].append([p.player_score for p in state[2]])
+            rec["round"].append(state[1])
+            rec["next_player"].append(pl)
+            rec["reward"].append(rewards[0])
+            rec["terminal"].append(bool(terminal))
+            rec["winners"].append(0 if winners is None else sum(1 << w for w in winners))
+            if terminal:
+                break
+    assert rec["terminal"][-1], "the game did not end within MAX_STEPS plies"
+    return k, rec
+
+
+def gen_endgame(out_dir):
+    """Whole games of the REFERENCE from crafted endgame states (tests/golden/blokus_endgame.npz): the layout of
+    blokus_game_*.npz with every game's plies one behind the other (`game`: the game of a ply, `step`: its number inside
+    the game; `list_step` indexes plies), the full ordered list where it has fewer than 6 entries, plus the start states."""
+    board0, inv0, score0, round0, player0, family = endgame_starts()
+    G = len(board0)
+    from oracle import ref_loader
+    ref_loader.load()                                               # built once, here: the workers inherit it
+    with Pool(min(8, G)) as pool:
+        games = sorted(pool.map(_endgame_game, [(k, board0[k], inv0[k], score0[k], round0[k], player0[k]) for k in range(G)]),
+                       key=lambda kr: kr[0])
+    keys = ("action", "n_valid", "valid_hash", "board", "inv", "score", "round", "next_player", "reward", "terminal", "winners")
+    dtypes = dict(action=np.int32, n_valid=np.int32, valid_hash=np.uint64, board=np.int8, inv=np.uint32, score=np.int32,
+                  round=np.int32, next_player=np.int32, reward=np.int8, terminal=np.uint8, winners=np.uint8)
+    out = {k: [] for k in keys}
+    game, step, lists, list_step = [], [], [], []
+    for k, rec in games:
+        base = len(game)
+        for key in keys:
+            out[key] += rec[key]
+        game += [k] * len(rec["action"])
+        step += list(range(len(rec["action"])))
+        lists += rec["lists"]
+        list_step += [base + t for t in rec["list_step"]]
+        print("blokus endgame", k, "family", ENDGAME_FAMILIES[family[k]][0], "plies", len(rec["action"]), "final scores",
+              rec["score"][-1], "winners", rec["winners"][-1])
+    np.savez_compressed(os.path.join(out_dir, "blokus_endgame.npz"),
+                        start_board=board0.astype(np.int8), start_inv=inv0.astype(np.uint32), start_score=score0.astype(np.int32),
+                        start_round=round0.astype(np.int32), start_player=player0.astype(np.int32), family=family,
+                        game=np.array(game, np.int32), step=np.array(step, np.int32),
+                        lists=np.array(lists, np.int32).reshape(-1, ENDGAME_LIST_BELOW), list_step=np.array(list_step, np.int32),
+                        **{key: np.array(out[key], dtypes[key]) for key in keys})
+
+
 def gen(R, out_dir, n_games=8):
     with Pool(min(8, n_games)) as pool:
         games = pool.map(play_game, list(range(1, n_games + 1)))
@@ -437,6 +539,7 @@ def gen(R, out_dir, n_games=8):
     gen_lattice(out_dir)
     gen_records(R, out_dir)
     gen_illegal(R, out_dir)
+    gen_endgame(out_dir)
 
 
 def gen_observe(R, out_dir, n_steps=28):
@@ -494,5 +597,7 @@ if __name__ == "__main__":
         gen_records(ref_loader.load(), out)
     elif "illegal" in sys.argv[1:]:
         gen_illegal(ref_loader.load(), out)
+    elif "endgame" in sys.argv[1:]:
+        gen_endgame(out)
     else:
         gen_observe(ref_loader.load(), out)

@@ -79,7 +79,7 @@ def blokus_step_single(st, seat, learner_action, seed, first_env_id=0, rank=Fals
                 assert was_learner, "a drawn action raised"
                 reward[b] = r[0]
                 break
-            c += 1
+            c = (c + 1) & M32
             if term[0]:
                 done[b] = 1
                 winners[b] = ws[0]
@@ -94,28 +94,36 @@ def blokus_step_single(st, seat, learner_action, seed, first_env_id=0, rank=Fals
     return reward, done, winners, n_valid, ob, op, osc
 
 
-def blokus_one_playout(st, b, seed, g, c0, first, a, r):
-    """(winners mask, plies, final scores) of playout r of row (b, a); `first` the candidate id or None"""
-    one = blokus_one(st, b)
-    plies, c = 0, c0
-    if first is not None:
-        _, term, ws = O.blokus_step(one, np.array([first], np.int32))
-        plies = 1
-        if term[0]:
-            return int(ws[0]), plies, one.score[0].copy()
-    while True:
+def blokus_random_plies(one, seed, g, c, c2=0, tag=RNG.CRL_TAG_BLOKUS_PLAYOUT, max_plies=None):
+    """The playout's ply loop on the one-game state `one` (mutated, never reset): random plies from step counter c up to
+    the first terminal one, or `max_plies` of them.  -> (winners mask or None while the game goes on, plies played, the
+    counter after them).  With tag=CRL_TAG_BLOKUS and c2=0 the draws are the rollout's."""
+    plies = 0
+    while max_plies is None or plies < max_plies:
         ids = blokus_list(one)
-        word = blokus_word(seed, g, c, (a << 16) | r, RNG.CRL_TAG_BLOKUS_PLAYOUT)
+        word = blokus_word(seed, g, c, c2, tag)
         act = int(ids[(word * len(ids)) >> 32]) if len(ids) else -1
         _, term, ws = O.blokus_step(one, np.array([act], np.int32))
         plies += 1
         c = (c + 1) & M32
         if term[0]:
-            return int(ws[0]), plies, one.score[0].copy()
+            return int(ws[0]), plies, c
+    return None, plies, c
 
 
-def blokus_playout(st, seed, R, cand=None, A=1, first_env_id=0, tcount=None):
-    """crl_blokus_playout on the oracle state `st`."""
+def blokus_one_playout(st, b, seed, g, c0, first, a, r, tag=RNG.CRL_TAG_BLOKUS_PLAYOUT):
+    """(winners mask, plies, final scores) of playout r of row (b, a); `first` the candidate id or None"""
+    one = blokus_one(st, b)
+    if first is not None:
+        _, term, ws = O.blokus_step(one, np.array([first], np.int32))
+        if term[0]:
+            return int(ws[0]), 1, one.score[0].copy()
+    mask, plies, _ = blokus_random_plies(one, seed, g, c0, (a << 16) | r, tag)
+    return mask, plies + (first is not None), one.score[0].copy()
+
+
+def blokus_playout(st, seed, R, cand=None, A=1, first_env_id=0, tcount=None, rows=None):
+    """crl_blokus_playout on the oracle state `st`.  rows: optional iterable of (b, a) to compute (the others stay 0)."""
     B = st.B
     if cand is None:
         assert A == 1
@@ -126,10 +134,13 @@ def blokus_playout(st, seed, R, cand=None, A=1, first_env_id=0, tcount=None):
     played = np.zeros((B, A), np.uint32)
     len_sum = np.zeros((B, A), np.uint32)
     score_sum = np.zeros((B, A, 4), np.int32)
-    for b in range(B):
+    todo = {}
+    for b, a in (rows if rows is not None else [(b, a) for b in range(B) for a in range(A)]):
+        todo.setdefault(int(b), []).append(int(a))
+    for b, columns in todo.items():
         legal = set(int(i) for i in blokus_list(blokus_one(st, b))) if cand is not None else None
         c0 = 0 if tcount is None else int(tcount[b])
-        for a in range(A):
+        for a in columns:
             first = None
             if cand is not None:
                 v = int(cand[b, a])

@@ -48,6 +48,58 @@ def replay_games(golden, be):
     return T
 
 
+PIECE_CELLS = np.array([1, 2, 3, 3, 4, 4, 4, 4, 4] + [5] * 12)
+
+
+def replay_endgames(golden, make_backend):
+    """The reference's own games from crafted endgame states (blokus_endgame.npz, oracle/gen_golden_blokus.py endgame:
+    inventories of one or two pieces, players who hold nothing, corners taken in round 0), every game to its terminal ply:
+    the ordered lists, the steps and the states after them.  Returns what the games held: the plies with +15, with +20,
+    the '' plies by a player who holds nothing, and the terminal plies that leave every inventory empty."""
+    g = golden("blokus_endgame")
+    G = len(g["start_round"])
+    be = make_backend(G)
+    be.set_state(g["start_board"], g["start_inv"], g["start_score"], g["start_round"], g["start_player"])
+    ply_of = {(int(e), int(s)): i for i, (e, s) in enumerate(zip(g["game"], g["step"]))}
+    list_of = {int(i): row for i, row in zip(g["list_step"], g["lists"])}
+    seen = dict(plus15=0, plus20=0, empty_pass=0, all_out=0)
+    inv, score, mover = g["start_inv"].copy(), g["start_score"].copy(), g["start_player"].copy()
+    for t in range(int(g["step"].max()) + 1):
+        count, ids = be.valid(2048)
+        action = np.full(G, -1, np.int32)
+        live = [e for e in range(G) if (e, t) in ply_of]
+        for e in live:
+            i = ply_of[(e, t)]
+            assert count[e] == g["n_valid"][i], ("n_valid", e, t, count[e], g["n_valid"][i])
+            row = ids[e, :count[e]]
+            assert list_hash(row) == g["valid_hash"][i], ("valid list order", e, t)
+            assert (i in list_of) == (count[e] < 6), ("short lists are stored in full", e, t)
+            if i in list_of:
+                assert np.array_equal(list_of[i][:count[e]], row) and (list_of[i][count[e]:] == -1).all(), ("list", e, t)
+            action[e] = g["action"][i]
+        r, term, win = be.step(action)
+        s = be.state()
+        for e in live:
+            i = ply_of[(e, t)]
+            assert np.array_equal(s["board"][e], g["board"][i]), ("board", e, t)
+            assert np.array_equal(s["inv"][e], g["inv"][i]), ("inventory", e, t)
+            assert np.array_equal(s["score"][e], g["score"][i]), ("score", e, t)
+            assert s["round"][e] == g["round"][i] and s["to_move"][e] == g["next_player"][i], ("turn", e, t)
+            assert r[e] == g["reward"][i] and term[e] == g["terminal"][i] and win[e] == g["winners"][i], ("outcome", e, t)
+            assert bool(g["terminal"][i]) == ((e, t + 1) not in ply_of), ("games are stored to their terminal ply", e, t)
+            m = int(mover[e])
+            if action[e] >= 0:                                       # what the fixture itself holds, for the caller
+                extra = int(g["score"][i][m]) - int(score[e, m]) - int(PIECE_CELLS[action[e] // 16000])
+                assert extra == (0 if g["inv"][i][m] else (20 if action[e] // 16000 == 0 else 15)), ("bonus", e, t)
+                seen["plus15"] += extra == 15
+                seen["plus20"] += extra == 20
+            seen["empty_pass"] += action[e] < 0 and inv[e, m] == 0
+            seen["all_out"] += bool(g["terminal"][i]) and not g["inv"][i].any()
+            inv[e], score[e], mover[e] = g["inv"][i], g["score"][i], g["next_player"][i]
+    assert min(seen.values()) >= 1, seen
+    return seen
+
+
 def check_bonus(golden, make_backend):
     g = golden("blokus_bonus")
     n = len(g["action"])

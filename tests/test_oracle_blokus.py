@@ -3,7 +3,7 @@ import numpy as np
 
 from oracle import oracle as O
 from backends import OracleBlokus
-from blokus_replay import GAMES, check_bonus, check_illegal, replay_games
+from blokus_replay import GAMES, check_bonus, check_illegal, replay_endgames, replay_games
 
 
 def test_piece_table_kat():
@@ -71,6 +71,14 @@ def test_lattice_boards_reference_lists(golden):
 
 def test_last_piece_bonus(golden):
     check_bonus(golden, OracleBlokus)
+
+
+def test_reference_endgames(golden):
+    """24 games the REFERENCE played from crafted endgame states to their terminal plies (oracle/gen_golden_blokus.py
+    endgame): the oracle is pinned to it where inventories run out, with both bonuses, on passes by players who hold
+    nothing and on a terminal ply that leaves every inventory empty."""
+    seen = replay_endgames(golden, OracleBlokus)
+    assert seen["plus15"] >= 10 and seen["plus20"] >= 10, seen
 
 
 def test_not_listed_actions_reference_golden(golden):

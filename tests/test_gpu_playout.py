@@ -1,12 +1,8 @@
 """Batched random playouts on the GPU (crl_ttt_playout / crl_blokus_playout): bit-exact against the numpy restatement of
 the header's contract (tests/ttt_ref.py, tests/blokus_ref.py) on ragged batches of random positions, the outcome counts of
 every reachable 3x3 position against exact probabilities, flat Monte Carlo against the random agent through the single-player
-vector env, lane indices past 2^31, graph capture, determinism, read-only inputs, and a smoke run of
-tools/playout_rate.py."""
+vector env, lane indices past 2^31, graph capture, determinism and read-only inputs."""
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,8 +14,6 @@ from tests import ttt_probes as TP
 from tests.gpu_util import DEV, blokus_batch as _blokus_batch, first_episodes, np_of as _np, ttt_batch as _ttt_batch, u32_of as _u32
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _ttt_check(tb, st, tcount, Rn, cand, seed, first_env_id):
@@ -277,15 +271,3 @@ def test_graph_capture_and_determinism():
     x = tb.playout(64, seed=1)["wins"].clone()
     assert torch.equal(x, tb.playout(64, seed=1)["wins"])
     assert not torch.equal(x, tb.playout(64, seed=2)["wins"])
-
-
-# ------------------------------------------------------------------ the rate tool
-def test_playout_rate_tool_smoke(tmp_path):
-    out = tmp_path / "rate.jsonl"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "playout_rate.py"), "--tiny", "--out", str(out)],
-                       cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    import json
-    rows = [json.loads(line) for line in out.read_text().splitlines()]
-    assert {row["game"] for row in rows} == {"tictactoe", "blokus"}
-    assert all(row["playouts_per_s"] > 0 and row["plies_per_s"] > 0 for row in rows)

@@ -2,12 +2,8 @@
 (tests/tron_ref.py) on ragged batches of mid-game positions over board sizes, player counts, both agents, both
 stop modes and step caps; outcome counts of a tiny board against exact probabilities; read-only inputs, overwritten
 outputs, determinism, graph replay, lane indices past 2^31; flat Monte Carlo in TronSinglePlayerVectorEnv against a
-random and an avoid learner; and a smoke run of tools/tron_playout_rate.py."""
-import json
+random and an avoid learner."""
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,8 +14,6 @@ from tests import tron_ref as TR
 from tests.gpu_util import DEV, first_episodes, np_of as _np, tron_put
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _positions(N, P, B, seed):
@@ -253,13 +247,3 @@ def test_flat_mc_beats_random_learner():
     print("\nfirst episode (return, steps, win rate): flat MC %s  random %s  avoid %s" % (mc, rnd, avd))
     assert mc[0] >= rnd[0] + 10.0 and mc[1] >= 2 * rnd[1], (mc, rnd)
     assert mc[0] >= avd[0] - 2.0, (mc, avd)                # reported; expected to beat the avoid learner too
-
-
-def test_tron_playout_rate_tool_smoke(tmp_path):
-    out = tmp_path / "rate.jsonl"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "tron_playout_rate.py"), "--tiny", "--out", str(out)],
-                       cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    rows = [json.loads(line) for line in out.read_text().splitlines()]
-    assert {row["agent"] for row in rows} == {"random", "avoid"}
-    assert all(row["playouts_per_s"] > 0 and row["steps_per_s"] > 0 and row["loop_ms"] > 0 for row in rows)

@@ -10,7 +10,6 @@ and the loop states are identical.  Prints one JSON line per shape and writes th
     python tools/avoid_rate.py [--batch 65536] [--sizes 19,40] [--steps 20,1024] [--reps 3] [--out FILE]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -19,19 +18,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from tools.common import measure as M  # noqa: E402
 
 
-def _time(fn, reps):
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    out = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        out.append(start.elapsed_time(stop) * 1e3)          # us
-    return min(out), sorted(out)[len(out) // 2]
+def _min_median_us(fn, reps):
+    ts = [ms * 1e3 for ms in M.isolated(fn, reps)]
+    return min(ts), M.median(ts)
 
 
 def main():
@@ -45,8 +37,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from colosseumrl_amd.batched import TronBatch
-    if not torch.cuda.is_available():
-        raise SystemExit("avoid_rate.py needs a GPU")
+    M.require_gpu("avoid_rate.py")
     torch.cuda.set_device(0)
     B, P, noise = args.batch, args.players, args.noise
     rows = []
@@ -65,9 +56,9 @@ def main():
             torch.cuda.synchronize()
             same = all(torch.equal(a, b) for a, b in zip((fused.board, fused.heads, fused.dirs, fused.deaths, fused.tcount),
                                                         (loop.board, loop.heads, loop.dirs, loop.deaths, loop.tcount)))
-            t_fused = _time(lambda: fused.rollout_avoid(T, 7, noise), args.reps)
-            t_loop = _time(run_loop, args.reps)
-            t_rnd = _time(lambda: rnd.rollout(T, 7, kernel="gquad"), args.reps)
+            t_fused = _min_median_us(lambda: fused.rollout_avoid(T, 7, noise), args.reps)
+            t_loop = _min_median_us(run_loop, args.reps)
+            t_rnd = _min_median_us(lambda: rnd.rollout(T, 7, kernel="gquad"), args.reps)
             torch.cuda.synchronize()
             # (the loop keeps no episode statistics -- crl_tron_step does not --, so state and step counter are compared)
             same = same and all(torch.equal(a, b) for a, b in zip((fused.board, fused.heads, fused.dirs, fused.deaths, fused.tcount),
@@ -80,14 +71,12 @@ def main():
                    "loop_over_fused": round(t_loop[1] / t_fused[1], 2), "fused_over_gquad_random": round(t_fused[1] / t_rnd[1], 2),
                    "mean_episode_len_avoid": round(mean_len(fused), 2), "mean_episode_len_random": round(mean_len(rnd), 2),
                    "fused_equals_loop": bool(same)}
-            print(json.dumps(row), flush=True)
+            M.emit(row)
             rows.append(row)
             del fused, loop, rnd
             torch.cuda.empty_cache()
     if args.out:
-        with open(args.out, "w") as f:
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
+        M.write_rows(args.out, rows)
     return 0 if all(r["fused_equals_loop"] for r in rows) else 1
 
 

@@ -11,23 +11,12 @@ if "-h" in sys.argv[1:] or "--help" in sys.argv[1:]:     # usage without touchin
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 import bench
+from tools.common import measure as M
 
 wl, T = sys.argv[1], int(sys.argv[2])
 game, kw = bench.WORKLOADS[wl][:2]
 for B in [int(x) for x in sys.argv[3].split(",")]:
     st = bench.make_stepper(game, kw, B, torch.device("cuda", 0), 0)
-    for _ in range(3):
-        st.rollout(T, 0)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            st.rollout(T, 0)
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / 10)
-    ts.sort()
-    print("%s T=%d B=%-8d %8.4f ms per launch  %.4g env-steps/s" % (wl, T, B, ts[2], B * T / (ts[2] * 1e-3)), flush=True)
+    ms = M.median(M.back_to_back(lambda: st.rollout(T, 0), calls=10, rounds=5, warmup=3))
+    print("%s T=%d B=%-8d %8.4f ms per launch  %.4g env-steps/s" % (wl, T, B, ms, B * T / (ms * 1e-3)), flush=True)
     del st

@@ -18,22 +18,11 @@ if "-h" in sys.argv[1:] or "--help" in sys.argv[1:]:     # usage without touchin
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from colosseumrl_amd.batched import TronBatch
+from tools.common import measure as M
 
 def timed(fn, reps=10, rounds=5):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3 / reps)
-    ts.sort()
-    return ts[len(ts) // 2]
+    """us per call: the median round of `reps` back-to-back calls, after two warm-up calls"""
+    return M.median(M.back_to_back(fn, reps, rounds, warmup=2)) * 1e3
 
 
 arg = sys.argv[1:]
@@ -79,19 +68,7 @@ if arg and arg[0] == "kernels":
         for kern in KERNS:
             row = []
             for T in Ts:
-                for _ in range(2):
-                    st.rollout(T, 1, kernel=kern)
-                torch.cuda.synchronize()
-                ts = []
-                for _ in range(3):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(5):
-                        st.rollout(T, 1, kernel=kern)
-                    e1.record()
-                    torch.cuda.synchronize()
-                    ts.append(e0.elapsed_time(e1) * 1e3 / 5)
-                row.append("%8.1f" % sorted(ts)[1])
+                row.append("%8.1f" % timed(lambda: st.rollout(T, 1, kernel=kern), reps=5, rounds=3))
             print("N=%d %-6s us per launch at T=%s: %s" % (N, kern, ",".join(map(str, Ts)), " ".join(row)), flush=True)
         del st
     sys.exit(0)

@@ -12,22 +12,12 @@ import os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch  # noqa: E402
 from colosseumrl_amd.batched import TronBatch  # noqa: E402
+from tools.common import measure as M  # noqa: E402
 
 
-def gpu_us(fn, calls, rounds=5):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(calls):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3 / calls)
-    ts.sort()
-    return [round(ts[len(ts) // 2], 2), round(ts[0], 2)]
+def median_min_us(fn, calls):
+    ts = M.back_to_back(fn, calls, rounds=5, warmup=1)
+    return [round(M.median(ts) * 1e3, 2), round(min(ts) * 1e3, 2)]
 
 
 def main():
@@ -37,12 +27,12 @@ def main():
         tb = TronBatch(20, 4, B)
         calls = 10 if B > 200000 else 100
         fo = tb.step_observe(None, seed=7, out=None)
-        rec = {"step_observe_us": gpu_us(lambda: tb.step_observe(None, seed=7, out=fo), calls)}
+        rec = {"step_observe_us": median_min_us(lambda: tb.step_observe(None, seed=7, out=fo), calls)}
         buf = tb.observe_all()
-        rec["observe_all_us"] = gpu_us(lambda: tb.observe_all(buf), calls)
-        rec["rollout20_us"] = gpu_us(lambda: tb.rollout(20, 3), calls)
+        rec["observe_all_us"] = median_min_us(lambda: tb.observe_all(buf), calls)
+        rec["rollout20_us"] = median_min_us(lambda: tb.rollout(20, 3), calls)
         pl = torch.randint(0, 4, (B,), dtype=torch.int8, device="cuda")
-        rec["observe_us"] = gpu_us(lambda: tb.observe(pl), calls)
+        rec["observe_us"] = median_min_us(lambda: tb.observe(pl), calls)
         nbytes = 5 * 400 * B
         rec["step_observe_TBs"] = round(nbytes / rec["step_observe_us"][0] / 1e6, 3)
         out["b%d" % B] = rec

@@ -2,107 +2,68 @@
 """A/B of library VARIANTS (tools/lib_variant.sh) on one device: every variant runs in its own process (the library is
 loaded once per process), rounds interleaved so that clock drift hits all alike.
 
-    python tools/lib_ab.py [--isolated] <workload> <steps per launch>[,<steps>...] <tag>=<path to .so> [<tag>=<path> ...]
+    python tools/lib_ab.py [--isolated] [--rounds 3] <workload> <steps per launch>[,<steps>...] <tag>=<path to .so> [<tag>=<path> ...]
 
 Default: launches back to back (steady state).  --isolated: one launch between two synchronisations, the way bench.py's
 contract region times a short launch (HIP-event time of the launch and wall clock of launch + events + synchronise).
 
 workload: a bench.py WORKLOADS name.  Prints per variant and launch length the median / min kernel time over the rounds
 (HIP events around a batch of launches) and env-steps/s."""
+import argparse
 import json
 import os
-import subprocess
 import sys
-if "-h" in sys.argv[1:] or "--help" in sys.argv[1:]:     # usage without touching the GPU (tests/test_tools_smoke.py)
-    print(__doc__)
-    sys.exit(0)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.common import measure as M  # noqa: E402
 
-CHILD = r"""
-import json, os, sys
-sys.path.insert(0, %(root)r)
-import torch
-import bench
-game, kw, batch, chunk = bench.WORKLOADS[%(wl)r][:4]
-st = bench.make_stepper(game, kw, batch, torch.device("cuda", 0), 0)
-out = {}
-for T in %(Ts)r:
-    reps = max(3, min(200, int(0.05 / max(1e-5, T * 4e-7))))
-    for _ in range(3):
-        st.rollout(T, 0)
-    torch.cuda.synchronize()
-    best = []
-    for rnd in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            st.rollout(T, 0)
-        e1.record()
-        torch.cuda.synchronize()
-        best.append(e0.elapsed_time(e1) / reps)
-    best.sort()
-    out[str(T)] = [best[len(best) // 2], best[0]]
-print("AB " + json.dumps(out))
-"""
 
-# isolated launches, the way bench.py's contract region times one: synchronise, event, launch, event, synchronise
-CHILD_ISOLATED = r"""
-import json, os, sys, time
-sys.path.insert(0, %(root)r)
-import torch
-import bench
-game, kw, batch, chunk = bench.WORKLOADS[%(wl)r][:4]
-st = bench.make_stepper(game, kw, batch, torch.device("cuda", 0), 0)
-out = {}
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-for T in %(Ts)r:
-    for _ in range(20):
-        st.rollout(T, 0)
-    torch.cuda.synchronize()
-    wall, ev = [], []
-    for i in range(300):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        e0.record()
-        st.rollout(T, 0)
-        e1.record()
-        torch.cuda.synchronize()
-        wall.append((time.perf_counter() - t0) * 1e3)
-        ev.append(e0.elapsed_time(e1))
-    wall.sort(); ev.sort()
-    out[str(T)] = [ev[150], ev[15], wall[150]]
-print("AB " + json.dumps(out))
-"""
+def child(wl, Ts, isolated):
+    """one round of one variant: {T: [median ms, min ms]}, isolated {T: [median ms, 5th percentile ms, median wall ms]}, as a
+    JSON line behind "AB " """
+    import torch
+    import bench
+    game, kw, batch, chunk = bench.WORKLOADS[wl][:4]
+    st = bench.make_stepper(game, kw, batch, torch.device("cuda", 0), 0)
+    out = {}
+    for T in Ts:
+        if isolated:
+            ev, wall = M.isolated(lambda: st.rollout(T, 0), 300, warmup=20, wall=True)
+            out[str(T)] = [M.median(ev), sorted(ev)[15], M.median(wall)]
+        else:
+            calls = max(3, min(200, int(0.05 / max(1e-5, T * 4e-7))))
+            ts = M.back_to_back(lambda: st.rollout(T, 0), calls, rounds=5, warmup=3)
+            out[str(T)] = [M.median(ts), min(ts)]
+    print("AB " + json.dumps(out))
 
 
 def main():
-    isolated = "--isolated" in sys.argv
-    if isolated:
-        sys.argv.remove("--isolated")
-    wl, Ts = sys.argv[1], [int(t) for t in sys.argv[2].split(",")]
-    variants = [a.split("=", 1) for a in sys.argv[3:]]
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--isolated", action="store_true")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("workload")
+    ap.add_argument("steps")
+    ap.add_argument("variants", nargs="*", metavar="tag=path")
+    a = ap.parse_args()
+    wl, Ts = a.workload, [int(t) for t in a.steps.split(",")]
+    if a.child:
+        return child(wl, Ts, a.isolated)
+    variants = [v.split("=", 1) for v in a.variants]
     import bench
     batch = bench.WORKLOADS[wl][2]
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", wl, a.steps] + (["--isolated"] if a.isolated else [])
     res = {tag: {str(T): [] for T in Ts} for tag, _ in variants}
-    for rnd in range(3):
-        for tag, path in variants:
-            env = dict(os.environ, CRL_LIB_PATH=path)
-            p = subprocess.run([sys.executable, "-c", (CHILD_ISOLATED if isolated else CHILD) % {"root": ROOT, "wl": wl, "Ts": Ts}], env=env, stdout=subprocess.PIPE,
-                               stderr=subprocess.PIPE, text=True, timeout=600)
-            line = [l for l in p.stdout.splitlines() if l.startswith("AB ")]
-            if p.returncode != 0 or not line:
-                print("variant %s failed: %s" % (tag, p.stderr[-2000:]))
-                return 1
-            for T, v in json.loads(line[-1][3:]).items():
-                res[tag][T].append(v)
+    for tag, result in M.alternate(cmd, variants, a.rounds, 600, "AB "):
+        for T, v in result.items():
+            res[tag][T].append(v)
     for T in Ts:
         for tag, _ in variants:
-            med = sorted(v[0] for v in res[tag][str(T)])[1]
+            med = M.median([v[0] for v in res[tag][str(T)]])
             mn = min(v[1] for v in res[tag][str(T)])
-            if isolated:
-                wall = sorted(v[2] for v in res[tag][str(T)])[1]
+            if a.isolated:
+                wall = M.median([v[2] for v in res[tag][str(T)]])
                 print("%s T=%-5d %-12s isolated launch: events median %7.2f us  p5 %7.2f us   launch+2 events+sync wall %7.2f us" % (wl, T, tag, med * 1e3, mn * 1e3, wall * 1e3), flush=True)
                 continue
             print("%s T=%-5d %-12s median %9.4f ms  min %9.4f ms  -> %.4g env-steps/s" % (wl, T, tag, med, mn, batch * T / (med * 1e-3)), flush=True)

@@ -17,7 +17,6 @@ Prints one JSON line per configuration and writes them to --out.
                                     [--out profiles/mcts_agent_rate.jsonl] [--tiny]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -26,23 +25,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from tools.common import measure as M  # noqa: E402
 
 DEV = "cuda:0"
-SHAPES = [((3, 3), 3, 2), ((3, 5), 3, 3), ((3, 3, 3), 3, 4), ((5, 5), 4, 3)]
-
-
-def _timed(fn):
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop)
-
-
-def _median(ts):
-    return sorted(ts)[len(ts) // 2]
 
 
 def _uniform_actions(valid, cells, gen):
@@ -60,20 +45,20 @@ def _steps(tb, seat, gen, reps, seed, timed=None, **opponent):
     for i in range(reps + 1):
         act = _uniform_actions(out["valid"], tb.n_cells, gen)
         before = tb.tcount.clone()
-        ms = _timed(lambda: tb.step_single(seat, act, seed, out=out, **opponent))
+        ms = M.isolated(lambda: tb.step_single(seat, act, seed, out=out, **opponent), 1)[0]
         if i:
             ts.append(ms)
             plies += int((tb.tcount - before).to(torch.int64).sum()) - tb.B      # (the learner's ply is one of them)
             if timed is not None:
-                extra.append(_timed(timed))
-    return _median(ts), plies / (reps * tb.B), extra
+                extra += M.isolated(timed, 1)
+    return M.median(ts), plies / (reps * tb.B), extra
 
 
 def rows_of(shapes, B, S, R, T, reps, seed=1):
     from colosseumrl_amd.batched import TTTBatch
     rows = []
     for dims, k, p in shapes:
-        name = "x".join(map(str, dims)) + "_k%d_p%d" % (k, p)
+        name = M.shape_name(dims, k, p)
         gen = torch.Generator(device=DEV)
         gen.manual_seed(7)
         seat = torch.zeros(B, dtype=torch.int8, device=DEV)
@@ -84,16 +69,15 @@ def rows_of(shapes, B, S, R, T, reps, seed=1):
         tr = TTTBatch(dims, k, p, B, device=DEV)
         ms_random, _, _ = _steps(tr, seat, gen, reps, seed)
         tb.reset()
-        tb.rollout_mcts(T, S, R, seed)                                        # warm-up
-        ms_roll = _median([_timed(lambda: tb.rollout_mcts(T, S, R, seed)) for _ in range(reps)])
-        ms_mcts = _median(mcts_ts)
+        ms_roll = M.median(M.isolated(lambda: tb.rollout_mcts(T, S, R, seed), reps, warmup=1))
+        ms_mcts = M.median(mcts_ts)
         floor = (p - 1) * ms_mcts + ms_random
         row = {"game": "tictactoe", "shape": name, "B": B, "S": S, "R": R, "noise": 0.0, "learner": "uniform, seat 0",
                "step_single_mcts_ms": round(ms, 4), "searches_per_call": round(searches, 3),
                "ms_per_search": round(ms / max(searches, 1e-9), 4), "mcts_ms": round(ms_mcts, 4),
                "step_single_random_ms": round(ms_random, 4), "floor_ms": round(floor, 4), "step_over_floor": round(ms / floor, 3),
                "rollout_plies": T, "rollout_mcts_ms": round(ms_roll, 4), "rollout_plies_per_s": round(B * T / ms_roll * 1e3)}
-        print(json.dumps(row), flush=True)
+        M.emit(row)
         rows.append(row)
         del tb, tr
         torch.cuda.empty_cache()
@@ -110,17 +94,13 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcts_agent_rate.jsonl"))
     ap.add_argument("--tiny", action="store_true", help="a smoke run: one shape, 64 games, 16 simulations, R = 4, 2 plies")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("mcts_agent_rate.py needs a GPU")
+    M.require_gpu("mcts_agent_rate.py")
     torch.cuda.set_device(0)
     if args.tiny:
-        rows = rows_of(SHAPES[:1], 64, 16, 4, 2, 1)
+        rows = rows_of(M.TTT_SHAPES[:1], 64, 16, 4, 2, 1)
     else:
-        rows = rows_of(SHAPES, args.batch, args.simulations, args.playouts, args.plies, args.reps)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        for r in rows:
-            f.write(json.dumps(r) + "\n")
+        rows = rows_of(M.TTT_SHAPES, args.batch, args.simulations, args.playouts, args.plies, args.reps)
+    M.write_rows(args.out, rows)
     return 0
 
 

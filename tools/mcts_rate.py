@@ -16,7 +16,6 @@ Prints one JSON line per configuration and writes them to --out.
     python tools/mcts_rate.py [--reps 3] [--batch 4096] [--simulations 128] [--sample 4] [--out profiles/mcts_rate.jsonl] [--tiny]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -26,23 +25,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from tools.common import measure as M  # noqa: E402
 
 DEV = "cuda:0"
-SHAPES = [((3, 3), 3, 2), ((3, 5), 3, 3), ((3, 3, 3), 3, 4), ((5, 5), 4, 3)]
-
-
-def _median_ms(fn, reps):
-    fn()                                                    # warm-up
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        ts.append(start.elapsed_time(stop))
-    return sorted(ts)[len(ts) // 2]
 
 
 def _sampled_plies(dims, k, p, S, R, seed, sample, out):
@@ -63,15 +48,15 @@ def rows_of(shapes, B, S, Rs, reps, sample, seed=1):
     from colosseumrl_amd.batched import TTTBatch
     rows = []
     for dims, k, p in shapes:
-        name = "x".join(map(str, dims)) + "_k%d_p%d" % (k, p)
+        name = M.shape_name(dims, k, p)
         tb = TTTBatch(dims, k, p, B, device=DEV)
         for R in Rs:
             out = tb.mcts(S, R, seed)
-            ms = _median_ms(lambda: tb.mcts(S, R, seed, out=out), reps)
+            ms = M.median(M.isolated(lambda: tb.mcts(S, R, seed, out=out), reps, warmup=1))
             playouts, plies = _sampled_plies(dims, k, p, S, R, seed, min(sample, B), out)
             flat_r = -(-S * R // tb.n_cells)
             fo = tb.playout(flat_r, tb._all_cells)
-            ms_flat = _median_ms(lambda: tb.flat_mc_action(flat_r, seed, out=fo), reps)
+            ms_flat = M.median(M.isolated(lambda: tb.flat_mc_action(flat_r, seed, out=fo), reps, warmup=1))
             flat_plies = int(fo["len_sum"].to(torch.int64).sum())
             row = {"game": "tictactoe", "shape": name, "B": B, "S": S, "R": R, "positions": "empty board",
                    "mcts_ms": round(ms, 4), "simulations_per_s": round(B * S / ms * 1e3),
@@ -81,7 +66,7 @@ def rows_of(shapes, B, S, Rs, reps, sample, seed=1):
                    "flat_mc_playouts_per_position": flat_r * tb.n_cells, "flat_mc_ms": round(ms_flat, 4),
                    "flat_mc_plies_per_s": round(flat_plies / ms_flat * 1e3)}
             row["mcts_over_flat_mc_time"] = round(ms / ms_flat, 3)
-            print(json.dumps(row), flush=True)
+            M.emit(row)
             rows.append(row)
         del tb
         torch.cuda.empty_cache()
@@ -97,17 +82,13 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcts_rate.jsonl"))
     ap.add_argument("--tiny", action="store_true", help="a smoke run: one shape, 64 positions, 16 simulations, R = 4")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("mcts_rate.py needs a GPU")
+    M.require_gpu("mcts_rate.py")
     torch.cuda.set_device(0)
     if args.tiny:
-        rows = rows_of(SHAPES[:1], 64, 16, [4], 1, 2)
+        rows = rows_of(M.TTT_SHAPES[:1], 64, 16, [4], 1, 2)
     else:
-        rows = rows_of(SHAPES, args.batch, args.simulations, [16, 64], args.reps, args.sample)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        for r in rows:
-            f.write(json.dumps(r) + "\n")
+        rows = rows_of(M.TTT_SHAPES, args.batch, args.simulations, [16, 64], args.reps, args.sample)
+    M.write_rows(args.out, rows)
     return 0
 
 

@@ -16,7 +16,6 @@ TicTacToe: 3x3 P2, 3x5 P3, 3x3x3 P4, 5x5 K4 P3 from the empty board (cand = NULL
     python tools/playout_rate.py [--reps 3] [--out profiles/playout_rate.jsonl] [--tiny]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -25,22 +24,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from tools.common import measure as M  # noqa: E402
 
 DEV = "cuda:0"
-
-
-def _median_ms(fn, reps):
-    fn()                                                    # warm-up
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        ts.append(start.elapsed_time(stop))
-    return sorted(ts)[len(ts) // 2]
 
 
 def _lane_efficiency(make, n):
@@ -54,25 +40,25 @@ def ttt_rows(shapes, sizes, reps, roll_steps, roll_cap):
     from colosseumrl_amd.batched import TTTBatch
     rows = []
     for dims, k, p in shapes:
-        name = "x".join(map(str, dims)) + "_k%d_p%d" % (k, p)
+        name = M.shape_name(dims, k, p)
         eff = _lane_efficiency(lambda n: TTTBatch(dims, k, p, n, device=DEV), 1 << 16)
         for log2 in sizes:
             B = 1 << 14 if log2 > 16 else 1 << (log2 // 2)
             R = (1 << log2) // B
             tb = TTTBatch(dims, k, p, B, device=DEV)
             out = tb.playout(R)
-            ms = _median_ms(lambda: tb.playout(R, out=out), reps)
+            ms = M.median(M.isolated(lambda: tb.playout(R, out=out), reps, warmup=1))
             plies = int(out["len_sum"].to(torch.int64).sum())
             n_roll = min(B * R, roll_cap)
             roll = TTTBatch(dims, k, p, n_roll, device=DEV)
-            ms_roll = _median_ms(lambda: roll.rollout(roll_steps), reps)
+            ms_roll = M.median(M.isolated(lambda: roll.rollout(roll_steps), reps, warmup=1))
             row = {"game": "tictactoe", "shape": name, "B": B, "A": 1, "R": R, "playouts": B * R, "ms": round(ms, 3),
                    "playouts_per_s": round(B * R / ms * 1e3), "plies_per_s": round(plies / ms * 1e3),
                    "mean_plies": round(plies / (B * R), 3),
                    "rollout_games": n_roll, "rollout_env_steps_per_s": round(n_roll * roll_steps / ms_roll * 1e3),
                    "lane_efficiency": round(eff, 4)}
             row["plies_over_rollout"] = round(row["plies_per_s"] / row["rollout_env_steps_per_s"], 3)
-            print(json.dumps(row), flush=True)
+            M.emit(row)
             rows.append(row)
             del tb, roll, out
             torch.cuda.empty_cache()
@@ -97,11 +83,11 @@ def blokus_rows(configs, reps, roll_steps):
                 cols.append(bb.select(rank)[0])
             cand = torch.stack(cols, dim=1).contiguous()
         out = bb.playout(R, cand)
-        ms = _median_ms(lambda: bb.playout(R, cand, out=out), reps)
+        ms = M.median(M.isolated(lambda: bb.playout(R, cand, out=out), reps, warmup=1))
         plies = int(out["len_sum"].to(torch.int64).sum())
         n = B * A * R
         roll = BlokusBatch(n, device=DEV)
-        ms_roll = _median_ms(lambda: roll.rollout(roll_steps), reps)
+        ms_roll = M.median(M.isolated(lambda: roll.rollout(roll_steps), reps, warmup=1))
         row = {"game": "blokus", "B": B, "A": A, "R": R, "playouts": n, "start_plies": warm, "ms": round(ms, 3),
                "playouts_per_s": round(n / ms * 1e3), "plies_per_s": round(plies / ms * 1e3),
                "mean_plies": round(plies / n, 2), "rollout_games": n,
@@ -109,7 +95,7 @@ def blokus_rows(configs, reps, roll_steps):
                "rollout_us_per_ply": round(ms_roll * 1e3 / roll_steps, 2),
                "playout_us_per_mean_ply": round(ms * 1e3 / (plies / n), 2)}
         row["plies_over_rollout"] = round(row["plies_per_s"] / row["rollout_env_steps_per_s"], 3)
-        print(json.dumps(row), flush=True)
+        M.emit(row)
         rows.append(row)
         del bb, roll, out
         torch.cuda.empty_cache()
@@ -122,19 +108,14 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "playout_rate.jsonl"))
     ap.add_argument("--tiny", action="store_true", help="a few thousand playouts per configuration (a smoke run)")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("playout_rate.py needs a GPU")
+    M.require_gpu("playout_rate.py")
     torch.cuda.set_device(0)
-    shapes = [((3, 3), 3, 2), ((3, 5), 3, 3), ((3, 3, 3), 3, 4), ((5, 5), 4, 3)]
     if args.tiny:
-        rows = ttt_rows(shapes[:1], [12], 1, 8, 1 << 12) + blokus_rows([(8, 2, 2, 16), (16, 1, 1, 0)], 1, 4)
+        rows = ttt_rows(M.TTT_SHAPES[:1], [12], 1, 8, 1 << 12) + blokus_rows([(8, 2, 2, 16), (16, 1, 1, 0)], 1, 4)
     else:
-        rows = (ttt_rows(shapes, [24, 28], args.reps, 16, 1 << 24)
+        rows = (ttt_rows(M.TTT_SHAPES, [24, 28], args.reps, 16, 1 << 24)
                 + blokus_rows([(1024, 16, 16, 16), (16384, 1, 1, 0)], args.reps, 16))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        for r in rows:
-            f.write(json.dumps(r) + "\n")
+    M.write_rows(args.out, rows)
     return 0
 
 

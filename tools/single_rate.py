@@ -13,7 +13,6 @@ Prints one JSON line per game and writes them all to --out.
     python tools/single_rate.py [--blokus-batch 16384] [--ttt-batch 262144] [--steps 20] [--reps 5] [--out FILE]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -22,19 +21,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from tools.common import measure as M  # noqa: E402
 
 
-def _time(fn, reps):
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    out = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        out.append(start.elapsed_time(stop) * 1e3)          # us
-    return min(out), sorted(out)[len(out) // 2]
+def _min_median_us(fn, reps):
+    ts = [ms * 1e3 for ms in M.isolated(fn, reps)]
+    return min(ts), M.median(ts)
 
 
 def _measure(name, B, P, make, steps, reps, fused_action, chain_action, rank=False, seed=3):
@@ -57,9 +49,9 @@ def _measure(name, B, P, make, steps, reps, fused_action, chain_action, rank=Fal
     run_single()
     run_chain()
     roll.rollout(steps * P, seed)
-    t_single = _time(run_single, reps)
-    t_chain = _time(run_chain, reps)
-    t_roll = _time(lambda: roll.rollout(steps * P, seed), reps)
+    t_single = _min_median_us(run_single, reps)
+    t_chain = _min_median_us(run_chain, reps)
+    t_roll = _min_median_us(lambda: roll.rollout(steps * P, seed), reps)
     torch.cuda.synchronize()
     row = {"game": name, "B": B, "P": P, "steps": steps,
            "fused_us_per_step": round(t_single[1] / steps, 2), "chain_us_per_step": round(t_chain[1] / steps, 2),
@@ -69,7 +61,7 @@ def _measure(name, B, P, make, steps, reps, fused_action, chain_action, rank=Fal
            "chain_over_fused": round(t_chain[1] / t_single[1], 2),
            "fused_over_rollout": round(t_single[1] / t_roll[1], 2),
            "fused_done_per_game_step": round(float(outs["s"]["done"].float().mean()), 4)}
-    print(json.dumps(row), flush=True)
+    M.emit(row)
     del single, chain, roll
     torch.cuda.empty_cache()
     return row
@@ -84,8 +76,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from colosseumrl_amd.batched import BlokusBatch, TTTBatch
-    if not torch.cuda.is_available():
-        raise SystemExit("single_rate.py needs a GPU")
+    M.require_gpu("single_rate.py")
     torch.cuda.set_device(0)
     rows = []
     gen = torch.Generator(device="cuda:0")
@@ -103,9 +94,7 @@ def main():
     rows.append(_measure("blokus", args.blokus_batch, 4, lambda: BlokusBatch(args.blokus_batch, device="cuda:0"),
                          args.steps, args.reps, lambda i: ranks[i], lambda i: None, rank=True))
     if args.out:
-        with open(args.out, "w") as f:
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
+        M.write_rows(args.out, rows)
     return 0
 
 

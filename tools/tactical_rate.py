@@ -21,40 +21,21 @@ which leaves build/parent_src/colosseumrl_amd/libcolosseum_hip.so.  Prints one J
 import argparse
 import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from tools.common import measure as M  # noqa: E402
 
 DEV = "cuda:0"
-SHAPES = [((3, 3), 3, 2), ((3, 5), 3, 3), ((3, 3, 3), 3, 4), ((5, 5), 4, 3)]
+SHAPES = M.TTT_SHAPES
 TACTICAL_ENTRIES = ("crl_ttt_winning_cells", "crl_ttt_sample_tactical", "crl_ttt_rollout_tactical",
                     "crl_ttt_step_single_tactical", "crl_ttt_playout_tactical")
 FIGURES = ("step_single_us", "playout_plies_per_s", "rollout_env_steps_per_s")
 
 
-def shape_name(dims, k, p):
-    return "x".join(map(str, dims)) + "_k%d_p%d" % (k, p)
-
-
 # ------------------------------------------------------------------ one round, in a process of its own
-def _median_ms(fn, reps):
-    import torch
-    fn()                                                    # warm-up
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        ts.append(start.elapsed_time(stop))
-    return sorted(ts)[len(ts) // 2]
-
-
 def _exports(lib_path, names):
     """whether the library exports every one of the entries"""
     import ctypes
@@ -63,17 +44,17 @@ def _exports(lib_path, names):
 
 
 def child(a):
-    """one round: {shape: {figure_agent: value}} as a JSON line behind "ROUND " """
+    """one round: {shape: {figure_agent: value}} as a JSON line behind "ROUND "; a child that is given a library is the
+    parent's"""
     import torch
     from colosseumrl_amd import _native
-    tactical = not a.parent or _exports(_native.LIB_PATH, TACTICAL_ENTRIES)
+    tactical = not os.environ.get("CRL_LIB_PATH") or _exports(_native.LIB_PATH, TACTICAL_ENTRIES)
     agents = ["random", "tactical"] if tactical else ["random"]
     if not tactical:                                        # a build from before the tactical entries exports none of them
         for name in TACTICAL_ENTRIES:
             _native.PROTOTYPES.pop(name)
     from colosseumrl_amd.batched import TTTBatch
-    if not torch.cuda.is_available():
-        raise SystemExit("tactical_rate.py needs a GPU")
+    M.require_gpu("tactical_rate.py")
     torch.cuda.set_device(0)
     gen = torch.Generator(device=DEV)
     gen.manual_seed(1)
@@ -95,42 +76,22 @@ def child(a):
                     bufs["s"] = tb.step_single(seat, acts[i], 3, out=bufs.get("s"), **kw_single)
             tb.reset()
             tb.step_single(seat, None, 3, **kw_single)
-            row["step_single_us_" + agent] = _median_ms(run_single, a.reps) * 1e3 / a.steps
+            row["step_single_us_" + agent] = M.median(M.isolated(run_single, a.reps, warmup=1)) * 1e3 / a.steps
             po = pb.playout(R, **kw_playout)
-            ms = _median_ms(lambda: pb.playout(R, out=po, **kw_playout), a.reps)
+            ms = M.median(M.isolated(lambda: pb.playout(R, out=po, **kw_playout), a.reps, warmup=1))
             row["playout_plies_per_s_" + agent] = int(po["len_sum"].to(torch.int64).sum()) / (ms * 1e-3)
             roll = (lambda: tb.rollout_tactical(a.roll_steps, 3, a.noise)) if agent == "tactical" else (lambda: tb.rollout(a.roll_steps, 3))
             tb.reset()
-            row["rollout_env_steps_per_s_" + agent] = a.batch * a.roll_steps / (_median_ms(roll, a.reps) * 1e-3)
+            row["rollout_env_steps_per_s_" + agent] = a.batch * a.roll_steps / (M.median(M.isolated(roll, a.reps, warmup=1)) * 1e-3)
         if tactical:
-            row["winning_cells_us"] = _median_ms(tb.winning_cells, a.reps) * 1e3     # (the positions the rollouts left)
-        out[shape_name(dims, k, p)] = row
+            row["winning_cells_us"] = M.median(M.isolated(tb.winning_cells, a.reps, warmup=1)) * 1e3     # (the positions the rollouts left)
+        out[M.shape_name(dims, k, p)] = row
         del tb, pb
         torch.cuda.empty_cache()
     print("ROUND " + json.dumps(out), flush=True)
 
 
 # ------------------------------------------------------------------ the rounds, alternating builds
-def _round(a, parent_lib):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--batch", str(a.batch), "--playouts", str(a.playouts),
-           "--playout-batch", str(a.playout_batch), "--steps", str(a.steps), "--roll-steps", str(a.roll_steps),
-           "--reps", str(a.reps), "--shapes", str(a.shapes), "--noise", str(a.noise)] + (["--parent"] if parent_lib else [])
-    env = dict(os.environ)
-    env.pop("CRL_LIB_PATH", None)
-    if parent_lib:
-        env["CRL_LIB_PATH"] = os.path.abspath(parent_lib)
-    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=a.round_timeout)
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("ROUND ")]
-    if r.returncode != 0 or not lines:
-        raise SystemExit("a measurement round failed (%s build):\n%s%s" % ("parent" if parent_lib else "this", r.stdout, r.stderr))
-    return json.loads(lines[-1][len("ROUND "):])
-
-
-def _summary(values):
-    v = sorted(values)
-    return v[len(v) // 2], [v[0], v[-1]]
-
-
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=3)
@@ -147,7 +108,6 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tactical_rate.jsonl"))
     ap.add_argument("--tiny", action="store_true", help="a seconds-long smoke run (two shapes, 1,024 games, 2^12 playouts, one round)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--parent", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.tiny:
         a.rounds, a.reps, a.batch, a.playouts, a.playout_batch, a.steps, a.roll_steps, a.shapes = 1, 1, 1024, 1 << 12, 64, 4, 8, 2
@@ -155,39 +115,38 @@ def main():
         return child(a)
     if a.parent_lib and not os.path.exists(a.parent_lib):
         raise SystemExit("--parent-lib %s does not exist" % a.parent_lib)
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--batch", str(a.batch), "--playouts", str(a.playouts),
+           "--playout-batch", str(a.playout_batch), "--steps", str(a.steps), "--roll-steps", str(a.roll_steps),
+           "--reps", str(a.reps), "--shapes", str(a.shapes), "--noise", str(a.noise)]
+    builds = [("this", None)] + ([("parent", a.parent_lib)] if a.parent_lib else [])
     here, parent = [], []
-    for _ in range(a.rounds):
-        here.append(_round(a, None))
-        if a.parent_lib:
-            parent.append(_round(a, a.parent_lib))
+    for tag, result in M.alternate(cmd, builds, a.rounds, a.round_timeout, "ROUND ", cwd=ROOT):
+        (parent if tag == "parent" else here).append(result)
     rows = []
     for dims, k, p in SHAPES[:a.shapes]:
-        name = shape_name(dims, k, p)
+        name = M.shape_name(dims, k, p)
         row = {"game": "tictactoe", "shape": name, "B": a.batch, "noise": a.noise, "playouts": a.playouts, "steps": a.steps,
                "roll_steps": a.roll_steps, "rounds": a.rounds}
         for fig in FIGURES:
             for agent in ("random", "tactical"):
-                row[fig + "_" + agent], row[fig + "_" + agent + "_spread"] = _summary([r[name][fig + "_" + agent] for r in here])
+                row[fig + "_" + agent], row[fig + "_" + agent + "_spread"] = M.spread([r[name][fig + "_" + agent] for r in here])
             row[fig + "_random_parent"], row[fig + "_random_parent_spread"] = \
-                _summary([r[name][fig + "_random"] for r in parent]) if parent else (None, None)
+                M.spread([r[name][fig + "_random"] for r in parent]) if parent else (None, None)
             if parent and fig + "_tactical" in parent[0][name]:         # (a parent with the tactical entries)
                 row[fig + "_tactical_parent"], row[fig + "_tactical_parent_spread"] = \
-                    _summary([r[name][fig + "_tactical"] for r in parent])
-        row["winning_cells_us"], row["winning_cells_us_spread"] = _summary([r[name]["winning_cells_us"] for r in here])
+                    M.spread([r[name][fig + "_tactical"] for r in parent])
+        row["winning_cells_us"], row["winning_cells_us_spread"] = M.spread([r[name]["winning_cells_us"] for r in here])
         if parent and "winning_cells_us" in parent[0][name]:
             row["winning_cells_us_parent"], row["winning_cells_us_parent_spread"] = \
-                _summary([r[name]["winning_cells_us"] for r in parent])
+                M.spread([r[name]["winning_cells_us"] for r in parent])
         row["step_single_tactical_over_random"] = row["step_single_us_tactical"] / row["step_single_us_random"]
         row["playout_random_over_tactical"] = row["playout_plies_per_s_random"] / row["playout_plies_per_s_tactical"]
         row["rollout_random_over_tactical"] = row["rollout_env_steps_per_s_random"] / row["rollout_env_steps_per_s_tactical"]
         row = {k_: (round(v, 3) if isinstance(v, float) else [round(x, 3) for x in v] if isinstance(v, list) else v)
                for k_, v in row.items()}
-        print(json.dumps(row), flush=True)
+        M.emit(row)
         rows.append(row)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        for r in rows:
-            f.write(json.dumps(r) + "\n")
+    M.write_rows(a.out, rows)
 
 
 if __name__ == "__main__":

@@ -15,30 +15,15 @@ Prints one JSON line per shape and writes them to --out.
     python tools/territory_rate.py [--reps 3] [--out profiles/territory_rate.jsonl] [--tiny]
 """
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from tools.common import measure as M  # noqa: E402
 
 DEV = "cuda:0"
-
-
-def _median_ms(fn, reps):
-    import torch
-    fn()                                                    # warm-up
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        ts.append(start.elapsed_time(stop))
-    return sorted(ts)[len(ts) // 2]
 
 
 def _mean_depth(tb, n):
@@ -61,22 +46,22 @@ def rows(shapes, reps, playouts, depth_sample):
         torch.cuda.synchronize()
         cand = torch.arange(3, dtype=torch.int32, device=DEV).expand(B, 3).contiguous() if A == 3 else None
         to = tb.territory(cand)
-        ms = _median_ms(lambda: tb.territory(cand, out=to), reps)
+        ms = M.median(M.isolated(lambda: tb.territory(cand, out=to), reps, warmup=1))
         ob = tb.observe_all()
-        oms = _median_ms(lambda: tb.observe_all(out=ob), reps)
+        oms = M.median(M.isolated(lambda: tb.observe_all(out=ob), reps, warmup=1))
         acts = torch.zeros((4, B), dtype=torch.int8, device=DEV)
-        tms = _median_ms(lambda: tb.sample_territory(3, 0.1, out=acts, advance=False), reps)
-        ams = _median_ms(lambda: tb.sample_avoid(3, 0.1, out=acts, advance=False), reps)
+        tms = M.median(M.isolated(lambda: tb.sample_territory(3, 0.1, out=acts, advance=False), reps, warmup=1))
+        ams = M.median(M.isolated(lambda: tb.sample_avoid(3, 0.1, out=acts, advance=False), reps, warmup=1))
         row = {"N": N, "P": 4, "B": B, "A": A, "ms": round(ms, 4), "instances_per_s": B * A / (ms * 1e-3),
                "mean_depth": round(_mean_depth(tb, depth_sample), 2), "observe_all_ms": round(oms, 4),
                "sample_territory_ms": round(tms, 4), "sample_avoid_ms": round(ams, 4)}
         if A == 3:
-            dms = _median_ms(lambda: tb.territory_action(out=to), reps)
+            dms = M.median(M.isolated(lambda: tb.territory_action(out=to), reps, warmup=1))
             po = tb.playout(playouts, cand, 1, agent="avoid", until="seat_done")
-            fms = _median_ms(lambda: tb.flat_mc_action(playouts, 1, "avoid", 0.1, None, "seat_done", 0, po), reps)
+            fms = M.median(M.isolated(lambda: tb.flat_mc_action(playouts, 1, "avoid", 0.1, None, "seat_done", 0, po), reps, warmup=1))
             row.update({"decision_ms": round(dms, 4), "flat_mc_playouts": playouts, "flat_mc_ms": round(fms, 4),
                         "decision_cheaper": dms < fms, "flat_mc_over_decision": fms / dms})
-        print(json.dumps(row), flush=True)
+        M.emit(row)
         out.append(row)
         del tb
         torch.cuda.empty_cache()
@@ -91,14 +76,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "territory_rate.jsonl"))
     ap.add_argument("--tiny", action="store_true", help="a seconds-long smoke run (64 positions, 19x19 x 3 and 20x20 x 1, 4 playouts)")
     a = ap.parse_args()
+    M.require_gpu("territory_rate.py")
     if a.tiny:
         res = rows([(19, 64, 3), (20, 64, 1)], 1, 4, 16)
     else:
         res = rows([(19, 4096, 3), (40, 4096, 3), (20, 65536, 1)], a.reps, a.playouts, a.depth_sample)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        for r in res:
-            f.write(json.dumps(r) + "\n")
+    M.write_rows(a.out, res)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,6 @@ Prints one JSON line per configuration and writes them to --out.
     python tools/tron_playout_rate.py [--reps 3] [--out profiles/tron_playout_rate.jsonl] [--tiny]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -23,22 +22,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from tools.common import measure as M  # noqa: E402
 
 DEV = "cuda:0"
-
-
-def _median_ms(fn, reps):
-    fn()                                                    # warm-up
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        ts.append(start.elapsed_time(stop))
-    return sorted(ts)[len(ts) // 2]
 
 
 def _positions(N, B, agent):
@@ -86,24 +72,24 @@ def rows(N_list, B, A, R, reps, roll_steps):
             tb = _positions(N, B, agent)
             cand = torch.arange(A, dtype=torch.int32, device=DEV).expand(B, A).contiguous()
             po = tb.playout(R, cand, 1, agent=agent)
-            ms = _median_ms(lambda: tb.playout(R, cand, 1, agent=agent, out=po), reps)
+            ms = M.median(M.isolated(lambda: tb.playout(R, cand, 1, agent=agent, out=po), reps, warmup=1))
             steps = int(po["len_sum"].sum().item())
             n_play = int(po["played"].sum().item())
             games = B * A * R
             rb = TronBatch(N, 4, games, device=DEV)
             if agent == "avoid":
-                rms = _median_ms(lambda: rb.rollout_avoid(roll_steps, 3, 0.1), reps)
+                rms = M.median(M.isolated(lambda: rb.rollout_avoid(roll_steps, 3, 0.1), reps, warmup=1))
             else:
-                rms = _median_ms(lambda: rb.rollout(roll_steps, 3), reps)
+                rms = M.median(M.isolated(lambda: rb.rollout(roll_steps, 3), reps, warmup=1))
             del rb
             roll_rate = games * roll_steps / (rms * 1e-3)
-            lms = _median_ms(lambda: _loop(tb, cand, R, agent, 0.1, 1), max(1, reps))
+            lms = M.median(M.isolated(lambda: _loop(tb, cand, R, agent, 0.1, 1), max(1, reps), warmup=1))
             row = {"agent": agent, "N": N, "P": 4, "B": B, "A": A, "R": R, "ms": round(ms, 4),
                    "playouts_per_s": n_play / (ms * 1e-3), "steps_per_s": steps / (ms * 1e-3),
                    "mean_len": steps / max(n_play, 1), "rollout_env_steps_per_s": roll_rate,
                    "steps_over_rollout": (steps / (ms * 1e-3)) / roll_rate, "loop_ms": round(lms, 3),
                    "speedup_over_loop": lms / ms}
-            print(json.dumps(row), flush=True)
+            M.emit(row)
             out.append(row)
             del tb
             torch.cuda.empty_cache()
@@ -117,14 +103,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tron_playout_rate.jsonl"))
     ap.add_argument("--tiny", action="store_true", help="a seconds-long smoke run (64 positions x 3 x 8, 19x19 only)")
     a = ap.parse_args()
+    M.require_gpu("tron_playout_rate.py")
     if a.tiny:
         res = rows([19], 64, 3, 8, 1, 8)
     else:
         res = rows([19, 40], 4096, 3, 64, a.reps, a.roll_steps)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        for r in res:
-            f.write(json.dumps(r) + "\n")
+    M.write_rows(a.out, res)
 
 
 if __name__ == "__main__":

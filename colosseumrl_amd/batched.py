@@ -531,6 +531,53 @@ class TronBatch(_RolloutStepper):
         mean = o["ret_sum"].to(torch.float64) / float(playouts)
         return _flat_mc_pick(mean - mean.amin(dim=1, keepdim=True), o["played"], cands)
 
+    # -- tree search for one seat; the contract is with crl_tron_mcts in include/colosseum_hip.h
+    @functools.cached_property
+    def mcts_max_simulations(self) -> int:
+        """the most simulations ``mcts`` takes on this board (``crl_tron_mcts_max_simulations``: the tree, the path and the
+        bitboards of a search stay in LDS); boards of 90x90 and more have no search and raise here"""
+        rc = self._lib.crl_tron_mcts_max_simulations(self._ctx.handle)
+        if rc < 0:
+            check(rc, "crl_tron_mcts_max_simulations")
+        return int(rc)
+
+    def mcts(self, simulations: int, playouts: int = 16, seed: int = 0, exploration: float = 1.0, agent: str = "random",
+             noise: float = 0.1, seat: Optional[torch.Tensor] = None, max_steps: int = 0, out: Optional[dict] = None):
+        """A tree search (UCT) for the seat ``seat[b]`` (int8 [B]; None: player 0) in every game, ONE launch
+        (``crl_tron_mcts``): each game builds a tree of its own over the SEAT's three actions by ``simulations`` descents (at
+        most ``mcts_max_simulations``); the other players are part of the transition, played by ``agent`` ("random", or
+        "avoid" with ``noise``) from counter-based draws, and each new leaf is valued by ``playouts`` (1 .. 1024) games of
+        that agent that stop with the game, with the seat's death, or after ``max_steps`` > 0 steps.  ``exploration`` (0 ..
+        65535 / 256; 0 = pure exploitation) multiplies sqrt(log2 n_parent / n_child) on a value scale of 0 .. 1.  The draws
+        are keyed by ``seed``, the game ids and ``tcount`` as the counter base (the call reads the state and writes none of
+        it).  Returns {'visits', 'value' int32 [B, 3]: simulations through the root's child at each action (0 forward, 1
+        right, 2 left) and the seat's half-points there (2 per playout the seat survives as a winner, 1 per playout the
+        cap stopped with the seat alive), 'nodes' int32 [B], 'best' int32 [B]: the most visited action (ties: the larger
+        value, then the lower action; -1 where the seat is dead or the game is over)}; ``out`` reuses such a dict.  The
+        visit counts are the policy target of an AlphaZero-style trainer.  No host synchronisation; capturable into a
+        graph."""
+        S = _int_in("simulations", simulations, 1, self.mcts_max_simulations)
+        R = _int_in("playouts", playouts, 1, 1024)
+        cexp = _exploration("exploration", exploration)
+        _one_of("agent", agent, ("random", "avoid"))
+        noise = _unit("noise", noise)
+        _int_in("max_steps", max_steps, 0, 65535)
+        _seat(seat, self.B, self.device)
+        i32 = torch.int32
+        out = _out_dict(out, {"visits": (i32, (self.B, 3)), "value": (i32, (self.B, 3)), "nodes": (i32, (self.B,)),
+                              "best": (i32, (self.B,))}, self.device)
+        self._call("crl_tron_mcts", _seed(seed), self.first_env_id, *self._state(), _ptr(self.tcount), _ptr(seat), S, R, cexp,
+                   noise, max_steps, _ptr(out["visits"]), _ptr(out["value"]), _ptr(out["nodes"]), _ptr(out["best"]),
+                   _native.CRL_PLAYOUT_AVOID if agent == "avoid" else 0)
+        return out
+
+    def mcts_action(self, simulations: int, playouts: int = 16, seed: int = 0, exploration: float = 1.0, agent: str = "random",
+                    noise: float = 0.1, seat: Optional[torch.Tensor] = None, max_steps: int = 0,
+                    out: Optional[dict] = None) -> torch.Tensor:
+        """``mcts``'s most visited action as an int64 [B] action for ``step_single`` (-1 where the seat is dead or the game
+        is over): the arg-max is the kernel's own ``best``, only widened here.  No host synchronisation; capturable."""
+        return self.mcts(simulations, playouts, seed, exploration, agent, noise, seat, max_steps, out)["best"].to(torch.int64)
+
     # -- Voronoi territory of every game's position (the deterministic evaluator beside playout)
     def territory(self, candidates: Optional[torch.Tensor] = None, seat: Optional[torch.Tensor] = None,
                   out: Optional[dict] = None):

@@ -198,6 +198,14 @@ int crl_diag_bounds(uint32_t *out12)
     }
 #endif
     int rc = crl_tron_bounds(out12);
+    if (rc == CRL_OK) {                                          // tron_mcts.hip counts on its own: one sum, the first offender of the two
+        unsigned int m[4] = {0, 0, 0, 0};
+        rc = crl_tron_mcts_bounds(m);
+        if (rc == CRL_OK && m[0] != 0u) {
+            if (out12[0] == 0u) { out12[1] = m[1]; out12[2] = m[2]; out12[3] = m[3]; }
+            out12[0] += m[0];
+        }
+    }
     if (rc == CRL_OK) rc = crl_ttt_bounds(out12 + 4);
     if (rc == CRL_OK) rc = crl_blokus_bounds(out12 + 8);
     if (rc != CRL_OK) return rc;

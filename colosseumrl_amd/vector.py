@@ -105,6 +105,15 @@ class TronSinglePlayerVectorEnv:
         host synchronisation; capturable."""
         return self.batch.territory_action(None, out)
 
+    def mcts_action(self, simulations: int, playouts: int = 16, seed: int = 1, exploration: float = 1.0, max_steps: int = 0,
+                    out: Optional[dict] = None) -> torch.Tensor:
+        """A tree search for the learner on the env's own games (``TronBatch.mcts_action``): seat 0, the other players
+        modelled by the avoid agent with the env's noise -- whatever the env's opponent --, which also plays the playouts.
+        ``seed`` keys the search (its draws never coincide with the env's own).  -> int64 [B] in {0, 1, 2} for ``step``,
+        one launch, no host synchronisation, capturable.  ``out``: the ``TronBatch.mcts`` dict to reuse (its 'visits' are a
+        policy target)."""
+        return self.batch.mcts_action(simulations, playouts, seed, exploration, "avoid", self.noise, None, max_steps, out)
+
 
 class TicTacToeVectorEnv:
     """B turn-based TicTacToe games.  ``step`` takes int8 cell indices [B] for the player to move (-1 = pass)."""

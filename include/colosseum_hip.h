@@ -89,7 +89,8 @@ const char *crl_last_error(void);
  *      So were crl_ttt_winning_cells and crl_ttt_sample_tactical / _rollout_tactical / _step_single_tactical /
  *      _playout_tactical (the win-or-block agent of TicTacToe: five new entries, two new Philox tags), and
  *      crl_ttt_mcts / crl_ttt_mcts_max_simulations (batched tree search: two new entries, one new Philox tag), and
- *      crl_ttt_sample_mcts / _rollout_mcts / _step_single_mcts (the search as a seated agent: three new entries, no new tag). */
+ *      crl_ttt_sample_mcts / _rollout_mcts / _step_single_mcts (the search as a seated agent: three new entries, no new tag), and
+ *      crl_tron_mcts / crl_tron_mcts_max_simulations (batched tree search for one seat of Tron: two new entries, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -339,6 +340,76 @@ int crl_tron_playout(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t firs
                      double noise, int max_steps,
                      uint32_t *wins, uint32_t *played, uint32_t *len_sum, int32_t *ret_sum,
                      uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------ batched tree search for a seat (UCT), Tron
+ * crl_tron_mcts: from each of B positions build a search tree of its own for ONE seat by S simulations s = 0 .. S-1, in
+ * order, each evaluated by R playouts, and report the root's children.  One launch, no host sync.  Added under revision 113:
+ * two new entries, no new Philox tag, no existing struct, argument list or RNG contract changed.
+ * The search is single-agent: the tree branches on the seat's three actions only.  Every other player is part of the
+ * transition, played by a scripted MODEL (the random or the avoid agent) from counter-based draws, so a node's position is a
+ * pure function of the root and the edge sequence.
+ * State.  Read only, in crl_tron_playout's layouts: board / heads / dirs / deaths as crl_tron_step has them, tcount uint32 [B]
+ * the counter base (NULL means 0), seat int8 [B] the player searched for (NULL means player 0).  g = the low 32 bits of
+ * first_env_id + b.  A cell is occupied iff its value is > 0.
+ * Flags.  CRL_PLAYOUT_AVOID only: the model and the playouts then use the avoid agent with `noise`, else the random agent
+ * (noise is checked and otherwise unused).
+ * Nodes.  Node 0 is the root, position b.  A node holds n, the number of simulations that passed through it; w, the seat's
+ * half-points summed over them (the root's w stays 0); and three child slots, for the actions 0 forward, 1 right, 2 left
+ * (crl_tron_step_single's encoding), all empty at first.
+ * A tree step from a node at depth k (edges from the root) with edge action e has step counter c = tcount[b] + k (uint32
+ * arithmetic).  The seat plays e.  Every other live player q plays the model agent, decided on the pre-step position:
+ *   random  W = Philox4x32-10(ctr = {g, c >> 3, 0xFFFF0000, 0x54700000 | (q >> 2)}, key = {seed lo, seed hi}), then
+ *           crl_tron_rollout's digit rule with j = c & 7 and q & 3;
+ *   avoid   W = Philox4x32-10(ctr = {g, c, 0xFFFF0000, 0x54610000 | q}, key = {seed lo, seed hi}), then
+ *           crl_tron_sample_avoid's rule (threshold, clamped probes, side bit).
+ * The step itself is crl_tron_step without reset.  These are the two playout tags; crl_tron_playout has a < 65535 and the
+ * leaves below have s <= 4094, so the third word 0xFFFF0000 belongs to the tree steps alone.  The node reached is CLOSED iff
+ * the seat is dead or at most one player is alive; a closed node's outcome is 2 half-points iff the seat is alive, else 0.
+ * Descent, as crl_ttt_mcts's.  A simulation starts at the root with a private copy of the position.  At an open node v:
+ *   expand: if some action has no child, take the lowest such action e; a new node with the next free index becomes v's
+ *           child at e, the tree step e is played, and the new node is the leaf, closed or not;
+ *   select: else take the child u that maximises score(v, u), ties to the lowest action, and play its tree step; a closed
+ *           child is the leaf, else the descent continues at u.
+ * Score, crl_ttt_mcts's, in 64-bit integers with floor divisions:
+ *   exploit = (w_u << 15) / (n_u * R)                                        in [0, 65536]
+ *   lg(n), n >= 1: m = the index of n's leading one, f = ((n << (31 - m)) >> 23) & 255, lg(n) = 256 m + f
+ *   X = (lg(n_v) << 24) / n_u
+ *   score = exploit + ((cexp * isqrt(X)) >> 8),  isqrt the exact floor square root
+ * (cexp / 256 multiplies sqrt(log2 n_v / n_u) on a value scale of 0 .. 1: 256 is the usual choice, 0 pure exploitation).
+ * Evaluation of the leaf L at depth d.  Closed: all R playouts have L's outcome and no draw is made.  Open: playouts
+ * r = 0 .. R-1, each crl_tron_playout's playout from L's position as it stands (cand == NULL there: no forced action), with
+ * the counter base tcount[b] + d, the third counter word (s << 16) | r, the flag's agent and `noise`; it stops after the
+ * first terminal step, after the step in which the seat dies (CRL_PLAYOUT_UNTIL_SEAT_DONE's rule), or after max_steps
+ * playout steps when max_steps > 0.  Half-points of a playout: 2 if its last step was terminal with the seat in the winners
+ * mask; 1 if the cap stopped it (the step was not terminal) with the seat alive; else 0.
+ * Backup.  n += 1 on every node of the path from the root to L; w += the sum of the playouts' half-points on every node of
+ * it but the root.
+ * Outputs, every word overwritten:
+ *   visits uint32 [B][3], value uint32 [B][3]   n and w of the root's child at each action, 0 where there is none;
+ *   nodes  uint32 [B]                           the node count, root included;
+ *   best   int32  [B]                           the most visited action; ties go to the larger w, then to the lower action.
+ * A position is skipped (zeros, nodes 0, best -1) when the seat is outside [0, P), the seat is dead (deaths[seat][b] != 0),
+ * or P >= 2 and fewer than two players are alive.
+ * Limits (CRL_EINVAL, with a crl_last_error message, before any device work): NULL state or output pointers, B out of range
+ * (as crl_tron_playout), S outside [1, S_max], R outside [1, 1024], cexp > 65535, noise outside [0, 1] or NaN, max_steps
+ * outside [0, 65535], flags other than CRL_PLAYOUT_AVOID, a context that is not a Tron context.
+ * S_max = min(4095, (65536 - 264 * ceil(N*N / 32)) / 16 - 1): one wave's tree and path (16 bytes per node) and its 66
+ * occupancy bitboards (root, working copy, 64 playouts) fit 64 KB of one workgroup's LDS, and s fits its counter word --
+ * 4,078 on 5x5, 3,897 on 19x19, 3,880 on 20x20, 3,270 on 40x40, 1,983 on 64x64.  Boards of 90x90 and more leave no room
+ * (S_max < 1): both entries answer CRL_EUNSUPPORTED there.  crl_tron_mcts_max_simulations returns S_max of the context
+ * (CRL_EINVAL on a context that is not a Tron context).
+ * Precondition as crl_tron_playout: heads outside the board are clamped onto it (wrong results, never a wild access).
+ * One wave per tree, the tree in LDS, one to four waves per workgroup; the descent is wave-uniform, lanes 0..2 score the
+ * children, lane r plays playout r on a private bitboard (R > 64 in passes), lane i backs up the node at depth i.  Nothing is
+ * shared between waves, so the results do not depend on their order.  Games are walked in a grid-stride loop with 64-bit
+ * indices. */
+int crl_tron_mcts_max_simulations(const crl_ctx *ctx);
+int crl_tron_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                  const int8_t *board, const int16_t *heads, const int8_t *dirs, const int8_t *deaths,
+                  const uint32_t *tcount, const int8_t *seat,
+                  int S, int R, uint32_t cexp, double noise, int max_steps,
+                  uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best,
+                  uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ Voronoi territory (Tron)
  * crl_tron_territory: for each of B positions and A forced first actions of a seat, the number of free cells every player

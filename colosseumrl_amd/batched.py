@@ -578,6 +578,38 @@ class TronBatch(_RolloutStepper):
         is over): the arg-max is the kernel's own ``best``, only widened here.  No host synchronisation; capturable."""
         return self.mcts(simulations, playouts, seed, exploration, agent, noise, seat, max_steps, out)["best"].to(torch.int64)
 
+    # -- the same search with Voronoi territory at the leaves; the contract is with crl_tron_mcts_territory
+    def mcts_territory(self, simulations: int, seed: int = 0, exploration: float = 1.0, agent: str = "random", noise: float = 0.1,
+                       seat: Optional[torch.Tensor] = None, value_scale: int = 256, out: Optional[dict] = None):
+        """``mcts`` with Voronoi territory as the leaf evaluator, ONE launch (``crl_tron_mcts_territory``; boards up to
+        64x64): the same tree over the SEAT's three actions, the same model ``agent`` in the tree steps, but a new leaf is
+        valued by one flood of its position instead of playouts -- ``floor(2 V a_s / (a_s + a_o))`` half-points on the
+        scale V = ``value_scale`` (1 .. 1024), with a_s the seat's territory and a_o the best other live player's; V when
+        nobody has any; a closed leaf 2 V if the seat is alive, else 0.  Nothing is drawn at a leaf.  ``simulations`` is at
+        most ``mcts_max_simulations``; ``exploration`` as in ``mcts``.  Returns {'visits', 'value' int32 [B, 3], 'nodes',
+        'best' int32 [B]} as ``mcts`` does ('value' on the scale of V); ``out`` reuses such a dict.  The state is only read.
+        No host synchronisation; capturable into a graph."""
+        S = _int_in("simulations", simulations, 1, self.mcts_max_simulations)
+        cexp = _exploration("exploration", exploration)
+        _one_of("agent", agent, ("random", "avoid"))
+        noise = _unit("noise", noise)
+        _seat(seat, self.B, self.device)
+        V = _int_in("value_scale", value_scale, 1, 1024)
+        i32 = torch.int32
+        out = _out_dict(out, {"visits": (i32, (self.B, 3)), "value": (i32, (self.B, 3)), "nodes": (i32, (self.B,)),
+                              "best": (i32, (self.B,))}, self.device)
+        self._call("crl_tron_mcts_territory", _seed(seed), self.first_env_id, *self._state(), _ptr(self.tcount), _ptr(seat), S, V,
+                   cexp, noise, _ptr(out["visits"]), _ptr(out["value"]), _ptr(out["nodes"]), _ptr(out["best"]),
+                   _native.CRL_PLAYOUT_AVOID if agent == "avoid" else 0)
+        return out
+
+    def mcts_territory_action(self, simulations: int, seed: int = 0, exploration: float = 1.0, agent: str = "random",
+                              noise: float = 0.1, seat: Optional[torch.Tensor] = None, value_scale: int = 256,
+                              out: Optional[dict] = None) -> torch.Tensor:
+        """``mcts_territory``'s most visited action as an int64 [B] action for ``step_single`` (-1 where the seat is dead or
+        the game is over): the kernel's own ``best``, only widened here.  No host synchronisation; capturable."""
+        return self.mcts_territory(simulations, seed, exploration, agent, noise, seat, value_scale, out)["best"].to(torch.int64)
+
     # -- Voronoi territory of every game's position (the deterministic evaluator beside playout)
     def territory(self, candidates: Optional[torch.Tensor] = None, seat: Optional[torch.Tensor] = None,
                   out: Optional[dict] = None):

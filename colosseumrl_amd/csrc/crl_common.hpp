@@ -120,7 +120,7 @@ static inline unsigned crl_playout_blocks(const uint64_t n_lanes, const uint64_t
 // GPU AddressSanitizer is not available on this pool, so the data-dependent LDS / table accesses of the kernels carry
 // explicit range checks in a build of their own (tools/gpu_bounds.sh): a failing check does not fault, it counts itself
 // and keeps the first offender -- {failures, code, value, limit} per translation unit, read by crl_diag_bounds().  The
-// shipped build compiles none of it (the macros expand to nothing).  Codes: 1xx tron.hip (170..179: tron_mcts.hip, whose
+// shipped build compiles none of it (the macros expand to nothing).  Codes: 1xx tron.hip (170..189: tron_mcts.hip, whose
 // counters crl_diag_bounds folds into tron's four words), 2xx ttt.hip, 3xx blokus.hip.
 #ifdef CRL_BOUNDS
 namespace {

@@ -16,6 +16,9 @@
 //   [the playout bitboards: word w of slot k at w * (64 W) + k, slot = 64 wave + lane   (tron_playout_kernel's layout)]
 //   [per wave: n[S + 1] | w[S + 1] | child uint16 [S + 1][3], 0 = none | path uint16 [S + 1] | root[nwords] | work[nwords]]
 // 16 (S + 1) + 264 nwords bytes per wave, which is what bounds S (tron_mcts_max_simulations below).
+//
+// crl_tron_mcts_territory is the same search with one Voronoi flood of the leaf's position in the
+// place of the playouts: tron_mcts_territory_kernel below, without the playout bitboards (16 (S + 1) + 8 nwords bytes per wave).
 #include "crl_common.hpp"
 
 namespace {
@@ -366,6 +369,260 @@ tron_mcts_kernel(const int N, const int NN, const uint32_t inv_n, const int64_t 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ territory leaves
+// crl_tron_mcts_territory: the same tree, the same descent, and a leaf valued by ONE Voronoi flood of
+// its position instead of R playouts.  The flood is tron_territory.hip's register flood (terr_flood_rows there), restated
+// here from the contract of crl_tron_territory: lane y is board row y, the row one 32- or 64-bit word, vertical neighbours
+// by the two DPP wave shifts, frontiers and sums in registers, an empty ballot ends the loop.
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t tm_dpp(const uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);   // (no source lane: 0)
+}
+template <int CTRL>
+__device__ __forceinline__ uint64_t tm_dpp(const uint64_t v)
+{
+    return (uint64_t)tm_dpp<CTRL>((uint32_t)v) | ((uint64_t)tm_dpp<CTRL>((uint32_t)(v >> 32)) << 32);
+}
+constexpr int kTmDppWaveShl1 = 0x130;   // lane i reads lane i + 1
+constexpr int kTmDppWaveShr1 = 0x138;   // lane i reads lane i - 1
+
+__device__ __forceinline__ int tm_popc(const uint32_t v) { return __popc(v); }
+__device__ __forceinline__ int tm_popc(const uint64_t v) { return __popcll(v); }
+
+// 32 bits of the flat bitboard from bit `bit` on (any alignment): two dword reads and a funnel shift.  The second read is
+// clamped onto the board's last word; it is only used where the run reaches into it.
+__device__ __forceinline__ uint32_t tm_bits32(const uint32_t *bits, const int nwords, const int bit, const int code)
+{
+    const int i0 = bit >> 5, i1 = min(i0 + 1, nwords - 1);
+    CRL_BOUNDS_LT(i0, nwords, code);
+    CRL_BOUNDS_LT(i1, nwords, code + 1);
+    (void)code;
+    return (uint32_t)((((uint64_t)bits[i1] << 32) | (uint64_t)bits[i0]) >> (bit & 31));
+}
+
+// board row y (N <= 8 sizeof(W) cells from bit y * N on) of the flat bitboard, occupied cells set
+template <typename W>
+__device__ __forceinline__ W tm_row(const uint32_t *bits, const int nwords, const int N, const int y)
+{
+    const int bit = y * N;
+    W row = (W)tm_bits32(bits, nwords, bit, 180);
+    if constexpr (sizeof(W) == 8) row |= (W)tm_bits32(bits, nwords, bit + 32, 182) << 32;   // (N >= 33: bit + 32 < (y + 1) N <= N*N)
+    return row;
+}
+
+// The leaf's areas: crl_tron_territory's definition with nobody forced on the position (work bitboard, ps).  Every lane of
+// the wave runs this (the cross-lane reads need all 64); area[p] is the wave's total, alike in every lane.
+template <int P, typename W>
+__device__ __forceinline__ void tm_leaf_areas(const int N, const int NN, const int nwords, const int lane, const uint32_t *work_bits,
+                                              const TmPos<P> &ps, int (&area)[P])
+{
+    const bool in_row = lane < N;
+    const W rowmask = (W)(N >= (int)(8 * sizeof(W)) ? ~(W)0 : (((W)1 << N) - 1u));
+    W free = in_row ? (W)~tm_row<W>(work_bits, nwords, N, in_row ? lane : 0) & rowmask : (W)0;
+    W nw[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {                               // the first cells forward / right / left that lie in this row
+        W bits = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int dd = (ps.d[p] + (a == 0 ? 0 : a == 1 ? 1 : 3)) & 3;
+            const int nx = ps.x[p] + (dd == 1) - (dd == 3), ny = ps.y[p] + (dd == 2) - (dd == 0);
+            const bool on = ((ps.alive >> p) & 1u) && (unsigned)nx < (unsigned)N && ny == lane;   // (ny == lane < N: on the board)
+            bits |= on ? (W)1 << (nx & (int)(8 * sizeof(W) - 1)) : (W)0;
+        }
+        nw[p] = bits & free;
+    }
+    const W up_ok = (in_row && lane > 0) ? ~(W)0 : (W)0;         // takes from lane - 1: not the first row
+    const W dn_ok = lane < N - 1 ? ~(W)0 : (W)0;                 // takes from lane + 1: not the last row (nor lane N's zeros)
+    int mine[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) mine[p] = 0;
+    for (int lvl = 0; lvl <= NN; ++lvl) {                        // (hard bound: a level with a new bit claims a cell)
+        W once = 0, twice = 0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) { twice |= once & nw[p]; once |= nw[p]; }
+#pragma unroll
+        for (int p = 0; p < P; ++p) mine[p] += tm_popc((W)(nw[p] & ~twice));
+        free &= ~once;
+        if (__ballot(once != 0) == 0ull) break;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const W f = nw[p];
+            nw[p] = ((W)(f << 1) | (W)(f >> 1) | (tm_dpp<kTmDppWaveShr1>(f) & up_ok) | (tm_dpp<kTmDppWaveShl1>(f) & dn_ok)) & free;
+        }
+    }
+    // the sums over the wave, two 16-bit sums per shuffled word (an area is at most 64 * 64), a butterfly: every lane ends
+    // with the totals
+    constexpr int H = (P + 1) / 2;
+    uint32_t v[H];
+#pragma unroll
+    for (int j = 0; j < H; ++j) v[j] = 0u;
+#pragma unroll
+    for (int p = 0; p < P; ++p) v[p >> 1] |= (uint32_t)mine[p] << ((p & 1) * 16);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+#pragma unroll
+        for (int j = 0; j < H; ++j) v[j] += (uint32_t)__shfl_xor((int)v[j], off);
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) area[p] = __builtin_amdgcn_readfirstlane((int)((v[p >> 1] >> ((p & 1) * 16)) & 0xffffu));
+}
+
+template <int P, bool AVOID, typename W>
+__global__ void __launch_bounds__(256)
+tron_mcts_territory_kernel(const int N, const int NN, const uint32_t inv_n, const int64_t B, const uint32_t seed_lo,
+                           const uint32_t seed_hi, const uint64_t first_env_id, const int8_t *__restrict__ board,
+                           const int16_t *__restrict__ heads, const int8_t *__restrict__ dirs, const int8_t *__restrict__ deaths,
+                           const uint32_t *__restrict__ tcount, const int8_t *__restrict__ seat_in, const int S, const int V,
+                           const uint32_t cexp, const uint64_t thr, const int nwords, const uint32_t wave_words,
+                           uint32_t *__restrict__ visits, uint32_t *__restrict__ value, uint32_t *__restrict__ nodes,
+                           int32_t *__restrict__ best)
+{
+    // per wave: n[S + 1] | w[S + 1] | child uint16 [S + 1][3] | path uint16 [S + 1] | root[nwords] | work[nwords]
+    extern __shared__ __attribute__((aligned(16))) uint32_t tm_lds[];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), n_waves = (int)(blockDim.x >> 6);
+    uint32_t *n_arr = tm_lds + (uint32_t)wave * wave_words, *w_arr = n_arr + (S + 1);
+    uint16_t *child = reinterpret_cast<uint16_t *>(w_arr + (S + 1)), *path = child + 3 * (S + 1);
+    uint32_t *root_bits = w_arr + 3 * (S + 1), *work_bits = root_bits + nwords;
+    const TmBoard work = {work_bits, 1, 0, nwords};
+    constexpr uint32_t kTreeStep = 0xFFFF0000u;                 // the third counter word of the tree steps' draws
+
+    for (int64_t b = (int64_t)blockIdx.x * n_waves + wave; b < B; b += (int64_t)gridDim.x * n_waves) {
+        // ---- the root position, alike in every lane
+        const int sp = seat_in ? __builtin_amdgcn_readfirstlane((int)seat_in[b]) : 0;
+        TmPos<P> p0;
+        p0.alive = 0u;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            p0.h[p] = min(max(__builtin_amdgcn_readfirstlane((int)heads[p * B + b]), 0), NN - 1);   // (a broken state: wrong results, no wild access)
+            p0.y[p] = (int)__umulhi((uint32_t)p0.h[p], inv_n);
+            p0.x[p] = p0.h[p] - p0.y[p] * N;
+            p0.d[p] = __builtin_amdgcn_readfirstlane((int)dirs[p * B + b]) & 3;
+            p0.alive |= (__builtin_amdgcn_readfirstlane((int)deaths[p * B + b]) == 0 ? 1u : 0u) << p;
+        }
+        const uint32_t tc = tcount ? (uint32_t)__builtin_amdgcn_readfirstlane((int)tcount[b]) : 0u;
+        const uint32_t gid = (uint32_t)(first_env_id + (uint64_t)b);
+        if (!((unsigned)sp < (unsigned)P && ((p0.alive >> (sp & 7)) & 1u) && (P == 1 || __popc(p0.alive) >= 2))) {   // skipped: zeros
+            if (lane < 3) { visits[b * 3 + lane] = 0u; value[b * 3 + lane] = 0u; }
+            if (lane == 0) { nodes[b] = 0u; best[b] = -1; }
+            continue;
+        }
+        // ---- the root bitboard, lanes over words; the root node
+        for (int w = lane; w < nwords; w += 64) root_bits[w] = tm_occ_run(board + b * NN + 32 * w, min(32, NN - 32 * w));
+        if (lane == 0) { n_arr[0] = 0u; w_arr[0] = 0u; path[0] = 0; }
+        if (lane < 3) child[lane] = 0;
+        tm_wave_sync();
+        int nn = 1;                                              // nodes so far
+        for (int s = 0; s < S; ++s) {
+            for (int w = lane; w < nwords; w += 64) work_bits[w] = root_bits[w];
+            tm_wave_sync();
+            TmPos<P> ps = p0;
+            int v = 0, d = 0;
+            bool closed, seat_alive;
+            for (;;) {
+                CRL_BOUNDS_LT(v, S + 1, 184);
+                const uint32_t cu = lane < 3 ? child[v * 3 + lane] : 0u;
+                CRL_BOUNDS_LT(cu, S + 1, 185);
+                const unsigned long long fresh = __ballot(lane < 3 && cu == 0u);
+                int e, u;
+                if (fresh) {                                     // expand: the lowest action without a child
+                    e = (int)__builtin_ctzll(fresh);
+                    u = nn++;
+                    CRL_BOUNDS_LT(u, S + 1, 186);
+                    if (lane == 0) { child[v * 3 + e] = (uint16_t)u; n_arr[u] = 0u; w_arr[u] = 0u; }
+                    if (lane < 3) child[u * 3 + lane] = 0;
+                } else {                                         // select: lane a scores the child at action a
+                    const uint32_t lgv = tm_lg(n_arr[v]);
+                    uint32_t key = 0;
+                    if (lane < 3) {
+                        const uint32_t nu = n_arr[cu], wu = w_arr[cu];
+                        const uint64_t exploit = tm_div((uint64_t)wu << 15, nu * (uint32_t)V);
+                        const uint64_t X = tm_div((uint64_t)lgv << 24, nu);
+                        const uint64_t score = exploit + (((uint64_t)cexp * tm_isqrt(X)) >> 8);   // < 2^26
+                        key = (((uint32_t)score << 2) | (uint32_t)(3 - lane)) + 1u;               // ties: the lowest action
+                    }
+                    // the arg-max over the three lanes (every lane runs the reads: they sit outside the branch above)
+                    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, 0), k1 = (uint32_t)__builtin_amdgcn_readlane((int)key, 1),
+                                   k2 = (uint32_t)__builtin_amdgcn_readlane((int)key, 2);
+                    const uint32_t top = max(k0, max(k1, k2));
+                    e = 3 - (int)((top - 1u) & 3u);
+                    const int c0 = __builtin_amdgcn_readlane((int)cu, 0), c1 = __builtin_amdgcn_readlane((int)cu, 1),
+                              c2 = __builtin_amdgcn_readlane((int)cu, 2);
+                    u = e == 0 ? c0 : e == 1 ? c1 : c2;
+                }
+                d += 1;
+                CRL_BOUNDS_LT(d, S + 1, 187);
+                if (lane == 0) path[d] = (uint16_t)u;
+                // ---- the tree step at depth d - 1: the seat plays e, the others the model agent on the pre-step position
+                int code[P];
+                const uint32_t c = tc + (uint32_t)(d - 1);
+                if constexpr (AVOID) {
+                    tm_avoid_codes<P>(N, work, ps, gid, c, kTreeStep, seed_lo, seed_hi, thr, code);
+                } else {
+                    TmDraw dr = {};
+                    tm_random_refill<P>(gid, c, kTreeStep, seed_lo, seed_hi, dr);
+                    tm_random_codes<P>(c, dr, code);
+                }
+#pragma unroll
+                for (int p = 0; p < P; ++p) code[p] = (p == sp) ? e + (e >> 1) : code[p];
+                tm_step<P>(N, work, ps, code);
+                seat_alive = (ps.alive >> sp) & 1u;
+                closed = !seat_alive || __popc(ps.alive) <= 1;
+                if (fresh || closed || d >= S) break;            // (d >= S: never, a path of d edges has d nodes below the root)
+                v = u;
+            }
+            // ---- evaluate the leaf: its outcome when it is closed, else one flood of its position (no draw)
+            uint32_t sum = seat_alive ? 2u * (uint32_t)V : 0u;   // half-points on the scale of V (wave-uniform)
+            if (__builtin_amdgcn_readfirstlane((int)closed) == 0) {     // (alike in every lane: all 64 run the flood)
+                tm_wave_sync();
+                int area[P];
+                tm_leaf_areas<P, W>(N, NN, nwords, lane, work_bits, ps, area);
+                uint32_t a_s = 0u, a_o = 0u;
+#pragma unroll
+                for (int p = 0; p < P; ++p) {                    // (dead players hold 0)
+                    a_s = p == sp ? (uint32_t)area[p] : a_s;
+                    a_o = p == sp ? a_o : max(a_o, (uint32_t)area[p]);
+                }
+                const uint32_t den = a_s + a_o;
+                sum = den == 0u ? (uint32_t)V : (uint32_t)tm_div((uint64_t)(2u * (uint32_t)V * a_s), den);
+            }
+            // ---- back up: lane i adds to the node at depth i (distinct nodes: no atomics), 64 entries per pass
+            tm_wave_sync();
+            for (int i0 = 0; i0 <= d; i0 += 64) {
+                const int i = i0 + lane;
+                if (i <= d) {
+                    const uint32_t node = path[i];
+                    CRL_BOUNDS_LT(node, S + 1, 188);
+                    n_arr[node] += 1u;
+                    if (i > 0) w_arr[node] += sum;
+                }
+            }
+            tm_wave_sync();
+        }
+        // ---- the root's children: visits, value, the most visited (then the larger w, then the lower action)
+        const uint32_t cu = lane < 3 ? child[lane] : 0u;
+        CRL_BOUNDS_LT(cu, S + 1, 189);
+        const uint32_t vis = cu ? n_arr[cu] : 0u, val = cu ? w_arr[cu] : 0u;
+        if (lane < 3) { visits[b * 3 + lane] = vis; value[b * 3 + lane] = val; }
+        int pick = -1;
+        uint32_t pick_n = 0u, pick_w = 0u;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {                            // (every lane runs the reads)
+            const uint32_t ca = (uint32_t)__builtin_amdgcn_readlane((int)cu, a), na = (uint32_t)__builtin_amdgcn_readlane((int)vis, a),
+                           wa = (uint32_t)__builtin_amdgcn_readlane((int)val, a);
+            const bool better = ca != 0u && (pick < 0 || na > pick_n || (na == pick_n && wa > pick_w));
+            pick = better ? a : pick;
+            pick_n = better ? na : pick_n;
+            pick_w = better ? wa : pick_w;
+        }
+        if (lane == 0) { nodes[b] = (uint32_t)nn; best[b] = pick; }
+        tm_wave_sync();                                          // the next tree starts behind these reads
+    }
+}
+
 // S_max of crl_tron_mcts (include/colosseum_hip.h): the tree, the path and the 66 bitboards of one wave within 64 KB, and
 // s < 4095 (its counter word); below 1 on boards of 90x90 and more
 constexpr uint32_t kTmLds = 65536u;
@@ -437,6 +694,52 @@ int crl_tron_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_e
         TRON_DISPATCH_P(cfg.P, TRON_MCTS_LAUNCH(false));
     }
 #undef TRON_MCTS_LAUNCH
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_tron_mcts_territory(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                            const int8_t *board, const int16_t *heads, const int8_t *dirs, const int8_t *deaths,
+                            const uint32_t *tcount, const int8_t *seat, int S, int V, uint32_t cexp, double noise,
+                            uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best, uint32_t flags, void *stream)
+{
+    TRON_CTX_CHECK("crl_tron_mcts_territory");
+    CRL_REQUIRE(board && heads && dirs && deaths, "crl_tron_mcts_territory: NULL state pointer");
+    CRL_REQUIRE(visits && value && nodes && best, "crl_tron_mcts_territory: NULL output pointer");
+    const crl_tron_cfg &cfg = ctx->tron;
+    if (cfg.N > 64) {                                            // the flood is one lane per board row
+        crl_set_error("crl_tron_mcts_territory: a %dx%d board is wider than 64, the widest the in-wave flood takes", cfg.N, cfg.N);
+        return CRL_EUNSUPPORTED;
+    }
+    const int s_max = tron_mcts_max_simulations(cfg.N);         // crl_tron_mcts's, so that the two searches' trees compare
+    CRL_REQUIRE(S >= 1 && S <= s_max, "crl_tron_mcts_territory: S=%d out of range 1..%d (a %dx%d board)", S, s_max, cfg.N, cfg.N);
+    CRL_REQUIRE(V >= 1 && V <= 1024, "crl_tron_mcts_territory: V=%d out of range 1..1024", V);
+    CRL_REQUIRE(cexp <= 65535u, "crl_tron_mcts_territory: cexp=%u out of range 0..65535", cexp);
+    CRL_REQUIRE(noise >= 0.0 && noise <= 1.0, "crl_tron_mcts_territory: noise=%g not in [0, 1]", noise);
+    CRL_REQUIRE((flags & ~CRL_PLAYOUT_AVOID) == 0u, "crl_tron_mcts_territory: unknown flags 0x%x", flags);
+    // one to four waves per workgroup, as many as fit in 64 KB (four up to S = 959 on 64x64, more on smaller boards); a
+    // grid-stride loop past 2^20 workgroups
+    const int NN = cfg.N * cfg.N, nwords = (NN + 31) >> 5;
+    const uint32_t wave_bytes = 16u * (uint32_t)(S + 1) + 8u * (uint32_t)nwords;
+    uint32_t waves = kTmLds / wave_bytes;
+    waves = waves > 4u ? 4u : waves;
+    waves = (int64_t)waves > B ? (uint32_t)B : waves;
+    const uint64_t want = ((uint64_t)B + waves - 1u) / waves;
+    const unsigned blocks = (unsigned)(want < (1u << 20) ? want : (1u << 20));
+    const uint32_t wave_words = 4u * (uint32_t)(S + 1) + 2u * (uint32_t)nwords;
+    const uint32_t inv_n = (uint32_t)(0x100000000ull / (uint32_t)cfg.N) + 1u;   // y = umulhi(h, inv_n) is exact for h < N*N <= 2^15
+    const uint64_t thr = crl_noise_threshold(noise);
+    hipStream_t st = (hipStream_t)stream;
+#define TRON_MCTS_TERR_LAUNCH(AV_, W_)                                                                                      \
+    hipLaunchKernelGGL((tron_mcts_territory_kernel<PP, AV_, W_>), dim3(blocks), dim3(64u * waves), (size_t)waves * wave_bytes, st, \
+                       cfg.N, NN, inv_n, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, board, heads, dirs, deaths,   \
+                       tcount, seat, S, V, cexp, thr, nwords, wave_words, visits, value, nodes, best)
+    if (flags & CRL_PLAYOUT_AVOID) {
+        TRON_DISPATCH_P(cfg.P, { if (cfg.N <= 32) TRON_MCTS_TERR_LAUNCH(true, uint32_t); else TRON_MCTS_TERR_LAUNCH(true, uint64_t); });
+    } else {
+        TRON_DISPATCH_P(cfg.P, { if (cfg.N <= 32) TRON_MCTS_TERR_LAUNCH(false, uint32_t); else TRON_MCTS_TERR_LAUNCH(false, uint64_t); });
+    }
+#undef TRON_MCTS_TERR_LAUNCH
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }

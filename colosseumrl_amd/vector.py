@@ -114,6 +114,15 @@ class TronSinglePlayerVectorEnv:
         policy target)."""
         return self.batch.mcts_action(simulations, playouts, seed, exploration, "avoid", self.noise, None, max_steps, out)
 
+    def mcts_territory_action(self, simulations: int, seed: int = 1, exploration: float = 1.0,
+                              out: Optional[dict] = None) -> torch.Tensor:
+        """``mcts_action`` with Voronoi territory at the leaves (``TronBatch.mcts_territory_action``; boards up to 64x64):
+        seat 0, the other players modelled by the avoid agent with the env's noise -- whatever the env's opponent --, a leaf
+        valued by one flood of its position, no playouts.  ``seed`` keys the model's draws.  -> int64 [B] in {0, 1, 2} for
+        ``step``, one launch, no host synchronisation, capturable.  ``out``: the ``TronBatch.mcts_territory`` dict to
+        reuse."""
+        return self.batch.mcts_territory_action(simulations, seed, exploration, "avoid", self.noise, None, 256, out)
+
 
 class TicTacToeVectorEnv:
     """B turn-based TicTacToe games.  ``step`` takes int8 cell indices [B] for the player to move (-1 = pass)."""

@@ -90,7 +90,8 @@ const char *crl_last_error(void);
  *      _playout_tactical (the win-or-block agent of TicTacToe: five new entries, two new Philox tags), and
  *      crl_ttt_mcts / crl_ttt_mcts_max_simulations (batched tree search: two new entries, one new Philox tag), and
  *      crl_ttt_sample_mcts / _rollout_mcts / _step_single_mcts (the search as a seated agent: three new entries, no new tag), and
- *      crl_tron_mcts / crl_tron_mcts_max_simulations (batched tree search for one seat of Tron: two new entries, no new tag). */
+ *      crl_tron_mcts / crl_tron_mcts_max_simulations (batched tree search for one seat of Tron: two new entries, no new tag), and
+ *      crl_tron_mcts_territory (that search with Voronoi territory at the leaves: one new entry, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -410,6 +411,47 @@ int crl_tron_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_e
                   int S, int R, uint32_t cexp, double noise, int max_steps,
                   uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best,
                   uint32_t flags, void *stream);
+/* crl_tron_mcts_territory: crl_tron_mcts with Voronoi territory as the leaf evaluator -- a leaf is valued by ONE flood of its
+ * position, there are no playouts, and nothing is drawn at a leaf.  One launch, no host sync.  Added under revision 113: one
+ * new entry, no new Philox tag, no existing struct, argument list or RNG contract changed.
+ * Unchanged from crl_tron_mcts, word for word: the state layouts and the read-only state; g; the NULL rules of tcount and
+ * seat; nodes and child slots; the tree step at depth k (the seat plays e, every other live player the model agent -- the
+ * random agent, or with CRL_PLAYOUT_AVOID the avoid agent with `noise` -- from the two playout tags under the third counter
+ * word 0xFFFF0000 at counter tcount[b] + k); the CLOSED rule; expand / select with ties to the lowest action; the integer
+ * score with its lg, floor divisions and exact isqrt; backup; the four outputs and best's tie rule; the skipped-position rule
+ * (zeros, nodes 0, best -1).
+ * The differences.  V in [1, 1024] is the value scale and stands wherever R stands in crl_tron_mcts:
+ *   exploit = (w_u << 15) / (n_u * V),
+ * and a closed leaf is worth 2 V half-points iff the seat is alive, else 0.  There is no R, no max_steps and no draw at a
+ * leaf.  An OPEN leaf L is valued by one Voronoi flood of its position:
+ *   occupancy   the root's (a cell is occupied iff its board value is > 0, crl_tron_mcts's rule) plus every cell the tree
+ *               steps on the path moved a head onto; a cell is FREE iff it is not occupied in that sense;
+ *   players     LIVE, heads and directions are L's;
+ *   area[p]     crl_tron_territory's definition (below) on that position with nobody forced (its cand == NULL case): the
+ *               first cells forward / right / left that are on the board and free, d_p, strict first arrival, ties belong
+ *               to nobody, dead players get 0;
+ *   a_s = area[seat], a_o = the maximum of area[q] over the other live players q (0 if there is none);
+ *   half-points = (a_s + a_o == 0) ? V : floor(2 * V * a_s / (a_s + a_o)),  an integer in [0, 2 V].
+ * An even split gives V, a seat with no territory 0, P = 1 with room 2 V.  Nothing overflows: 2 * 1024 * 4096 < 2^32, and a
+ * node's w stays below 2^32 with n <= 4095.
+ * Flags.  CRL_PLAYOUT_AVOID only; it selects the model agent of the tree steps.  noise is checked always and used only then.
+ * Limits (CRL_EINVAL, with a crl_last_error message naming the argument, before any device work): NULL state or output
+ * pointers, B out of range (as crl_tron_mcts), S outside [1, S_max], V outside [1, 1024], cexp > 65535, noise outside [0, 1]
+ * or NaN, flags other than CRL_PLAYOUT_AVOID, a context that is not a Tron context.  S_max is crl_tron_mcts's
+ * (crl_tron_mcts_max_simulations), unchanged, so that trees of the two searches compare at any S -- although a wave here needs
+ * only 16 (S + 1) + 8 ceil(N*N / 32) bytes of LDS (the tree, the path, the root and the working bitboard; no playout slabs).
+ * Boards wider than 64 answer CRL_EUNSUPPORTED: the flood runs inside the wave with one lane per board row.  Widths 65..89,
+ * which crl_tron_mcts takes, are deliberately left out.
+ * One wave per tree in crl_tron_mcts's mapping, one to four waves per workgroup (as many as fit 64 KB: four up to S = 1,017
+ * on 19x19, 998 on 40x40, 959 on 64x64).  At an open leaf lane y < N is board row y: it cuts its row out of the working bitboard, builds the live
+ * players' first cells in it, and the wave floods as the register kernels of crl_tron_territory do (32-bit rows up to
+ * N = 32, 64-bit rows above). */
+int crl_tron_mcts_territory(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                            const int8_t *board, const int16_t *heads, const int8_t *dirs, const int8_t *deaths,
+                            const uint32_t *tcount, const int8_t *seat,
+                            int S, int V, uint32_t cexp, double noise,
+                            uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best,
+                            uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ Voronoi territory (Tron)
  * crl_tron_territory: for each of B positions and A forced first actions of a seat, the number of free cells every player

@@ -118,9 +118,15 @@ def test_territory_hand_boards():
 
 
 # ---- the agent
-@pytest.mark.parametrize("N,P,B", [(15, 4, 300), (19, 4, 130), (13, 3, 77), (20, 2, 65), (40, 4, 21), (33, 6, 10), (5, 2, 500),
-                                   (64, 8, 4), (70, 3, 3)] + [(65, P, 2) for P in range(1, 9)]
-                                  + [(100, 5, 2), (181, 1, 2), (181, 8, 2)])
+# (the third and fourth row: the remaining tron_sample_territory_rows_kernel<P, W> instances, so that both row words see
+# P = 1 .. 8; tests/test_tron_instances_host.py keeps the list whole)
+SAMPLE_SHAPES = ([(15, 4, 300), (19, 4, 130), (13, 3, 77), (20, 2, 65), (40, 4, 21), (33, 6, 10), (5, 2, 500), (64, 8, 4), (70, 3, 3)]
+                 + [(65, P, 2) for P in range(1, 9)] + [(100, 5, 2), (181, 1, 2), (181, 8, 2)]
+                 + [(9, 1, 10), (10, 5, 10), (11, 6, 10), (12, 7, 10), (16, 8, 10)]
+                 + [(34, 1, 10), (35, 2, 10), (36, 3, 10), (37, 5, 10), (38, 7, 10)])
+
+
+@pytest.mark.parametrize("N,P,B", SAMPLE_SHAPES)
 @pytest.mark.parametrize("noise", [0.0, 0.1, 1.0])
 def test_sample_territory_matches_restatement(N, P, B, noise):
     seed, first = 0xC0FFEE + N, 5

@@ -3,7 +3,8 @@ against the plain-Python restatement of the header's contract (tests/tron_mcts_r
 avoid-agent games at several fill levels with dead seats, finished games and seats out of range among them, a seat per game,
 counters that are odd, even and about to wrap, a game id base past 2^32, every board family and player count, both agents,
 the noise levels, walled-up positions whose whole tree is reached, the largest trees, every launch geometry, R across one
-and several passes, the caps -- and the strength of the search learner next to the avoid learner and flat Monte Carlo."""
+and several passes, the caps, hand-made positions at the step rule's sharp corners (a hit on a head with the seat moving first
+and second, a bystander, a board corner) -- and the strength of the search learner next to the avoid learner and flat Monte Carlo."""
 import functools
 
 import numpy as np
@@ -11,11 +12,13 @@ import pytest
 import torch
 
 from tests import tron_mcts_ref as M
+from tests import tron_mcts_territory_ref as T              # (the hand-made boards)
 from tests.gpu_util import DEV, first_episodes, np_of as _np, tron_put
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(5, 2), (7, 3), (13, 4), (19, 4), (20, 4), (33, 2), (40, 4), (64, 8), (9, 1)]
+# (the last three: the tron_mcts_kernel<P, AVOID> instances P = 5, 6, 7; tests/test_tron_instances_host.py keeps the list whole)
+SHAPES = [(5, 2), (7, 3), (13, 4), (19, 4), (20, 4), (33, 2), (40, 4), (64, 8), (9, 1), (9, 5), (11, 6), (12, 7)]
 shapes = pytest.mark.parametrize("N,P", SHAPES, ids=["%dx%dp%d" % (n, n, p) for n, p in SHAPES])
 agents = pytest.mark.parametrize("agent", ["random", "avoid"])
 FIRST_ENV_ID = (1 << 32) + 77
@@ -96,6 +99,7 @@ def test_batch_of_130(agent):
     tb, got = _check(st, seat, 8, 4, agent=agent, count=count)
     nodes = _np(got["nodes"])
     assert (nodes == 0).sum() >= 4 and (nodes > 1).sum() >= 100 and count["closed"] > 0 and count["playouts"] > 0
+    assert count["head_on"] > 0                                  # (random positions meet hits on a head too)
 
 
 def test_one_position():
@@ -195,6 +199,38 @@ def test_capped_playouts(max_steps, agent):
     st, seat = _positions(13, 4, 10)
     tb, got = _check(st, seat, 12, 4, agent=agent, max_steps=max_steps)
     assert (_np(got["value"]) % 2 == 1).any()                    # (a sum with an odd number of half-point-1 playouts)
+
+
+# ------------------------------------------------------------------ 10b. hand-made positions: the step rule's sharp corners
+@pytest.mark.parametrize("S", [3, 64])
+def test_hand_made_positions(S):
+    """Values a reader can work out on paper (avoid model, noise 0, R = 4); the boards are drawn in
+    tests/tron_mcts_territory_ref.py, the derivation stands in tests/test_tron_mcts_host.py::test_step_rule_corners_by_hand.
+
+    Head-on, with the seat moving first (seat 0) and second (seat 1): the two heads are one free cell apart and the model
+    player steps onto it, so the seat's forward move is a hit on a head that kills both -- the forward child is closed and
+    worth 0 at every visit; a turn leaves the model player in a dead end, which the seat outlives: 2 per playout, so S = 3
+    gives [0, 2R, 2R].  The bystander (seat 2): the other two kill each other in every first tree step and the seat is alone
+    alive whatever it plays -- three closed, won children, 2R a visit, never a fourth node.  The corner: forward and left
+    leave the board, to the right the seat outlives the other player's shorter row: [0, 2R, 0] at S = 3."""
+    Rn = 4
+    for seat in (0, 1):
+        count = M.new_count()
+        tb, got = _check(T.head_on_state(), np.array([seat], np.int8), S, Rn, agent="avoid", noise=0.0, count=count)
+        assert count["head_on"] == 1                              # (the one expansion of the forward child)
+        value, visits = _np(got["value"])[0].tolist(), _np(got["visits"])[0].tolist()
+        assert value[0] == 0 and _np(got["best"])[0] != 0 and visits[0] >= 1 and sum(visits) == S
+        if S == 3:
+            assert value == [0, 2 * Rn, 2 * Rn] and _np(got["best"]).tolist() == [1]
+    count = M.new_count()
+    tb, got = _check(T.head_on_state(3), np.array([2], np.int8), S, Rn, agent="avoid", noise=0.0, count=count)
+    assert count["head_on"] == 3 and count["playouts"] == 0 and count["closed"] == S
+    assert _np(got["nodes"]).tolist() == [4] and (_np(got["visits"]) >= 1).all()
+    assert np.array_equal(_np(got["value"]), 2 * Rn * _np(got["visits"]))
+    tb, got = _check(T.corner_state(), None, S, Rn, agent="avoid", noise=0.0)
+    value = _np(got["value"])[0].tolist()
+    assert value[0] == 0 and value[2] == 0 and _np(got["best"]).tolist() == [1]
+    assert S != 3 or value == [0, 2 * Rn, 0]
 
 
 # ------------------------------------------------------------------ 11. the wrappers

@@ -23,7 +23,10 @@ from tests.gpu_util import DEV, first_episodes, np_of as _np, tron_put
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHAPES = [(5, 2), (7, 3), (9, 1), (9, 3), (13, 4), (19, 4), (31, 3), (32, 2), (33, 2), (40, 4), (63, 5), (64, 8)]
+# (the second row: the remaining tron_mcts_territory_kernel<P, AVOID, W> instances, 32-bit rows with P = 5 .. 8 and 64-bit rows
+# with P = 1, 3, 6, 7; tests/test_tron_instances_host.py keeps the list whole)
+SHAPES = [(5, 2), (7, 3), (9, 1), (9, 3), (13, 4), (19, 4), (31, 3), (32, 2), (33, 2), (40, 4), (63, 5), (64, 8),
+          (10, 5), (11, 6), (12, 7), (16, 8), (34, 1), (35, 3), (36, 6), (37, 7)]
 shapes = pytest.mark.parametrize("N,P", SHAPES, ids=["%dx%dp%d" % (n, n, p) for n, p in SHAPES])
 agents = pytest.mark.parametrize("agent", ["random", "avoid"])
 FIRST_ENV_ID = (1 << 32) + 77
@@ -118,6 +121,7 @@ def test_batch_of_130(agent):
     count = T.new_count()
     tb, got = _check(st, seat, 8, agent=agent, count=count)
     assert count["skipped"] == 4 == (_np(got["nodes"]) == 0).sum() and count["closed"] > 0 and count["flooded"] > 500
+    assert count["head_on"] > 0                                  # (random positions meet hits on a head too)
 
 
 def test_one_position():
@@ -207,6 +211,33 @@ def test_hand_made_positions():
     tb, got = _check(T.pocket_state(), None, 64, cexp=64, agent="avoid", noise=0.0)
     assert _np(got["best"]).tolist() == [1]
     assert tb.territory_action().tolist() == [0]                 # the one-ply territory-greedy action enters the fork
+
+
+@pytest.mark.parametrize("S", [3, 64])
+def test_hand_made_step_rule_corners(S):
+    """The step rule's sharp corners with a flood at the leaves (avoid model, noise 0, V = 256); the derivation stands in
+    tests/test_tron_mcts_territory_host.py::test_step_rule_corners_by_hand.  Head-on with the seat moving first (seat 0) and
+    second (seat 1): forward is a hit on a head that kills both, closed and worth 0 at every visit; after a turn the seat has
+    two cells and the model player, in its dead end, none: floor(2 V 2 / 2) = 512.  The bystander (seat 2): three closed, won
+    children, 2 V a visit, never a fourth node and never a flood.  The corner: forward and left leave the board, to the right
+    five cells against two: floor(512 * 5 / 7) = 365."""
+    for seat in (0, 1):
+        count = T.new_count()
+        tb, got = _check(T.head_on_state(), np.array([seat], np.int8), S, agent="avoid", noise=0.0, count=count)
+        value, visits = _np(got["value"])[0].tolist(), _np(got["visits"])[0].tolist()
+        assert value[0] == 0 and _np(got["best"])[0] != 0 and visits[0] >= 1 and sum(visits) == S and count["closed"] >= visits[0]
+        assert count["head_on"] == 1                              # (the one expansion of the forward child)
+        if S == 3:
+            assert value == [0, 512, 512] and _np(got["best"]).tolist() == [1] and count["flooded"] == 2
+    count = T.new_count()
+    tb, got = _check(T.head_on_state(3), np.array([2], np.int8), S, agent="avoid", noise=0.0, count=count)
+    assert _np(got["nodes"]).tolist() == [4] and (_np(got["visits"]) >= 1).all() and count["closed"] == S and count["flooded"] == 0
+    assert count["head_on"] == 3
+    assert np.array_equal(_np(got["value"]), 512 * _np(got["visits"]))
+    tb, got = _check(T.corner_state(), None, S, agent="avoid", noise=0.0)
+    value = _np(got["value"])[0].tolist()
+    assert value[0] == 0 and value[2] == 0 and _np(got["best"]).tolist() == [1]
+    assert S != 3 or value == [0, 365, 0]
 
 
 # ------------------------------------------------------------------ 9. the wrappers

@@ -7,6 +7,7 @@ import pytest
 
 from tests import rng_ref as RNG
 from tests import tron_mcts_ref as M
+from tests import tron_mcts_territory_ref as T
 from tests import tron_ref as TR
 from tests.host_util import D, fake as _fake, lib as _lib, tron_context, ttt_context
 
@@ -255,6 +256,43 @@ def test_search_avoids_the_pocket():
         v, w, n, best = M.tron_mcts(st, S, 8, agent="avoid", noise=0.0, seed=S)
         assert best[0] == 1 and v[0, 1] > v[0, 0] >= 1 and v[0, 2] >= 1
         assert w[0, 0] == 0 and w[0, 2] == 0 and w[0, 1] > 0 and n[0] > 4 and v[0].sum() == S
+
+
+@pytest.mark.parametrize("S", [3, 64])
+def test_step_rule_corners_by_hand(S):
+    """The step rule's sharp corners on positions whose values can be worked out on paper (avoid model, noise 0, R = 4;
+    tests/tron_mcts_territory_ref.py draws the boards).
+
+    Head-on: player 0 at (1, 3) heading east, player 1 at (3, 3) heading west, the one free cell (2, 3) between them.  The
+    model player steps forward (its cell ahead is free).  If the seat steps forward too, the lower player takes (2, 3) and the
+    higher one runs into that head: the mover dies and, the cell being the other's head, so does its owner -- whichever of
+    the two the seat is, it is dead: the forward child is closed and worth 0 at every visit.  If the seat turns into its own
+    column, the model player stands in (2, 3) with the seat's trail ahead and walls on both sides and dies on the next step,
+    the seat (forward along its column) survives it alone: each of the R playouts is worth 2.  So S = 3 gives [0, 2R, 2R].
+
+    The bystander: players 0 and 1 kill each other in every first tree step, seat 2 moves onto a free cell whichever way it
+    turns and is alone alive: three closed, won children and never a fourth node.
+
+    The corner: the seat at (0, 0) heading north; forward and left leave the board (closed, 0).  To the right it has five
+    more cells of the top row, the other player two more of its three: on the third playout step the other player dies, the
+    seat wins: 2R."""
+    Rn = 4
+    seats = lambda s: np.array([s], np.int8)
+    for seat in (0, 1):                                       # the seat moves first, the seat moves second
+        count = M.new_count()
+        v, w, n, best = M.tron_mcts(T.head_on_state(), S, Rn, seat=seats(seat), agent="avoid", noise=0.0, count=count)
+        assert w[0, 0] == 0 and best[0] != 0 and v[0].sum() == S and v[0, 0] >= 1
+        assert count["head_on"] == 1 and count["closed"] >= v[0, 0]     # (one hit on a head: the expansion of the forward child)
+        if S == 3:
+            assert w.tolist() == [[0, 2 * Rn, 2 * Rn]] and n.tolist() == [4] and best.tolist() == [1]
+    count = M.new_count()
+    v, w, n, best = M.tron_mcts(T.head_on_state(3), S, Rn, seat=seats(2), agent="avoid", noise=0.0, count=count)
+    assert n.tolist() == [4] and (w == 2 * Rn * v).all() and v[0].sum() == S and (v >= 1).all()
+    assert count["head_on"] == 3 and count["playouts"] == 0 and count["closed"] == S
+    v, w, n, best = M.tron_mcts(T.corner_state(), S, Rn, agent="avoid", noise=0.0)
+    assert w[0, 0] == 0 and w[0, 2] == 0 and best.tolist() == [1] and v[0].sum() == S
+    if S == 3:
+        assert w.tolist() == [[0, 2 * Rn, 0]]
 
 
 def test_skipped_positions():

@@ -233,6 +233,32 @@ def test_search_leaves_the_pocket_alone():
     assert best3[0] == 0 and w3.tolist() == [[(512 * 10) // 16, (512 * 8) // 14, 0]]     # one ply deep it agrees with greedy
 
 
+@pytest.mark.parametrize("S", [3, 64])
+def test_step_rule_corners_by_hand(S):
+    """The positions of tests/test_tron_mcts_host.py::test_step_rule_corners_by_hand with a flood at the leaves (avoid model,
+    noise 0, V = 256).  Head-on, the seat first or second: forward is closed and lost.  After a turn into its own column the
+    seat has the two cells left of that half-column, the model player in the dead end (2, 3) has none: floor(2 V 2 / 2) = 2 V,
+    so S = 3 gives [0, 512, 512].  The bystander: three closed, won children, 2 V a visit.  The corner: forward and left
+    leave the board; to the right the seat keeps five cells of its row against the other player's two: floor(512 * 5 / 7) =
+    365."""
+    seats = lambda s: np.array([s], np.int8)
+    for seat in (0, 1):
+        count = T.new_count()
+        v, w, n, best = T.tron_mcts_territory(T.head_on_state(), S, seat=seats(seat), agent="avoid", noise=0.0, count=count)
+        assert w[0, 0] == 0 and best[0] != 0 and v[0].sum() == S and v[0, 0] >= 1 and count["closed"] >= v[0, 0]
+        assert count["head_on"] == 1                              # (one hit on a head: the expansion of the forward child)
+        if S == 3:
+            assert w.tolist() == [[0, 512, 512]] and n.tolist() == [4] and best.tolist() == [1] and count["flooded"] == 2
+    count = T.new_count()
+    v, w, n, best = T.tron_mcts_territory(T.head_on_state(3), S, seat=seats(2), agent="avoid", noise=0.0, count=count)
+    assert n.tolist() == [4] and (w == 512 * v).all() and v[0].sum() == S and count["closed"] == S and count["flooded"] == 0
+    assert count["head_on"] == 3
+    v, w, n, best = T.tron_mcts_territory(T.corner_state(), S, agent="avoid", noise=0.0)
+    assert w[0, 0] == 0 and w[0, 2] == 0 and best.tolist() == [1] and v[0].sum() == S
+    if S == 3:
+        assert w.tolist() == [[0, 365, 0]]
+
+
 def test_skipped_positions_and_read_only_state():
     st = M.positions(7, 3, 6, np.random.default_rng(3))
     st.deaths[:, 0] = 0

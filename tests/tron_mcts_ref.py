@@ -71,8 +71,9 @@ def pos_of(st, b):
                [int(x) for x in st.deaths[:, b]])
 
 
-def step(N, pos, act):
-    """crl_tron_step without reset, in place; act: P values of 0, +1, -1.  -> (terminal, winners mask)"""
+def step(N, pos, act, count=None):
+    """crl_tron_step without reset, in place; act: P values of 0, +1, -1.  -> (terminal, winners mask).  `count`: a dict whose
+    'head_on' grows by one for every move onto a head (the hit that also kills the owner of the head)"""
     P = len(pos.h)
     bd, h, d, k = pos.board, pos.h, pos.d, pos.k
     for i in range(P):
@@ -89,6 +90,8 @@ def step(N, pos, act):
             k[i] = enemy
             if h[enemy - 1] == y * N + x:
                 k[enemy - 1] = i + 1
+                if count is not None:
+                    count["head_on"] += 1
         else:
             bd[y * N + x] = i + 1
             h[i] = y * N + x
@@ -136,11 +139,11 @@ def model_actions(N, pos, agent, thr, k0, k1, g, c, c2):
     return out
 
 
-def tree_step(N, pos, seat, e, agent, thr, k0, k1, g, c):
+def tree_step(N, pos, seat, e, agent, thr, k0, k1, g, c, count=None):
     """the tree step with edge action e at step counter c, in place: the seat plays e, the others the model agent"""
     act = model_actions(N, pos, agent, thr, k0, k1, g, c, TREE_STEP)
     act[seat] = _ACT[e]
-    return step(N, pos, act)
+    return step(N, pos, act, count)
 
 
 def is_closed(pos, seat):
@@ -152,7 +155,7 @@ def playout(N, pos, seat, agent, thr, k0, k1, g, c, c2, max_steps, count=None):
     pos = pos.copy()
     length = 0
     while True:
-        term, wm = step(N, pos, model_actions(N, pos, agent, thr, k0, k1, g, c, c2))
+        term, wm = step(N, pos, model_actions(N, pos, agent, thr, k0, k1, g, c, c2), count)
         length += 1
         if term or pos.k[seat] or (max_steps and length == max_steps):
             if count is not None:
@@ -166,7 +169,8 @@ def playout(N, pos, seat, agent, thr, k0, k1, g, c, c2, max_steps, count=None):
 
 def search(N, root, seat, S, R, cexp, agent, noise, max_steps, seed, g, tc, count=None):
     """one tree from `root` (never written): (visits [3], value [3], nodes, best).  `count`: a dict whose 'playouts', 'steps',
-    'depth' (summed leaf depths) and 'closed' (closed leaves) are added to."""
+    'depth' (summed leaf depths), 'closed' (closed leaves) and 'head_on' (moves onto a head, in tree steps and playouts) are
+    added to."""
     k0, k1, thr = seed & M32, (seed >> 32) & M32, threshold(noise)
     n, w, child, where, closed = [0], [0], [[None] * 3], [root], [False]
     for s in range(S):
@@ -176,7 +180,7 @@ def search(N, root, seat, S, R, cexp, agent, noise, max_steps, seed, g, tc, coun
             if fresh:                                            # expand
                 e = fresh[0]
                 pos = where[v].copy()
-                tree_step(N, pos, seat, e, agent, thr, k0, k1, g, (tc + len(path) - 1) & M32)
+                tree_step(N, pos, seat, e, agent, thr, k0, k1, g, (tc + len(path) - 1) & M32, count)
                 n.append(0), w.append(0), child.append([None] * 3), where.append(pos), closed.append(is_closed(pos, seat))
                 u = child[v][e] = len(n) - 1
             else:                                                # select
@@ -207,7 +211,7 @@ def search(N, root, seat, S, R, cexp, agent, noise, max_steps, seed, g, tc, coun
 
 
 def new_count():
-    return {"playouts": 0, "steps": 0, "depth": 0, "closed": 0}
+    return {"playouts": 0, "steps": 0, "depth": 0, "closed": 0, "head_on": 0}
 
 
 def tron_mcts(st, S, R, cexp=256, seed=0, first_env_id=0, tcount=None, seat=None, agent="random", noise=0.1, max_steps=0,

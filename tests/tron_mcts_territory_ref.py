@@ -99,7 +99,7 @@ def search(N, root, seat, S, Vs, cexp, agent, noise, seed, g, tc, count=None, me
             fresh = e is not None
             if fresh:                                            # expand: the lowest action without a child
                 pos = where[v].copy()
-                tree_step(N, pos, seat, e, agent, thr, k0, k1, g, (tc + len(path) - 1) & M32)
+                tree_step(N, pos, seat, e, agent, thr, k0, k1, g, (tc + len(path) - 1) & M32, count)
                 n.append(0), w.append(0), child.append([None] * 3), where.append(pos), closed.append(is_closed(pos, seat))
                 u = child[v][e] = len(n) - 1
             else:                                                # select: the best score, ties to the lowest action
@@ -130,8 +130,8 @@ def search(N, root, seat, S, Vs, cexp, agent, noise, seed, g, tc, count=None, me
 
 def new_count():
     """closed / flooded leaves, flooded leaves with a contested cell and with a_s + a_o == 0 ('empty'), summed leaf depths,
-    summed flood levels, skipped positions"""
-    return {"closed": 0, "flooded": 0, "contested": 0, "empty": 0, "depth": 0, "levels": 0, "skipped": 0}
+    summed flood levels, skipped positions, moves onto a head in the tree steps ('head_on')"""
+    return {"closed": 0, "flooded": 0, "contested": 0, "empty": 0, "depth": 0, "levels": 0, "skipped": 0, "head_on": 0}
 
 
 def tron_mcts_territory(st, S, Vs=256, cexp=256, seed=0, first_env_id=0, tcount=None, seat=None, agent="random", noise=0.1,
@@ -179,6 +179,24 @@ def corridor_state():
 def nowhere_state():
     """5x5, both players with one free cell ahead and walls everywhere else: after the step forward nobody has a first cell"""
     return hand_state(5, 2, [(1, 1), (1, 3)], [1, 1], [(2, 1), (2, 3)])
+
+
+def head_on_state(P=2):
+    """7x7.  Player 0 at (1, 3) heading east and player 1 at (3, 3) heading west, ONE free cell, (2, 3), between them; each
+    has its own column free above and below it (x = 1 and x = 3, three cells each way), everything else is wall -- so (2, 3)
+    is a dead end with walls above and below.  With P = 3 a bystander, player 2, stands at (5, 3) heading north with one
+    free cell ahead, to its right and to its left."""
+    free = [(2, 3)] + [(x, y) for x in (1, 3) for y in (0, 1, 2, 4, 5, 6)]
+    if P == 2:
+        return hand_state(7, 2, [(1, 3), (3, 3)], [1, 3], free)
+    assert P == 3
+    return hand_state(7, 3, [(1, 3), (3, 3), (5, 3)], [1, 3, 0], free + [(5, 2), (6, 3), (4, 3)])
+
+
+def corner_state():
+    """7x7, the seat in the corner (0, 0) heading north: forward and left leave the board, to its right the free top row
+    (six cells); the other player at (0, 6) heading east with three free cells ahead of it along the bottom row"""
+    return hand_state(7, 2, [(0, 0), (0, 6)], [0, 1], [(x, 0) for x in range(1, 7)] + [(x, 6) for x in (1, 2, 3)])
 
 
 def pocket_state():

@@ -656,6 +656,47 @@ class TronBatch(_RolloutStepper):
         _unit("noise", noise)          # (ValueError here; sample_avoid leaves a bad noise to its C entry: NativeError)
         return self._sample_scripted("sample_territory", seed, noise, players, out, advance)
 
+    # -- the territory tree search as a seated opponent for one step; the contract is with crl_tron_sample_mcts_territory
+    def mcts_agent_max_simulations(self, players=None) -> int:
+        """the most simulations ``sample_mcts_territory`` takes for these ``players`` (None: all) on this board
+        (``crl_tron_sample_mcts_territory_max_simulations``: the trees of a game's players share one workgroup's LDS, so
+        the more players search, the smaller each tree); boards wider than 64 have no such agent and raise here"""
+        mask = _player_mask(players, self.P, "mcts_agent_max_simulations")
+        if mask == 0:
+            raise ValueError("mcts_agent_max_simulations: players is empty")
+        rc = self._lib.crl_tron_sample_mcts_territory_max_simulations(self._ctx.handle, mask)
+        if rc < 0:
+            check(rc, "crl_tron_sample_mcts_territory_max_simulations")
+        return int(rc)
+
+    def sample_mcts_territory(self, simulations: int, seed: int = 0, exploration: float = 1.0, noise: float = 0.0, players=None,
+                              out: Optional[torch.Tensor] = None, advance: bool = True, agent: str = "random",
+                              model_noise: float = 0.1, value_scale: int = 256):
+        """Actions of the territory tree search seated at ``players`` at each game's step counter (``tcount``), ONE launch
+        (``crl_tron_sample_mcts_territory``; boards up to 64x64): with probability ``noise`` a uniform action (the draw of
+        ``sample_territory``), else the ``best`` of ``mcts_territory(simulations, seed, exploration, agent, model_noise,
+        seat=p, value_scale)`` for each named player p, all decided on the current (pre-step) boards; a player in a game
+        that is over plays 0.  ``simulations`` is at most ``mcts_agent_max_simulations(players)``.  ``players`` / ``out`` /
+        ``advance`` as ``sample_avoid``: only the named players' rows of ``out`` (int8 [P, B] in the ``step`` encoding; a new
+        zeroed tensor when None) are written, and the counter advances once per game.  No host synchronisation; capturable
+        into a graph."""
+        mask = _player_mask(players, self.P, "sample_mcts_territory")
+        if mask == 0:
+            raise ValueError("sample_mcts_territory: players is empty")
+        cexp = _exploration("exploration", exploration)
+        noise = _unit("noise", noise)
+        _one_of("agent", agent, ("random", "avoid"))
+        model_noise = _unit("model_noise", model_noise)
+        V = _int_in("value_scale", value_scale, 1, 1024)
+        S = _int_in("simulations", simulations, 1, self.mcts_agent_max_simulations(players))
+        if out is None:
+            out = torch.zeros((self.P, self.B), dtype=torch.int8, device=self.device)
+        else:
+            _want(out, torch.int8, (self.P, self.B), self.device, "out")
+        self._call("crl_tron_sample_mcts_territory", _seed(seed), self.first_env_id, _ptr(self.tcount), int(advance), noise, mask,
+                   *self._state(), S, V, cexp, model_noise, _native.CRL_PLAYOUT_AVOID if agent == "avoid" else 0, _ptr(out))
+        return out
+
     # -- T fused steps with every player on the avoid agent, auto-reset
     def rollout_avoid(self, steps: int, seed: int = 0, noise: float = 0.1):
         """``rollout`` with every player on the reference's ``SimpleAvoidAgent(noise)`` instead of the random agent

@@ -19,6 +19,8 @@
 //
 // crl_tron_mcts_territory is the same search with one Voronoi flood of the leaf's position in the
 // place of the playouts: tron_mcts_territory_kernel below, without the playout bitboards (16 (S + 1) + 8 nwords bytes per wave).
+// crl_tron_sample_mcts_territory seats that search at the players of a mask:
+// tron_sample_mcts_territory_kernel, one workgroup per game, one wave and one such slice of LDS per masked player.
 #include "crl_common.hpp"
 
 namespace {
@@ -623,6 +625,227 @@ tron_mcts_territory_kernel(const int N, const int NN, const uint32_t inv_n, cons
     }
 }
 
+// one wave's slice of LDS: n[S + 1] | w[S + 1] | child uint16 [S + 1][3] | path uint16 [S + 1] | root[nwords] | work[nwords],
+// 4 (S + 1) + 2 nwords dwords from `base` on
+struct TmTree {
+    uint32_t *n_arr, *w_arr;
+    uint16_t *child, *path;
+    uint32_t *root_bits, *work_bits;
+};
+
+__device__ __forceinline__ TmTree tm_tree_at(uint32_t *base, const int S, const int nwords)
+{
+    TmTree t;
+    t.n_arr = base;
+    t.w_arr = t.n_arr + (S + 1);
+    t.child = reinterpret_cast<uint16_t *>(t.w_arr + (S + 1));
+    t.path = t.child + 3 * (S + 1);
+    t.root_bits = t.w_arr + 3 * (S + 1);
+    t.work_bits = t.root_bits + nwords;
+    return t;
+}
+
+// the root position of game b, alike in every lane
+template <int P>
+__device__ __forceinline__ TmPos<P> tm_root_pos(const int N, const int NN, const uint32_t inv_n, const int64_t B, const int64_t b,
+                                                const int16_t *__restrict__ heads, const int8_t *__restrict__ dirs,
+                                                const int8_t *__restrict__ deaths)
+{
+    TmPos<P> p0;
+    p0.alive = 0u;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        p0.h[p] = min(max(__builtin_amdgcn_readfirstlane((int)heads[p * B + b]), 0), NN - 1);   // (a broken state: wrong results, no wild access)
+        p0.y[p] = (int)__umulhi((uint32_t)p0.h[p], inv_n);
+        p0.x[p] = p0.h[p] - p0.y[p] * N;
+        p0.d[p] = __builtin_amdgcn_readfirstlane((int)dirs[p * B + b]) & 3;
+        p0.alive |= (__builtin_amdgcn_readfirstlane((int)deaths[p * B + b]) == 0 ? 1u : 0u) << p;
+    }
+    return p0;
+}
+
+// The search of crl_tron_mcts_territory for the live seat sp of ONE position, by one wave in its own slice of LDS, for
+// tron_sample_mcts_territory_kernel (below): the body of tron_mcts_territory_kernel (above) from the root bitboard (built from
+// `cells`, the position's N*N board bytes) to the pick, statement for statement, with the same CRL_BOUNDS_LT sites.  It is a
+// second copy: with both kernels on this function crl_tron_mcts_territory measured 1.0-2.2 % slower than before (DESIGN.md
+// section 4.5g), so that kernel stays as it was; a change to the search goes into both, and the differential test of the two
+// entries (tests/test_gpu_tron_mcts_agent.py) holds them to each other.  Returns best (never -1: S >= 1); vis / val are the
+// root's child at action `lane` in lanes 0..2, nn the node count.  The caller has checked the skipped-position rule and puts
+// a tm_wave_sync between this and the next use of the slice.
+template <int P, bool AVOID, typename W>
+__device__ __forceinline__ int tm_territory_search(const int N, const int NN, const int nwords, const int lane,
+                                                   const int8_t *__restrict__ cells, const TmPos<P> &p0, const int sp,
+                                                   const uint32_t tc, const uint32_t gid, const uint32_t seed_lo,
+                                                   const uint32_t seed_hi, const int S, const int V, const uint32_t cexp,
+                                                   const uint64_t thr, const TmTree &t, uint32_t &vis, uint32_t &val, int &nn)
+{
+    uint32_t *const n_arr = t.n_arr, *const w_arr = t.w_arr, *const root_bits = t.root_bits, *const work_bits = t.work_bits;
+    uint16_t *const child = t.child, *const path = t.path;
+    const TmBoard work = {work_bits, 1, 0, nwords};
+    constexpr uint32_t kTreeStep = 0xFFFF0000u;                 // the third counter word of the tree steps' draws
+    // ---- the root bitboard, lanes over words; the root node
+    for (int w = lane; w < nwords; w += 64) root_bits[w] = tm_occ_run(cells + 32 * w, min(32, NN - 32 * w));
+    if (lane == 0) { n_arr[0] = 0u; w_arr[0] = 0u; path[0] = 0; }
+    if (lane < 3) child[lane] = 0;
+    tm_wave_sync();
+    nn = 1;                                                  // nodes so far
+    for (int s = 0; s < S; ++s) {
+        for (int w = lane; w < nwords; w += 64) work_bits[w] = root_bits[w];
+        tm_wave_sync();
+        TmPos<P> ps = p0;
+        int v = 0, d = 0;
+        bool closed, seat_alive;
+        for (;;) {
+            CRL_BOUNDS_LT(v, S + 1, 184);
+            const uint32_t cu = lane < 3 ? child[v * 3 + lane] : 0u;
+            CRL_BOUNDS_LT(cu, S + 1, 185);
+            const unsigned long long fresh = __ballot(lane < 3 && cu == 0u);
+            int e, u;
+            if (fresh) {                                     // expand: the lowest action without a child
+                e = (int)__builtin_ctzll(fresh);
+                u = nn++;
+                CRL_BOUNDS_LT(u, S + 1, 186);
+                if (lane == 0) { child[v * 3 + e] = (uint16_t)u; n_arr[u] = 0u; w_arr[u] = 0u; }
+                if (lane < 3) child[u * 3 + lane] = 0;
+            } else {                                         // select: lane a scores the child at action a
+                const uint32_t lgv = tm_lg(n_arr[v]);
+                uint32_t key = 0;
+                if (lane < 3) {
+                    const uint32_t nu = n_arr[cu], wu = w_arr[cu];
+                    const uint64_t exploit = tm_div((uint64_t)wu << 15, nu * (uint32_t)V);
+                    const uint64_t X = tm_div((uint64_t)lgv << 24, nu);
+                    const uint64_t score = exploit + (((uint64_t)cexp * tm_isqrt(X)) >> 8);   // < 2^26
+                    key = (((uint32_t)score << 2) | (uint32_t)(3 - lane)) + 1u;               // ties: the lowest action
+                }
+                // the arg-max over the three lanes (every lane runs the reads: they sit outside the branch above)
+                const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, 0), k1 = (uint32_t)__builtin_amdgcn_readlane((int)key, 1),
+                               k2 = (uint32_t)__builtin_amdgcn_readlane((int)key, 2);
+                const uint32_t top = max(k0, max(k1, k2));
+                e = 3 - (int)((top - 1u) & 3u);
+                const int c0 = __builtin_amdgcn_readlane((int)cu, 0), c1 = __builtin_amdgcn_readlane((int)cu, 1),
+                          c2 = __builtin_amdgcn_readlane((int)cu, 2);
+                u = e == 0 ? c0 : e == 1 ? c1 : c2;
+            }
+            d += 1;
+            CRL_BOUNDS_LT(d, S + 1, 187);
+            if (lane == 0) path[d] = (uint16_t)u;
+            // ---- the tree step at depth d - 1: the seat plays e, the others the model agent on the pre-step position
+            int code[P];
+            const uint32_t c = tc + (uint32_t)(d - 1);
+            if constexpr (AVOID) {
+                tm_avoid_codes<P>(N, work, ps, gid, c, kTreeStep, seed_lo, seed_hi, thr, code);
+            } else {
+                TmDraw dr = {};
+                tm_random_refill<P>(gid, c, kTreeStep, seed_lo, seed_hi, dr);
+                tm_random_codes<P>(c, dr, code);
+            }
+#pragma unroll
+            for (int p = 0; p < P; ++p) code[p] = (p == sp) ? e + (e >> 1) : code[p];
+            tm_step<P>(N, work, ps, code);
+            seat_alive = (ps.alive >> sp) & 1u;
+            closed = !seat_alive || __popc(ps.alive) <= 1;
+            if (fresh || closed || d >= S) break;            // (d >= S: never, a path of d edges has d nodes below the root)
+            v = u;
+        }
+        // ---- evaluate the leaf: its outcome when it is closed, else one flood of its position (no draw)
+        uint32_t sum = seat_alive ? 2u * (uint32_t)V : 0u;   // half-points on the scale of V (wave-uniform)
+        if (__builtin_amdgcn_readfirstlane((int)closed) == 0) {     // (alike in every lane: all 64 run the flood)
+            tm_wave_sync();
+            int area[P];
+            tm_leaf_areas<P, W>(N, NN, nwords, lane, work_bits, ps, area);
+            uint32_t a_s = 0u, a_o = 0u;
+#pragma unroll
+            for (int p = 0; p < P; ++p) {                    // (dead players hold 0)
+                a_s = p == sp ? (uint32_t)area[p] : a_s;
+                a_o = p == sp ? a_o : max(a_o, (uint32_t)area[p]);
+            }
+            const uint32_t den = a_s + a_o;
+            sum = den == 0u ? (uint32_t)V : (uint32_t)tm_div((uint64_t)(2u * (uint32_t)V * a_s), den);
+        }
+        // ---- back up: lane i adds to the node at depth i (distinct nodes: no atomics), 64 entries per pass
+        tm_wave_sync();
+        for (int i0 = 0; i0 <= d; i0 += 64) {
+            const int i = i0 + lane;
+            if (i <= d) {
+                const uint32_t node = path[i];
+                CRL_BOUNDS_LT(node, S + 1, 188);
+                n_arr[node] += 1u;
+                if (i > 0) w_arr[node] += sum;
+            }
+        }
+        tm_wave_sync();
+    }
+    // ---- the root's children: visits, value, the most visited (then the larger w, then the lower action)
+    const uint32_t cu = lane < 3 ? child[lane] : 0u;
+    CRL_BOUNDS_LT(cu, S + 1, 189);
+    vis = cu ? n_arr[cu] : 0u;
+    val = cu ? w_arr[cu] : 0u;
+    int pick = -1;
+    uint32_t pick_n = 0u, pick_w = 0u;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {                            // (every lane runs the reads)
+        const uint32_t ca = (uint32_t)__builtin_amdgcn_readlane((int)cu, a), na = (uint32_t)__builtin_amdgcn_readlane((int)vis, a),
+                       wa = (uint32_t)__builtin_amdgcn_readlane((int)val, a);
+        const bool better = ca != 0u && (pick < 0 || na > pick_n || (na == pick_n && wa > pick_w));
+        pick = better ? a : pick;
+        pick_n = better ? na : pick_n;
+        pick_w = better ? wa : pick_w;
+    }
+    return pick;
+}
+
+// the k-th set bit of mask (k < popcount(mask))
+__device__ __forceinline__ int tm_kth_bit(uint32_t mask, int k)
+{
+    while (k-- > 0) mask &= mask - 1u;
+    return (int)__builtin_ctz(mask);
+}
+
+// crl_tron_sample_mcts_territory: the search above as a seated agent.  One workgroup holds one game,
+// wave j is the j-th player of the mask (m = popcount(pmask) waves, 64 m threads) with a slice of LDS of its own, so the m
+// searches of a game run side by side and share nothing.  The games are walked in a grid-stride loop that is uniform over the
+// workgroup: every wave, whether it searches, is noisy or sits on a dead seat, makes the same trips and meets the ONE
+// workgroup barrier of a trip -- every wave has read the game's counter in front of it, wave 0 advances the counter behind it.
+template <int P, bool AVOID, typename W>
+__global__ void __launch_bounds__(512)
+tron_sample_mcts_territory_kernel(const int N, const int NN, const uint32_t inv_n, const int64_t B, const uint32_t seed_lo,
+                                  const uint32_t seed_hi, const uint64_t first_env_id, const int8_t *__restrict__ board,
+                                  const int16_t *__restrict__ heads, const int8_t *__restrict__ dirs,
+                                  const int8_t *__restrict__ deaths, uint32_t *tcount, const int advance, const uint64_t noise_thr,
+                                  const uint32_t pmask, const int S, const int V, const uint32_t cexp, const uint64_t thr,
+                                  const int nwords, const uint32_t wave_words, int8_t *__restrict__ actions)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t tm_lds[];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    CRL_BOUNDS_LT(wave, __popc(pmask), 190);
+    CRL_BOUNDS_LT((uint32_t)wave * wave_words + wave_words - 1u, (uint32_t)(blockDim.x >> 6) * wave_words, 191);
+    const int sp = tm_kth_bit(pmask, wave);                     // this wave's seat
+    const TmTree tree = tm_tree_at(tm_lds + (uint32_t)wave * wave_words, S, nwords);
+
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {       // (alike in every wave of the workgroup)
+        const TmPos<P> p0 = tm_root_pos<P>(N, NN, inv_n, B, b, heads, dirs, deaths);
+        const uint32_t tc = (uint32_t)__builtin_amdgcn_readfirstlane((int)tcount[b]);
+        const uint32_t gid = (uint32_t)(first_env_id + (uint64_t)b);
+        __syncthreads();                                         // every wave holds the counter: wave 0 may advance it
+        if (advance && threadIdx.x == 0u) tcount[b] = tc + 1u;
+        int a = 0;                                               // dead players: 0
+        if ((p0.alive >> sp) & 1u) {
+            const philox_out wv = philox4x32_10(gid, tc, (uint32_t)sp, CRL_TAG_TRON_TERRITORY, seed_lo, seed_hi);   // (wave-uniform)
+            if ((uint64_t)wv.w[0] < noise_thr) {
+                a = (int)__umulhi(wv.w[1], 3u);
+            } else if (P == 1 || __popc(p0.alive) >= 2) {        // (else crl_tron_mcts_territory skips: best -1 plays 0)
+                uint32_t vis, val;
+                int nn;
+                a = tm_territory_search<P, AVOID, W>(N, NN, nwords, lane, board + b * NN, p0, sp, tc, gid, seed_lo, seed_hi, S, V, cexp,
+                                                     thr, tree, vis, val, nn);
+                tm_wave_sync();                                  // the next tree starts behind the pick's reads
+            }
+        }
+        if (lane == 0) actions[(int64_t)sp * B + b] = (int8_t)(a == 2 ? -1 : a);
+    }
+}
+
 // S_max of crl_tron_mcts (include/colosseum_hip.h): the tree, the path and the 66 bitboards of one wave within 64 KB, and
 // s < 4095 (its counter word); below 1 on boards of 90x90 and more
 constexpr uint32_t kTmLds = 65536u;
@@ -631,6 +854,15 @@ int tron_mcts_max_simulations(const int N)
     const int nwords = (N * N + 31) >> 5;
     const int s = ((int)kTmLds - 264 * nwords) / 16 - 1;        // (C's division: a negative numerator stays below 1)
     return s < 4095 ? s : 4095;
+}
+
+// S_agent of crl_tron_sample_mcts_territory: m waves of crl_tron_mcts_territory's per-wave LDS (16 (S + 1) + 8 nwords bytes)
+// in one workgroup's 64 KB, and no more than S_max above
+int tron_mcts_agent_max_simulations(const int N, const int m)
+{
+    const int nwords = (N * N + 31) >> 5;
+    const int s = ((int)kTmLds / m - 8 * nwords) / 16 - 1, s_max = tron_mcts_max_simulations(N);
+    return s < s_max ? s : s_max;
 }
 
 } // namespace
@@ -740,6 +972,69 @@ int crl_tron_mcts_territory(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64
         TRON_DISPATCH_P(cfg.P, { if (cfg.N <= 32) TRON_MCTS_TERR_LAUNCH(false, uint32_t); else TRON_MCTS_TERR_LAUNCH(false, uint64_t); });
     }
 #undef TRON_MCTS_TERR_LAUNCH
+    CRL_LAUNCH_CHECK();
+    return CRL_OK;
+}
+
+int crl_tron_sample_mcts_territory_max_simulations(const crl_ctx *ctx, uint32_t player_mask)
+{
+    CRL_REQUIRE(ctx != nullptr && ctx->game == CRL_GAME_TRON, "crl_tron_sample_mcts_territory_max_simulations: ctx is not a tron context");
+    const crl_tron_cfg &cfg = ctx->tron;
+    CRL_REQUIRE(player_mask != 0u, "crl_tron_sample_mcts_territory_max_simulations: player_mask is empty");
+    CRL_REQUIRE((player_mask >> cfg.P) == 0u, "crl_tron_sample_mcts_territory_max_simulations: player_mask 0x%x names players beyond P=%d",
+                player_mask, cfg.P);
+    if (cfg.N > 64) {
+        crl_set_error("crl_tron_sample_mcts_territory_max_simulations: a %dx%d board is wider than 64, the widest the in-wave flood takes",
+                      cfg.N, cfg.N);
+        return CRL_EUNSUPPORTED;
+    }
+    return tron_mcts_agent_max_simulations(cfg.N, __builtin_popcount(player_mask));
+}
+
+int crl_tron_sample_mcts_territory(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, uint32_t *tcount, int advance,
+                                   double noise, uint32_t player_mask, const int8_t *board, const int16_t *heads, const int8_t *dirs,
+                                   const int8_t *deaths, int S, int V, uint32_t cexp, double model_noise, uint32_t flags,
+                                   int8_t *actions, void *stream)
+{
+    TRON_CTX_CHECK("crl_tron_sample_mcts_territory");
+    CRL_REQUIRE(tcount && actions, "crl_tron_sample_mcts_territory: NULL tcount / actions pointer");
+    CRL_REQUIRE(board && heads && dirs && deaths, "crl_tron_sample_mcts_territory: NULL state pointer");
+    const crl_tron_cfg &cfg = ctx->tron;
+    CRL_REQUIRE(player_mask != 0u, "crl_tron_sample_mcts_territory: player_mask is empty");
+    CRL_REQUIRE((player_mask >> cfg.P) == 0u, "crl_tron_sample_mcts_territory: player_mask 0x%x names players beyond P=%d", player_mask,
+                cfg.P);
+    if (cfg.N > 64) {                                            // the flood is one lane per board row
+        crl_set_error("crl_tron_sample_mcts_territory: a %dx%d board is wider than 64, the widest the in-wave flood takes", cfg.N, cfg.N);
+        return CRL_EUNSUPPORTED;
+    }
+    CRL_REQUIRE(noise >= 0.0 && noise <= 1.0, "crl_tron_sample_mcts_territory: noise=%g not in [0, 1]", noise);
+    CRL_REQUIRE(model_noise >= 0.0 && model_noise <= 1.0, "crl_tron_sample_mcts_territory: model_noise=%g not in [0, 1]", model_noise);
+    const uint32_t m = (uint32_t)__builtin_popcount(player_mask);
+    const int s_agent = tron_mcts_agent_max_simulations(cfg.N, (int)m);
+    CRL_REQUIRE(S >= 1 && S <= s_agent, "crl_tron_sample_mcts_territory: S=%d out of range 1..%d (a %dx%d board, %u players in the mask)",
+                S, s_agent, cfg.N, cfg.N, m);
+    CRL_REQUIRE(V >= 1 && V <= 1024, "crl_tron_sample_mcts_territory: V=%d out of range 1..1024", V);
+    CRL_REQUIRE(cexp <= 65535u, "crl_tron_sample_mcts_territory: cexp=%u out of range 0..65535", cexp);
+    CRL_REQUIRE((flags & ~CRL_PLAYOUT_AVOID) == 0u, "crl_tron_sample_mcts_territory: unknown flags 0x%x", flags);
+    // one workgroup per game, one wave per masked player, each with crl_tron_mcts_territory's per-wave LDS (m of them fit 64 KB:
+    // that is S_agent); a grid-stride loop past 2^20 workgroups
+    const int NN = cfg.N * cfg.N, nwords = (NN + 31) >> 5;
+    const uint32_t wave_bytes = 16u * (uint32_t)(S + 1) + 8u * (uint32_t)nwords;
+    const unsigned blocks = (unsigned)(B < ((int64_t)1 << 20) ? B : ((int64_t)1 << 20));
+    const uint32_t wave_words = 4u * (uint32_t)(S + 1) + 2u * (uint32_t)nwords;
+    const uint32_t inv_n = (uint32_t)(0x100000000ull / (uint32_t)cfg.N) + 1u;   // y = umulhi(h, inv_n) is exact for h < N*N <= 2^15
+    const uint64_t noise_thr = crl_noise_threshold(noise), thr = crl_noise_threshold(model_noise);
+    hipStream_t st = (hipStream_t)stream;
+#define TRON_MCTS_AGENT_LAUNCH(AV_, W_)                                                                                     \
+    hipLaunchKernelGGL((tron_sample_mcts_territory_kernel<PP, AV_, W_>), dim3(blocks), dim3(64u * m), (size_t)m * wave_bytes, st, \
+                       cfg.N, NN, inv_n, B, (uint32_t)seed, (uint32_t)(seed >> 32), first_env_id, board, heads, dirs, deaths,   \
+                       tcount, advance, noise_thr, player_mask, S, V, cexp, thr, nwords, wave_words, actions)
+    if (flags & CRL_PLAYOUT_AVOID) {
+        TRON_DISPATCH_P(cfg.P, { if (cfg.N <= 32) TRON_MCTS_AGENT_LAUNCH(true, uint32_t); else TRON_MCTS_AGENT_LAUNCH(true, uint64_t); });
+    } else {
+        TRON_DISPATCH_P(cfg.P, { if (cfg.N <= 32) TRON_MCTS_AGENT_LAUNCH(false, uint32_t); else TRON_MCTS_AGENT_LAUNCH(false, uint64_t); });
+    }
+#undef TRON_MCTS_AGENT_LAUNCH
     CRL_LAUNCH_CHECK();
     return CRL_OK;
 }

@@ -11,7 +11,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .batched import BlokusBatch, TronBatch, TTTBatch, _exploration, _int_in, _unit, _want
+from .batched import BlokusBatch, TronBatch, TTTBatch, _exploration, _int_in, _one_of, _unit, _want
 
 
 class TronVectorEnv:
@@ -53,23 +53,40 @@ class TronSinglePlayerVectorEnv:
     captured into a HIP graph (``torch.cuda.graph``).  The opponents' draws follow ``crl_tron_sample_avoid``'s contract
     at each game's step counter, keyed by ``seed``.
     ``opponent="territory"`` puts the opponents on the territory-greedy agent instead (``crl_tron_sample_territory``: the
-    first action with the best Voronoi score, with the same ``noise``): only the opponents' sampling launch changes."""
+    first action with the best Voronoi score, with the same ``noise``): only the opponents' sampling launch changes.
+    ``opponent="mcts_territory"`` seats the territory tree search (``crl_tron_sample_mcts_territory``,
+    ``TronBatch.sample_mcts_territory``'s moves; boards up to 64x64): with probability ``noise`` a uniform action, else the
+    most visited action of ``simulations`` descents with ``exploration``, the other players modelled by ``model`` ("random"
+    or "avoid") with ``model_noise`` (None: the env's ``noise``).  Still two launches per step; ``simulations`` is at most
+    ``TronBatch.mcts_agent_max_simulations`` of the opponents.  The four keywords are checked and otherwise unused with the
+    other opponents."""
+
+    OPPONENTS = ("avoid", "territory", "mcts_territory")
 
     def __init__(self, board_size: int = 15, num_players: int = 4, batch: int = 1024, noise: float = 0.1, seed: int = 0,
-                 spawn_offset: int = 2, device="cuda", opponent: str = "avoid"):
+                 spawn_offset: int = 2, device="cuda", opponent: str = "avoid", simulations: int = 48,
+                 exploration: float = 1.0, model: str = "avoid", model_noise: Optional[float] = None):
         if num_players < 1:
             raise ValueError("num_players must be at least 1")
-        if opponent not in ("avoid", "territory"):
-            raise ValueError("opponent must be 'avoid' or 'territory', got %r" % (opponent,))
+        if opponent not in self.OPPONENTS:
+            raise ValueError("opponent must be 'avoid', 'territory' or 'mcts_territory', got %r" % (opponent,))
         self.opponent = opponent
+        _exploration("exploration", exploration)
+        _one_of("model", model, ("random", "avoid"))
+        self._search = dict(simulations=_int_in("simulations", simulations, 1, 4095), exploration=exploration, agent=model,
+                            model_noise=None if model_noise is None else _unit("model_noise", model_noise))
         self.batch = TronBatch(board_size, num_players, batch, device=device, spawn_offset=spawn_offset)
         self.num_players, self.num_envs = num_players, batch
         self.noise, self.seed = float(noise), int(seed)
         if not 0.0 <= self.noise <= 1.0:
             raise ValueError("noise=%r not in [0, 1]" % (noise,))
+        if self._search["model_noise"] is None:
+            self._search["model_noise"] = self.noise
         dev = self.batch.device
         self._actions = torch.zeros((num_players, batch), dtype=torch.int8, device=dev)
         self._opponents = list(range(1, num_players))
+        if opponent == "mcts_territory" and self._opponents:
+            _int_in("simulations", simulations, 1, self.batch.mcts_agent_max_simulations(self._opponents))
         self.reward = torch.zeros((batch,), dtype=torch.int8, device=dev)
         self.done = torch.zeros((batch,), dtype=torch.uint8, device=dev)
         self.terminal = torch.zeros((batch,), dtype=torch.uint8, device=dev)
@@ -85,7 +102,9 @@ class TronSinglePlayerVectorEnv:
     def step(self, action: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict]:
         b = self.batch
         _want(action, torch.int64, (b.B,), b.device, "action")
-        if self._opponents:
+        if self._opponents and self.opponent == "mcts_territory":
+            b.sample_mcts_territory(seed=self.seed, noise=self.noise, players=self._opponents, out=self._actions, **self._search)
+        elif self._opponents:
             sample = b.sample_territory if self.opponent == "territory" else b.sample_avoid
             sample(self.seed, self.noise, players=self._opponents, out=self._actions)
         b.step_single(self._actions, action, self.reward, self.done, self.terminal)

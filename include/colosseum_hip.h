@@ -91,7 +91,8 @@ const char *crl_last_error(void);
  *      crl_ttt_mcts / crl_ttt_mcts_max_simulations (batched tree search: two new entries, one new Philox tag), and
  *      crl_ttt_sample_mcts / _rollout_mcts / _step_single_mcts (the search as a seated agent: three new entries, no new tag), and
  *      crl_tron_mcts / crl_tron_mcts_max_simulations (batched tree search for one seat of Tron: two new entries, no new tag), and
- *      crl_tron_mcts_territory (that search with Voronoi territory at the leaves: one new entry, no new tag). */
+ *      crl_tron_mcts_territory (that search with Voronoi territory at the leaves: one new entry, no new tag), and
+ *      crl_tron_sample_mcts_territory / _max_simulations (that search as a seated agent: two new entries, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -452,6 +453,38 @@ int crl_tron_mcts_territory(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64
                             int S, int V, uint32_t cexp, double noise,
                             uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best,
                             uint32_t flags, void *stream);
+/* crl_tron_sample_mcts_territory: the search of crl_tron_mcts_territory as a SEATED agent -- one action for every masked player
+ * of every game, one launch, no host sync.  Added under revision 113: two new entries, no new Philox tag, no existing struct,
+ * argument list or RNG contract changed.  The contract is made of two that exist.
+ * crl_tron_sample_territory's (below), word for word: player_mask (rows outside it are never written), advance (!= 0
+ * increments tcount[b], once per game whatever the mask), actions[p*B+b] in the crl_tron_step encoding (0, +1, -1), dead
+ * players get 0, g = the low 32 bits of first_env_id + b and c = tcount[b].  The state is read only.
+ * For a live masked player p:
+ *   W = Philox4x32-10(ctr = {g, c, p, 0x54760000}, key = {seed lo, seed hi})      (crl_tron_sample_territory's own draw)
+ *   noisy  iff  W[0] < thr(noise), thr as crl_tron_sample_avoid's;  noisy: a = mulhi32(W[1], 3): 0 forward, 1 right, 2 left
+ *          -- so at noise = 1 the call returns exactly what crl_tron_sample_territory returns at noise = 1;
+ *   else:  a = `best` of crl_tron_mcts_territory on the same state with seat = p, the same seed, first_env_id, tcount, S, V,
+ *          cexp and flags, and model_noise as its `noise`; best = -1 (fewer than two players alive with P >= 2) plays 0.
+ * All players decide on the pre-step state, and every search of game b reads tcount[b] before the call advances it.
+ * Limits (CRL_EINVAL, with a crl_last_error message naming the argument, before any device work): NULL pointers (tcount and
+ * actions included), B out of range (as crl_tron_mcts), player_mask zero or with bits >= P, noise or model_noise outside
+ * [0, 1] or NaN, S outside [1, S_agent], V outside [1, 1024], cexp > 65535, flags other than CRL_PLAYOUT_AVOID, a context that
+ * is not a Tron context.  With m = popcount(player_mask) and nwords = ceil(N*N / 32),
+ *   S_agent(N, m) = min(S_max of crl_tron_mcts, floor((floor(65536 / m) - 8 nwords) / 16) - 1):
+ * m waves of crl_tron_mcts_territory's per-wave LDS (16 (S + 1) + 8 nwords bytes) in one 64 KB workgroup -- 1,358 on 19x19
+ * with m = 3, 447 on 64x64 with m = 8.  crl_tron_sample_mcts_territory_max_simulations returns S_agent of the context and the
+ * mask (CRL_EINVAL on a context that is not a Tron context or a bad mask).  Boards wider than 64 answer CRL_EUNSUPPORTED in
+ * both entries, as crl_tron_mcts_territory does.
+ * One workgroup per game, wave j the j-th masked player with a tree of its own in its own slice of LDS (64 m threads); the
+ * noise draw is wave-uniform and comes first, a noisy wave or a dead seat skips the search.  Every wave reads the counter,
+ * then comes the one workgroup barrier of a game, then wave 0 stores c + 1.  Games are walked in a grid-stride loop with
+ * 64-bit indices. */
+int crl_tron_sample_mcts_territory_max_simulations(const crl_ctx *ctx, uint32_t player_mask);
+int crl_tron_sample_mcts_territory(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                                   uint32_t *tcount, int advance, double noise, uint32_t player_mask,
+                                   const int8_t *board, const int16_t *heads, const int8_t *dirs, const int8_t *deaths,
+                                   int S, int V, uint32_t cexp, double model_noise, uint32_t flags,
+                                   int8_t *actions, void *stream);
 
 /* ------------------------------------------------------------------ Voronoi territory (Tron)
  * crl_tron_territory: for each of B positions and A forced first actions of a seat, the number of free cells every player

@@ -154,6 +154,8 @@ PROTOTYPES = {
     "crl_blokus_step_observe": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 15 + [_U32, _VP]),
     "crl_blokus_step_single": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 15 + [_U32, _VP]),
     "crl_blokus_playout": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 7 + [_I, _I] + [_VP] * 4 + [_U32, _VP]),
+    "crl_blokus_mcts_max_simulations": (_I, [_VP]),
+    "crl_blokus_mcts": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 7 + [_I, _I, _I, _I, _U32] + [_VP] * 5 + [_U32, _VP]),
     "crl_tron_rollout_bind": (_I, [_VP, _I64, _U64, _VP, _VP, _VP, _VP, TronStats, _U32, C.POINTER(_VP)]),
     "crl_ttt_rollout_bind": (_I, [_VP, _I64, _U64, _VP, _VP, _VP, TTTStats, C.POINTER(_VP)]),
     "crl_blokus_rollout_bind": (_I, [_VP, _I64, _U64, _VP, _VP, _VP, _VP, _VP, BlokusStats, C.POINTER(_VP)]),

@@ -1312,6 +1312,47 @@ class BlokusBatch(_RolloutStepper):
         mover = (self.to_move.to(torch.int64) & 3).view(-1, 1, 1).expand(self.B, A, 1)
         return _flat_mc_pick(torch.gather(o["wins"], 2, mover).squeeze(2), o["played"], candidates)
 
+    # -- tree search with progressive widening; the contract is with crl_blokus_mcts in include/colosseum_hip.h
+    @functools.cached_property
+    def mcts_max_simulations(self) -> int:
+        """the most simulations ``mcts`` takes (``crl_blokus_mcts_max_simulations``: the tree stays in LDS)"""
+        rc = self._lib.crl_blokus_mcts_max_simulations(self._ctx.handle)
+        if rc < 0:
+            check(rc, "crl_blokus_mcts_max_simulations")
+        return int(rc)
+
+    def mcts(self, simulations: int, playouts: int = 1, candidates: Optional[torch.Tensor] = None, width: int = 8, seed: int = 0,
+             exploration: float = 1.0, out: Optional[dict] = None):
+        """A tree search for the player to move in every game, ONE launch (``crl_blokus_mcts``): each game builds a tree of
+        its own by ``simulations`` descents (at most ``mcts_max_simulations``), each new leaf valued by ``playouts`` (1 ..
+        1024) random games to their end.  A node is widened progressively: it gets its k-th child, a uniformly drawn legal
+        action, once it has about k^2 visits, up to ``width`` (1 .. 64) children.  With ``candidates`` (int32 [B, A], A <= 64
+        dense ids) the root's children are the legal, distinct candidates instead, slot = column; the nodes below widen.
+        ``exploration`` (0 .. 65535 / 256; 0 = pure exploitation) multiplies sqrt(log2 n_parent / n_child) on a value scale
+        of 0 .. 1.  The draws are keyed by ``seed``, the game ids and ``tcount`` as the counter base (the call reads the state
+        and writes none of it).  Returns {'ids' int32 [B, K]: the dense id of the root's child in each slot (-1 the pass, -2
+        an empty slot; K = A with candidates, else ``width``), 'visits', 'value' int32 [B, K]: simulations through that child
+        and the playouts the mover won behind it, 'nodes' int32 [B], 'best' int32 [B]: the id of the most visited child
+        (ties: the larger value, then the lowest slot; -2 where no candidate was playable)}; ``out`` reuses such a dict.  No
+        host synchronisation; capturable into a graph."""
+        S = _int_in("simulations", simulations, 1, self.mcts_max_simulations)
+        R = _int_in("playouts", playouts, 1, 1024)
+        A = _candidates(candidates, self.B, self.device, 64)
+        W = _int_in("width", width, 1, 64)
+        cexp = _exploration("exploration", exploration)
+        i32, BK = torch.int32, (self.B, A if candidates is not None else W)
+        out = _out_dict(out, {"ids": (i32, BK), "visits": (i32, BK), "value": (i32, BK), "nodes": (i32, (self.B,)),
+                              "best": (i32, (self.B,))}, self.device)
+        self._call("crl_blokus_mcts", _seed(seed), self.first_env_id, *self._state(), _ptr(self.tcount), _ptr(candidates), A, W, S, R,
+                   cexp, _ptr(out["ids"]), _ptr(out["visits"]), _ptr(out["value"]), _ptr(out["nodes"]), _ptr(out["best"]), 0)
+        return out
+
+    def mcts_action(self, simulations: int, playouts: int = 1, candidates: Optional[torch.Tensor] = None, width: int = 8,
+                    seed: int = 0, exploration: float = 1.0, out: Optional[dict] = None) -> torch.Tensor:
+        """``mcts``'s most visited child as an int64 [B] action for ``step_single`` (-1 = pass, also where no candidate was
+        playable).  No host synchronisation; capturable."""
+        return self.mcts(simulations, playouts, candidates, width, seed, exploration, out)["best"].to(torch.int64).clamp_(min=-1)
+
     def board(self):
         out = torch.empty((self.B, 20, 20), dtype=torch.int8, device=self.device)
         self._call("crl_blokus_board", _ptr(self.occ), _ptr(out))

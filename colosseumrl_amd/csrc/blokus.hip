@@ -958,6 +958,13 @@ __device__ __forceinline__ bool blk_move_legal(const BlkTables &T, const WaveLds
     const int64_t b = (int64_t)blockIdx.x * 4 + wave_;                                            \
     if (b >= B) return;
 
+// Everything above is what blokus_mcts.hip builds its kernel from: it includes this file with BLK_DEVICE_ONLY set and
+// stops here.  The search is a translation unit of its own so that the kernels below compile to what they compile to
+// without it (with the search kernel in this one, blokus_rollout_kernel went from 57 to 59 VGPRs).
+#ifdef BLK_DEVICE_ONLY
+} // namespace
+#else
+
 // ---- diagnostic build only (-DBLK_STAMPS): where a rollout step spends its cycles.  Stamp values leave the
 // kernel through g_blk_stamps alone; no output depends on them.  The shipped build compiles none of this.
 #if defined(BLK_STAMPS) || defined(BLK_COUNTERS)
@@ -1411,7 +1418,8 @@ blokus_rollout_kernel(const BlkTables *__restrict__ tables, const int64_t B, con
 // loop ends at the first terminal ply.  That loop body is NOT shared with the rollout, on purpose: with the ply in one
 // __forceinline__ helper called from both, blokus_rollout_kernel -- the benchmark's headline kernel, bound by instruction
 // issue -- went from 0 to 12 bytes of scratch, from 57 to 61 VGPRs and from 1772 to 1840 instructions.  Change both loops
-// together.  Lane 0 adds the playout's outcome into its row (integer atomics onto the zeros the launcher wrote).
+// together -- and with them the leaf playouts of blokus_mcts_kernel (blokus_mcts.hip), a third copy of the loop under the
+// search's counter words.  Lane 0 adds the playout's outcome into its row (integer atomics onto the zeros the launcher wrote).
 __device__ __forceinline__ uint64_t blk_uniform64(const uint64_t v)
 {
     return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v)
@@ -2223,3 +2231,5 @@ int crl_blokus_rollout_bind(const crl_ctx *ctx, int64_t B, uint64_t first_env_id
 }
 
 } // extern "C"
+
+#endif // BLK_DEVICE_ONLY

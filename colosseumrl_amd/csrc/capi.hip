@@ -208,6 +208,14 @@ int crl_diag_bounds(uint32_t *out12)
     }
     if (rc == CRL_OK) rc = crl_ttt_bounds(out12 + 4);
     if (rc == CRL_OK) rc = crl_blokus_bounds(out12 + 8);
+    if (rc == CRL_OK) {                                          // blokus_mcts.hip counts on its own, as tron_mcts.hip does
+        unsigned int m[4] = {0, 0, 0, 0};
+        rc = crl_blokus_mcts_bounds(m);
+        if (rc == CRL_OK && m[0] != 0u) {
+            if (out12[8] == 0u) { out12[9] = m[1]; out12[10] = m[2]; out12[11] = m[3]; }
+            out12[8] += m[0];
+        }
+    }
     if (rc != CRL_OK) return rc;
 #ifdef CRL_BOUNDS
     return 1;                                                    // the asserts are compiled in

@@ -339,3 +339,13 @@ class BlokusSinglePlayerVectorEnv:
     def step(self, action: torch.Tensor):
         _want(action, torch.int64, (self.num_envs,), self.batch.device, "action")
         return self._step(action)
+
+    def mcts_action(self, simulations: int, playouts: int = 1, width: int = 8, seed: int = 1, exploration: float = 1.0,
+                    candidates: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A tree search with progressive widening for the learner on the env's own games (``BlokusBatch.mcts_action``):
+        int64 [B] dense ids for ``step`` (-1 = pass) of an env made with ``action="id"``.  After ``reset`` / ``step`` it is
+        the learner's turn in every game, so the searched mover is the learner; every seat below the root plays the
+        search's own moves.  One launch, no host synchronisation, capturable."""
+        if self.rank:
+            raise ValueError("mcts_action returns dense ids: the env must be made with action='id'")
+        return self.batch.mcts_action(simulations, playouts, candidates, width, seed, exploration)

@@ -92,7 +92,8 @@ const char *crl_last_error(void);
  *      crl_ttt_sample_mcts / _rollout_mcts / _step_single_mcts (the search as a seated agent: three new entries, no new tag), and
  *      crl_tron_mcts / crl_tron_mcts_max_simulations (batched tree search for one seat of Tron: two new entries, no new tag), and
  *      crl_tron_mcts_territory (that search with Voronoi territory at the leaves: one new entry, no new tag), and
- *      crl_tron_sample_mcts_territory / _max_simulations (that search as a seated agent: two new entries, no new tag). */
+ *      crl_tron_sample_mcts_territory / _max_simulations (that search as a seated agent: two new entries, no new tag), and
+ *      crl_blokus_mcts / crl_blokus_mcts_max_simulations (tree search with progressive widening: two new entries, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -1018,6 +1019,72 @@ int crl_ttt_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_en
                  int S, int R, uint32_t cexp,
                  uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best,
                  uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------ batched tree search with progressive widening, Blokus
+ * crl_blokus_mcts: from each of B positions build a search tree of its own by S simulations s = 0 .. S-1, in order, each
+ * evaluated by R random playouts, and report the root's children.  One launch, no host sync, capturable into a graph.  Added
+ * under revision 113: new entries only, no new Philox tag, no existing struct, argument list or RNG contract changed.
+ * The state is read only, in the layouts of crl_blokus_playout; tcount uint32 [B] may be NULL, which means 0.
+ *
+ * Nodes.  Node 0 is the root, position b.  A node holds n, the number of simulations that passed through it; w, the playouts
+ * won by the player who made the move INTO it (bit q of the terminal winners mask, so a tie counts for every tied player;
+ * the root's w stays 0); and an ordered list of children, empty at first.  For a node v: p_v is its mover, L_v the number
+ * of legal actions of p_v there (crl_blokus_valid's count), d_v its depth in plies from the root.
+ * Children.  A position has hundreds of legal actions, so a node is widened progressively: it gets its k-th child only
+ * once it has been visited about k^2 times, and that child is a uniformly drawn legal action.
+ *   widening node (every node; the root when cand == NULL): cap = min(W, max(L_v, 1)).  With c children and n visits so far
+ *     (this simulation not counted) the node EXPANDS iff c < cap and c * c <= n, else it SELECTS.  The new child is the pass
+ *     (id -1) when L_v == 0; else u = Philox4x32-10(ctr = {g, 0x80000000 | d_v, s, 0x42500000}, key = {seed lo, seed hi})[0],
+ *     rho = mulhi32(u, L_v), and while rho is the rank of an existing child of v: rho = (rho + 1) mod L_v; the child is legal
+ *     action number rho of p_v in reference order (crl_blokus_select's answer), appended as slot c.
+ *   candidate root (cand != NULL, int32 [B][A], 1 <= A <= 64): column a is PLAYABLE iff cand[b][a] is a legal dense id of the
+ *     mover (crl_blokus_is_valid) and differs from every earlier playable column of the row.  The root expands the lowest
+ *     playable column that has no child; when all have one it selects.  Slot = column.  The nodes below the root widen as
+ *     above.  A row with no playable column is skipped: every slot empty, nodes 0, best -2.
+ * Descent.  A simulation starts at the root on a private copy of the position.
+ *   expand: the new child's ply is played as crl_blokus_step plays it; the child is the leaf, also when that ply is terminal.
+ *   select: the child with the greatest score(v, u) is taken, ties to the lowest slot, and its ply is played; if the ply is
+ *           terminal that child is the leaf, else the descent continues there.
+ * Score, crl_ttt_mcts's with wins counting 1, in 64-bit integers with floor divisions (lg and isqrt as stated there):
+ *   exploit = (w_u << 16) / (n_u * R),  X = (lg(n_v) << 24) / n_u,  score = exploit + ((cexp * isqrt(X)) >> 8).
+ * Evaluation of the leaf at depth d.  A terminal ply gives all R playouts its winners mask, and nothing is drawn.  Else R
+ * playouts r = 0 .. R-1, each crl_blokus_playout's random ply loop from the leaf's position to the first terminal ply:
+ * ply k has step counter c = tcount[b] + d + k (uint32 arithmetic), game id g = first_env_id + b (low 32 bits) and
+ *   w = Philox4x32-10(ctr = {g, (c >> 2) | 0x40000000, (s << 16) | r, 0x42500000}, key = {seed lo, seed hi})[c & 3];
+ * the mover plays legal action number mulhi32(w, n) of its n legal actions in reference order, '' (pass) when n = 0.
+ * Counter space: crl_blokus_playout's second counter word is c >> 2 < 2^30; the search sets bit 30 (playouts) or bit 31
+ * (widening draws) of that word, so under the shared tag 0x42500000 no block of one is a block of the other.
+ * Backup.  Every node on the path: n += 1; every one but the root, q the player who moved into it: w += the playouts whose
+ * winners mask has bit q.
+ * Outputs, every word overwritten; K = A with candidates, else W:
+ *   ids    int32  [B][K]   the child's dense id, -1 for the pass, -2 for an empty slot;
+ *   visits uint32 [B][K], value uint32 [B][K]   the child's n and w, 0 for an empty slot;
+ *   nodes  uint32 [B]      the node count, root included;
+ *   best   int32  [B]      the id of the root child with the most visits; ties go to the larger w, then to the lowest slot.
+ * Blokus keeps no "game over" field, so a finished position is not special: its root gets the pass as its only child and
+ * that ply is terminal.
+ * Limits (CRL_EINVAL, with a crl_last_error message, before any device work): NULL state or output pointers, B out of range
+ * (as the siblings), A outside [1, 64] with cand or A != 1 without it, W outside [1, 64], S outside [1, S_max], R outside
+ * [1, 1024], cexp > 65535, flags != 0, a context that is not a Blokus one.
+ * S_max = min(65535, (45056 - 1280) / 24 - 1) = 1823: a node takes 24 bytes of LDS (n, w, id, rank, L_v, and parent / slot /
+ * terminal / child count in one word), a tree besides its S + 1 nodes 1,280 bytes (the path of at most min(S, 336) plies --
+ * 84 placements exist and at most three passes separate two of them --, the playout counts, the child slots of the node
+ * being looked at), and the trees of a workgroup get 45,056 bytes of its 64 KB beside the piece tables and the four waves'
+ * boards; s has 16 bits in its counter word.  crl_blokus_mcts_max_simulations returns S_max (a negative code on a bad
+ * context).
+ * The tree lives in LDS.  R < 4: one wave per tree, as many trees per workgroup (up to four) as fit; R >= 4: one workgroup
+ * per tree, every wave replaying the descent on its own board and taking every fourth playout, wave 0 writing the tree
+ * between workgroup barriers.  Both give the same bits.  The wave's lanes are the children while it selects (the arg-max is
+ * a cross-lane reduction, ties by the lowest lane) and while it probes the ranks.  A node caches its id, its rank, L_v once
+ * counted and whether the ply into it was terminal, so a descent through existing nodes only places pieces.  Nothing is
+ * shared between trees, so the results do not depend on the order of the waves. */
+int crl_blokus_mcts_max_simulations(const crl_ctx *ctx);
+int crl_blokus_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                    const uint32_t *occ, const uint32_t *inv, const int32_t *score, const int32_t *round,
+                    const int32_t *to_move, const uint32_t *tcount,
+                    const int32_t *cand, int A, int W, int S, int R, uint32_t cexp,
+                    int32_t *ids, uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best,
+                    uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ the tree search as a seated agent of TicTacToe
  * The search of crl_ttt_mcts in the three forms the random and the tactical agent have: one step, a fused rollout with

@@ -156,6 +156,9 @@ PROTOTYPES = {
     "crl_blokus_playout": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 7 + [_I, _I] + [_VP] * 4 + [_U32, _VP]),
     "crl_blokus_mcts_max_simulations": (_I, [_VP]),
     "crl_blokus_mcts": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 7 + [_I, _I, _I, _I, _U32] + [_VP] * 5 + [_U32, _VP]),
+    "crl_blokus_sample_mcts": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 6 + [_I, _I, _I, _I, _U32, C.c_double, _VP, _VP]),
+    "crl_blokus_rollout_mcts": (_I, [_VP, _I64, _U64, _U64, _I, _I, _I, _I, _U32, C.c_double] + [_VP] * 5 + [BlokusStats, _VP]),
+    "crl_blokus_step_single_mcts": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 15 + [_I, _I, _I, _U32, C.c_double, _U32, _VP]),
     "crl_tron_rollout_bind": (_I, [_VP, _I64, _U64, _VP, _VP, _VP, _VP, TronStats, _U32, C.POINTER(_VP)]),
     "crl_ttt_rollout_bind": (_I, [_VP, _I64, _U64, _VP, _VP, _VP, TTTStats, C.POINTER(_VP)]),
     "crl_blokus_rollout_bind": (_I, [_VP, _I64, _U64, _VP, _VP, _VP, _VP, _VP, BlokusStats, C.POINTER(_VP)]),

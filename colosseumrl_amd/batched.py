@@ -1263,8 +1263,11 @@ class BlokusBatch(_RolloutStepper):
             out["ids"] = self.valid_list(int(list_cap), out=ids)[1]
         return out
 
+    OPPONENTS = ("random", "mcts")          # who `step_single` seats
+
     def step_single(self, seat: torch.Tensor, learner_action: Optional[torch.Tensor] = None, seed: int = 0,
-                    rank: bool = False, out: Optional[dict] = None):
+                    rank: bool = False, out: Optional[dict] = None, opponent: str = "random", noise: float = 0.0,
+                    simulations: int = 64, playouts: int = 1, width: int = 8, exploration: float = 1.0):
         """One step of "learner at seat[b] against the random agent" in every game, ONE launch (``crl_blokus_step_single``):
         the learner plays ``learner_action`` (int64 [B]: a dense or extended id, < 0 = pass; with ``rank=True`` the index
         into its ordered legal list, outside [0, count) = pass) when it is its turn, the random agent plays the other
@@ -1272,14 +1275,20 @@ class BlokusBatch(_RolloutStepper):
         advances to the learner's turn.  seat int8 [B].  Returns {'board', 'pieces', 'score' (the learner's observation),
         'n_valid' int32 [B] (its number of legal actions), 'reward' int8 [B] (its final rank when a game ended, else 0, or
         a ``CRL_BLOKUS_*_ERROR`` code for an action the reference's next_state raises on -- that game then stays as it
-        was), 'done' uint8 [B], 'winners' uint8 [B]}; every ply, the learner's included, advances ``tcount``."""
+        was), 'done' uint8 [B], 'winners' uint8 [B]}; every ply, the learner's included, advances ``tcount``.
+        ``opponent="mcts"``: every other seat plays the search agent (``crl_blokus_step_single_mcts``; ``sample_mcts``'s moves)
+        with ``simulations``, ``playouts``, ``width``, ``exploration`` and ``noise``; still one launch.  The keywords are
+        checked for either opponent and used only with that one."""
         _want(seat, torch.int8, (self.B,), self.device, "seat")
         if learner_action is not None:
             _want(learner_action, torch.int64, (self.B,), self.device, "learner_action")
+        opponent = _one_of("opponent", opponent, self.OPPONENTS)
+        search = self._agent_args(simulations, playouts, width, exploration, noise)
+        name, tail = ("crl_blokus_step_single_mcts", search) if opponent == "mcts" else ("crl_blokus_step_single", ())
         out = out or _alloc(dict(self._obs_spec(), done=(torch.uint8, (self.B,))), self.device)
-        self._call("crl_blokus_step_single", _seed(seed), self.first_env_id, *self._state(), _ptr(seat), _ptr(learner_action),
+        self._call(name, _seed(seed), self.first_env_id, *self._state(), _ptr(seat), _ptr(learner_action),
                    _ptr(self.tcount), _ptr(self.reward), _ptr(out["done"]), _ptr(self.winners), _ptr(out["n_valid"]),
-                   _ptr(out["board"]), _ptr(out["pieces"]), _ptr(out["score"]), CRL_STEP_RANK_ACTION if rank else 0)
+                   _ptr(out["board"]), _ptr(out["pieces"]), _ptr(out["score"]), *tail, CRL_STEP_RANK_ACTION if rank else 0)
         out["reward"], out["winners"] = self.reward, self.winners
         return out
 
@@ -1352,6 +1361,34 @@ class BlokusBatch(_RolloutStepper):
         """``mcts``'s most visited child as an int64 [B] action for ``step_single`` (-1 = pass, also where no candidate was
         playable).  No host synchronisation; capturable."""
         return self.mcts(simulations, playouts, candidates, width, seed, exploration, out)["best"].to(torch.int64).clamp_(min=-1)
+
+    # -- the search as a seated agent; the contract is with crl_blokus_sample_mcts in include/colosseum_hip.h
+    def _agent_args(self, simulations, playouts, width, exploration, noise):
+        """(W, S, R, cexp, noise) of the search agent as the C entries take them, checked"""
+        S = _int_in("simulations", simulations, 1, self.mcts_max_simulations)
+        R = _int_in("playouts", playouts, 1, 1024)
+        W = _int_in("width", width, 1, 64)
+        return (W, S, R, _exploration("exploration", exploration), _unit("noise", noise))
+
+    def sample_mcts(self, simulations: int, playouts: int = 1, width: int = 8, seed: int = 0, exploration: float = 1.0,
+                    noise: float = 0.0, advance: bool = True):
+        """The search agent for one step (``crl_blokus_sample_mcts``): int32 [B] dense id at each game's step counter -- -1
+        (pass) for a mover without actions, with probability ``noise`` the random agent's action (``sample``'s draw: at
+        ``noise=1`` the same move), else ``best`` of ``mcts(simulations, playouts, None, width, seed, exploration)`` on the
+        position with the counter as its base.  ``step(sample_mcts(...), auto_reset=True)`` T times == ``rollout_mcts(T,
+        ...)``.  One launch; no host synchronisation, capturable into a graph."""
+        search = self._agent_args(simulations, playouts, width, exploration, noise)
+        act = torch.empty((self.B,), dtype=torch.int32, device=self.device)
+        self._call("crl_blokus_sample_mcts", _seed(seed), self.first_env_id, *self._state(), _ptr(self.tcount), int(advance),
+                   *search, _ptr(act))
+        return act
+
+    def rollout_mcts(self, steps: int, simulations: int, playouts: int = 1, width: int = 8, seed: int = 0,
+                     exploration: float = 1.0, noise: float = 0.0):
+        """``rollout`` with every seat on the search agent (``crl_blokus_rollout_mcts``): self-play of the search in one
+        launch, with the same statistics tensors, ``results()`` rows and step counter."""
+        search = self._agent_args(simulations, playouts, width, exploration, noise)
+        self._call("crl_blokus_rollout_mcts", _seed(seed), self.first_env_id, int(steps), *search, *self._state(), self._stats())
 
     def board(self):
         out = torch.empty((self.B, 20, 20), dtype=torch.int8, device=self.device)

@@ -1167,7 +1167,8 @@ blokus_step_observe_kernel(const BlkTables *__restrict__ tables, const int64_t B
 // a chain of step_observe calls reloads the board and rebuilds the allowed / corner rows per ply.  Each ply is made of what
 // blokus_step_observe_kernel's is: blk_agent_word's draw, blk_encode of the selected move, blk_next_state.  Its own are the
 // learner's action (an id or a rank), the learner's reward and the restart without a flag.  The loop runs on wave-uniform
-// values (mover, seat, step counter), so it costs no divergence.
+// values (mover, seat, step counter), so it costs no divergence.  (blokus_mcts_agent.hip holds a copy of this loop with the
+// search agent as the opponents: change them together.)
 __global__ void __launch_bounds__(256, BLK_WAVES_PER_SIMD)
 blokus_step_single_kernel(const BlkTables *__restrict__ tables, const int64_t B, const uint32_t seed_lo, const uint32_t seed_hi,
                           const uint64_t first_env_id, uint32_t *__restrict__ occ, uint32_t *__restrict__ inv_g,

@@ -20,6 +20,8 @@
 // and the terminal test (blk_anyone_moves on the pre-move rows, as blk_next_state).
 // The leaf's playouts are blokus_playout_kernel's ply loop under the search's counter words -- a COPY, as that loop is
 // one of blokus_rollout_kernel's (see the comment above blokus_playout_kernel): change the three together.
+// blokus_mcts_agent.hip holds a COPY of this kernel's search, from the root's set-up to the pick of the most visited
+// child, without the candidate root (the seated search agent): change them together.
 #define BLK_DEVICE_ONLY
 #include "blokus.hip"
 

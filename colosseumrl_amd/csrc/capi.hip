@@ -216,6 +216,14 @@ int crl_diag_bounds(uint32_t *out12)
             out12[8] += m[0];
         }
     }
+    if (rc == CRL_OK) {                                          // ... and so does blokus_mcts_agent.hip
+        unsigned int m[4] = {0, 0, 0, 0};
+        rc = crl_blokus_mcts_agent_bounds(m);
+        if (rc == CRL_OK && m[0] != 0u) {
+            if (out12[8] == 0u) { out12[9] = m[1]; out12[10] = m[2]; out12[11] = m[3]; }
+            out12[8] += m[0];
+        }
+    }
     if (rc != CRL_OK) return rc;
 #ifdef CRL_BOUNDS
     return 1;                                                    // the asserts are compiled in

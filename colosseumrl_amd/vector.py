@@ -309,13 +309,24 @@ class BlokusSinglePlayerVectorEnv:
     ``ids[b, :n_valid[b]]`` is written).  All of them are buffers that the next ``step`` / ``reset`` rewrites.
     A step is ONE launch (``crl_blokus_step_single``; a second, ``crl_blokus_valid_list``, with ``list_cap`` > 0), has no
     host synchronisation and can be captured into a HIP graph.  The opponents' draws are ``crl_blokus_sample``'s at each
-    game's step counter, keyed by ``seed``; the learner's ply advances the counter as well."""
+    game's step counter, keyed by ``seed``; the learner's ply advances the counter as well.
+    ``opponent="mcts"`` seats the tree search in the other three seats (``crl_blokus_step_single_mcts``,
+    ``BlokusBatch.sample_mcts``'s moves): with probability ``noise`` the random agent's action, else the most visited child
+    of ``simulations`` descents of ``playouts`` playouts each, nodes up to ``width`` children wide, with ``exploration``.
+    The step stays one launch.  The five keywords are checked and otherwise unused with the random opponent."""
 
-    def __init__(self, batch: int = 1024, seat=0, seed: int = 0, list_cap: int = 0, action: str = "id", device="cuda"):
+    def __init__(self, batch: int = 1024, seat=0, seed: int = 0, list_cap: int = 0, action: str = "id", device="cuda",
+                 opponent: str = "random", noise: float = 0.0, simulations: int = 64, playouts: int = 1, width: int = 8,
+                 exploration: float = 1.0):
         if action not in ("id", "rank"):
             raise ValueError("action must be 'id' or 'rank', not %r" % (action,))
         if list_cap < 0:
             raise ValueError("list_cap must be >= 0")
+        self.opponent = _one_of("opponent", opponent, BlokusBatch.OPPONENTS)
+        _exploration("exploration", exploration)
+        self._search = dict(noise=_unit("noise", noise), simulations=_int_in("simulations", simulations, 1, 1823),   # S_max of crl_blokus_mcts
+                            playouts=_int_in("playouts", playouts, 1, 1024), width=_int_in("width", width, 1, 64),
+                            exploration=exploration)
         self.batch = BlokusBatch(batch, device=device)
         self.num_players, self.num_envs, self.seed = 4, batch, int(seed)
         self.list_cap, self.rank = int(list_cap), action == "rank"
@@ -325,7 +336,8 @@ class BlokusSinglePlayerVectorEnv:
                      if self.list_cap > 0 else None)
 
     def _step(self, action):
-        self._out = self.batch.step_single(self.seat, action, self.seed, rank=self.rank, out=self._out)
+        self._out = self.batch.step_single(self.seat, action, self.seed, rank=self.rank, out=self._out, opponent=self.opponent,
+                                           **self._search)
         o = self._out
         info = {"n_valid": o["n_valid"], "winners": o["winners"]}
         if self._ids is not None:

@@ -1086,6 +1086,54 @@ int crl_blokus_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first
                     int32_t *ids, uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best,
                     uint32_t flags, void *stream);
 
+/* ------------------------------------------------------------------ the tree search as a seated agent of Blokus
+ * The search of crl_blokus_mcts in the three forms the random agent has: one step, a fused rollout with every seat on it, and
+ * the opponents of the single-player step.  Added under revision 113: new entries only, no new Philox tag, no existing
+ * struct, argument list or RNG contract changed.
+ * The search agent has the parameters W, S, R, cexp (crl_blokus_mcts's) and noise in [0, 1].  Its move for the mover
+ * p = to_move[b] & 3 at step counter c of global game g = first_env_id + b (low 32 bits):
+ *   1. n = the number of legal actions of p (crl_blokus_valid's count).  n == 0: the action is -1 (the pass); nothing is
+ *      drawn and nothing is searched.  (crl_blokus_mcts would answer the same: the pass would be the root's only child.)
+ *   2. u = Philox4x32-10(ctr = {g, 0xC0000000 | (c >> 2), 0, 0x42500000}, key = {seed lo, seed hi})[c & 3].  Both top bits
+ *      of the second counter word are set: crl_blokus_playout has neither, the search's playouts set only bit 30 and its
+ *      widening draws only bit 31, so under the shared tag no block of one is a block of another.
+ *   3. noisy  iff  u < thr,  thr = min(2^32, ceil(noise * 2^32)): noise = 0 is never noisy, noise = 1 always.
+ *   4. noisy: the action is crl_blokus_sample's at that counter -- its word under tag 0x424c0000, rank mulhi32(word, n).
+ *      With noise = 1 the agent therefore is the random agent bit for bit.
+ *   5. else the action is `best` of crl_blokus_mcts(cand = NULL, A = 1, W, S, R, cexp) on this position with tcount[b] taken
+ *      as c; every draw of that search is exactly as its contract says.  The root always widens (no candidate roots).
+ * Errors (CRL_EINVAL, with a crl_last_error message, before any device work; the context's check comes last): everything
+ * the random sibling of each entry refuses, W outside [1, 64], S outside [1, S_max] (crl_blokus_mcts_max_simulations: the
+ * same 1823 -- the word that hands `best` to the other waves of a workgroup fits the spare bytes of a tree's fixed part),
+ * R outside [1, 1024], cexp > 65535, noise outside [0, 1] or NaN.
+ * The tree lives in LDS with crl_blokus_mcts's layout and mappings: R < 4 one wave per game (up to four games per workgroup
+ * as the trees fit), R >= 4 one workgroup per game, every wave replaying the game and the search's descents, wave 0 writing
+ * the tree, the state and the outputs.  Both give the same bits.  The wave's LDS board is the search's scratch, so between
+ * searches the wave keeps the position in registers; a noisy ply or a pass does not search.
+ *
+ * action[b] = the search agent's move at step counter tcount[b]; advance != 0 also increments tcount (passes included), as
+ * crl_blokus_sample.  The state is read only. */
+int crl_blokus_sample_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, const uint32_t *occ,
+                           const uint32_t *inventory, const int32_t *score, const int32_t *round, const int32_t *to_move,
+                           uint32_t *tcount, int advance, int W, int S, int R, uint32_t cexp, double noise,
+                           int32_t *action, void *stream);
+/* crl_blokus_rollout with EVERY seat on the search agent: the same auto-reset, crl_blokus_stats bookkeeping and results row,
+ * the same checks of T (T = 0 launches nothing).  It has no launch-plan bind entry.
+ * T x (crl_blokus_sample_mcts(advance = 1); crl_blokus_step with CRL_STEP_AUTO_RESET) == crl_blokus_rollout_mcts(T). */
+int crl_blokus_rollout_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id, int T, int W, int S, int R,
+                            uint32_t cexp, double noise, uint32_t *occ, uint32_t *inv, int32_t *score, int32_t *round,
+                            int32_t *to_move, crl_blokus_stats stats, void *stream);
+/* crl_blokus_step_single word for word, except that in its step 2 the opponents' action is what
+ * crl_blokus_sample_mcts(advance = 1) returns on that state -- the opponents who open a game that restarted inside the call
+ * included: they search from the empty board.  The learner's ply (by id or by rank), the error codes that leave the game as
+ * it was, and the reward, done, winners, n_valid and observation outputs are that entry's. */
+int crl_blokus_step_single_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                                uint32_t *occ, uint32_t *inv, int32_t *score, int32_t *round, int32_t *to_move,
+                                const int8_t *seat, const int64_t *learner_action, uint32_t *tcount,
+                                int8_t *reward, uint8_t *done, uint8_t *winners, int32_t *n_valid,
+                                int8_t *obs_board, uint8_t *obs_pieces, int32_t *obs_score,
+                                int W, int S, int R, uint32_t cexp, double noise, uint32_t flags, void *stream);
+
 /* ------------------------------------------------------------------ the tree search as a seated agent of TicTacToe
  * The search of crl_ttt_mcts in the three forms the random and the tactical agent have: one step, a fused rollout with
  * every seat on it, and the opponents of the single-player step.  Added under revision 113: new entries only, no new Philox

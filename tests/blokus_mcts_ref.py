@@ -82,8 +82,16 @@ class Node:
 
 def search(root, S, R, W=8, cexp=256, seed=0, g=0, tc=0, cand=None, count=None):
     """the tree of one position.  cand: a sequence of A dense ids, or None.  count: a dict whose 'plies' / 'playouts' grow
-    by what the leaf playouts played."""
+    by what the leaf playouts played, and which counts the edges the search went over: 'depth' the longest path in plies
+    (a maximum), 'deep' the simulations whose path has 64 plies or more, 'sel_term' those that end on a terminal node
+    reached by selection, 'probes' / 'wraps' the steps of the rank probe and those of them that go from L - 1 to 0, 'full'
+    the expansions that give a node with L >= 1 legal actions its L-th child, 'deep_sel' the selections between two or more
+    children below a node of depth 63 or more (they read n and w of nodes 64 plies or more down the path)."""
     assert 1 <= S <= S_MAX and 1 <= R <= 1024 and 1 <= W <= 64 and 0 <= cexp <= 65535
+
+    def note(key, by=1):
+        if count is not None:
+            count[key] = count.get(key, 0) + by
     pl0 = int(root.to_move[0]) & 3
     K = W if cand is None else len(cand)
     top = Node()
@@ -118,8 +126,11 @@ def search(root, S, R, W=8, cexp=256, seed=0, g=0, tc=0, cand=None, count=None):
                         rho = (widen_word(seed, g, d, s) * v.L) >> 32
                         taken = set(u.rank for u in v.slots.values())
                         while rho in taken:
+                            note("probes")
+                            note("wraps", int(rho + 1 == v.L))
                             rho = (rho + 1) % v.L
                         act = int(ids[rho])
+                        note("full", int(c + 1 == v.L))
                 term, ws = _step(one, act)
                 u = Node(act, rho, term)
                 v.slots[slot] = u
@@ -127,6 +138,7 @@ def search(root, S, R, W=8, cexp=256, seed=0, g=0, tc=0, cand=None, count=None):
             else:
                 slot = max(sorted(v.slots), key=lambda k: score(v.n, v.slots[k].n, v.slots[k].w, R, cexp))   # (the first of equals)
                 u = v.slots[slot]
+                note("deep_sel", int(d >= 63 and c >= 2))
                 term, ws = _step(one, u.id)
                 assert term == u.term
             d += 1
@@ -134,6 +146,10 @@ def search(root, S, R, W=8, cexp=256, seed=0, g=0, tc=0, cand=None, count=None):
             if expand or term or d >= MAX_DEPTH:
                 break
             v = u
+        if count is not None:
+            count["depth"] = max(count.get("depth", 0), d)
+            note("deep", int(d >= 64))
+            note("sel_term", int(term and not expand))
         if term:
             wins = [R * ((ws >> q) & 1) for q in range(4)]
         else:

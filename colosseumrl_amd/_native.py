@@ -136,6 +136,11 @@ PROTOTYPES = {
     "crl_ttt_sample_mcts": (_I, [_VP, _I64, _U64, _U64, _VP, _VP, _VP, _I, _I, _I, _U32, C.c_double, _VP, _VP]),
     "crl_ttt_rollout_mcts": (_I, [_VP, _I64, _U64, _U64, _I, _I, _I, _U32, C.c_double, _VP, _VP, _VP, TTTStats, _VP]),
     "crl_ttt_step_single_mcts": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 11 + [_I, _I, _I, _U32, C.c_double, _U32, _VP]),
+    "crl_ttt_puct_tree_bytes": (_I64, [_VP, _I]),
+    "crl_ttt_puct_begin": (_I, [_VP, _I64, _VP, _VP, _VP, _I, _VP, _VP]),
+    "crl_ttt_puct_select": (_I, [_VP, _I64, _VP, _I, _U32, _U32, _I] + [_VP] * 5 + [_U32, _VP]),
+    "crl_ttt_puct_backup": (_I, [_VP, _I64, _VP, _I, _VP, _VP, _U32, _VP]),
+    "crl_ttt_puct_root": (_I, [_VP, _I64, _VP, _I] + [_VP] * 6 + [_VP]),
     "crl_blokus_create": (_I, [C.POINTER(_VP)]),
     "crl_blokus_placement": (_I, [_I, _I, _I, _VP]),
     "crl_blokus_stamps": (_I, [_VP, _I]),

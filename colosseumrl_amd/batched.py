@@ -1062,6 +1062,113 @@ class TTTBatch(_RolloutStepper):
         self._call("crl_ttt_rollout_mcts", _seed(seed), self.first_env_id, int(steps), S, R, cexp, noise, _ptr(self.occ),
                    _ptr(self.winner), _ptr(self.to_move), self._stats())
 
+    # -- the search valued by the caller's network (PUCT); the contract is with crl_ttt_puct_begin in include/colosseum_hip.h
+    PUCT_MAX_CAPACITY = 4095
+
+    def _puct_open(self):
+        if getattr(self, "_puct_cap", None) is None:
+            raise ValueError("no search is open: call puct_begin(capacity) first")
+        return self._puct_tree, self._puct_cap
+
+    def _puct_select_spec(self):
+        return dict(self._obs_spec(), mover=(torch.int8, (self.B,)), pending=(torch.uint8, (self.B,)),
+                    leaf_occ=(torch.int32, (self.P, self.B)))
+
+    def _puct_root_spec(self):
+        i32, Bc = torch.int32, (self.B, self.n_cells)
+        return {"visits": (i32, Bc), "value": (i32, Bc), "prior": (i32, Bc), "nodes": (i32, (self.B,)), "sims": (i32, (self.B,)),
+                "best": (i32, (self.B,))}
+
+    def puct_begin(self, capacity: int):
+        """Opens a search of at most ``capacity`` (1 .. 4095) simulations from every game's position (``crl_ttt_puct_begin``):
+        the trees live in a device tensor of this stepper, allocated here or reused when the capacity is the last one's, and
+        hold their own copy of the position -- the batch may be stepped while the search is open.  Finished positions make
+        skipped trees.  One launch, no host synchronisation."""
+        cap = _int_in("capacity", capacity, 1, self.PUCT_MAX_CAPACITY)
+        if getattr(self, "_puct_cap", None) != cap:
+            nbytes = self._lib.crl_ttt_puct_tree_bytes(self._ctx.handle, cap)
+            if nbytes < 0:
+                check(int(nbytes), "crl_ttt_puct_tree_bytes")
+            with torch.cuda.device(self.device):
+                self._puct_tree = torch.empty((self.B, int(nbytes) // 16, 2), dtype=torch.int64, device=self.device)   # (16-byte units)
+            self._puct_cap = cap
+        self._call("crl_ttt_puct_begin", _ptr(self.occ), _ptr(self.winner), _ptr(self.to_move), cap, _ptr(self._puct_tree))
+
+    def puct_select(self, exploration: float = 1.25, fpu: float = 0.5, rel_mod: Optional[int] = None, out: Optional[dict] = None):
+        """One descent of every open tree (``crl_ttt_puct_select``): ``exploration`` is c of the PUCT score (0 .. 65535 / 256),
+        ``fpu`` the value in [0, 1] of a child without a visit.  Returns the leaves that wait for the caller's network:
+        {'board' int8 [B, cells] relative to the leaf's mover, 'valid' int32 [B] empties mask, 'mover' int8 [B], 'pending'
+        uint8 [B], 'leaf_occ' int32 [P, B] the leaf position in the state layout}; rows whose tree has no pending leaf (skipped,
+        a terminal leaf, at capacity) are zeros with mover -1.  ``out`` reuses such a dict.  One launch, no host synchronisation."""
+        tree, cap = self._puct_open()
+        cpuct = _exploration("exploration", exploration)
+        fpu16 = int(round(65536.0 * _unit("fpu", fpu)))
+        rel = self.P if rel_mod is None else _int_in("rel_mod", rel_mod, 1, 127)
+        out = _out_dict(out, self._puct_select_spec(), self.device)
+        self._call("crl_ttt_puct_select", _ptr(tree), cap, cpuct, fpu16, rel, _ptr(out["board"]), _ptr(out["valid"]),
+                   _ptr(out["mover"]), _ptr(out["pending"]), _ptr(out["leaf_occ"]), 0)
+        return out
+
+    def puct_backup(self, prior: torch.Tensor, value: torch.Tensor):
+        """Expands the pending leaves with ``prior`` (uint16 [B, cells], or int16 of the same bits: any weights, normalised
+        over the leaf's empty cells) and backs ``value`` up (int32 [B, P]: the value on 0 .. 65536 of the leaf's mover, then of
+        the players after it in turn order); terminal leaves back their outcome up (``crl_ttt_puct_backup``).  One launch."""
+        tree, cap = self._puct_open()
+        if not isinstance(prior, torch.Tensor) or prior.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            raise ValueError("prior must be a uint16 (or int16) tensor of shape (%d, %d)" % (self.B, self.n_cells))
+        _want(prior, prior.dtype, (self.B, self.n_cells), self.device, "prior")
+        if not isinstance(value, torch.Tensor):
+            raise ValueError("value must be an int32 tensor of shape (%d, %d)" % (self.B, self.P))
+        _want(value, torch.int32, (self.B, self.P), self.device, "value")
+        self._call("crl_ttt_puct_backup", _ptr(tree), cap, _ptr(prior), _ptr(value), 0)
+
+    def puct_root(self, out: Optional[dict] = None):
+        """The root of every open tree (``crl_ttt_puct_root``): {'visits', 'value', 'prior' int32 [B, cells]: simulations through
+        the root's child at each cell, its summed value for the root's mover (65536 per won simulation) and the root's stored
+        priors, 'nodes', 'sims', 'best' int32 [B]: the most visited cell (ties: the larger value, then the lowest cell; -1
+        without a visited child)}.  The visit counts are the policy target of an AlphaZero-style trainer.  One launch."""
+        tree, cap = self._puct_open()
+        out = _out_dict(out, self._puct_root_spec(), self.device)
+        self._call("crl_ttt_puct_root", _ptr(tree), cap, _ptr(out["visits"]), _ptr(out["value"]), _ptr(out["prior"]),
+                   _ptr(out["nodes"]), _ptr(out["sims"]), _ptr(out["best"]))
+        return out
+
+    @staticmethod
+    def puct_quantize(policy: torch.Tensor, value: torch.Tensor):
+        """(float policy [B, cells]: any non-negative weights, float value [B, P] in [0, 1]) -> (int16 prior holding the
+        contract's uint16 bits, int32 value on 0 .. 65536) for ``puct_backup``.  Each row's weights are scaled so that its
+        greatest is 65535 (the backup normalises over the empty cells anyway); NaN counts as 0.  Torch operations only."""
+        pol = torch.nan_to_num(policy.to(torch.float32), nan=0.0, posinf=0.0).clamp_min(0.0)
+        top = pol.amax(dim=1, keepdim=True).clamp_min(1e-30)
+        q = torch.round(pol * (65535.0 / top)).to(torch.int32).clamp(0, 65535)
+        prior = torch.where(q >= 32768, q - 65536, q).to(torch.int16)
+        val = torch.round(torch.nan_to_num(value.to(torch.float32), nan=0.5).clamp(0.0, 1.0) * 65536.0).to(torch.int32)
+        return prior.contiguous(), val.contiguous()
+
+    def puct(self, evaluate, simulations: int, exploration: float = 1.25, fpu: float = 0.5, out: Optional[dict] = None):
+        """A whole search: ``puct_begin(simulations)``, then ``simulations`` times ``puct_select`` -> ``evaluate(leaves)`` ->
+        ``puct_backup``, then ``puct_root``.  ``evaluate`` takes the select dict and returns (prior, value), either the integer
+        tensors of ``puct_backup`` or float tensors (then ``puct_quantize`` turns them).  Two launches per simulation beside the
+        caller's network; no host synchronisation.  Returns the root dict (``out`` reuses one)."""
+        if not callable(evaluate):
+            raise ValueError("evaluate must be callable: the select dict -> (prior, value)")
+        S = _int_in("simulations", simulations, 1, self.PUCT_MAX_CAPACITY)
+        _exploration("exploration", exploration), _unit("fpu", fpu)
+        self.puct_begin(S)
+        leaves = None
+        for _ in range(S):
+            leaves = self.puct_select(exploration, fpu, out=leaves)
+            prior, value = evaluate(leaves)
+            if prior.is_floating_point() or value.is_floating_point():
+                prior, value = self.puct_quantize(prior, value)
+            self.puct_backup(prior, value)
+        return self.puct_root(out)
+
+    def puct_action(self, evaluate, simulations: int, exploration: float = 1.25, fpu: float = 0.5,
+                    out: Optional[dict] = None) -> torch.Tensor:
+        """``puct``'s most visited cell as an int64 [B] action for ``step_single`` (-1 where the game is over)."""
+        return self.puct(evaluate, simulations, exploration, fpu, out)["best"].to(torch.int64)
+
     def rollout(self, steps: int, seed: int = 0):
         self._rollout_plan(steps, seed)
 

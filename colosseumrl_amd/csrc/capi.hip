@@ -207,6 +207,14 @@ int crl_diag_bounds(uint32_t *out12)
         }
     }
     if (rc == CRL_OK) rc = crl_ttt_bounds(out12 + 4);
+    if (rc == CRL_OK) {                                          // ttt_puct.hip counts on its own, as tron_mcts.hip does
+        unsigned int m[4] = {0, 0, 0, 0};
+        rc = crl_ttt_puct_bounds(m);
+        if (rc == CRL_OK && m[0] != 0u) {
+            if (out12[4] == 0u) { out12[5] = m[1]; out12[6] = m[2]; out12[7] = m[3]; }
+            out12[4] += m[0];
+        }
+    }
     if (rc == CRL_OK) rc = crl_blokus_bounds(out12 + 8);
     if (rc == CRL_OK) {                                          // blokus_mcts.hip counts on its own, as tron_mcts.hip does
         unsigned int m[4] = {0, 0, 0, 0};

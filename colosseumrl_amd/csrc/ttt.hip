@@ -306,6 +306,11 @@ __device__ __forceinline__ int ttt_tactical_move(const ttt_dirs &dd, const uint3
     return nth_set_bit(S, (int)__umulhi(v, (uint32_t)__popc(S)));
 }
 
+// Everything above, and the dispatch macros behind the kernels, is what ttt_puct.hip builds its kernels from: it includes
+// this file with TTT_DEVICE_ONLY set and takes neither the kernels nor the entries.  That search is a translation unit of
+// its own so that the kernels below compile to what they compile to without it.
+#ifndef TTT_DEVICE_ONLY
+
 template <int P, int ND>
 __global__ void __launch_bounds__(256)
 ttt_step_kernel(const ttt_dirs dd, const int64_t B, uint32_t *__restrict__ occ, int8_t *__restrict__ winner,
@@ -1898,6 +1903,8 @@ inline const uint32_t *ttt_win_table_here(const crl_ctx *ctx)
 // floor(2^32 / cells) + 1: ttt_write_boards divides by the cell count with one multiply-high
 inline uint32_t ttt_inv_cells(const int cells) { return cells == 1 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint64_t)cells) + 1u; }
 
+#endif // TTT_DEVICE_ONLY (the kernels)
+
 } // namespace
 
 #define TTT_DISPATCH_P(P_, ...)            \
@@ -1938,6 +1945,8 @@ inline uint32_t ttt_inv_cells(const int cells) { return cells == 1 ? 0u : (uint3
 // (a launcher that serves an agent's entry as well gets its noise by pointer, NULL from the random agent's entry, and
 // checks it where the tactical entry always did)
 #define TTT_NOISE_CHECK(fn) CRL_REQUIRE(noise == nullptr || (*noise >= 0.0 && *noise <= 1.0), "%s: noise=%g outside [0, 1]", fn, *noise)   /* (NaN fails too) */
+
+#ifndef TTT_DEVICE_ONLY
 
 int crl_ttt_bounds(unsigned int *out4)
 {
@@ -2497,3 +2506,5 @@ int crl_ttt_step_single_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint6
 }
 
 } // extern "C"
+
+#endif // TTT_DEVICE_ONLY (the entries)

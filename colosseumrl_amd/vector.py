@@ -290,6 +290,14 @@ class TicTacToeSinglePlayerVectorEnv:
         ``TTTBatch.mcts`` dict to reuse (its 'visits' are a policy target)."""
         return self.batch.mcts_action(simulations, playouts, seed, exploration, out)
 
+    def puct_action(self, evaluate, simulations: int, exploration: float = 1.25, fpu: float = 0.5,
+                    out: Optional[dict] = None) -> torch.Tensor:
+        """A tree search valued by the caller's network for the learner on the env's own games (``TTTBatch.puct_action``):
+        ``evaluate`` takes the leaves (``TTTBatch.puct_select``'s dict) and returns (prior, value).  int64 [B] actions for
+        ``step``; two launches per simulation beside the network, no host synchronisation.  ``out``: the ``TTTBatch.puct_root``
+        dict to reuse (its 'visits' are a policy target)."""
+        return self.batch.puct_action(evaluate, simulations, exploration, fpu, out)
+
 
 class BlokusSinglePlayerVectorEnv:
     """B Blokus games of one learner against the random agent in the other three seats: the turn-based counterpart of

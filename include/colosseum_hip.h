@@ -93,7 +93,8 @@ const char *crl_last_error(void);
  *      crl_tron_mcts / crl_tron_mcts_max_simulations (batched tree search for one seat of Tron: two new entries, no new tag), and
  *      crl_tron_mcts_territory (that search with Voronoi territory at the leaves: one new entry, no new tag), and
  *      crl_tron_sample_mcts_territory / _max_simulations (that search as a seated agent: two new entries, no new tag), and
- *      crl_blokus_mcts / crl_blokus_mcts_max_simulations (tree search with progressive widening: two new entries, no new tag). */
+ *      crl_blokus_mcts / crl_blokus_mcts_max_simulations (tree search with progressive widening: two new entries, no new tag), and
+ *      crl_ttt_puct_tree_bytes / _begin / _select / _backup / _root (tree search valued by the caller: five new entries, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -1019,6 +1020,103 @@ int crl_ttt_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_en
                  int S, int R, uint32_t cexp,
                  uint32_t *visits, uint32_t *value, uint32_t *nodes, int32_t *best,
                  uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------ tree search valued by the caller's network (PUCT), TicTacToe
+ * crl_ttt_puct_*: B search trees that stay in device memory between launches.  One launch (select) descends every tree to a
+ * leaf and writes the leaves out in observation layout; the caller runs its network on that batch, on the same stream; a
+ * second launch (backup) expands the leaves with the returned priors and backs the returned values up.  Two launches per
+ * simulation for the whole batch, no host synchronisation, capturable into a graph.  The search draws nothing: its contract
+ * is integer arithmetic alone.  Added under revision 113: five new entries, no new Philox tag, no existing struct, argument
+ * list or RNG contract changed.
+ * `tree` is a caller-owned device buffer of B * crl_ttt_puct_tree_bytes(ctx, S_cap) bytes, 16-byte aligned.  Its layout is
+ * the library's own business and is opaque to the caller (DESIGN.md 4.5j states it).  Every call on a buffer takes the
+ * S_cap, the B and the context that crl_ttt_puct_begin took.
+ *
+ * Tree and nodes
+ * - `begin` copies position b into tree b: the P occupancy words and the mover. No later call reads the game state, so the
+ *   batch may be stepped while a search is open.
+ * - `begin` makes node 0 the root. The root is *unexpanded*, with n = 0, node count 1 and simulation count 0.
+ * - A position that is over (`winner[b] >= 0`, or no empty cell), or whose `to_move[b]` is outside [0, P), makes a *skipped*
+ *   tree. Its node count is 0, every later call leaves it alone, and `root` reports zeros and `best` -1.
+ * - A node holds n (uint32), w (uint32), one prior slot (uint16) per cell and one child slot (uint16, 0 = none) per cell. w is
+ *   the summed value of the player who moved INTO it, on the 0..65536 scale.
+ * - A node is *expanded* once a backup has given it priors.
+ *
+ * `select`, simulation s
+ * - The descent starts at the root on a private copy of the root position.
+ * - At node v:
+ *   - If v is unexpanded, v is the leaf and it is *pending*.
+ *   - Otherwise score every empty cell e of the position at v. Take the greatest score, ties to the lowest cell.
+ *   - If v has no child at e, a new unexpanded node with the next free index becomes that child.
+ *   - Play e as `crl_ttt_step` plays it.
+ *   - If that ply ends the game, the child is the leaf, it is *terminal* and not pending. Otherwise the descent continues
+ *     at the child.
+ * - The score is in 64-bit integers with floor divisions. Let n_u, w_u be those of the child at e, or 0, 0 where there is
+ *   none. Let P_e be v's stored prior at e.
+ *   - `exploit = n_u ? w_u / n_u : fpu`
+ *   - `explore = (cpuct * P_e * isqrt(n_v << 16)) / ((1 + n_u) << 16)`, with isqrt the exact floor root
+ *   - `score = exploit + explore`
+ *   - `cpuct = 256` is c = 1.0.
+ * - The path (at most cells + 1 node indices) and the leaf's kind are kept in the tree until `backup`.
+ * - A `select` on a tree with a path outstanding drops that path and descends again. Nothing has changed, so it arrives at
+ *   the same leaf.
+ * - A tree whose simulation count has reached `S_cap` is not descended: no path, pending 0.
+ * - Outputs, every word overwritten. For a pending leaf with mover m:
+ *   - `board` int8 [B][cells], relative to m under `rel_mod`, exactly as `crl_ttt_board` writes it.
+ *   - `valid` uint32 [B], the empties mask.
+ *   - `mover` int8 [B] = m.
+ *   - `pending` uint8 [B] = 1.
+ *   - `leaf_occ` uint32 [P][B], the leaf position in the state layout, so that it can be handed to any other entry.
+ *   - For every other tree: zeros, `mover` -1, `pending` 0.
+ *
+ * `backup`
+ * - A tree without an outstanding path is left alone.
+ * - Pending leaf L with empties E and mover m:
+ *   - Let SUM = sum over e in E of `prior[b][e]`, with `prior` uint16 [B][cells]; entries at occupied cells are ignored.
+ *   - For e in E, L's prior slot is `min(65535, (prior[e] << 16) / SUM)`, or `min(65535, 65536 / |E|)` when SUM = 0. Other
+ *     slots are 0.
+ *   - L becomes expanded.
+ *   - The value of player (m + j) mod P is `value[b][j]` clamped to [0, 65536], with `value` int32 [B][P].
+ * - Terminal leaf:
+ *   - `prior` and `value` are not read.
+ *   - The winner's value is 65536 and every other player's is 0.
+ *   - A draw gives every player 32768.
+ * - Every node on the path gets n += 1.
+ * - Every node on the path but the root gets w += the value of the player who moved into it.
+ * - The simulation count goes up by 1 and the path is cleared.
+ *
+ * `root`, every word overwritten
+ * - `visits`, `value` uint32 [B][cells]: n and w of the root's child at each cell, 0 where there is none.
+ * - `prior` uint32 [B][cells]: the root's stored priors.
+ * - `nodes`, `sims` uint32 [B].
+ * - `best` int32 [B]: the cell of the most visited child, ties to the larger w, then to the lowest cell. -1 when no child has
+ *   a visit.
+ *
+ * Refused with `CRL_EINVAL` and a `crl_last_error` message, before any device work
+ * - NULL pointers, other than `leaf_occ`.
+ * - A `tree` pointer that is not 16-byte aligned.
+ * - B out of range, as the siblings define it.
+ * - `S_cap` outside [1, 4095]. Child slots are 16 bits and w stays below 2^32. A wider index is a later change.
+ * - `cpuct` > 65535.
+ * - `fpu` > 65536.
+ * - `rel_mod` as `crl_ttt_board` checks it (>= 1: the board is always relative to a player here).
+ * - `flags != 0`.
+ * - A context with cells < P, or a context that is not tictactoe.
+ * crl_ttt_puct_tree_bytes returns the bytes of ONE tree, a multiple of 16 that grows with S_cap, or a negative code (a bad
+ * context, S_cap out of range).
+ * One wave per tree in every kernel, 64-bit tree offsets, grid-stride loops; nothing is shared between waves, so the results
+ * do not depend on their order. */
+int64_t crl_ttt_puct_tree_bytes(const crl_ctx *ctx, int S_cap);
+int crl_ttt_puct_begin(const crl_ctx *ctx, int64_t B, const uint32_t *occ, const int8_t *winner, const int8_t *to_move,
+                       int S_cap, void *tree, void *stream);
+int crl_ttt_puct_select(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, uint32_t cpuct, uint32_t fpu, int rel_mod,
+                        int8_t *board, uint32_t *valid, int8_t *mover, uint8_t *pending, uint32_t *leaf_occ /* may be NULL */,
+                        uint32_t flags, void *stream);
+int crl_ttt_puct_backup(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, const uint16_t *prior, const int32_t *value,
+                        uint32_t flags, void *stream);
+int crl_ttt_puct_root(const crl_ctx *ctx, int64_t B, void *tree, int S_cap,
+                      uint32_t *visits, uint32_t *value, uint32_t *prior, uint32_t *nodes, uint32_t *sims, int32_t *best,
+                      void *stream);
 
 /* ------------------------------------------------------------------ batched tree search with progressive widening, Blokus
  * crl_blokus_mcts: from each of B positions build a search tree of its own by S simulations s = 0 .. S-1, in order, each

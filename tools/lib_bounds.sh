@@ -9,7 +9,7 @@ OUT=$ROOT/build/bounds
 mkdir -p "$OUT"
 rm -f "$OUT"/*.o "$OUT/libcolosseum_hip.so"        # a failed compile must not link against an object of an earlier run
 pids=()
-SRCS="capi tron tron_territory tron_mcts ttt blokus blokus_mcts blokus_mcts_agent"
+SRCS="capi tron tron_territory tron_mcts ttt ttt_puct blokus blokus_mcts blokus_mcts_agent"
 for f in $SRCS; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -DCRL_BOUNDS \
       -c "$ROOT/colosseumrl_amd/csrc/$f.hip" -o "$OUT/$f.o" &

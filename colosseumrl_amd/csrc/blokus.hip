@@ -958,9 +958,52 @@ __device__ __forceinline__ bool blk_move_legal(const BlkTables &T, const WaveLds
     const int64_t b = (int64_t)blockIdx.x * 4 + wave_;                                            \
     if (b >= B) return;
 
-// Everything above is what blokus_mcts.hip builds its kernel from: it includes this file with BLK_DEVICE_ONLY set and
-// stops here.  The search is a translation unit of its own so that the kernels below compile to what they compile to
-// without it (with the search kernel in this one, blokus_rollout_kernel went from 57 to 59 VGPRs).
+// state_to_observation of game b for observer pl (BlokusEnvironment.py:752-768) by the wave that holds the game's row
+// bitboards in LDS: board = -1 empty else (owner - observer) % 4, rotated by np.rot90(k=-pl), four cells (one dword) per
+// lane and trip; pieces[r][i] = inventory bit i of player (r + observer) % 4; score rolled by -observer.
+__device__ __forceinline__ void blk_write_observation(const uint32_t (&occ)[4][BN], const uint32_t (&inv)[4], const int (&score)[4],
+                                                      const int pl, const int64_t b, const int lane, int8_t *__restrict__ obs_board,
+                                                      uint8_t *__restrict__ obs_pieces, int32_t *__restrict__ obs_score)
+{
+    for (int d = lane; d < BN * BN / 4; d += 64) {
+        const int i = d / (BN / 4), j0 = (d - i * (BN / 4)) * 4;
+        uint32_t word = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = j0 + k;
+            int y, x;                                            // source cell of np.rot90(m, k=-pl)[i][j]
+            switch (pl) {
+                case 0: y = i; x = j; break;
+                case 1: y = BN - 1 - j; x = i; break;
+                case 2: y = BN - 1 - i; x = BN - 1 - j; break;
+                default: y = j; x = BN - 1 - i; break;
+            }
+            int v = -1;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v = ((occ[c][y] >> x) & 1u) ? ((c - pl) & 3) : v;
+            word |= (uint32_t)(v & 0xff) << (8 * k);
+        }
+        reinterpret_cast<uint32_t *>(obs_board + b * (BN * BN))[d] = word;
+    }
+    for (int cell = lane; cell < 4 * NPIECE; cell += 64) {       // pieces[r][piece] of player (r + observer) % 4
+        const int r = cell / NPIECE, piece = cell - r * NPIECE;
+        uint32_t iv = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) iv = (c == ((r + pl) & 3)) ? inv[c] : iv;
+        obs_pieces[b * 4 * NPIECE + cell] = (uint8_t)((iv >> piece) & 1u);
+    }
+    if (lane < 4) {                                              // np.roll(score, -observer)
+        int sc = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) sc = (c == ((lane + pl) & 3)) ? score[c] : sc;
+        obs_score[b * 4 + lane] = sc;
+    }
+}
+
+// Everything above is what blokus_mcts.hip and blokus_mcts_agent.hip build their kernels from: they include this file with
+// BLK_DEVICE_ONLY set and stop here (the search itself is blokus_mcts_search.hpp).  The searches are translation units of
+// their own so that the kernels below compile to what they compile to without them (with the search kernel in this one,
+// blokus_rollout_kernel went from 57 to 59 VGPRs).
 #ifdef BLK_DEVICE_ONLY
 } // namespace
 #else
@@ -1071,48 +1114,6 @@ blokus_sample_kernel(const BlkTables *__restrict__ tables, const int64_t B, cons
     if (lane == 0) {
         action[b] = id;
         if (advance) tcount[b] = tc + 1u;
-    }
-}
-
-// state_to_observation of game b for observer pl (BlokusEnvironment.py:752-768) by the wave that holds the game's row
-// bitboards in LDS: board = -1 empty else (owner - observer) % 4, rotated by np.rot90(k=-pl), four cells (one dword) per
-// lane and trip; pieces[r][i] = inventory bit i of player (r + observer) % 4; score rolled by -observer.
-__device__ __forceinline__ void blk_write_observation(const uint32_t (&occ)[4][BN], const uint32_t (&inv)[4], const int (&score)[4],
-                                                      const int pl, const int64_t b, const int lane, int8_t *__restrict__ obs_board,
-                                                      uint8_t *__restrict__ obs_pieces, int32_t *__restrict__ obs_score)
-{
-    for (int d = lane; d < BN * BN / 4; d += 64) {
-        const int i = d / (BN / 4), j0 = (d - i * (BN / 4)) * 4;
-        uint32_t word = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int j = j0 + k;
-            int y, x;                                            // source cell of np.rot90(m, k=-pl)[i][j]
-            switch (pl) {
-                case 0: y = i; x = j; break;
-                case 1: y = BN - 1 - j; x = i; break;
-                case 2: y = BN - 1 - i; x = BN - 1 - j; break;
-                default: y = j; x = BN - 1 - i; break;
-            }
-            int v = -1;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) v = ((occ[c][y] >> x) & 1u) ? ((c - pl) & 3) : v;
-            word |= (uint32_t)(v & 0xff) << (8 * k);
-        }
-        reinterpret_cast<uint32_t *>(obs_board + b * (BN * BN))[d] = word;
-    }
-    for (int cell = lane; cell < 4 * NPIECE; cell += 64) {       // pieces[r][piece] of player (r + observer) % 4
-        const int r = cell / NPIECE, piece = cell - r * NPIECE;
-        uint32_t iv = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) iv = (c == ((r + pl) & 3)) ? inv[c] : iv;
-        obs_pieces[b * 4 * NPIECE + cell] = (uint8_t)((iv >> piece) & 1u);
-    }
-    if (lane < 4) {                                              // np.roll(score, -observer)
-        int sc = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) sc = (c == ((lane + pl) & 3)) ? score[c] : sc;
-        obs_score[b * 4 + lane] = sc;
     }
 }
 
@@ -1419,8 +1420,9 @@ blokus_rollout_kernel(const BlkTables *__restrict__ tables, const int64_t B, con
 // loop ends at the first terminal ply.  That loop body is NOT shared with the rollout, on purpose: with the ply in one
 // __forceinline__ helper called from both, blokus_rollout_kernel -- the benchmark's headline kernel, bound by instruction
 // issue -- went from 0 to 12 bytes of scratch, from 57 to 61 VGPRs and from 1772 to 1840 instructions.  Change both loops
-// together -- and with them the leaf playouts of blokus_mcts_kernel (blokus_mcts.hip), a third copy of the loop under the
-// search's counter words.  Lane 0 adds the playout's outcome into its row (integer atomics onto the zeros the launcher wrote).
+// together -- and with them the leaf playouts of the tree search (blk_mcts_search, blokus_mcts_search.hpp), a third copy of
+// the loop under the search's counter words.  (One helper for this loop and the search's was built and measured, and not
+// kept: DESIGN 4.5h.)  Lane 0 adds the playout's outcome into its row (integer atomics onto the zeros the launcher wrote).
 __device__ __forceinline__ uint64_t blk_uniform64(const uint64_t v)
 {
     return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v)

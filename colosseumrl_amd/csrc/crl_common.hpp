@@ -121,8 +121,9 @@ static inline unsigned crl_playout_blocks(const uint64_t n_lanes, const uint64_t
 // explicit range checks in a build of their own (tools/gpu_bounds.sh): a failing check does not fault, it counts itself
 // and keeps the first offender -- {failures, code, value, limit} per translation unit, read by crl_diag_bounds().  The
 // shipped build compiles none of it (the macros expand to nothing).  Codes: 1xx tron.hip (170..189: tron_mcts.hip, whose
-// counters crl_diag_bounds folds into tron's four words), 2xx ttt.hip (230..239: ttt_puct.hip, folded into ttt's), 3xx blokus.hip (350..359: blokus_mcts.hip, 360..369:
-// blokus_mcts_agent.hip; each also counts what it includes of blokus.hip, and both are folded into blokus's four words).
+// counters crl_diag_bounds folds into tron's four words), 2xx ttt.hip (230..239: ttt_puct.hip, folded into ttt's), 3xx blokus.hip (350..359:
+// blokus_mcts_search.hpp, the one search text of blokus_mcts.hip and blokus_mcts_agent.hip; each of the two units counts in
+// words of its own, what it includes of blokus.hip too, and both are folded into blokus's four words; 360..369 are retired).
 #ifdef CRL_BOUNDS
 namespace {
 __device__ unsigned int g_crl_bounds[4];

@@ -110,6 +110,11 @@ PROTOTYPES = {
     "crl_tron_sample_mcts_territory": (_I, [_VP, _I64, _U64, _U64, _VP, _I, C.c_double, _U32] + [_VP] * 4 +
                                        [_I, _I, _U32, C.c_double, _U32, _VP, _VP]),
     "crl_tron_sample_mcts_territory_max_simulations": (_I, [_VP, _U32]),
+    "crl_tron_puct_tree_bytes": (_I64, [_VP, _I]),
+    "crl_tron_puct_begin": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 6 + [_I, C.c_double, _U32, _VP, _VP]),
+    "crl_tron_puct_select": (_I, [_VP, _I64, _VP, _I, _U32, _U32] + [_VP] * 10 + [_U32, _VP]),
+    "crl_tron_puct_backup": (_I, [_VP, _I64, _VP, _I, _VP, _VP, _U32, _VP]),
+    "crl_tron_puct_root": (_I, [_VP, _I64, _VP, _I] + [_VP] * 6 + [_VP]),
     "crl_tron_territory": (_I, [_VP, _I64] + [_VP] * 6 + [_I] + [_VP] * 2 + [_VP]),
     "crl_tron_sample_territory": (_I, [_VP, _I64, _U64, _U64, _VP, _I, C.c_double, _U32] + [_VP] * 5 + [_VP]),
     "crl_ttt_create": (_I, [_I, _I, _I, _I, _I, C.POINTER(_VP)]),

@@ -610,6 +610,131 @@ class TronBatch(_RolloutStepper):
         the game is over): the kernel's own ``best``, only widened here.  No host synchronisation; capturable."""
         return self.mcts_territory(simulations, seed, exploration, agent, noise, seat, value_scale, out)["best"].to(torch.int64)
 
+    # -- the search valued by the caller's network (PUCT); the contract is with crl_tron_puct_begin in include/colosseum_hip.h
+    PUCT_MAX_CAPACITY = 4095
+
+    def _puct_open(self):
+        if getattr(self, "_puct_cap", None) is None:
+            raise ValueError("no search is open: call puct_begin(capacity) first")
+        return self._puct_tree, self._puct_cap
+
+    def _puct_select_spec(self):
+        B, P, NN = self.B, self.P, self.N * self.N
+        i8, i16 = torch.int8, torch.int16
+        return {"obs_board": (i8, (B, NN)), "obs_heads": (i16, (P, B)), "obs_dirs": (i8, (P, B)), "obs_deaths": (i8, (P, B)),
+                "pending": (torch.uint8, (B,)), "depth": (torch.int32, (B,)),
+                "leaf_board": (i8, (B, NN)), "leaf_heads": (i16, (P, B)), "leaf_dirs": (i8, (P, B)), "leaf_deaths": (i8, (P, B))}
+
+    def _puct_root_spec(self):
+        i32 = torch.int32
+        return {"visits": (i32, (self.B, 3)), "value": (i32, (self.B, 3)), "prior": (i32, (self.B, 3)), "nodes": (i32, (self.B,)),
+                "sims": (i32, (self.B,)), "best": (i32, (self.B,))}
+
+    def puct_begin(self, capacity: int, seed: int = 0, agent: str = "random", noise: float = 0.1,
+                   seat: Optional[torch.Tensor] = None):
+        """Opens a search of at most ``capacity`` (1 .. 4095) simulations for the seat ``seat[b]`` (int8 [B]; None: player 0)
+        from every game's position (``crl_tron_puct_begin``).  The tree branches on the SEAT's three actions; the other
+        players are part of the transition, played by ``agent`` ("random", or "avoid" with ``noise``) from draws keyed by
+        ``seed``, the game ids and ``tcount``.  The trees live in a device tensor of this stepper, allocated here or reused
+        when the capacity is the last one's, and hold their own copy of the position -- the batch may be stepped while the
+        search is open.  A dead seat, a seat out of range and a finished game make skipped trees.  One launch, no host
+        synchronisation."""
+        cap = _int_in("capacity", capacity, 1, self.PUCT_MAX_CAPACITY)
+        _one_of("agent", agent, ("random", "avoid"))
+        noise = _unit("noise", noise)
+        _seat(seat, self.B, self.device)
+        if getattr(self, "_puct_cap", None) != cap:
+            nbytes = self._lib.crl_tron_puct_tree_bytes(self._ctx.handle, cap)
+            if nbytes < 0:
+                check(int(nbytes), "crl_tron_puct_tree_bytes")
+            with torch.cuda.device(self.device):
+                self._puct_tree = torch.empty((self.B, int(nbytes) // 16, 2), dtype=torch.int64, device=self.device)   # (16-byte units)
+            self._puct_cap = cap
+        self._call("crl_tron_puct_begin", _seed(seed), self.first_env_id, *self._state(), _ptr(self.tcount), _ptr(seat), cap, noise,
+                   _native.CRL_PLAYOUT_AVOID if agent == "avoid" else 0, _ptr(self._puct_tree))
+
+    def puct_select(self, exploration: float = 1.25, fpu: float = 0.5, out: Optional[dict] = None):
+        """One descent of every open tree (``crl_tron_puct_select``): ``exploration`` is c of the PUCT score (0 .. 65535 / 256),
+        ``fpu`` the value in [0, 1] of a child without a visit.  Returns the leaves that wait for the caller's network:
+        {'obs_board' int8 [B, N*N], 'obs_heads' int16 [P, B], 'obs_dirs', 'obs_deaths' int8 [P, B]: the leaf as ``observe``
+        shows it to the seat, 'pending' uint8 [B], 'depth' int32 [B]: the edges from the root (the leaf's counter base is
+        tcount + depth), 'leaf_board', 'leaf_heads', 'leaf_dirs', 'leaf_deaths': the leaf position in the state layout, for
+        ``territory`` or ``playout`` of another stepper}; rows whose tree has no pending leaf (skipped, a terminal leaf, at
+        capacity) are zeros.  ``out`` reuses such a dict.  One launch, no host synchronisation."""
+        tree, cap = self._puct_open()
+        cpuct = _exploration("exploration", exploration)
+        fpu16 = int(round(65536.0 * _unit("fpu", fpu)))
+        out = _out_dict(out, self._puct_select_spec(), self.device)
+        self._call("crl_tron_puct_select", _ptr(tree), cap, cpuct, fpu16, _ptr(out["obs_board"]), _ptr(out["obs_heads"]),
+                   _ptr(out["obs_dirs"]), _ptr(out["obs_deaths"]), _ptr(out["pending"]), _ptr(out["depth"]), _ptr(out["leaf_board"]),
+                   _ptr(out["leaf_heads"]), _ptr(out["leaf_dirs"]), _ptr(out["leaf_deaths"]), 0)
+        return out
+
+    def puct_backup(self, prior: torch.Tensor, value: torch.Tensor):
+        """Expands the pending leaves with ``prior`` (uint16 [B, 3], or int16 of the same bits: any weights for forward, right,
+        left, normalised by the backup) and backs ``value`` up (int32 [B]: the seat's value on 0 .. 65536); terminal leaves
+        back their outcome up (``crl_tron_puct_backup``).  One launch."""
+        tree, cap = self._puct_open()
+        if not isinstance(prior, torch.Tensor) or prior.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            raise ValueError("prior must be a uint16 (or int16) tensor of shape (%d, 3)" % self.B)
+        _want(prior, prior.dtype, (self.B, 3), self.device, "prior")
+        if not isinstance(value, torch.Tensor):
+            raise ValueError("value must be an int32 tensor of shape (%d,)" % self.B)
+        _want(value, torch.int32, (self.B,), self.device, "value")
+        self._call("crl_tron_puct_backup", _ptr(tree), cap, _ptr(prior), _ptr(value), 0)
+
+    def puct_root(self, out: Optional[dict] = None):
+        """The root of every open tree (``crl_tron_puct_root``): {'visits', 'value', 'prior' int32 [B, 3]: simulations through
+        the root's child at each action (0 forward, 1 right, 2 left), the seat's summed value there (65536 per won simulation)
+        and the root's stored priors, 'nodes', 'sims', 'best' int32 [B]: the most visited action (ties: the larger value, then
+        the lower action; -1 without a visited child)}.  The visit counts are the policy target of an AlphaZero-style trainer.
+        One launch."""
+        tree, cap = self._puct_open()
+        out = _out_dict(out, self._puct_root_spec(), self.device)
+        self._call("crl_tron_puct_root", _ptr(tree), cap, _ptr(out["visits"]), _ptr(out["value"]), _ptr(out["prior"]),
+                   _ptr(out["nodes"]), _ptr(out["sims"]), _ptr(out["best"]))
+        return out
+
+    @staticmethod
+    def puct_quantize(policy: torch.Tensor, value: torch.Tensor):
+        """(float policy [B, 3]: any non-negative weights, float value [B] in [0, 1]) -> (int16 prior holding the contract's
+        uint16 bits, int32 value on 0 .. 65536) for ``puct_backup``.  Each row's weights are scaled so that its greatest is
+        65535 (the backup normalises anyway); NaN counts as 0 in the policy and as 0.5 in the value.  Torch operations only."""
+        pol = torch.nan_to_num(policy.to(torch.float32), nan=0.0, posinf=0.0).clamp_min(0.0)
+        top = pol.amax(dim=1, keepdim=True).clamp_min(1e-30)
+        q = torch.round(pol * (65535.0 / top)).to(torch.int32).clamp(0, 65535)
+        prior = torch.where(q >= 32768, q - 65536, q).to(torch.int16)
+        val = torch.round(torch.nan_to_num(value.to(torch.float32), nan=0.5).clamp(0.0, 1.0) * 65536.0).to(torch.int32)
+        return prior.contiguous(), val.contiguous()
+
+    def puct(self, evaluate, simulations: int, exploration: float = 1.25, fpu: float = 0.5, seed: int = 0, agent: str = "random",
+             noise: float = 0.1, seat: Optional[torch.Tensor] = None, out: Optional[dict] = None):
+        """A whole search: ``puct_begin(simulations, seed, agent, noise, seat)``, then ``simulations`` times ``puct_select`` ->
+        ``evaluate(leaves)`` -> ``puct_backup``, then ``puct_root``.  ``evaluate`` takes the select dict and returns (prior,
+        value), either the integer tensors of ``puct_backup`` or float tensors (then ``puct_quantize`` turns them).  Two
+        launches per simulation beside the caller's network; no host synchronisation.  Returns the root dict (``out`` reuses
+        one)."""
+        if not callable(evaluate):
+            raise ValueError("evaluate must be callable: the select dict -> (prior, value)")
+        S = _int_in("simulations", simulations, 1, self.PUCT_MAX_CAPACITY)
+        _exploration("exploration", exploration), _unit("fpu", fpu)
+        self.puct_begin(S, seed, agent, noise, seat)
+        leaves = None
+        for _ in range(S):
+            leaves = self.puct_select(exploration, fpu, out=leaves)
+            prior, value = evaluate(leaves)
+            if prior.is_floating_point() or value.is_floating_point():
+                prior, value = self.puct_quantize(prior, value)
+            self.puct_backup(prior, value)
+        return self.puct_root(out)
+
+    def puct_action(self, evaluate, simulations: int, exploration: float = 1.25, fpu: float = 0.5, seed: int = 0,
+                    agent: str = "random", noise: float = 0.1, seat: Optional[torch.Tensor] = None,
+                    out: Optional[dict] = None) -> torch.Tensor:
+        """``puct``'s most visited action as an int64 [B] action in {0, 1, 2} for ``step_single`` (-1 where the seat is dead or
+        the game is over)."""
+        return self.puct(evaluate, simulations, exploration, fpu, seed, agent, noise, seat, out)["best"].to(torch.int64)
+
     # -- Voronoi territory of every game's position (the deterministic evaluator beside playout)
     def territory(self, candidates: Optional[torch.Tensor] = None, seat: Optional[torch.Tensor] = None,
                   out: Optional[dict] = None):

@@ -206,6 +206,14 @@ int crl_diag_bounds(uint32_t *out12)
             out12[0] += m[0];
         }
     }
+    if (rc == CRL_OK) {                                          // ... and so does tron_puct.hip
+        unsigned int m[4] = {0, 0, 0, 0};
+        rc = crl_tron_puct_bounds(m);
+        if (rc == CRL_OK && m[0] != 0u) {
+            if (out12[0] == 0u) { out12[1] = m[1]; out12[2] = m[2]; out12[3] = m[3]; }
+            out12[0] += m[0];
+        }
+    }
     if (rc == CRL_OK) rc = crl_ttt_bounds(out12 + 4);
     if (rc == CRL_OK) {                                          // ttt_puct.hip counts on its own, as tron_mcts.hip does
         unsigned int m[4] = {0, 0, 0, 0};

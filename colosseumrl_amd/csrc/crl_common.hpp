@@ -120,8 +120,8 @@ static inline unsigned crl_playout_blocks(const uint64_t n_lanes, const uint64_t
 // GPU AddressSanitizer is not available on this pool, so the data-dependent LDS / table accesses of the kernels carry
 // explicit range checks in a build of their own (tools/gpu_bounds.sh): a failing check does not fault, it counts itself
 // and keeps the first offender -- {failures, code, value, limit} per translation unit, read by crl_diag_bounds().  The
-// shipped build compiles none of it (the macros expand to nothing).  Codes: 1xx tron.hip (170..189: tron_mcts.hip, whose
-// counters crl_diag_bounds folds into tron's four words), 2xx ttt.hip (230..239: ttt_puct.hip, folded into ttt's), 3xx blokus.hip (350..359:
+// shipped build compiles none of it (the macros expand to nothing).  Codes: 1xx tron.hip (170..191: tron_mcts.hip, 165..167 and
+// 192..199: tron_puct.hip, whose counters crl_diag_bounds folds into tron's four words), 2xx ttt.hip (230..239: ttt_puct.hip, folded into ttt's), 3xx blokus.hip (350..359:
 // blokus_mcts_search.hpp, the one search text of blokus_mcts.hip and blokus_mcts_agent.hip; each of the two units counts in
 // words of its own, what it includes of blokus.hip too, and both are folded into blokus's four words; 360..369 are retired).
 #ifdef CRL_BOUNDS
@@ -147,6 +147,7 @@ __device__ __forceinline__ void crl_bounds_fail(const unsigned code, const unsig
 // {failures, first code, first value, first limit} of one translation unit (zeros in the shipped build)
 int crl_tron_bounds(unsigned int *out4);
 int crl_tron_mcts_bounds(unsigned int *out4);
+int crl_tron_puct_bounds(unsigned int *out4);
 int crl_ttt_bounds(unsigned int *out4);
 int crl_ttt_puct_bounds(unsigned int *out4);
 int crl_blokus_bounds(unsigned int *out4);

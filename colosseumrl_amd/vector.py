@@ -142,6 +142,15 @@ class TronSinglePlayerVectorEnv:
         reuse."""
         return self.batch.mcts_territory_action(simulations, seed, exploration, "avoid", self.noise, None, 256, out)
 
+    def puct_action(self, evaluate, simulations: int, exploration: float = 1.25, fpu: float = 0.5, seed: int = 1,
+                    out: Optional[dict] = None) -> torch.Tensor:
+        """A tree search valued by the caller's network for the learner on the env's own games (``TronBatch.puct_action``):
+        seat 0, the other players modelled by the avoid agent with the env's noise -- whatever the env's opponent --,
+        ``evaluate`` the select dict -> (prior, value).  ``seed`` keys the model's draws.  -> int64 [B] in {0, 1, 2} for
+        ``step``, two launches per simulation beside the network, no host synchronisation.  ``out``: the ``TronBatch.puct_root``
+        dict to reuse (its 'visits' are a policy target)."""
+        return self.batch.puct_action(evaluate, simulations, exploration, fpu, seed, "avoid", self.noise, None, out)
+
 
 class TicTacToeVectorEnv:
     """B turn-based TicTacToe games.  ``step`` takes int8 cell indices [B] for the player to move (-1 = pass)."""

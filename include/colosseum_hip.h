@@ -94,7 +94,8 @@ const char *crl_last_error(void);
  *      crl_tron_mcts_territory (that search with Voronoi territory at the leaves: one new entry, no new tag), and
  *      crl_tron_sample_mcts_territory / _max_simulations (that search as a seated agent: two new entries, no new tag), and
  *      crl_blokus_mcts / crl_blokus_mcts_max_simulations (tree search with progressive widening: two new entries, no new tag), and
- *      crl_ttt_puct_tree_bytes / _begin / _select / _backup / _root (tree search valued by the caller: five new entries, no new tag). */
+ *      crl_ttt_puct_tree_bytes / _begin / _select / _backup / _root (tree search valued by the caller: five new entries, no new tag), and
+ *      crl_tron_puct_tree_bytes / _begin / _select / _backup / _root (that search for one seat of Tron: five new entries, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -1117,6 +1118,120 @@ int crl_ttt_puct_backup(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, co
 int crl_ttt_puct_root(const crl_ctx *ctx, int64_t B, void *tree, int S_cap,
                       uint32_t *visits, uint32_t *value, uint32_t *prior, uint32_t *nodes, uint32_t *sims, int32_t *best,
                       void *stream);
+
+/* ------------------------------------------------------------------ tree search valued by the caller's network (PUCT), Tron
+ * crl_tron_puct_*: crl_ttt_puct_*'s design for ONE seat of Tron.  B search trees stay in device memory between launches; one
+ * launch (select) descends every tree to a leaf and writes the leaves out in observation layout; the caller runs its network
+ * on that batch, on the same stream; a second launch (backup) expands the leaves with the returned priors and backs the
+ * returned values up.  Two launches per simulation for the whole batch, no host synchronisation, capturable into a graph.
+ * Added under revision 113: five new entries, no new Philox tag, no existing struct, argument list or RNG contract changed.
+ * As in crl_tron_mcts the tree branches on the seat's three actions only.  Every other player is part of the transition,
+ * played by a scripted MODEL (the random or the avoid agent) from counter-based draws, so a node's position is a pure function
+ * of the root and the edge sequence: a tree holds the root position and no other, and `select` replays the edges.
+ * `tree` is a caller-owned device buffer of B * crl_tron_puct_tree_bytes(ctx, S_cap) bytes, 16-byte aligned.  Its layout is
+ * the library's own business and is opaque to the caller (DESIGN.md 4.5k states it).  Every call on a buffer takes the
+ * S_cap, the B and the context that crl_tron_puct_begin took.
+ *
+ * Tree and nodes
+ * - `begin` copies into tree b everything a later call needs: the root board bytes, heads (clamped onto the board,
+ *   crl_tron_playout's precondition), dirs & 3, deaths, `tcount[b]` (NULL means 0), the seat `seat[b]` (NULL means player 0),
+ *   g = the low 32 bits of `first_env_id + b`, the seed, the model (with CRL_PLAYOUT_AVOID the avoid agent with `noise`, else
+ *   the random agent; noise is checked and otherwise unused) and the noise threshold.  The state has crl_tron_step's layouts
+ *   and is read only.  No later call reads the game state, so the batch may be stepped while a search is open.
+ * - `begin` makes node 0 the root. The root is *unexpanded*, with n = 0, node count 1 and simulation count 0.
+ * - A position is skipped when the seat is outside [0, P), the seat is dead (deaths[seat][b] != 0), or P >= 2 and fewer than
+ *   two players are alive (crl_tron_mcts's rule).  It makes a *skipped* tree. Its node count is 0, every later call leaves it
+ *   alone, and `root` reports zeros and `best` -1.
+ * - A node holds n (uint32), w (uint32), three prior slots (uint16) and three child slots (uint16, 0 = none), for the actions
+ *   0 forward, 1 right, 2 left (crl_tron_step_single's encoding). w is the seat's summed value on the 0..65536 scale.
+ * - A node is *expanded* once a backup has given it priors.
+ *
+ * `select`, simulation s
+ * - The descent starts at the root on a private copy of the root position.
+ * - At node v at depth k (edges from the root):
+ *   - If v is unexpanded, v is the leaf and it is *pending*.
+ *   - Otherwise score the three actions e. Take the greatest score, ties to the lowest action.
+ *   - If v has no child at e, a new unexpanded node with the next free index becomes that child.
+ *   - Play the tree step e, which is crl_tron_mcts's tree step: its step counter is c = tcount + k (uint32 arithmetic).  The
+ *     seat plays e.  Every other live player q plays the model agent, decided on the pre-step position:
+ *       random  W = Philox4x32-10(ctr = {g, c >> 3, 0xFFFF0000, 0x54700000 | (q >> 2)}, key = {seed lo, seed hi}), then
+ *               crl_tron_rollout's digit rule with j = c & 7 and q & 3;
+ *       avoid   W = Philox4x32-10(ctr = {g, c, 0xFFFF0000, 0x54610000 | q}, key = {seed lo, seed hi}), then
+ *               crl_tron_sample_avoid's rule (threshold, clamped probes, side bit).
+ *     The step itself is crl_tron_step without reset, with owners: the board keeps the player ids and the killer ids in
+ *     `deaths` come out exactly as crl_tron_step writes them.
+ *   - If the node reached is CLOSED (the seat is dead or at most one player is alive), the child is the leaf, it is *terminal*
+ *     and not pending, and its value is 65536 iff the seat is alive, else 0. Otherwise the descent continues at the child.
+ * - The score is in 64-bit integers with floor divisions. Let n_u, w_u be those of the child at e, or 0, 0 where there is
+ *   none. Let P_e be v's stored prior at e.
+ *   - `exploit = n_u ? w_u / n_u : fpu`
+ *   - `explore = (cpuct * P_e * isqrt(n_v << 16)) / ((1 + n_u) << 16)`, with isqrt the exact floor root
+ *   - `score = exploit + explore`
+ *   - `cpuct = 256` is c = 1.0.
+ * - The path (at most S_cap + 1 node indices) and the leaf's kind are kept in the tree until `backup`.
+ * - A `select` on a tree with a path outstanding drops that path and descends again. Nothing has changed, so it arrives at
+ *   the same leaf.
+ * - A tree whose simulation count has reached `S_cap` is not descended: no path, pending 0.
+ * - Outputs, every word overwritten. For a pending leaf:
+ *   - `obs_board` int8 [B][N*N], `obs_heads` int16 [P][B], `obs_dirs` int8 [P][B], `obs_deaths` int8 [P][B]: exactly what
+ *     crl_tron_observe with `player[b]` = the seat writes for the leaf position.
+ *   - `pending` uint8 [B] = 1.
+ *   - `depth` uint32 [B]: the edges from the root to the leaf, so the leaf's counter base is `tcount + depth`.
+ *   - `leaf_board`, `leaf_heads`, `leaf_dirs`, `leaf_deaths` (all four NULL, or none): the leaf position in the state layout,
+ *     so that it can be handed to crl_tron_territory, crl_tron_playout or any other entry.
+ *   - For every other tree: zeros, `pending` 0.
+ *
+ * `backup`
+ * - A tree without an outstanding path is left alone.
+ * - Pending leaf L:
+ *   - Let SUM = `prior[b][0] + prior[b][1] + prior[b][2]`, with `prior` uint16 [B][3].
+ *   - L's prior slot at a is `min(65535, (prior[b][a] << 16) / SUM)`, or `min(65535, 65536 / 3)` each when SUM = 0.
+ *   - L becomes expanded.
+ *   - The value is `value[b]` clamped to [0, 65536], with `value` int32 [B]: the seat's.
+ * - Terminal leaf: `prior` and `value` are not read. The value is 65536 iff the seat is alive, else 0.
+ * - Every node on the path gets n += 1.
+ * - Every node on the path but the root gets w += the value.
+ * - The simulation count goes up by 1 and the path is cleared.
+ *
+ * `root`, every word overwritten
+ * - `visits`, `value` uint32 [B][3]: n and w of the root's child at each action, 0 where there is none.
+ * - `prior` uint32 [B][3]: the root's stored priors.
+ * - `nodes`, `sims` uint32 [B].
+ * - `best` int32 [B]: the most visited action, ties to the larger w, then to the lower action. -1 when no child has a visit.
+ *
+ * Refused with `CRL_EINVAL` and a `crl_last_error` message, before any device work
+ * - NULL pointers, other than `tcount`, `seat` and the leaf_* set.
+ * - A leaf_* set that is partly NULL.
+ * - A `tree` pointer that is not 16-byte aligned.
+ * - B out of range, as the siblings define it.
+ * - `S_cap` outside [1, 4095]. Child slots are 16 bits and w stays below 2^32. A wider index is a later change.
+ * - `cpuct` > 65535.
+ * - `fpu` > 65536.
+ * - `noise` outside [0, 1] or NaN.
+ * - Flags other than CRL_PLAYOUT_AVOID in `begin`; `flags != 0` elsewhere.
+ * - A context that is not a Tron context.
+ * A board whose byte copy (N*N rounded up to 16, plus 16 bytes) does not fit the 64 KB of one workgroup's LDS answers
+ * CRL_EUNSUPPORTED: that is N >= 256, beyond the N <= 181 of crl_tron_create, so every Tron context is supported.
+ * A board value outside 0..P is wrong input: the results are unspecified, and it is never a wild access.
+ * crl_tron_puct_tree_bytes returns the bytes of ONE tree, a multiple of 16 that grows with S_cap, or a negative code (a bad
+ * context, S_cap out of range).
+ * One wave per tree in every kernel, one to four waves per workgroup (as many byte boards as fit), 64-bit tree offsets,
+ * grid-stride loops; nothing is shared between waves, so the results do not depend on their order. */
+int64_t crl_tron_puct_tree_bytes(const crl_ctx *ctx, int S_cap);
+int crl_tron_puct_begin(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                        const int8_t *board, const int16_t *heads, const int8_t *dirs, const int8_t *deaths,
+                        const uint32_t *tcount /* may be NULL */, const int8_t *seat /* may be NULL */,
+                        int S_cap, double noise, uint32_t flags, void *tree, void *stream);
+int crl_tron_puct_select(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, uint32_t cpuct, uint32_t fpu,
+                         int8_t *obs_board, int16_t *obs_heads, int8_t *obs_dirs, int8_t *obs_deaths,
+                         uint8_t *pending, uint32_t *depth,
+                         int8_t *leaf_board, int16_t *leaf_heads, int8_t *leaf_dirs, int8_t *leaf_deaths /* all four NULL, or none */,
+                         uint32_t flags, void *stream);
+int crl_tron_puct_backup(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, const uint16_t *prior, const int32_t *value,
+                         uint32_t flags, void *stream);
+int crl_tron_puct_root(const crl_ctx *ctx, int64_t B, void *tree, int S_cap,
+                       uint32_t *visits, uint32_t *value, uint32_t *prior, uint32_t *nodes, uint32_t *sims, int32_t *best,
+                       void *stream);
 
 /* ------------------------------------------------------------------ batched tree search with progressive widening, Blokus
  * crl_blokus_mcts: from each of B positions build a search tree of its own by S simulations s = 0 .. S-1, in order, each

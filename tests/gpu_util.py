@@ -91,3 +91,15 @@ def first_episodes(env, policy, max_steps):
             break
     assert not bool(live.any())
     return last, ret, steps
+
+
+def tron_device_evaluator(leaves):
+    """an integer evaluator of the Tron tree searches' pending leaves in torch operations on the device (a hash of the
+    observed board and the seat's head): (prior int16 [B, 3], value int32 [B]) for TronBatch.puct_backup"""
+    import torch
+    b = leaves["obs_board"].to(torch.int32)
+    wgt = torch.arange(1, b.shape[1] + 1, device=b.device, dtype=torch.int32)
+    h = ((b + 2) * (wgt % 251)).sum(dim=1, keepdim=True) + leaves["obs_heads"][0].to(torch.int32).view(-1, 1) * 977
+    prior = ((h * 31 + torch.arange(1, 4, device=b.device, dtype=torch.int32) * 7919) % 32749).to(torch.int16)
+    value = ((h.view(-1) * 131) % 65537).to(torch.int32)
+    return prior, value

@@ -2,7 +2,8 @@
 offset a kernel forms must be 64-bit there.  A batch that size cannot be checked against the CPU oracle in seconds, so the
 test uses what the contract guarantees instead: a game's results depend on (seed, GLOBAL game id, step counter) alone, so
 the first, the last and the games around byte 2^32 of the big batch must equal, bit for bit, a small batch created with the same
-``first_env_id`` -- and the small batches are what every other test compares with the oracle.  A few seconds on a GPU box (27 GB of HBM)."""
+``first_env_id`` -- and the small batches are what every other test compares with the oracle.  A few seconds on a GPU box (27 GB of HBM);
+the tree-search test, whose grid-stride loops also take a second trip, 2.2 s (5 GB)."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -191,3 +192,46 @@ def test_blokus_states_beyond_4_gib():
         for name in ("occ", "inv", "score", "tcount", "n_episodes"):
             assert torch.equal(getattr(big, name)[lo:hi], getattr(s, name)), (name, lo)
         assert torch.equal(big.results(copy=False)[lo:hi], s.results(copy=False)), ("rows", lo)
+
+
+def test_tron_puct_trees_beyond_4_gib_and_a_second_trip_of_the_grid():
+    """The Tron search valued by the caller's network on 4 * 2^20 + 1,088 trees of 5x5 boards, capacity 40: 4.4 GB of trees,
+    and 1,088 more trees than the 2^20 workgroups of four waves that a grid is capped at, so that the grid-stride loops of
+    `begin`, `select`, `backup` and `root` take a second trip.  Four simulations valued on the device; every `select` output
+    and the root at the head, on either side of tree 4 * 2^20, around byte 2^32 of the tree buffer and at the tail against
+    small batches with the same global ids (which tests/test_gpu_tron_puct.py holds to the restatement)."""
+    import torch
+    from colosseumrl_amd.batched import TronBatch
+    from tests.gpu_util import tron_device_evaluator
+    N, P, cap, sims, seed = 5, 2, 40, 4, 0xC0FFEE
+    trip = 4 * 2 ** 20
+    B = trip + K
+    big = TronBatch(N, P, B, first_env_id=7)
+    tree_bytes = big._lib.crl_tron_puct_tree_bytes(big._ctx.handle, cap)
+    assert B * tree_bytes > 2 ** 32 and tree_bytes == 1040
+    mid = 2 ** 32 // tree_bytes - K // 2
+    windows = ((0, K), (mid, mid + K), (trip - K, trip), (trip, B))
+    assert K < mid and mid + K < trip - K
+    seat = (torch.arange(B, device="cuda") % 3 % 2).to(torch.int8)
+    big.tcount.copy_((torch.arange(B, device="cuda") * 2654435761 % 2 ** 32 - 2 ** 31).to(torch.int32))
+    smalls = [(lo, hi, TronBatch(N, P, hi - lo, first_env_id=7 + lo)) for lo, hi in windows]
+    for lo, hi, s in smalls:
+        s.tcount.copy_(big.tcount[lo:hi])
+    for lo, hi, t in [(0, B, big)] + smalls:
+        t.puct_begin(cap, seed, "random", 0.25, seat[lo:hi].contiguous())
+    big_leaves, small_leaves = None, [None] * len(smalls)
+    for sim in range(sims):
+        big_leaves = big.puct_select(out=big_leaves)
+        for i, (lo, hi, s) in enumerate(smalls):
+            small_leaves[i] = s.puct_select(out=small_leaves[i])
+            for key, got in small_leaves[i].items():
+                want = big_leaves[key][lo:hi] if big_leaves[key].shape[0] == B else big_leaves[key][:, lo:hi]
+                assert torch.equal(want, got), ("select", sim, key, lo)
+            s.puct_backup(*tron_device_evaluator(small_leaves[i]))
+        assert bool(big_leaves["pending"][trip:].any()) and bool(big_leaves["pending"][:K].any())
+        big.puct_backup(*tron_device_evaluator(big_leaves))
+    root = big.puct_root()
+    for lo, hi, s in smalls:
+        for key, got in s.puct_root().items():
+            assert torch.equal(root[key][lo:hi], got), ("root", key, lo)
+        assert bool((root["sims"][lo:hi] == sims).all()) and bool((root["nodes"][lo:hi] > 1).all())

@@ -1,9 +1,11 @@
 """The Tron search valued by the caller's network on the GPU (crl_tron_puct_*, TronBatch.puct_*): the `root` outputs and the
 `select` outputs of EVERY simulation bit for bit against the plain-Python restatement of the header's contract
 (tests/tron_puct_ref.py), the test evaluator applied on the host between `select` and `backup` -- the shapes of
-tests/tron_puct_cases.py, positions from the start layout to walled-up boards with skipped ones among them, B of 1, 5 and 130,
-the edge rows, a path deeper than 64 nodes --, the game state untouched, the batch stepped while a search is open, the pair
-captured into a graph, the wrappers, and a `puct_action` learner valued by territory next to the avoid learner."""
+tests/tron_puct_cases.py (every player count from 1 to 8), positions from the start layout to walled-up boards with skipped ones
+among them, B of 1, 5 and 130, the edge rows, a path deeper than 64 nodes, boards below 16 cells, output rows at odd byte
+offsets, the boards on either side of every change of `select`'s workgroup shape up to 181x181, trees of 4,095 simulations,
+the rows that meet every crash kind of the step --, the game state untouched, the batch stepped while a search is open, the
+pair captured into a graph, the wrappers, and a `puct_action` learner valued by territory next to the avoid learner."""
 import functools
 import math
 
@@ -13,7 +15,7 @@ import torch
 
 from tests import tron_puct_cases as CASES
 from tests import tron_puct_ref as R
-from tests.gpu_util import DEV, first_episodes, np_of as _np, tron_put, tron_state, u32_of
+from tests.gpu_util import DEV, first_episodes, np_of as _np, tron_device_evaluator as _device_evaluator, tron_put, tron_state, u32_of
 
 pytestmark = pytest.mark.gpu
 ROOT_KEYS = ("visits", "value", "prior", "nodes", "sims", "best")
@@ -23,7 +25,9 @@ LEAF_KEYS = ("leaf_board", "leaf_heads", "leaf_dirs", "leaf_deaths")
 def _batch(st, first_env_id=CASES.FIRST_ENV_ID):
     """a TronBatch holding the oracle state `st`, step counters included"""
     from colosseumrl_amd.batched import TronBatch
-    tb = TronBatch(st.N, st.P, st.B, device=DEV, first_env_id=first_env_id)
+    # (the start layout needs a 4x4 board; below that any distinct cells serve: the position is put over them)
+    start = None if st.N >= 4 else (list(range(st.P)), [0] * st.P)
+    tb = TronBatch(st.N, st.P, st.B, device=DEV, start=start, first_env_id=first_env_id)
     tron_put(tb, st.board, st.heads, st.dirs, st.deaths)
     tb.tcount.copy_(torch.from_numpy(st.tcount.view(np.int32)))
     return tb
@@ -89,12 +93,12 @@ def _reference(shape, B, S, S_cap=None, cpuct=256, fpu=32768, mode="mix", extra=
     """the restatement's root and per-simulation leaves of a case, computed once and shared"""
     N, P, agent = CASES.SHAPES[shape]
     return R.run(CASES.state(N, P, B), S, S_cap, cpuct, fpu, mode, None, True, extra, seed=CASES.SEED, first_env_id=CASES.FIRST_ENV_ID,
-                 seat=CASES.seats(P, B), agent=agent, noise=CASES.NOISE)
+                 seat=CASES.shape_seats(shape, B), agent=agent, noise=CASES.NOISE)
 
 
 def _compare(shape, B, S, what, **kw):
     N, P, agent = CASES.SHAPES[shape]
-    st, seat = CASES.state(N, P, B), CASES.seats(P, B)
+    st, seat = CASES.state(N, P, B), CASES.shape_seats(shape, B)
     ref_kw = {key: v for key, v in kw.items() if key in ("S_cap", "cpuct", "fpu", "mode", "extra")}
     want_root, want_seen = _reference(shape, B, S, **ref_kw)
     before = [a.copy() for a in (st.board, st.heads, st.dirs, st.deaths, st.tcount)]
@@ -162,15 +166,6 @@ def test_stepping_between_begin_and_root():
 
 
 # ------------------------------------------------------------------ 5. select -> evaluator on the device -> backup in one graph
-def _device_evaluator(leaves):
-    b = leaves["obs_board"].to(torch.int32)
-    wgt = torch.arange(1, b.shape[1] + 1, device=b.device, dtype=torch.int32)
-    h = ((b + 2) * (wgt % 251)).sum(dim=1, keepdim=True) + leaves["obs_heads"][0].to(torch.int32).view(-1, 1) * 977
-    prior = ((h * 31 + torch.arange(1, 4, device=b.device, dtype=torch.int32) * 7919) % 32749).to(torch.int16)
-    value = ((h.view(-1) * 131) % 65537).to(torch.int32)
-    return prior, value
-
-
 def test_graph_replay_equals_the_eager_run():
     N, P, agent = CASES.SHAPES[1]
     st, seat, S = CASES.state(N, P, 70), torch.from_numpy(CASES.seats(P, 70)).to(DEV), 40
@@ -223,7 +218,91 @@ def test_wrappers():
     assert a.dtype == torch.int64 and torch.equal(a, b) and bool(((a >= 0) & (a <= 2)).all())
 
 
-# ------------------------------------------------------------------ 7. strength, through the product
+# ------------------------------------------------------------------ 7. rows below one 16-byte chunk, rows at odd byte offsets
+def _compare_state(st, seat, agent, S, what, **kw):
+    """a search on the state `st` (not one of the table's shapes) against the restatement: every select and the root"""
+    ref_kw = {key: kw[key] for key in ("S_cap", "cpuct", "fpu", "mode", "extra") if key in kw}
+    want_root, want_seen = R.run(st, S, count=None, record=True, seed=CASES.SEED, first_env_id=CASES.FIRST_ENV_ID, seat=seat, agent=agent,
+                                 noise=kw.get("noise", CASES.NOISE), **ref_kw)
+    before = [a.copy() for a in (st.board, st.heads, st.dirs, st.deaths, st.tcount)]
+    tb, root, seen = _gpu_run(st, seat, agent, S, **kw)
+    assert len(seen) == len(want_seen)
+    for s, (g, w) in enumerate(zip(seen, want_seen)):
+        _same(g, w, (what, "select", s))
+    _same(root, want_root, (what, "root"))
+    assert all(np.array_equal(a, b) for a, b in zip(tron_state(tb) + [u32_of(tb.tcount)], before))
+    return root, seen
+
+
+@pytest.mark.parametrize("row", CASES.tiny_states(), ids=[row[0] for row in CASES.tiny_states()])
+def test_boards_below_16_cells(row):
+    name, st, seat, agent, noise = row
+    root, seen = _compare_state(st, seat, agent, CASES.TINY_S, name, noise=noise)
+    assert (root["nodes"] > 0).all() and seen[0]["pending"].all()
+
+
+@pytest.mark.parametrize("off", [1, 7, 15])
+@pytest.mark.parametrize("shape", [15, 7], ids=[CASES.SHAPE_IDS[i] for i in (15, 7)])
+def test_output_rows_at_odd_byte_offsets(shape, off):
+    """`obs_board` and `leaf_board` as views that start `off` and 16 - `off` bytes behind a 16-byte boundary of a larger buffer
+    (4x4: a row is one chunk and never aligned; 7x7: 49 bytes): the rows as the restatement has them, the guard bytes before and
+    behind the views untouched"""
+    N, P, agent = CASES.SHAPES[shape]
+    B, S, NN, G = 8, 20, N * N, 64
+    want_root, want_seen = _reference(shape, B, S)
+    tb = _batch(CASES.state(N, P, B))
+    tb.puct_begin(S, CASES.SEED, agent, CASES.NOISE, torch.from_numpy(CASES.shape_seats(shape, B)).to(DEV))
+    bufs = {key: torch.full((G + B * NN + G,), -7, dtype=torch.int8, device=DEV) for key in ("obs_board", "leaf_board")}
+    at = {"obs_board": 32 + off, "leaf_board": 48 - off}
+    out = {key: torch.empty(dims, dtype=dt, device=DEV) for key, (dt, dims) in tb._puct_select_spec().items()}
+    for key, buf in bufs.items():
+        assert buf.data_ptr() % 16 == 0
+        out[key] = buf[at[key]:at[key] + B * NN].view(B, NN)
+        assert out[key].data_ptr() % 16 == at[key] % 16 and out[key].is_contiguous()
+    for s in range(S):
+        got = _leaves_np(tb.puct_select(1.0, 0.5, out=out))       # (cpuct 256, fpu 32768: the reference's)
+        _same(got, want_seen[s], ("offset", off, "select", s))
+        for key, buf in bufs.items():
+            assert bool((buf[:at[key]] == -7).all()) and bool((buf[at[key] + B * NN:] == -7).all()), (key, s)
+        tb.puct_backup(*_eval_to_dev(*R.evaluator(got["obs_board"], got["obs_heads"], got["obs_dirs"])))
+    _same(_root_np(tb.puct_root()), want_root, ("offset", off, "root"))
+
+
+# ------------------------------------------------------------------ 8. the workgroup shapes of `select`: 4, 3, 2 waves and 1, up to 64 KB of LDS
+@pytest.mark.parametrize("N, P, B", CASES.LDS_CASES, ids=CASES.LDS_IDS)
+def test_every_workgroup_shape_of_select(N, P, B):
+    """127 | 128, 147 | 148, 180 | 181: the boards on either side of each change of the wave count (tests/test_tron_puct_host.py
+    restates the rule), B = 5 so that the last workgroup is ragged with 4, 3 and 2 waves; 181x181 has heads in the last row
+    and the last column"""
+    st, seat = CASES.lds_state(N, P, B)
+    root, seen = _compare_state(st, seat, "avoid", CASES.LDS_S, (N, P, B))
+    assert (root["sims"] == CASES.LDS_S).all()
+
+
+# ------------------------------------------------------------------ 9. trees of the greatest capacity
+@pytest.mark.parametrize("row", CASES.CAPACITY, ids=[row["id"] for row in CASES.CAPACITY])
+def test_trees_at_capacity(row):
+    """20x20 from the start layout, S = S_cap: 4,095 at the default exploration (trees of 3,860 and 3,789 nodes, 19 plies,
+    n up to 3,584), 1,024 at cpuct = 65,535; every select and the root, then two pairs past the capacity"""
+    st, S = CASES.capacity_state(), row["S"]
+    root, seen = _compare_state(st, None, "avoid", S, row["id"], cpuct=row["cpuct"], noise=CASES.CAPACITY_NOISE, extra=CASES.CAPACITY_EXTRA)
+    assert int(root["nodes"].max()) >= row["reaches"]["nodes"] and (root["sims"] == S).all()
+    for s in seen[S:]:
+        assert not s["pending"].any() and not s["obs_board"].any() and not s["depth"].any() and not s["obs_heads"].any()
+
+
+# ------------------------------------------------------------------ 10. the step's killer ids
+@pytest.mark.parametrize("agent", ["random", "avoid"])
+@pytest.mark.parametrize("N, P", CASES.CRASH_CASES, ids=["%dx%dp%d" % (N, N, P) for N, P in CASES.CRASH_CASES])
+def test_the_crash_rows(N, P, agent):
+    """the rows on which tests/test_tron_puct_host.py counts every crash kind above a pending leaf: the killer ids go out in
+    leaf_deaths and obs_deaths"""
+    st, seat = CASES.state(N, P, CASES.CRASH_B), CASES.crash_seats(P, CASES.CRASH_B)
+    root, seen = _compare_state(st, seat, agent, CASES.CRASH_S, ("crash", N, P, agent))
+    assert any(s["leaf_deaths"][:, s["pending"] == 1].any() for s in seen)
+
+
+# ------------------------------------------------------------------ 11. strength, through the product
 def _first_episode_wins(policy, games, seed=5, max_t=300):
     """the share of first episodes the learner wins in TronSinglePlayerVectorEnv(15, 4, noise 0.1)"""
     from colosseumrl_amd.vector import TronSinglePlayerVectorEnv

@@ -2,7 +2,9 @@
 refused with its message before any device work, the tree's size, the Python wrappers' argument checks and `puct_quantize`,
 and the plain-Python restatement of the header's contract (tests/tron_puct_ref.py) -- the properties any such tree has, its
 leaf positions against a replay with oracle.tron_step, the deep-path row closing where the GPU test says it does, and the
-case table of the GPU test reaching the edges it names."""
+case table of the GPU test reaching the edges it names: every player count among the shapes with every player seated, the
+hand-laid boards below 16 cells, the boards on either side of every change of `select`'s wave count, the capacity rows'
+tree sizes, and every crash kind of the step above a pending leaf under both models."""
 import ctypes as C
 
 import numpy as np
@@ -227,20 +229,19 @@ def _replay(st, b, seat, edges, agent, noise, seed, g, tc):
     return one
 
 
-@pytest.mark.parametrize("shape", [1, 3], ids=[CASES.SHAPE_IDS[i] for i in (1, 3)])
-def test_leaf_positions_equal_a_replay_with_the_oracle_step(shape):
-    N, P, agent = CASES.SHAPES[shape]
-    st, seat = CASES.state(N, P, 12), CASES.seats(P, 12)
-    sr = R.Search(st, 25, seed=CASES.SEED, first_env_id=CASES.FIRST_ENV_ID, seat=seat, agent=agent, noise=CASES.NOISE)
+def _replayed(st, seat, agent, noise, S, cpuct=256, count=None):
+    """S simulations on the restatement, every pending leaf (the leaf_* position and the observation) against a replay of its
+    edges with oracle.tron_step: the number of such leaves below the root"""
+    sr = R.Search(st, S, seed=CASES.SEED, first_env_id=CASES.FIRST_ENV_ID, seat=seat, agent=agent, noise=noise, count=count)
     checked = 0
-    for s in range(25):
-        leaves = sr.select()
+    for s in range(S):
+        leaves = sr.select(cpuct)
         for b, t in enumerate(sr.trees):
             if not leaves["pending"][b]:
                 continue
             edges = t.edges()
             assert leaves["depth"][b] == len(edges)
-            one = _replay(st, b, t.seat, edges, agent, CASES.NOISE, CASES.SEED, CASES.FIRST_ENV_ID + b, int(st.tcount[b]))
+            one = _replay(st, b, t.seat, edges, agent, noise, CASES.SEED, CASES.FIRST_ENV_ID + b, int(st.tcount[b]))
             assert np.array_equal(one.board[0], leaves["leaf_board"][b]) and np.array_equal(one.heads[:, 0], leaves["leaf_heads"][:, b])
             assert np.array_equal(one.dirs[:, 0], leaves["leaf_dirs"][:, b]) and np.array_equal(one.deaths[:, 0], leaves["leaf_deaths"][:, b])
             ob, oh, od, ok = O.tron_observe(one, np.array([t.seat], np.int8))
@@ -248,6 +249,13 @@ def test_leaf_positions_equal_a_replay_with_the_oracle_step(shape):
             assert np.array_equal(od[:, 0], leaves["obs_dirs"][:, b]) and np.array_equal(ok[:, 0], leaves["obs_deaths"][:, b])
             checked += len(edges) > 0
         sr.backup(*R.evaluator(leaves["obs_board"], leaves["obs_heads"], leaves["obs_dirs"]))
+    return checked
+
+
+@pytest.mark.parametrize("shape", [1, 3], ids=[CASES.SHAPE_IDS[i] for i in (1, 3)])
+def test_leaf_positions_equal_a_replay_with_the_oracle_step(shape):
+    N, P, agent = CASES.SHAPES[shape]
+    checked = _replayed(CASES.state(N, P, 12), CASES.seats(P, 12), agent, CASES.NOISE, 25)
     assert checked >= 12                                                         # (a leaf below the root per row, on average, at the least)
 
 
@@ -296,12 +304,152 @@ def test_the_case_table_reaches_its_edges():
             sr.backup(*R.evaluator(leaves["obs_board"], leaves["obs_heads"], leaves["obs_dirs"], case.get("mode", "mix")))
         for key, least in case["reaches"].items():
             assert count[key] >= least, (case["id"], key, count)
-    for shape, (N, P, agent) in zip(CASES.SHAPE_IDS, CASES.SHAPES):
+    for index, (shape, (N, P, agent)) in enumerate(zip(CASES.SHAPE_IDS, CASES.SHAPES)):
         count = R.new_count()
-        st, seat = CASES.state(N, P, 130), CASES.seats(P, 130)
+        st, seat = CASES.state(N, P, 130), CASES.shape_seats(index, 130)
+        if index < CASES.N_FIRST_SHAPES:
+            assert np.array_equal(seat, CASES.seats(P, 130))                      # (the first seven shapes keep their seats)
+        else:                                                                    # every player is the seat of a live tree
+            assert {t.seat for t in R.Search(st, 1, seat=seat).trees if not t.skipped} == set(range(P)), shape
         R.run(st, CASES.S_MAIN, count=count, seed=CASES.SEED, first_env_id=CASES.FIRST_ENV_ID, seat=seat, agent=agent,
               noise=CASES.NOISE)
         skipped = sum(t.skipped for t in R.Search(st, 1, seat=seat).trees)
         assert skipped >= 2 and count["terminal"] > 0 and count["created"] > 130, (shape, count)
         assert count["depth"] >= (1 if P == 1 else 3), (shape, count)
         assert 2 ** 32 - 3 in st.tcount.tolist()                                 # the counter wrap is among the rows
+
+
+def test_every_player_count_is_among_the_shapes():
+    """the eight template instances of `begin` and `select` all run, the odd player counts under both models, and the
+    smallest start-layout board with rows of one 16-byte chunk"""
+    assert {P for N, P, agent in CASES.SHAPES} == set(range(1, 9))
+    for P in (3, 5, 6, 7):
+        assert {agent for N, p, agent in CASES.SHAPES if p == P} == {"random", "avoid"}
+        assert all((N * N) % 16 for N, p, agent in CASES.SHAPES if p == P and N > 4)     # planes off the 16-byte grid
+    assert (4, 2, "avoid") in CASES.SHAPES and (4, 3, "random") in CASES.SHAPES
+    assert len(CASES.SHAPE_IDS) == len(CASES.SHAPES) == len(set(CASES.SHAPE_IDS))
+    assert CASES.SHAPES[:7] == [(5, 2, "random"), (13, 4, "avoid"), (20, 4, "random"), (9, 8, "random"), (9, 8, "avoid"), (33, 2, "avoid"),
+                                (5, 1, "random")]                                # appended, not reordered
+
+
+def test_the_hand_laid_boards_below_16_cells_reach_their_leaves():
+    """3x3 with two players: some row has a pending leaf below the root; 2x2 with one player: the root is pending and
+    nothing below it is.  Both are consistent positions (every head on a cell of its own colour) with rows that differ."""
+    for name, st, seat, agent, noise in CASES.tiny_states():
+        assert st.N * st.N < 16 and st.B == 8 and len(set(st.tcount.tolist())) == 8
+        assert len({(tuple(st.heads[:, b]), tuple(st.dirs[:, b])) for b in range(8)}) == 8
+        for b in range(8):
+            assert all(st.board[b, st.heads[p, b]] == p + 1 for p in range(st.P)) and len(set(st.heads[:, b].tolist())) == st.P
+        count = R.new_count()
+        root, seen = R.run(st, CASES.TINY_S, count=count, record=True, seed=CASES.SEED, first_env_id=CASES.FIRST_ENV_ID, seat=seat,
+                           agent=agent, noise=noise)
+        assert (root["nodes"] > 0).all() and (root["sims"] == CASES.TINY_S).all() and seen[0]["pending"].all(), name
+        below = sum(int(((s["pending"] == 1) & (s["depth"] > 0)).sum()) for s in seen)
+        if st.P == 1:
+            assert below == 0 and count["depth"] == 1 and count["terminal"] == 8 * (CASES.TINY_S - 1)
+        else:
+            assert below >= 1 and count["depth"] >= 2 and count["terminal"] > 0, (name, count)
+            assert _replayed(st, seat, agent, noise, CASES.TINY_S) == below
+
+
+def _waves(N):
+    """the header's rule for `select`: one wave's LDS is the byte board rounded up to 16 bytes plus 16 bytes; a workgroup
+    has as many waves as fit in 64 KB, four at the most"""
+    wave_lds = (N * N + 15) // 16 * 16 + 16
+    return min(4, 65536 // wave_lds), wave_lds
+
+
+def test_the_lds_cases_stand_on_either_side_of_every_change_of_the_wave_count():
+    waves = {N: _waves(N)[0] for N in range(2, 182)}                             # (181: the largest board a context takes)
+    assert all(1 <= w <= 4 for w in waves.values())
+    edges = sorted(N for N in range(2, 181) if waves[N] != waves[N + 1])
+    assert edges == [127, 147, 180] and [waves[N] for N in (127, 128, 147, 148, 180, 181)] == [4, 3, 3, 2, 2, 1]
+    assert sorted({N for N, P, B in CASES.LDS_CASES}) == sorted(edges + [N + 1 for N in edges])
+    assert _waves(127) == (4, 16160) and 4 * 16160 == 64640 and _waves(181) == (1, 32784)
+    for N, P, B in CASES.LDS_CASES:                                              # no wave count divides B: a ragged last workgroup
+        assert waves[N] == 1 or B % waves[N], (N, B)
+    assert (181, 8, 3) in CASES.LDS_CASES
+
+
+@pytest.mark.parametrize("N, P, B", CASES.LDS_CASES, ids=CASES.LDS_IDS)
+def test_the_lds_rows_search_open_mid_game_boards(N, P, B):
+    st, seat = CASES.lds_state(N, P, B)
+    count = R.new_count()
+    root, seen = R.run(st, CASES.LDS_S, count=count, record=True, seed=CASES.SEED, first_env_id=CASES.FIRST_ENV_ID, seat=seat,
+                       agent="avoid", noise=CASES.NOISE)
+    assert (root["nodes"] > 1).all() and (root["sims"] == CASES.LDS_S).all() and count["depth"] >= 3, count
+    if N == 181:
+        assert st.heads[0, 0] == N * N - 1 and st.heads[1, 1] > 32700 and st.heads[1, 1] // N == N - 1
+        # the seat of row 0 leaves the board over the last cell (forward and right: terminal leaves), and pending leaves below
+        # the root carry heads above 32,700 (row 1 along the last row)
+        assert sum(1 for s in seen if not s["pending"][0]) >= 2
+        assert any(s["pending"][1] and s["depth"][1] > 0 and s["leaf_heads"][1, 1] > 32700 for s in seen)
+        assert any(s["pending"][b] and s["depth"][b] > 0 and s["obs_heads"][:, b].max() > 32700 for s in seen for b in range(B))
+
+
+@pytest.mark.parametrize("row", CASES.CAPACITY, ids=[row["id"] for row in CASES.CAPACITY])
+def test_the_capacity_rows_grow_large_trees(row):
+    st = CASES.capacity_state()
+    count = R.new_count()
+    sr = R.Search(st, row["S"], seed=CASES.SEED, first_env_id=CASES.FIRST_ENV_ID, agent="avoid", noise=CASES.CAPACITY_NOISE, count=count)
+    differ = 0
+    for _ in range(row["S"]):
+        leaves = sr.select(row["cpuct"])
+        differ += not np.array_equal(leaves["obs_board"][0], leaves["obs_board"][1])
+        sr.backup(*R.evaluator(leaves["obs_board"], leaves["obs_heads"], leaves["obs_dirs"]))
+    print("\n%s: nodes %s, depth %d, greatest n below the root %s, greatest w %s, selects in which the rows differ %d"
+          % (row["id"], [t.nodes for t in sr.trees], count["depth"], [max(t.n[1:]) for t in sr.trees], [max(t.w) for t in sr.trees], differ))
+    assert max(t.nodes for t in sr.trees) >= row["reaches"]["nodes"]             # child indices above 255 (2048: above 11 bits)
+    assert count["depth"] >= row["reaches"]["depth"]
+    assert all(max(t.n[1:]) >= row["reaches"]["n"] for t in sr.trees)            # a node with n > 255
+    assert max(max(t.w) for t in sr.trees) >= row["reaches"].get("w", 0)         # w sums within a factor of four of 4095 * 65536
+    assert differ > row["S"] // 4                                                 # the two rows are two searches
+    assert all(t.sims == row["S"] for t in sr.trees)
+    sr.select(row["cpuct"])
+    assert count["refused"] == 2
+
+
+@pytest.mark.parametrize("agent", ["random", "avoid"])
+def test_the_crash_rows_meet_every_kind_on_the_way_to_a_pending_leaf(agent):
+    """every crash kind of tron_mcts_ref.CRASH_KINDS happens to a player other than the seat above a pending leaf, under each
+    model; the same leaves are held to a replay with oracle.tron_step"""
+    total = R.new_count()
+    for N, P in CASES.CRASH_CASES:
+        count = R.new_count()
+        below = _replayed(CASES.state(N, P, CASES.CRASH_B), CASES.crash_seats(P, CASES.CRASH_B), agent, CASES.NOISE, CASES.CRASH_S,
+                          count=count)
+        assert below > CASES.CRASH_B
+        for key in count:
+            total[key] += count[key]
+        if P == 8:                                                               # the eight-player rows meet the head-on kinds alone
+            assert all(count["crash_" + kind] > 0 for kind in "def"), (N, P, count)
+    print("\n%s: %s" % (agent, {kind: total["crash_" + kind] for kind in TM.CRASH_KINDS}))
+    assert all(total["crash_" + kind] > 0 for kind in TM.CRASH_KINDS), total
+
+
+def test_the_step_names_its_crash_kinds():
+    """tron_mcts_ref.step's events on hand-laid 5x5 positions, one per kind, each also held to oracle.tron_step"""
+    def play(P, heads, dirs, trail, dead, act):
+        st = O.TronState(5, P, 1)
+        for cell, v in trail.items():
+            st.board[0, cell] = v
+        for p, (h, d) in enumerate(zip(heads, dirs)):
+            st.heads[p, 0], st.dirs[p, 0], st.board[0, h] = h, d, p + 1
+        for p, k in dead.items():
+            st.deaths[p, 0] = k
+        pos, count = TM.pos_of(st, 0), {"events": []}
+        TM.step(5, pos, act, count)
+        O.tron_step(st, np.array(act, np.int8).reshape(P, 1))
+        assert pos.board == st.board[0].tolist() and pos.h == st.heads[:, 0].tolist() and pos.k == st.deaths[:, 0].tolist()
+        assert pos.d == [int(x) & 3 for x in st.dirs[:, 0]]
+        return count["events"], pos
+    # (a) off the board, (b) into another's trail, (c) into its own trail
+    ev, pos = play(3, [0, 12, 24], [0, 1, 1], {13: 3, 19: 3, 23: 3}, {}, [0, 0, -1])
+    assert ev == [("a", 0), ("b", 1), ("c", 2)] and pos.k == [1, 3, 3]
+    # (d) + (g): player 0 runs into the live head of player 2, who then neither moves nor turns; (e): player 1 runs into the
+    # head of player 3, dead before (killer id 4 overwritten with 2)
+    ev, pos = play(4, [11, 21, 12, 22], [1, 1, 0, 0], {}, {3: 4}, [0, 0, 1, 0])
+    assert ev == [("d", 2), ("e", 3), ("g", 2)] and pos.k == [3, 4, 1, 2] and pos.d == [1, 1, 0, 0]
+    # (f): players 0 and 1 go for cell 12; the later one dies against the earlier one's new head, and kills it
+    ev, pos = play(2, [11, 13], [1, 3], {}, {}, [0, 0])
+    assert ev == [("d", 0), ("f", 1)] and pos.k == [2, 1] and pos.h == [12, 13] and pos.board[12] == 1

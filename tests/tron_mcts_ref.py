@@ -73,11 +73,17 @@ def pos_of(st, b):
 
 def step(N, pos, act, count=None):
     """crl_tron_step without reset, in place; act: P values of 0, +1, -1.  -> (terminal, winners mask).  `count`: a dict whose
-    'head_on' grows by one for every move onto a head (the hit that also kills the owner of the head)"""
+    'head_on' (where it has one) grows by one for every move onto a head (the hit that also kills the owner of the head), and
+    to whose list 'events' (where it has one) every crash of the step is added as (kind, player), the kinds being those of
+    CRASH_KINDS"""
     P = len(pos.h)
     bd, h, d, k = pos.board, pos.h, pos.d, pos.k
+    events = None if count is None else count.get("events")
+    was_alive, moved = [x == 0 for x in k], [False] * P
     for i in range(P):
         if k[i] > 0:
+            if events is not None and was_alive[i]:
+                events.append(("g", i))                          # killed head-on by an earlier mover: no move, no turn
             continue
         x, y = h[i] % N, h[i] // N
         dr = (d[i] + act[i] + 4) % 4
@@ -85,22 +91,39 @@ def step(N, pos, act, count=None):
         d[i] = dr
         if x < 0 or x >= N or y < 0 or y >= N:
             k[i] = i + 1
+            if events is not None:
+                events.append(("a", i))
         elif bd[y * N + x] > 0:
             enemy = bd[y * N + x]
             k[i] = enemy
             if h[enemy - 1] == y * N + x:
+                if events is not None:                           # the owner of the head gets the mover's id: (d) alive, (e) dead
+                    events.append(("d" if k[enemy - 1] == 0 else "e", enemy - 1))
+                    if k[enemy - 1] == 0 and moved[enemy - 1]:
+                        events.append(("f", i))                  # both went for the same free cell; the later one is i
                 k[enemy - 1] = i + 1
-                if count is not None:
+                if count is not None and "head_on" in count:
                     count["head_on"] += 1
+            elif events is not None:
+                events.append(("c" if enemy == i + 1 else "b", i))
         else:
             bd[y * N + x] = i + 1
             h[i] = y * N + x
+            moved[i] = True
     mask = 0
     for i in range(P):
         if k[i] == 0:
             mask |= 1 << i
     term = bin(mask).count("1") <= 1
     return term, (mask if term else 0)
+
+
+# what can happen to a player in one step, by the killer id it leaves: (a) off the board: its own id; (b) into another
+# player's trail: that player's id; (c) into its own trail: its own id; (d) the owner of a live head that a mover runs
+# into: the mover's id (the mover gets the owner's); (e) the same for the head of a player that was dead already: its id is
+# overwritten; (f) the later of two movers to one free cell, head-on against the earlier one's new head; (g) a player
+# killed head-on by an earlier mover of the same step, at its own turn: it neither moves nor turns
+CRASH_KINDS = ("a", "b", "c", "d", "e", "f", "g")
 
 
 def _clamped(N, h, dr):

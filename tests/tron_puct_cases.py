@@ -13,7 +13,18 @@ from tests import tron_mcts_ref as TM
 # x 16 B); one player (closed at depth 1)
 SHAPES = [(5, 2, "random"), (13, 4, "avoid"), (20, 4, "random"), (9, 8, "random"), (9, 8, "avoid"), (33, 2, "avoid"), (5, 1, "random")]
 SHAPE_IDS = ["5x5p2-random", "13x13p4-avoid", "20x20p4-random", "9x9p8-random", "9x9p8-avoid", "33x33p2-avoid", "5x5p1-random"]
-BATCHES = (1, 5, 130)        # fewer trees than waves, a ragged last workgroup, more than one trip of a capped grid's stride
+# behind the first seven (appended: the ids above keep their meaning): the other four template instances, P = 3, 5, 6 and 7,
+# under both models on boards off the 16-byte grid (49 and 81 cells) -- tp_relative4's division by a P that is no power of
+# two, the second Philox block serving one, two and three of players 4..7, the seat rotation wrapping at such a P --, and
+# the smallest board the start layout has, 4x4: rows of exactly one 16-byte chunk, which is whole only where the output row
+# happens to be aligned
+N_FIRST_SHAPES = len(SHAPES)
+SHAPES += [(7, 3, "random"), (7, 3, "avoid"), (7, 5, "random"), (7, 5, "avoid"), (9, 6, "random"), (9, 6, "avoid"), (9, 7, "random"),
+           (9, 7, "avoid"), (4, 2, "avoid"), (4, 3, "random")]
+SHAPE_IDS += ["%dx%dp%d-%s" % (N, N, P, agent) for N, P, agent in SHAPES[N_FIRST_SHAPES:]]
+# fewer trees than waves; a ragged last workgroup; 33 workgroups of four waves, the last one ragged (ONE trip of the
+# grid-stride loop: the grid is capped at 2^20 workgroups, tests/test_gpu_large.py takes the second trip)
+BATCHES = (1, 5, 130)
 S_MAIN = 40
 SEED, FIRST_ENV_ID, NOISE = 0x1234567887654321, (1 << 32) - 2, 0.25     # (g wraps inside the batch)
 
@@ -43,6 +54,19 @@ def seats(P, B):
     s[np.arange(B) % 11 == 6] = P
     s[np.arange(B) % 11 == 10] = -1
     return s.astype(np.int8)
+
+
+def shape_seats(shape, B):
+    """the seats of a shape's rows: `seats` for the first seven shapes; for the later ones the even rows go through the
+    players one by one (b // 2 mod P: `seats` gives an even row b mod P, which never reaches an odd player of an even P), so
+    that at B = 130 every player is the seat of a live tree (tests/test_tron_puct_host.py requires it)"""
+    N, P, agent = SHAPES[shape]
+    s = seats(P, B)
+    if shape >= N_FIRST_SHAPES:
+        b = np.arange(B)
+        turn = (b % 2 == 0) & (b % 11 != 6) & (b % 11 != 10)
+        s[turn] = ((b // 2) % P)[turn]
+    return s
 
 
 def deep_state():
@@ -79,3 +103,81 @@ EDGE_CASES = [
 def edge_state(case):
     N, P, agent = SHAPES[case["shape"]]
     return state(N, P, 8), seats(P, 8), agent
+
+
+# ---- boards of fewer than 16 cells (tp_stream_row's `head = min(NN, ...)` decides, no whole chunk): the start layout needs
+# N >= 4, so these are laid by hand, 8 rows each with their own directions and step counters, S = 6
+def tiny_states():
+    """[(id, state, seat, agent, noise)]: 3x3 with two players -- the seat in a corner, player 1 in the opposite one, the
+    directions turning from row to row; 2x2 with one player, whose every child is closed (a single player's game is over
+    when it is dead, and only then), so that the root is the only pending leaf"""
+    three = O.TronState(3, 2, 8)
+    for b in range(8):
+        h0, h1 = ((0, 8), (2, 6), (8, 0), (6, 2))[b % 4]
+        three.heads[:, b], three.dirs[:, b] = [h0, h1], [b % 4, (b // 2 + 1) % 4]
+        three.board[b, h0], three.board[b, h1] = 1, 2
+        if b >= 4:                                               # a trail cell in the middle of an edge, next to the seat's corner
+            three.board[b, (1, 5, 7, 3)[b % 4]] = 1
+    three.tcount[:] = [0, 1, 6, 7, 8, 2 ** 32 - 1, 2 ** 31, 12345]
+    two = O.TronState(2, 1, 8)
+    for b in range(8):
+        two.heads[0, b], two.dirs[0, b] = b % 4, (b // 2) % 4
+        two.board[b, b % 4] = 1
+        if b >= 4:
+            two.board[b, (b + 2) % 4] = 1                        # the diagonal cell taken: it is never probed
+    two.tcount[:] = [3, 2 ** 32 - 1, 0, 9, 10, 11, 2 ** 31, 77]
+    return [("3x3p2-avoid", three, (np.arange(8) % 2 * (np.arange(8) >= 4)).astype(np.int8), "avoid", NOISE),
+            ("2x2p1-random", two, np.zeros(8, np.int8), "random", NOISE)]
+
+
+TINY_S = 6
+
+
+# ---- the workgroup shapes of `select`: four waves up to 127x127, three for 128..147, two for 148..180, one at 181
+LDS_CASES = [(127, 2, 5), (128, 2, 5), (147, 2, 5), (148, 2, 5), (180, 2, 5), (181, 2, 5), (181, 8, 3)]
+LDS_IDS = ["%dx%dp%d-B%d" % (N, N, P, B) for N, P, B in LDS_CASES]
+LDS_S = 12
+
+
+@functools.lru_cache(maxsize=None)
+def lds_state(N, P, B):
+    """(state, seat): avoid-agent games after at most 30 steps (the defaults play N*N / P oracle steps: seconds per board).
+    On the 181x181 board, row 0 has the seat's head in the last cell (32,760: the last row and the last column, forward and
+    right leave the board) and row 1 has player 1's head in the last row at cell 32,730, the top of what an int16 head and
+    umulhi(h, inv_n) have to carry.  The callers never write it."""
+    st = TM.positions(N, P, B, np.random.default_rng([N, P, B]), most=30)
+    seat = (np.arange(B) % P).astype(np.int8)
+    if N == 181:
+        for b, p, cell, d in ((0, 0, N * N - 1, 1), (1, 1, 180 * N + 150, 1)):
+            assert st.board[b, cell] == 0 and st.deaths[p, b] == 0 and seat[b] == p
+            st.board[b, cell], st.heads[p, b], st.dirs[p, b] = p + 1, cell, d     # (the old head stays behind as trail)
+    return st, seat
+
+
+# ---- a tree at the greatest capacity: 20x20, two players, the start layout, the avoid model at noise 0 (with the table's
+# noise the seat finds a line in which the other player kills itself within four plies, and the tree stays at 80 nodes), the
+# rows told apart by their step counters.  Second: the exploration term at the top of its range while n grows.
+CAPACITY = [{"id": "S=4095", "S": 4095, "cpuct": 256, "reaches": {"nodes": 2049, "depth": 12, "n": 256, "w": 1 << 26}},
+            {"id": "cpuct=65535", "S": 1024, "cpuct": 65535, "reaches": {"nodes": 257, "depth": 8, "n": 256}}]
+CAPACITY_NOISE, CAPACITY_EXTRA = 0.0, 2
+
+
+def capacity_state():
+    st = O.TronState(20, 2, 2)
+    O.tron_reset(st, *O.tron_start_positions(20, 2))
+    st.tcount[:] = [0, 2]                                        # (at noise 0 one coin of the avoid model tells the rows apart: 0 and 1 draw it alike)
+    return st
+
+
+# ---- the crash kinds of one tree step (tron_mcts_ref.CRASH_KINDS), each to be met by a player other than the seat on the
+# way to a pending leaf under both models: (shape, noise) with B = 32, S = 30.  Three players give (a) to (c), four the
+# head-on kinds, eight (on 49 and 81 cells) every kind including the head of a dead player
+CRASH_CASES = [(7, 3), (5, 4), (7, 4), (7, 8), (9, 8)]
+CRASH_B, CRASH_S = 32, 30
+
+
+def crash_seats(P, B):
+    """the players in turn on the even rows (the odd ones keep player 0, whose walk late_positions leaves free)"""
+    s = (np.arange(B) // 2) % P
+    s[np.arange(B) % 2 == 1] = 0
+    return s.astype(np.int8)

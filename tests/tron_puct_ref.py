@@ -9,8 +9,10 @@ position from the descent that made the node instead of replaying the edges in e
 replays them with oracle.tron_step.
 
 `count`: a dict (see `new_count`) of what a search went over -- the deepest path, terminal leaves, nodes made on the way down,
-backups with zero-sum priors, prior slots that hit the 65535 clamp, selects refused at capacity -- so that a test can
-require that its cases reach the edges they name.
+backups with zero-sum priors, prior slots that hit the 65535 clamp, selects refused at capacity, and, under "crash_a" ..
+"crash_g", the pending leaves on whose way from the root a player other than the seat met that crash kind of
+tron_mcts_ref.CRASH_KINDS (so that its killer id is in the leaf that goes out) -- so that a test can require that its cases
+reach the edges they name.
 
 `evaluator`: the deterministic integer test evaluator, a pure function of (obs_board, obs_heads, obs_dirs) written once in
 numpy, so that the host tests and the GPU tests apply the same function between select and backup."""
@@ -20,13 +22,15 @@ import numpy as np
 
 from oracle import oracle as O
 from tests.rng_ref import M32, threshold
-from tests.tron_mcts_ref import is_closed, pos_of, tree_step
+from tests.tron_mcts_ref import CRASH_KINDS, is_closed, pos_of, tree_step
 
 FULL_VALUE, MAX_S = 65536, 4095
 
 
 def new_count():
-    return {"depth": 0, "terminal": 0, "created": 0, "zero_sum": 0, "clamped": 0, "refused": 0}
+    count = {"depth": 0, "terminal": 0, "created": 0, "zero_sum": 0, "clamped": 0, "refused": 0}
+    count.update(("crash_" + kind, 0) for kind in CRASH_KINDS)
+    return count
 
 
 def tree_bytes_floor(S_cap, N):
@@ -60,6 +64,7 @@ class Tree:
         self.prior, self.child, self.expanded, self.where = [[0] * 3], [[0] * 3], [False], [root.copy()]
         self.sims = 0
         self.path, self.kind = None, None                        # kind: "pending" | "terminal"
+        self.met = [frozenset()]                                 # per node: the crash kinds players other than the seat met on the way
 
     @property
     def nodes(self):
@@ -86,8 +91,10 @@ class Tree:
             e = max(range(3), key=key)
             if not self.child[v][e]:
                 pos = self.where[v].copy()
+                step_count = {"events": []}
                 tree_step(self.N, pos, self.seat, e, self.agent, self.thr, self.k0, self.k1, self.g,
-                          (self.tc + len(path) - 1) & M32)
+                          (self.tc + len(path) - 1) & M32, step_count)
+                self.met.append(self.met[v] | {kind for kind, who in step_count["events"] if who != self.seat})
                 self.n.append(0), self.w.append(0), self.expanded.append(False)
                 self.prior.append([0] * 3), self.child.append([0] * 3), self.where.append(pos)
                 self.child[v][e] = len(self.n) - 1
@@ -106,6 +113,9 @@ class Tree:
         self.path = path
         if count is not None:
             count["depth"] = max(count["depth"], len(path) - 1)
+            if self.kind == "pending":
+                for kind in self.met[path[-1]]:
+                    count["crash_" + kind] += 1
         return (self.where[path[-1]], len(path) - 1) if self.kind == "pending" else None
 
     def edges(self):

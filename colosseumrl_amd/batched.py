@@ -169,6 +169,17 @@ def _out_dict(out: Optional[dict], spec: dict, device) -> dict:
     return out
 
 
+def _puct_quantize(policy: torch.Tensor, value: torch.Tensor):
+    """float weights [B, K] and float values in [0, 1] -> (int16 holding uint16 bits, each row's greatest weight 65535; int32 on
+    0 .. 65536) for the ``puct_backup`` of any game: a NaN weight counts as 0, a NaN value as 0.5.  Torch operations only."""
+    pol = torch.nan_to_num(policy.to(torch.float32), nan=0.0, posinf=0.0).clamp_min(0.0)
+    top = pol.amax(dim=1, keepdim=True).clamp_min(1e-30)
+    q = torch.round(pol * (65535.0 / top)).to(torch.int32).clamp(0, 65535)
+    prior = torch.where(q >= 32768, q - 65536, q).to(torch.int16)
+    val = torch.round(torch.nan_to_num(value.to(torch.float32), nan=0.5).clamp(0.0, 1.0) * 65536.0).to(torch.int32)
+    return prior.contiguous(), val.contiguous()
+
+
 def _flat_mc_pick(value: torch.Tensor, played: torch.Tensor, ids: torch.Tensor):
     """int64 [B]: ids[b, a] of the greatest value among the played rows (ties: the lowest a), -1 where none was played"""
     value = torch.where(played > 0, value, torch.full_like(value, -1))
@@ -1263,12 +1274,7 @@ class TTTBatch(_RolloutStepper):
         """(float policy [B, cells]: any non-negative weights, float value [B, P] in [0, 1]) -> (int16 prior holding the
         contract's uint16 bits, int32 value on 0 .. 65536) for ``puct_backup``.  Each row's weights are scaled so that its
         greatest is 65535 (the backup normalises over the empty cells anyway); NaN counts as 0.  Torch operations only."""
-        pol = torch.nan_to_num(policy.to(torch.float32), nan=0.0, posinf=0.0).clamp_min(0.0)
-        top = pol.amax(dim=1, keepdim=True).clamp_min(1e-30)
-        q = torch.round(pol * (65535.0 / top)).to(torch.int32).clamp(0, 65535)
-        prior = torch.where(q >= 32768, q - 65536, q).to(torch.int16)
-        val = torch.round(torch.nan_to_num(value.to(torch.float32), nan=0.5).clamp(0.0, 1.0) * 65536.0).to(torch.int32)
-        return prior.contiguous(), val.contiguous()
+        return _puct_quantize(policy, value)
 
     def puct(self, evaluate, simulations: int, exploration: float = 1.25, fpu: float = 0.5, out: Optional[dict] = None):
         """A whole search: ``puct_begin(simulations)``, then ``simulations`` times ``puct_select`` -> ``evaluate(leaves)`` ->
@@ -1621,6 +1627,125 @@ class BlokusBatch(_RolloutStepper):
         launch, with the same statistics tensors, ``results()`` rows and step counter."""
         search = self._agent_args(simulations, playouts, width, exploration, noise)
         self._call("crl_blokus_rollout_mcts", _seed(seed), self.first_env_id, int(steps), *search, *self._state(), self._stats())
+
+    # -- the search valued by the caller's network (PUCT) over sampled candidates; the contract is with crl_blokus_puct_begin
+    # in include/colosseum_hip.h
+    PUCT_MAX_CAPACITY = 4095
+
+    def _puct_open(self):
+        if getattr(self, "_puct_cap", None) is None:
+            raise ValueError("no search is open: call puct_begin(capacity) first")
+        return self._puct_tree, self._puct_cap, self._puct_width
+
+    def _puct_select_spec(self):
+        i32, B, W = torch.int32, self.B, self._puct_width
+        return {"board": (torch.int8, (B, 20, 20)), "pieces": (torch.uint8, (B, 4, 21)), "score": (i32, (B, 4)),
+                "cand": (i32, (B, W)), "n_cand": (i32, (B,)), "n_legal": (i32, (B,)), "mover": (torch.int8, (B,)),
+                "pending": (torch.uint8, (B,)), "depth": (i32, (B,)), "leaf_occ": (i32, (B, 4, 20)), "leaf_inv": (i32, (B, 4)),
+                "leaf_score": (i32, (B, 4)), "leaf_round": (i32, (B,)), "leaf_to_move": (i32, (B,))}
+
+    def _puct_root_spec(self):
+        i32, BW = torch.int32, (self.B, self._puct_width)
+        return {"ids": (i32, BW), "visits": (i32, BW), "value": (i32, BW), "prior": (i32, BW), "nodes": (i32, (self.B,)),
+                "sims": (i32, (self.B,)), "best": (i32, (self.B,))}
+
+    def puct_begin(self, capacity: int, width: int = 16, seed: int = 0):
+        """Opens a search of at most ``capacity`` (1 .. 4095) simulations whose nodes have at most ``width`` (1 .. 64) sampled
+        candidate actions, from every game's position (``crl_blokus_puct_begin``): the trees live in a device tensor of this
+        stepper, allocated here or reused when capacity and width are the last ones', and hold their own copy of the position
+        -- the batch may be stepped while the search is open.  ``seed``, the game ids and ``tcount`` key the candidate draws.
+        One launch, no host synchronisation."""
+        cap = _int_in("capacity", capacity, 1, self.PUCT_MAX_CAPACITY)
+        W = _int_in("width", width, 1, 64)
+        if (getattr(self, "_puct_cap", None), getattr(self, "_puct_width", None)) != (cap, W):
+            nbytes = self._lib.crl_blokus_puct_tree_bytes(self._ctx.handle, cap, W)
+            if nbytes < 0:
+                check(int(nbytes), "crl_blokus_puct_tree_bytes")
+            with torch.cuda.device(self.device):
+                self._puct_tree = torch.empty((self.B, int(nbytes) // 16, 2), dtype=torch.int64, device=self.device)   # (16-byte units)
+            self._puct_cap, self._puct_width = cap, W
+        self._call("crl_blokus_puct_begin", _seed(seed), self.first_env_id, *self._state(), _ptr(self.tcount), cap, W,
+                   _ptr(self._puct_tree))
+
+    def puct_select(self, exploration: float = 1.25, fpu: float = 0.5, out: Optional[dict] = None):
+        """One descent of every open tree (``crl_blokus_puct_select``): ``exploration`` is c of the PUCT score (0 .. 65535 / 256),
+        ``fpu`` the value in [0, 1] of a child without a visit.  Returns the leaves that wait for the caller's network:
+        {'board' int8 [B, 20, 20], 'pieces' uint8 [B, 4, 21], 'score' int32 [B, 4]: the observation of the leaf's mover, 'cand'
+        int32 [B, width]: the dense ids of the leaf's sampled candidates (-1 the pass, -2 beyond 'n_cand'), 'n_cand', 'n_legal'
+        int32 [B], 'mover' int8 [B], 'pending' uint8 [B], 'depth' int32 [B], 'leaf_occ', 'leaf_inv', 'leaf_score',
+        'leaf_round', 'leaf_to_move': the leaf position in the state layout}; rows whose tree has no pending leaf (a terminal
+        leaf, at capacity) are zeros with cand -2 and mover -1.  ``out`` reuses such a dict.  One launch, no host
+        synchronisation."""
+        tree, cap, W = self._puct_open()
+        cpuct = _exploration("exploration", exploration)
+        fpu16 = int(round(65536.0 * _unit("fpu", fpu)))
+        out = _out_dict(out, self._puct_select_spec(), self.device)
+        self._call("crl_blokus_puct_select", _ptr(tree), cap, W, cpuct, fpu16, _ptr(out["board"]), _ptr(out["pieces"]),
+                   _ptr(out["score"]), _ptr(out["cand"]), _ptr(out["n_cand"]), _ptr(out["n_legal"]), _ptr(out["mover"]),
+                   _ptr(out["pending"]), _ptr(out["depth"]), _ptr(out["leaf_occ"]), _ptr(out["leaf_inv"]), _ptr(out["leaf_score"]),
+                   _ptr(out["leaf_round"]), _ptr(out["leaf_to_move"]), 0)
+        return out
+
+    def puct_backup(self, prior: torch.Tensor, value: torch.Tensor):
+        """Expands the pending leaves with ``prior`` (uint16 [B, width], or int16 of the same bits: any weights of the leaf's
+        candidates, normalised over them) and backs ``value`` up (int32 [B, 4]: the value on 0 .. 65536 of the leaf's mover,
+        then of the players after it in turn order); terminal leaves back their outcome up (``crl_blokus_puct_backup``).  One
+        launch."""
+        tree, cap, W = self._puct_open()
+        if not isinstance(prior, torch.Tensor) or prior.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            raise ValueError("prior must be a uint16 (or int16) tensor of shape (%d, %d)" % (self.B, W))
+        _want(prior, prior.dtype, (self.B, W), self.device, "prior")
+        if not isinstance(value, torch.Tensor):
+            raise ValueError("value must be an int32 tensor of shape (%d, 4)" % self.B)
+        _want(value, torch.int32, (self.B, 4), self.device, "value")
+        self._call("crl_blokus_puct_backup", _ptr(tree), cap, W, _ptr(prior), _ptr(value), 0)
+
+    def puct_root(self, out: Optional[dict] = None):
+        """The root of every open tree (``crl_blokus_puct_root``): {'ids' int32 [B, width]: the root's candidates (-1 the pass,
+        -2 an empty slot), 'visits', 'value', 'prior' int32 [B, width]: simulations through the child in each slot, its summed
+        value for the root's mover (65536 per won simulation) and the root's stored priors, 'nodes', 'sims', 'best' int32 [B]:
+        the id of the most visited child (ties: the larger value, then the lowest slot; -2 without a visited child)}.  The
+        visit counts over 'ids' are the policy target of an AlphaZero-style trainer.  One launch."""
+        tree, cap, W = self._puct_open()
+        out = _out_dict(out, self._puct_root_spec(), self.device)
+        self._call("crl_blokus_puct_root", _ptr(tree), cap, W, _ptr(out["ids"]), _ptr(out["visits"]), _ptr(out["value"]),
+                   _ptr(out["prior"]), _ptr(out["nodes"]), _ptr(out["sims"]), _ptr(out["best"]))
+        return out
+
+    @staticmethod
+    def puct_quantize(policy: torch.Tensor, value: torch.Tensor):
+        """(float policy [B, width]: any non-negative weights of the candidates, float value [B, 4] in [0, 1]) -> (int16 prior
+        holding the contract's uint16 bits, int32 value on 0 .. 65536) for ``puct_backup``.  Each row's weights are scaled so
+        that its greatest is 65535 (the backup normalises over the candidates anyway); a NaN weight counts as 0, a NaN value
+        as 0.5.  Torch operations only."""
+        return _puct_quantize(policy, value)
+
+    def puct(self, evaluate, simulations: int, width: int = 16, exploration: float = 1.25, fpu: float = 0.5, seed: int = 0,
+             out: Optional[dict] = None):
+        """A whole search: ``puct_begin(simulations, width, seed)``, then ``simulations`` times ``puct_select`` ->
+        ``evaluate(leaves)`` -> ``puct_backup``, then ``puct_root``.  ``evaluate`` takes the select dict and returns (prior,
+        value), either the integer tensors of ``puct_backup`` or float tensors (then ``puct_quantize`` turns them).  Two
+        launches per simulation beside the caller's network; no host synchronisation.  Returns the root dict (``out`` reuses
+        one)."""
+        if not callable(evaluate):
+            raise ValueError("evaluate must be callable: the select dict -> (prior, value)")
+        S = _int_in("simulations", simulations, 1, self.PUCT_MAX_CAPACITY)
+        _exploration("exploration", exploration), _unit("fpu", fpu)
+        self.puct_begin(S, width, seed)
+        leaves = None
+        for _ in range(S):
+            leaves = self.puct_select(exploration, fpu, out=leaves)
+            prior, value = evaluate(leaves)
+            if prior.is_floating_point() or value.is_floating_point():
+                prior, value = self.puct_quantize(prior, value)
+            self.puct_backup(prior, value)
+        return self.puct_root(out)
+
+    def puct_action(self, evaluate, simulations: int, width: int = 16, exploration: float = 1.25, fpu: float = 0.5, seed: int = 0,
+                    out: Optional[dict] = None) -> torch.Tensor:
+        """``puct``'s most visited child as an int64 [B] dense id for ``step_single`` (-1 = pass, also where no child has a
+        visit)."""
+        return self.puct(evaluate, simulations, width, exploration, fpu, seed, out)["best"].to(torch.int64).clamp_(min=-1)
 
     def board(self):
         out = torch.empty((self.B, 20, 20), dtype=torch.int8, device=self.device)

@@ -378,3 +378,14 @@ class BlokusSinglePlayerVectorEnv:
         if self.rank:
             raise ValueError("mcts_action returns dense ids: the env must be made with action='id'")
         return self.batch.mcts_action(simulations, playouts, candidates, width, seed, exploration)
+
+    def puct_action(self, evaluate, simulations: int, width: int = 16, exploration: float = 1.25, fpu: float = 0.5, seed: int = 0,
+                    out: Optional[dict] = None) -> torch.Tensor:
+        """A tree search valued by the caller's network for the learner on the env's own games (``BlokusBatch.puct_action``):
+        ``evaluate`` takes the leaves (``BlokusBatch.puct_select``'s dict: the observation, up to ``width`` sampled candidate
+        ids, the leaf in the state layout) and returns (prior over the candidates, value).  int64 [B] dense ids for ``step``
+        (-1 = pass) of an env made with ``action="id"``; two launches per simulation beside the network, no host
+        synchronisation.  ``out``: the ``BlokusBatch.puct_root`` dict to reuse (its 'visits' over 'ids' are a policy target)."""
+        if self.rank:
+            raise ValueError("puct_action returns dense ids: the env must be made with action='id'")
+        return self.batch.puct_action(evaluate, simulations, width, exploration, fpu, seed, out)

@@ -95,7 +95,9 @@ const char *crl_last_error(void);
  *      crl_tron_sample_mcts_territory / _max_simulations (that search as a seated agent: two new entries, no new tag), and
  *      crl_blokus_mcts / crl_blokus_mcts_max_simulations (tree search with progressive widening: two new entries, no new tag), and
  *      crl_ttt_puct_tree_bytes / _begin / _select / _backup / _root (tree search valued by the caller: five new entries, no new tag), and
- *      crl_tron_puct_tree_bytes / _begin / _select / _backup / _root (that search for one seat of Tron: five new entries, no new tag). */
+ *      crl_tron_puct_tree_bytes / _begin / _select / _backup / _root (that search for one seat of Tron: five new entries, no new tag), and
+ *      crl_blokus_puct_tree_bytes / _begin / _select / _backup / _root (that search over sampled candidates in Blokus: five new
+ *      entries, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -1233,6 +1235,136 @@ int crl_tron_puct_root(const crl_ctx *ctx, int64_t B, void *tree, int S_cap,
                        uint32_t *visits, uint32_t *value, uint32_t *prior, uint32_t *nodes, uint32_t *sims, int32_t *best,
                        void *stream);
 
+/* ------------------------------------------------------------------ tree search valued by the caller's network (PUCT), Blokus
+ * crl_blokus_puct_*: crl_ttt_puct_*'s design over SAMPLED actions (Hubert et al., "Learning and Planning in Complex Action
+ * Spaces").  B search trees stay in device memory between launches; one launch (select) descends every tree to a leaf and
+ * writes the leaves out in observation layout, each with at most W candidate actions drawn from its legal list; the caller's
+ * network scores those candidates and values the leaf, on the same stream; a second launch (backup) expands the leaves with
+ * the returned weights and backs the returned values up.  Two launches per simulation for the whole batch, no host
+ * synchronisation, capturable into a graph.  With a uniform proposal the network's weights normalised over the sample are the
+ * priors.  Added under revision 113: five new entries, no new Philox tag, no existing struct, argument list or RNG contract
+ * changed.
+ * `tree` is a caller-owned device buffer of B * crl_blokus_puct_tree_bytes(ctx, S_cap, W) bytes, 16-byte aligned.  Its layout
+ * is the library's own business and is opaque to the caller (DESIGN.md 4.5l states it).  Every call on a buffer takes the
+ * S_cap, the W, the B and the context that crl_blokus_puct_begin took.
+ *
+ * Tree and nodes
+ * - `begin` copies into tree b everything a later call needs: the 80 occupancy words, the inventories, the scores, the round,
+ *   `to_move[b] & 3`, `tcount[b]` (NULL means 0), g = the low 32 bits of `first_env_id + b`, and the seed.  The state has
+ *   crl_blokus_playout's layouts and is read only.  No later call reads the game state, so the batch may be stepped while a
+ *   search is open.
+ * - `begin` makes node 0 the root. The root is *unexpanded*, with n = 0, node count 1 and simulation count 0.
+ * - Blokus keeps no "game over" field. As in crl_blokus_mcts a finished position is not special, and there are no skipped
+ *   trees: its root gets the pass as its only candidate and that ply is terminal.
+ * - A node holds n (uint32) and w (uint32); K, its number of candidates; per slot k < K a dense id (int32, -1 for the pass),
+ *   a prior (uint16) and a child slot (uint16, 0 = none); and whether the ply into it was terminal. w is the summed value of
+ *   the player who moved INTO it, on the 0..65536 scale.
+ * - A node is *expanded* once a backup has given it priors.
+ *
+ * Candidates of a node v
+ * - They are fixed the first time v is a pending leaf.  Let p be its mover and L the number of p's legal actions
+ *   (crl_blokus_valid's count).  Ranks are into the legal list in reference order (crl_blokus_valid_list's order,
+ *   crl_blokus_select's ranks).
+ * - L = 0: K = 1 and the one candidate is the pass (id -1).
+ * - 1 <= L <= W: K = L and candidate k is the action of rank k.
+ * - L > W: K = W, one action from each of W strata.
+ *   - `lo_k = floor(k * L / W)`, `hi_k = floor((k + 1) * L / W)`, `rank_k = lo_k + mulhi32(u_k, hi_k - lo_k)`.
+ *   - `u_k = Philox4x32-10(ctr = {g, 0xC0000000 | v, 0x80000000 | ((tcount & 0x07FFFFFF) << 4) | (k >> 2), 0x42500000},
+ *     key = {seed lo, seed hi})[k & 3]`, with tcount the root's, as `begin` took it.
+ *   - The ranks are distinct and ascending, so the ids are too; every legal action has about the same chance W / L, and the
+ *     strata spread the sample over the pieces and the anchors.
+ * - Counter space: the seated search agent's noise draw (crl_blokus_sample_mcts) also sets both top bits of the second
+ *   counter word under the shared tag 0x42500000, but its third word is 0.  Here bit 31 of the third word is always set, so
+ *   no block of one draw is a block of another.
+ *
+ * `select`, simulation s
+ * - The descent starts at the root on a private copy of the root position.
+ * - At node v:
+ *   - If v is unexpanded, v is the leaf and it is *pending*.
+ *   - Otherwise score the slots k < K_v. Take the greatest score, ties to the lowest slot.
+ *   - If v has no child at that slot, a new unexpanded node with the next free index becomes that child.
+ *   - Play the slot's ply (its id, or the pass) as `crl_blokus_step` plays it.
+ *   - If that ply is terminal, the child is the leaf, it is *terminal* and not pending. Otherwise the descent continues at the
+ *     child.
+ * - The score is the siblings', in 64-bit integers with floor divisions. Let n_u, w_u be those of the child at slot k, or 0, 0
+ *   where there is none. Let P_k be v's stored prior at k.
+ *   - `exploit = n_u ? w_u / n_u : fpu`
+ *   - `explore = (cpuct * P_k * isqrt(n_v << 16)) / ((1 + n_u) << 16)`, with isqrt the exact floor root
+ *   - `score = exploit + explore`
+ *   - `cpuct = 256` is c = 1.0.
+ * - The path and the leaf's kind are kept in the tree until `backup`. It holds at most min(S_cap, 337) + 1 node indices: 84
+ *   placements exist, and at most three passes separate two of them.
+ * - A `select` on a tree with a path outstanding drops that path and descends again. Nothing has changed, so it arrives at
+ *   the same leaf.
+ * - A tree whose simulation count has reached `S_cap` is not descended: no path, pending 0.
+ * - Outputs, every word overwritten. For a pending leaf with mover m:
+ *   - `obs_board` int8 [B][20][20], `obs_pieces` uint8 [B][4][21], `obs_score` int32 [B][4]: exactly what
+ *     `crl_blokus_observe` with `player[b]` = m writes for the leaf position.
+ *   - `cand` int32 [B][W]: the K ids, then -2.
+ *   - `n_cand` int32 [B] = K, `n_legal` int32 [B] = L.
+ *   - `mover` int8 [B] = m.
+ *   - `pending` uint8 [B] = 1.
+ *   - `depth` uint32 [B]: the plies from the root to the leaf.
+ *   - `leaf_occ` uint32 [B][4][20], `leaf_inv` uint32 [B][4], `leaf_score` int32 [B][4], `leaf_round` int32 [B],
+ *     `leaf_to_move` int32 [B] (all five NULL, or none): the leaf position in the state layout, so that it can be handed to
+ *     crl_blokus_playout or any other entry of another stepper.
+ *   - For every other tree: zeros, `cand` -2, `mover` -1, `pending` 0.
+ *   - `obs_board` is written a dword at a time, as crl_blokus_observe writes it: it must be 4-byte aligned.
+ *
+ * `backup`
+ * - A tree without an outstanding path is left alone.
+ * - Pending leaf with K candidates and mover m:
+ *   - Let SUM = the sum of `prior[b][k]` over k < K, with `prior` uint16 [B][W]; columns at k >= K are ignored.
+ *   - Slot k gets `min(65535, (prior[b][k] << 16) / SUM)`, or `min(65535, 65536 / K)` when SUM = 0.
+ *   - The leaf becomes expanded.
+ *   - The value of player (m + j) & 3 is `value[b][j]` clamped to [0, 65536], with `value` int32 [B][4].
+ * - Terminal leaf:
+ *   - `prior` and `value` are not read.
+ *   - Player q's value is 65536 iff bit q of the terminal winners mask is set, else 0: a shared best score counts for every
+ *     tied player, as in crl_blokus_mcts.
+ * - Every node on the path gets n += 1.
+ * - Every node on the path but the root gets w += the value of the player who moved into it.
+ * - The simulation count goes up by 1 and the path is cleared.
+ *
+ * `root`, every word overwritten
+ * - `ids` int32 [B][W]: the root's candidates, -1 for the pass, -2 beyond K or before the root is expanded.
+ * - `visits`, `value` uint32 [B][W]: n and w of the root's child at each slot, 0 where there is none.
+ * - `prior` uint32 [B][W]: the root's stored priors.
+ * - `nodes`, `sims` uint32 [B].
+ * - `best` int32 [B]: the id of the most visited child, ties to the larger w, then to the lowest slot. -2 when no child has a
+ *   visit.
+ *
+ * Refused with `CRL_EINVAL` and a `crl_last_error` message, before any device work
+ * - NULL pointers, other than `tcount` and the leaf_* set.
+ * - A leaf_* set that is partly NULL.
+ * - A `tree` pointer that is not 16-byte aligned.
+ * - B out of range, as the siblings define it.
+ * - `S_cap` outside [1, 4095]. Child slots are 16 bits and w stays below 2^32. A wider index is a later change.
+ * - `W` outside [1, 64].
+ * - `cpuct` > 65535.
+ * - `fpu` > 65536.
+ * - `flags != 0`.
+ * - A context that is not a Blokus one.
+ * crl_blokus_puct_tree_bytes returns the bytes of ONE tree, a multiple of 16 that grows with S_cap and W, or a negative code (a
+ * bad context, S_cap or W out of range).
+ * One wave per tree in every kernel, four waves per workgroup, 64-bit tree offsets, grid-stride loops; nothing is shared
+ * between waves, so the results do not depend on their order.  Every index read from a tree is clamped before it addresses
+ * anything: a buffer that never saw `begin` gives unspecified results, never a wild access. */
+int64_t crl_blokus_puct_tree_bytes(const crl_ctx *ctx, int S_cap, int W);
+int crl_blokus_puct_begin(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first_env_id,
+                          const uint32_t *occ, const uint32_t *inv, const int32_t *score, const int32_t *round,
+                          const int32_t *to_move, const uint32_t *tcount /* may be NULL */, int S_cap, int W, void *tree, void *stream);
+int crl_blokus_puct_select(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, int W, uint32_t cpuct, uint32_t fpu,
+                           int8_t *obs_board, uint8_t *obs_pieces, int32_t *obs_score, int32_t *cand, int32_t *n_cand,
+                           int32_t *n_legal, int8_t *mover, uint8_t *pending, uint32_t *depth,
+                           uint32_t *leaf_occ, uint32_t *leaf_inv, int32_t *leaf_score, int32_t *leaf_round,
+                           int32_t *leaf_to_move /* all five NULL, or none */, uint32_t flags, void *stream);
+int crl_blokus_puct_backup(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, int W, const uint16_t *prior, const int32_t *value,
+                           uint32_t flags, void *stream);
+int crl_blokus_puct_root(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, int W,
+                         int32_t *ids, uint32_t *visits, uint32_t *value, uint32_t *prior, uint32_t *nodes, uint32_t *sims,
+                         int32_t *best, void *stream);
+
 /* ------------------------------------------------------------------ batched tree search with progressive widening, Blokus
  * crl_blokus_mcts: from each of B positions build a search tree of its own by S simulations s = 0 .. S-1, in order, each
  * evaluated by R random playouts, and report the root's children.  One launch, no host sync, capturable into a graph.  Added
@@ -1309,7 +1441,8 @@ int crl_blokus_mcts(const crl_ctx *ctx, int64_t B, uint64_t seed, uint64_t first
  *      drawn and nothing is searched.  (crl_blokus_mcts would answer the same: the pass would be the root's only child.)
  *   2. u = Philox4x32-10(ctr = {g, 0xC0000000 | (c >> 2), 0, 0x42500000}, key = {seed lo, seed hi})[c & 3].  Both top bits
  *      of the second counter word are set: crl_blokus_playout has neither, the search's playouts set only bit 30 and its
- *      widening draws only bit 31, so under the shared tag no block of one is a block of another.
+ *      widening draws only bit 31, so under the shared tag no block of one is a block of another.  (crl_blokus_puct_select's
+ *      candidate draws set both bits too, with bit 31 of the THIRD word set where this draw's third word is 0.)
  *   3. noisy  iff  u < thr,  thr = min(2^32, ceil(noise * 2^32)): noise = 0 is never noisy, noise = 1 always.
  *   4. noisy: the action is crl_blokus_sample's at that counter -- its word under tag 0x424c0000, rank mulhi32(word, n).
  *      With noise = 1 the agent therefore is the random agent bit for bit.

@@ -1300,6 +1300,83 @@ class TTTBatch(_RolloutStepper):
         """``puct``'s most visited cell as an int64 [B] action for ``step_single`` (-1 where the game is over)."""
         return self.puct(evaluate, simulations, exploration, fpu, out)["best"].to(torch.int64)
 
+    # -- the policy-value MLP of that search in one launch; the contract is with crl_ttt_net_eval in include/colosseum_hip.h
+    def _net_tensors(self, hidden, policy, value, C: int):
+        """the L + 2 (W, b) pairs checked against the network's shape -> (H, L, weights, biases)"""
+        pairs = list(hidden) if isinstance(hidden, (list, tuple)) else None
+        if not pairs or len(pairs) > 3:
+            raise ValueError("hidden must be a list of 1..3 (W, b) pairs, got %r" % (None if pairs is None else len(pairs),))
+        pairs += [policy, value]
+        if any(not isinstance(p, (list, tuple)) or len(p) != 2 or not all(isinstance(t, torch.Tensor) for t in p) for p in pairs):
+            raise ValueError("every layer must be a (W, b) pair of tensors")
+        H, L = int(pairs[0][0].shape[0]) if pairs[0][0].dim() == 2 else 0, len(pairs) - 2
+        if H % 16 or not 16 <= H <= 256:
+            raise ValueError("the hidden width must be a multiple of 16 in [16, 256], got %d" % H)
+        outs = [H] * L + [self.n_cells, self.P]
+        ins = [self.n_cells * C] + [H] * (L + 1)
+        for i, ((W, b), n_out, n_in) in enumerate(zip(pairs, outs, ins)):
+            name = "policy" if i == L else ("value" if i == L + 1 else "hidden[%d]" % i)
+            _want(W.detach(), torch.float32, (n_out, n_in), self.device, name + " weight")
+            _want(b.detach(), torch.float32, (n_out,), self.device, name + " bias")
+        return H, L, [W.detach() for W, _ in pairs], [b.detach() for _, b in pairs]
+
+    def net_pack(self, hidden, policy, value, planes: Optional[int] = None, into=None):
+        """Packs a policy-value MLP for ``net_eval`` (``crl_ttt_net_pack``): ``hidden`` a list of 1..3 (W, b) of width H (a
+        multiple of 16 in 16 .. 256; the first W is [H, cells * planes], the others [H, H]), ``policy`` a (W [cells, H], b) and
+        ``value`` a (W [P, H], b), all float32 device tensors in torch's ``Linear`` layout; ``planes`` (1 .. 8, by default P) is
+        the number of one-hot planes a cell is expanded to.  Returns a ``TTTNet`` handle: ``repack(hidden, policy, value)`` into
+        the same buffer after an optimiser step, ``evaluator()`` for ``puct``.  One launch, no host synchronisation."""
+        C_ = _int_in("planes", self.P if planes is None else planes, 1, 8)
+        H, L, ws, bs = self._net_tensors(hidden, policy, value, C_)
+        if into is None:
+            nbytes = self._lib.crl_ttt_net_bytes(self._ctx.handle, C_, H, L)
+            if nbytes < 0:
+                check(int(nbytes), "crl_ttt_net_bytes")
+            with torch.cuda.device(self.device):
+                into = TTTNet(self, C_, H, L, torch.empty((int(nbytes) // 16, 2), dtype=torch.int64, device=self.device))   # (16-byte units)
+        elif (into.C, into.H, into.L) != (C_, H, L):
+            raise ValueError("repack: the network is (planes, H, L) = %r, the handle holds %r" % ((C_, H, L), (into.C, into.H, into.L)))
+        wp, bp = (C.c_void_p * (L + 2))(*[t.data_ptr() for t in ws]), (C.c_void_p * (L + 2))(*[t.data_ptr() for t in bs])
+        with _DevGuard(self.device):
+            check(self._lib.crl_ttt_net_pack(self._ctx.handle, C_, H, L, wp, bp, _ptr(into.packed), _stream()), "crl_ttt_net_pack")
+        return into
+
+    def net_eval(self, net, leaves, valid: Optional[torch.Tensor] = None, pending: Optional[torch.Tensor] = None, out=None):
+        """The packed network on a batch of leaves in one launch (``crl_ttt_net_eval``): ``leaves`` is the dict of
+        ``puct_select`` (its 'board', 'valid' and 'pending') or a board int8 [N, cells] relative to the mover with ``valid``
+        int32 [N] (by default the cells the board holds as empty) and ``pending`` uint8 [N] (by default every row).  Returns
+        (prior int16 [N, cells] holding uint16 bits, the greatest valid logit's cell 65535; value int32 [N, P] on 0 .. 65536),
+        what ``puct_backup`` takes; rows that are not pending are zeros.  ``out`` reuses such a pair."""
+        if not isinstance(net, TTTNet) or net.batch is not self:
+            raise ValueError("net must be a handle of this batch's net_pack")
+        if isinstance(leaves, dict):
+            board, valid, pending = leaves["board"], leaves["valid"], leaves["pending"]
+        else:
+            board = leaves
+        if not isinstance(board, torch.Tensor) or board.dim() != 2 or board.shape[0] < 1:
+            raise ValueError("board must be an int8 tensor of shape (N, %d)" % self.n_cells)
+        N = int(board.shape[0])
+        _want(board, torch.int8, (N, self.n_cells), self.device, "board")
+        if valid is None:
+            bits = (board < 0).to(torch.int64) << torch.arange(self.n_cells, device=self.device)
+            valid = bits.sum(dim=1).to(torch.int32)
+        _want(valid, torch.int32, (N,), self.device, "valid")
+        if pending is not None:
+            _want(pending, torch.uint8, (N,), self.device, "pending")
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = (torch.empty((N, self.n_cells), dtype=torch.int16, device=self.device),
+                       torch.empty((N, self.P), dtype=torch.int32, device=self.device))
+        prior, value = out
+        _want(prior, torch.int16, (N, self.n_cells), self.device, "out[0]")
+        _want(value, torch.int32, (N, self.P), self.device, "out[1]")
+        with _DevGuard(self.device):
+            rc = self._lib.crl_ttt_net_eval(self._ctx.handle, N, _ptr(net.packed), net.C, net.H, net.L, _ptr(board), _ptr(valid),
+                                            _ptr(pending), _ptr(prior), _ptr(value), 0, _stream())
+        if rc:
+            check(rc, "crl_ttt_net_eval")
+        return prior, value
+
     def rollout(self, steps: int, seed: int = 0):
         self._rollout_plan(steps, seed)
 
@@ -1311,6 +1388,30 @@ class TTTBatch(_RolloutStepper):
     def results_from_columns(self):
         cols = [self.n_episodes, self.len_sum, self.draw_count] + [self.win_count[p] for p in range(self.P)]
         return torch.stack(cols, dim=1).contiguous()
+
+
+class TTTNet:
+    """A policy-value MLP packed for ``TTTBatch.net_eval`` (made by ``TTTBatch.net_pack``): the packed device tensor and the
+    (planes C, width H, layers L) it was packed for."""
+
+    def __init__(self, batch, C_: int, H: int, L: int, packed: torch.Tensor):
+        self.batch, self.C, self.H, self.L, self.packed = batch, C_, H, L, packed
+
+    def repack(self, hidden, policy, value):
+        """the same network shape with new weights, into the same buffer: one launch, no host synchronisation"""
+        return self.batch.net_pack(hidden, policy, value, self.C, into=self)
+
+    def evaluator(self):
+        """A callable for ``TTTBatch.puct`` / ``puct_action``: the select dict -> the integer (prior, value) of ``net_eval``,
+        one launch per call, into one pair of buffers that every call reuses."""
+        out = []
+
+        def evaluate(leaves):
+            got = self.batch.net_eval(self, leaves, out=out[0] if out else None)
+            if not out:
+                out.append(got)
+            return got
+        return evaluate
 
 
 class TTTBoards(_Stepper):

@@ -2,10 +2,12 @@
 (board -> policy logits, one value per player) plays the batch against itself, every move a search of --simulations
 descents whose leaves the network values (two launches per simulation for the whole batch, the trees in HBM); the root's
 visit counts are the policy target and the final outcomes the value target.  Prints the learner's first-episode loss rate
-at seat 1 against the noise-free tactical (win-or-block) opponent before and after the iterations.  One run is one run: the
-figures it prints are what that run measured, nothing more.
+at seat 1 against the noise-free tactical (win-or-block) opponent before and after the iterations.  --evaluator hip runs the
+same network between select and backup as one launch (``TTTBatch.net_pack`` / ``net_eval``, re-packed after each training
+iteration) instead of torch's twenty-odd.  One run is one run: the figures it prints are what that run measured, nothing more.
 
     python examples/ttt_alphazero.py [--batch 1024] [--iterations 4] [--simulations 32] [--epochs 4] [--eval-games 1024]
+                                     [--evaluator torch|hip]
 """
 import argparse
 import os
@@ -34,8 +36,29 @@ class Net(torch.nn.Module):
         return self.policy(h), self.value(h)
 
 
+class HipEvaluator:
+    """the same network packed for ``TTTBatch.net_eval``: one launch per call on any batch of leaves, `repack` after training"""
+
+    def __init__(self, net):
+        self.net, self.tb = net, TTTBatch(DIMS, K, P, 1, device="cuda")
+        self.packed = self.tb.net_pack(*self.layers())
+
+    def layers(self):
+        body = [m for m in self.net.body if isinstance(m, torch.nn.Linear)]
+        return [(m.weight, m.bias) for m in body], (self.net.policy.weight, self.net.policy.bias), (self.net.value.weight, self.net.value.bias)
+
+    def repack(self):
+        self.packed.repack(*self.layers())
+
+    def __call__(self, leaves):
+        return self.tb.net_eval(self.packed, leaves)
+
+
 def evaluator(net):
     """the search's evaluator: leaves -> (policy weights, values in [0, 1] of the leaf's mover and the players after it)"""
+    if isinstance(net, HipEvaluator):
+        return net
+
     def evaluate(leaves):
         with torch.no_grad():
             logits, value = net(leaves["board"])
@@ -97,18 +120,22 @@ def main():
     ap.add_argument("--simulations", type=int, default=32)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--eval-games", type=int, default=1024)
+    ap.add_argument("--evaluator", choices=("torch", "hip"), default="torch", help="what runs between select and backup")
     args = ap.parse_args()
     torch.manual_seed(0)
     net = Net().to("cuda")
     opt = torch.optim.Adam(net.parameters(), lr=3e-3)
+    play = HipEvaluator(net) if args.evaluator == "hip" else net         # what the searches evaluate with (training is torch's)
     print("loss rate against tactical, seat 1, before: %.3f (%d games, %d simulations a move)"
-          % (loss_rate(net, args.eval_games, args.simulations), args.eval_games, args.simulations))
+          % (loss_rate(play, args.eval_games, args.simulations), args.eval_games, args.simulations))
     for it in range(args.iterations):
-        boards, policy, value = self_play(net, args.batch, args.simulations, seed=it)
+        boards, policy, value = self_play(play, args.batch, args.simulations, seed=it)
         loss = train(net, opt, boards, policy, value, args.epochs)
+        if play is not net:
+            play.repack()
         print("iteration %d: boards %s policy targets %s values %s, loss %.4f"
               % (it + 1, tuple(boards.shape), tuple(policy.shape), tuple(value.shape), loss))
-    print("loss rate against tactical, seat 1, after %d iterations: %.3f" % (args.iterations, loss_rate(net, args.eval_games, args.simulations)))
+    print("loss rate against tactical, seat 1, after %d iterations: %.3f" % (args.iterations, loss_rate(play, args.eval_games, args.simulations)))
 
 
 if __name__ == "__main__":

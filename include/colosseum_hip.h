@@ -97,7 +97,8 @@ const char *crl_last_error(void);
  *      crl_ttt_puct_tree_bytes / _begin / _select / _backup / _root (tree search valued by the caller: five new entries, no new tag), and
  *      crl_tron_puct_tree_bytes / _begin / _select / _backup / _root (that search for one seat of Tron: five new entries, no new tag), and
  *      crl_blokus_puct_tree_bytes / _begin / _select / _backup / _root (that search over sampled candidates in Blokus: five new
- *      entries, no new tag). */
+ *      entries, no new tag), and
+ *      crl_ttt_net_bytes / _pack / _eval (the policy-value MLP of the TicTacToe search in one launch: three new entries, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -1120,6 +1121,57 @@ int crl_ttt_puct_backup(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, co
 int crl_ttt_puct_root(const crl_ctx *ctx, int64_t B, void *tree, int S_cap,
                       uint32_t *visits, uint32_t *value, uint32_t *prior, uint32_t *nodes, uint32_t *sims, int32_t *best,
                       void *stream);
+
+/* ------------------------------------------------------------------ the policy-value MLP of that search in one launch, TicTacToe
+ * crl_ttt_net_*: the evaluator between `crl_ttt_puct_select` and `crl_ttt_puct_backup` as ONE launch: leaf boards -> one-hot
+ * planes -> a multi-layer perceptron (float32 MFMA) -> priors and values in the integer formats `crl_ttt_puct_backup` reads.
+ * Added under revision 113: three new entries, no new Philox tag, no existing struct, argument list or RNG contract changed.
+ * The only floating-point kernel of the library: its results are NOT bit-exact against another summation order (the tests
+ * hold it to 4 output units of a float64 evaluation).
+ *
+ * The network, for a context of `cells` cells and P players
+ * - Input: `board` int8 [B][cells], as `crl_ttt_puct_select` writes it. It is expanded to F = cells * C one-hot features:
+ *   feature `cell * C + c` is 1 where `board[cell] == c`, else 0. A cell value outside [0, C) sets no feature (an empty cell
+ *   does not, and neither does a value >= C under a larger `rel_mod`). C is in [1, 8].
+ * - L hidden layers (L in [1, 3]) of width H (a multiple of 16 in [16, 256]), each `relu(W x + b)`; the first is [H, F], the
+ *   others [H, H].
+ * - The policy head [cells, H] + bias gives the logits l; the value head [P, H] + bias gives v.
+ * - Every matrix is float32, row-major [out, in] (torch's `Linear.weight`), every bias float32 [out].
+ *
+ * `net_bytes` / `net_pack`
+ * - `crl_ttt_net_bytes` returns the bytes of one packed network, a multiple of 16 that grows with C, H and L, or a negative code.
+ * - `net` is a caller-owned device buffer of that many bytes, 16-byte aligned. Its layout is the library's own business
+ *   (DESIGN.md 4.5m states it). `eval` takes the C, H, L and the context that `pack` took.
+ * - `weight` and `bias` are HOST arrays of L + 2 DEVICE pointers: the hidden layers in order, then the policy head, then the
+ *   value head. `pack` reads the arrays before it returns and the matrices on the stream.
+ * - One launch, no allocation, no host synchronisation: a trainer may re-pack after every optimiser step.
+ *
+ * `net_eval`, every word of rows < B overwritten, nothing outside them touched
+ * - `valid` uint32 [B] is the mask E of the cells that may get a prior (select's empties mask; it is NOT derived from `board`).
+ * - `pending` uint8 [B], or NULL: a row with `pending[b] == 0` is written as zeros and is not computed. NULL evaluates every
+ *   row, which makes the call a plain policy outside a search.
+ * - `prior` uint16 [B][cells]: for e in E, `round(65535 * exp(l_e - max over E of l))`, so that the cell of the greatest valid
+ *   logit holds exactly 65535; 0 elsewhere; all zeros where E is empty. (`crl_ttt_puct_backup` normalises over E itself, so
+ *   no softmax denominator is needed.)
+ * - `value` int32 [B][P]: `round(65536 * sigmoid(v_j))`, always inside [0, 65536].
+ * - Rounding is to nearest, ties to even. A NaN logit gives prior 0, a NaN value 0.
+ * - One launch, no allocation, no synchronisation: capturable into a graph.
+ *
+ * Refused with `CRL_EINVAL` and a `crl_last_error` message, before any device work
+ * - NULL pointers, other than `pending` (a NULL entry of `weight` or `bias` included).
+ * - A `net` pointer that is not 16-byte aligned.
+ * - C outside [1, 8], H not a multiple of 16 in [16, 256], L outside [1, 3].
+ * - `flags != 0`.
+ * - B out of range, as the siblings define it.
+ * - A context that is not tictactoe.
+ * One wave per 16 leaves and trip, 64-bit row offsets, a grid-stride loop over the 16-leaf tiles; nothing is shared between
+ * waves, so the results do not depend on their order. */
+int64_t crl_ttt_net_bytes(const crl_ctx *ctx, int C, int H, int L);
+int crl_ttt_net_pack(const crl_ctx *ctx, int C, int H, int L, const float *const *weight, const float *const *bias, void *net,
+                     void *stream);
+int crl_ttt_net_eval(const crl_ctx *ctx, int64_t B, const void *net, int C, int H, int L, const int8_t *board,
+                     const uint32_t *valid, const uint8_t *pending /* may be NULL */, uint16_t *prior, int32_t *value,
+                     uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ tree search valued by the caller's network (PUCT), Tron
  * crl_tron_puct_*: crl_ttt_puct_*'s design for ONE seat of Tron.  B search trees stay in device memory between launches; one

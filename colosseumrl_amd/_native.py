@@ -149,6 +149,7 @@ PROTOTYPES = {
     "crl_ttt_net_bytes": (_I64, [_VP, _I, _I, _I]),
     "crl_ttt_net_pack": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "crl_ttt_net_eval": (_I, [_VP, _I64, _VP, _I, _I, _I] + [_VP] * 5 + [_U32, _VP]),
+    "crl_ttt_puct_search": (_I, [_VP, _I64, _VP, _I, _I, _VP, _I, _I, _I, _U32, _U32, _I, _U32, _VP]),
     "crl_blokus_puct_tree_bytes": (_I64, [_VP, _I, _I]),
     "crl_blokus_puct_begin": (_I, [_VP, _I64, _U64, _U64] + [_VP] * 6 + [_I, _I, _VP, _VP]),
     "crl_blokus_puct_select": (_I, [_VP, _I64, _VP, _I, _I, _U32, _U32] + [_VP] * 14 + [_U32, _VP]),

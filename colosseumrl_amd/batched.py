@@ -1377,6 +1377,37 @@ class TTTBatch(_RolloutStepper):
             check(rc, "crl_ttt_net_eval")
         return prior, value
 
+    # -- that search with that MLP, all simulations in one launch; the contract is with crl_ttt_puct_search
+    def puct_search(self, net, simulations: int, exploration: float = 1.25, fpu: float = 0.5, rel_mod: Optional[int] = None):
+        """``simulations`` (1 .. 4095) simulations of every open tree, valued by the packed ``net`` of this batch's
+        ``net_pack``, in ONE launch (``crl_ttt_puct_search``): the trees are left exactly as that many rounds of
+        ``puct_select`` -> ``net_eval`` -> ``puct_backup`` leave them, so the two paths may be mixed on one search.  Trees
+        that reach the capacity of ``puct_begin`` stay as they are.  No host synchronisation."""
+        tree, cap = self._puct_open()
+        if not isinstance(net, TTTNet) or net.batch is not self:
+            raise ValueError("net must be a handle of this batch's net_pack")
+        S = _int_in("simulations", simulations, 1, self.PUCT_MAX_CAPACITY)
+        cpuct = _exploration("exploration", exploration)
+        fpu16 = int(round(65536.0 * _unit("fpu", fpu)))
+        rel = self.P if rel_mod is None else _int_in("rel_mod", rel_mod, 1, 127)
+        self._call("crl_ttt_puct_search", _ptr(tree), cap, S, _ptr(net.packed), net.C, net.H, net.L, cpuct, fpu16, rel, 0)
+
+    def puct_net(self, net, simulations: int, exploration: float = 1.25, fpu: float = 0.5, out: Optional[dict] = None):
+        """A whole search valued by the packed ``net``: ``puct_begin(simulations)``, ``puct_search``, ``puct_root`` -- three
+        launches where ``puct(net.evaluator(), ...)`` makes three per simulation, with the same root dict."""
+        if not isinstance(net, TTTNet) or net.batch is not self:
+            raise ValueError("net must be a handle of this batch's net_pack")
+        S = _int_in("simulations", simulations, 1, self.PUCT_MAX_CAPACITY)
+        _exploration("exploration", exploration), _unit("fpu", fpu)
+        self.puct_begin(S)
+        self.puct_search(net, S, exploration, fpu)
+        return self.puct_root(out)
+
+    def puct_net_action(self, net, simulations: int, exploration: float = 1.25, fpu: float = 0.5,
+                        out: Optional[dict] = None) -> torch.Tensor:
+        """``puct_net``'s most visited cell as an int64 [B] action for ``step_single`` (-1 where the game is over)."""
+        return self.puct_net(net, simulations, exploration, fpu, out)["best"].to(torch.int64)
+
     def rollout(self, steps: int, seed: int = 0):
         self._rollout_plan(steps, seed)
 

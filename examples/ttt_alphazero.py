@@ -4,10 +4,11 @@ descents whose leaves the network values (two launches per simulation for the wh
 visit counts are the policy target and the final outcomes the value target.  Prints the learner's first-episode loss rate
 at seat 1 against the noise-free tactical (win-or-block) opponent before and after the iterations.  --evaluator hip runs the
 same network between select and backup as one launch (``TTTBatch.net_pack`` / ``net_eval``, re-packed after each training
-iteration) instead of torch's twenty-odd.  One run is one run: the figures it prints are what that run measured, nothing more.
+iteration) instead of torch's twenty-odd; --evaluator fused runs each self-play search as one launch, the network inside it
+(``TTTBatch.puct_net``; the evaluation games, which search through the vector env, keep the hip evaluator).  One run is one run: the figures it prints are what that run measured, nothing more.
 
     python examples/ttt_alphazero.py [--batch 1024] [--iterations 4] [--simulations 32] [--epochs 4] [--eval-games 1024]
-                                     [--evaluator torch|hip]
+                                     [--evaluator torch|hip|fused]
 """
 import argparse
 import os
@@ -54,6 +55,10 @@ class HipEvaluator:
         return self.tb.net_eval(self.packed, leaves)
 
 
+class FusedEvaluator(HipEvaluator):
+    """the hip evaluator whose self-play searches run whole in one launch (``TTTBatch.puct_net``)"""
+
+
 def evaluator(net):
     """the search's evaluator: leaves -> (policy weights, values in [0, 1] of the leaf's mover and the players after it)"""
     if isinstance(net, HipEvaluator):
@@ -72,9 +77,10 @@ def self_play(net, batch, simulations, seed):
     gen = torch.Generator(device="cuda").manual_seed(seed)
     boards, targets, movers, lives = [], [], [], []
     root = None
+    fused = tb.net_pack(*net.layers()) if isinstance(net, FusedEvaluator) else None      # (a packed network belongs to its batch)
     for _ in range(CELLS):
         live = (tb.winner < 0) & (tb.valid_mask() != 0)
-        root = tb.puct(evaluator(net), simulations, out=root)
+        root = tb.puct_net(fused, simulations, out=root) if fused else tb.puct(evaluator(net), simulations, out=root)
         visits = root["visits"].float()
         boards.append(tb.board(tb.to_move)), movers.append(tb.to_move.clone()), lives.append(live)
         targets.append(visits / visits.sum(dim=1, keepdim=True).clamp_min(1.0))
@@ -120,12 +126,13 @@ def main():
     ap.add_argument("--simulations", type=int, default=32)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--eval-games", type=int, default=1024)
-    ap.add_argument("--evaluator", choices=("torch", "hip"), default="torch", help="what runs between select and backup")
+    ap.add_argument("--evaluator", choices=("torch", "hip", "fused"), default="torch",
+                    help="what runs between select and backup; fused: the whole self-play search in one launch")
     args = ap.parse_args()
     torch.manual_seed(0)
     net = Net().to("cuda")
     opt = torch.optim.Adam(net.parameters(), lr=3e-3)
-    play = HipEvaluator(net) if args.evaluator == "hip" else net         # what the searches evaluate with (training is torch's)
+    play = {"torch": lambda n: n, "hip": HipEvaluator, "fused": FusedEvaluator}[args.evaluator](net)        # what the searches evaluate with (training is torch's)
     print("loss rate against tactical, seat 1, before: %.3f (%d games, %d simulations a move)"
           % (loss_rate(play, args.eval_games, args.simulations), args.eval_games, args.simulations))
     for it in range(args.iterations):

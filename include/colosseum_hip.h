@@ -98,7 +98,8 @@ const char *crl_last_error(void);
  *      crl_tron_puct_tree_bytes / _begin / _select / _backup / _root (that search for one seat of Tron: five new entries, no new tag), and
  *      crl_blokus_puct_tree_bytes / _begin / _select / _backup / _root (that search over sampled candidates in Blokus: five new
  *      entries, no new tag), and
- *      crl_ttt_net_bytes / _pack / _eval (the policy-value MLP of the TicTacToe search in one launch: three new entries, no new tag). */
+ *      crl_ttt_net_bytes / _pack / _eval (the policy-value MLP of the TicTacToe search in one launch: three new entries, no new tag), and
+ *      crl_ttt_puct_search (that search with that MLP, all simulations in one launch: one new entry, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -1172,6 +1173,34 @@ int crl_ttt_net_pack(const crl_ctx *ctx, int C, int H, int L, const float *const
 int crl_ttt_net_eval(const crl_ctx *ctx, int64_t B, const void *net, int C, int H, int L, const int8_t *board,
                      const uint32_t *valid, const uint8_t *pending /* may be NULL */, uint16_t *prior, int32_t *value,
                      uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------ that search and that MLP as one launch, TicTacToe
+ * crl_ttt_puct_search: `n_sims` simulations of every tree in ONE launch, valued by a network that `crl_ttt_net_pack` packed.
+ * Added under revision 113: one new entry, no new Philox tag, no existing struct, argument list or RNG contract changed.
+ *
+ * The contract is its siblings'
+ * - On trees made by `crl_ttt_puct_begin`, the call leaves EVERY BYTE of every tree exactly as `n_sims` repetitions of
+ *   (`crl_ttt_puct_select`, `crl_ttt_net_eval` on its board / valid outputs with its `pending`, `crl_ttt_puct_backup`) with the
+ *   same S_cap, cpuct, fpu, rel_mod, C, H and L leave it: skipped trees, trees whose simulation count has reached S_cap (they
+ *   stay as they are however large `n_sims` is), terminal leaves, the path slots and the header words included.
+ * - The priors and values are `crl_ttt_net_eval`'s bit for bit: the sums run in that kernel's order (the bias first, the
+ *   inputs ascending), the epilogue is its `round(65535 * exp(l - max))` and `round(65536 * sigmoid(v))`.
+ * - The tree layout is unchanged: `crl_ttt_puct_root`, `_select` and `_backup` work on the same trees before and after, and a
+ *   search may be continued by either path.
+ * - `net` is read only; leaves, priors and values never reach device memory outside the trees.
+ * - One launch, no allocation, no host synchronisation: capturable into a graph.
+ *
+ * Refused with `CRL_EINVAL` and a `crl_last_error` message, before any device work
+ * - NULL `tree` or `net`, or one that is not 16-byte aligned.
+ * - B out of range, `S_cap` outside [1, 4095], a context with cells < P or that is not tictactoe, as `crl_ttt_puct_select`.
+ * - `n_sims` outside [1, 4095].
+ * - C outside [1, 8], H not a multiple of 16 in [16, 256], L outside [1, 3], as `crl_ttt_net_eval`.
+ * - `cpuct` > 65535, `fpu` > 65536, `rel_mod` < 1, `flags != 0`.
+ * A workgroup of 16 waves per 16 trees (one MFMA tile of leaves), a wave per tree in every phase, 64-bit tree offsets, a
+ * grid-stride loop over the groups of 16; a ragged last group computes its missing rows on empty boards and touches no tree.
+ * Nothing is shared between workgroups, so the results do not depend on their order.  DESIGN.md 4.5n states the layout. */
+int crl_ttt_puct_search(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, int n_sims, const void *net, int C, int H, int L,
+                        uint32_t cpuct, uint32_t fpu, int rel_mod, uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ tree search valued by the caller's network (PUCT), Tron
  * crl_tron_puct_*: crl_ttt_puct_*'s design for ONE seat of Tron.  B search trees stay in device memory between launches; one

@@ -746,6 +746,83 @@ class TronBatch(_RolloutStepper):
         the game is over)."""
         return self.puct(evaluate, simulations, exploration, fpu, seed, agent, noise, seat, out)["best"].to(torch.int64)
 
+    # -- the policy-value MLP of that search in one launch; the contract is with crl_tron_net_eval in include/colosseum_hip.h
+    def _net_tensors(self, hidden, policy, value):
+        """the L + 2 (W, b) pairs checked against the network's shape -> (H, L, weights, biases)"""
+        pairs = list(hidden) if isinstance(hidden, (list, tuple)) else None
+        if not pairs or len(pairs) > 3:
+            raise ValueError("hidden must be a list of 1..3 (W, b) pairs, got %r" % (None if pairs is None else len(pairs),))
+        pairs += [policy, value]
+        if any(not isinstance(p, (list, tuple)) or len(p) != 2 or not all(isinstance(t, torch.Tensor) for t in p) for p in pairs):
+            raise ValueError("every layer must be a (W, b) pair of tensors")
+        H, L = int(pairs[0][0].shape[0]) if pairs[0][0].dim() == 2 else 0, len(pairs) - 2
+        if H % 16 or not 16 <= H <= 256:
+            raise ValueError("the hidden width must be a multiple of 16 in [16, 256], got %d" % H)
+        outs = [H] * L + [3, 1]
+        ins = [4 * self.N * self.N + 4] + [H] * (L + 1)
+        for i, ((W, b), n_out, n_in) in enumerate(zip(pairs, outs, ins)):
+            name = "policy" if i == L else ("value" if i == L + 1 else "hidden[%d]" % i)
+            _want(W.detach(), torch.float32, (n_out, n_in), self.device, name + " weight")
+            _want(b.detach(), torch.float32, (n_out,), self.device, name + " bias")
+        return H, L, [W.detach() for W, _ in pairs], [b.detach() for _, b in pairs]
+
+    def net_pack(self, hidden, policy, value, into=None):
+        """Packs a policy-value MLP for ``net_eval`` (``crl_tron_net_pack``): ``hidden`` a list of 1..3 (W, b) of width H (a
+        multiple of 16 in 16 .. 256; the first W is [H, 4 N N + 4] over the planes empty / own / other / head and the facing, the
+        others [H, H]), ``policy`` a (W [3, H], b) and ``value`` a (W [1, H], b), all float32 device tensors in torch's
+        ``Linear`` layout.  Returns a ``TronNet`` handle: ``repack(hidden, policy, value)`` into the same buffer after an
+        optimiser step, ``evaluator()`` for ``puct``.  One launch, no host synchronisation."""
+        H, L, ws, bs = self._net_tensors(hidden, policy, value)
+        if into is None:
+            nbytes = self._lib.crl_tron_net_bytes(self._ctx.handle, H, L)
+            if nbytes < 0:
+                check(int(nbytes), "crl_tron_net_bytes")
+            with torch.cuda.device(self.device):
+                into = TronNet(self, self.N, H, L, torch.empty((int(nbytes) // 16, 2), dtype=torch.int64, device=self.device))   # (16-byte units)
+        elif (into.N, into.H, into.L) != (self.N, H, L):
+            raise ValueError("repack: the network is (N, H, L) = %r, the handle holds %r" % ((self.N, H, L), (into.N, into.H, into.L)))
+        wp, bp = (C.c_void_p * (L + 2))(*[t.data_ptr() for t in ws]), (C.c_void_p * (L + 2))(*[t.data_ptr() for t in bs])
+        with _DevGuard(self.device):
+            check(self._lib.crl_tron_net_pack(self._ctx.handle, H, L, wp, bp, _ptr(into.packed), _stream()), "crl_tron_net_pack")
+        return into
+
+    def net_eval(self, net, leaves, heads: Optional[torch.Tensor] = None, dirs: Optional[torch.Tensor] = None,
+                 pending: Optional[torch.Tensor] = None, out=None):
+        """The packed network on a batch of leaves in one launch (``crl_tron_net_eval``): ``leaves`` is the dict of
+        ``puct_select`` (its 'obs_board', 'obs_heads', 'obs_dirs' and 'pending') or an observed board int8 [n, N*N] with
+        ``heads`` int16 [P, n], ``dirs`` int8 [P, n] (row 0: the seat's) and ``pending`` uint8 [n] (by default every row).
+        Returns (prior int16 [n, 3] holding uint16 bits, the greatest logit's action 65535; value int32 [n] on 0 .. 65536),
+        what ``puct_backup`` takes; rows that are not pending are zeros.  ``out`` reuses such a pair."""
+        if not isinstance(net, TronNet) or net.N != self.N or net.packed.device != self.device:
+            raise ValueError("net must be a handle of a net_pack on a batch of this board size and device")
+        if isinstance(leaves, dict):
+            board, heads, dirs, pending = leaves["obs_board"], leaves["obs_heads"], leaves["obs_dirs"], leaves["pending"]
+        else:
+            board = leaves
+        NN = self.N * self.N
+        if not isinstance(board, torch.Tensor) or board.dim() != 2 or board.shape[0] < 1:
+            raise ValueError("obs_board must be an int8 tensor of shape (n, %d)" % NN)
+        n = int(board.shape[0])
+        _want(board, torch.int8, (n, NN), self.device, "obs_board")
+        if not isinstance(heads, torch.Tensor) or not isinstance(dirs, torch.Tensor):
+            raise ValueError("obs_heads (int16) and obs_dirs (int8) must be tensors of shape (%d, %d)" % (self.P, n))
+        _want(heads, torch.int16, (self.P, n), self.device, "obs_heads")
+        _want(dirs, torch.int8, (self.P, n), self.device, "obs_dirs")
+        if pending is not None:
+            _want(pending, torch.uint8, (n,), self.device, "pending")
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = (torch.empty((n, 3), dtype=torch.int16, device=self.device), torch.empty((n,), dtype=torch.int32, device=self.device))
+        prior, value = out
+        _want(prior, torch.int16, (n, 3), self.device, "out[0]")
+        _want(value, torch.int32, (n,), self.device, "out[1]")
+        with _DevGuard(self.device):
+            rc = self._lib.crl_tron_net_eval(self._ctx.handle, n, _ptr(net.packed), net.H, net.L, _ptr(board), _ptr(heads), _ptr(dirs),
+                                             _ptr(pending), _ptr(prior), _ptr(value), 0, _stream())
+        if rc:
+            check(rc, "crl_tron_net_eval")
+        return prior, value
+
     # -- Voronoi territory of every game's position (the deterministic evaluator beside playout)
     def territory(self, candidates: Optional[torch.Tensor] = None, seat: Optional[torch.Tensor] = None,
                   out: Optional[dict] = None):
@@ -940,6 +1017,30 @@ class TronBatch(_RolloutStepper):
         cols += [self.ret_sum[p] for p in range(self.P)]
         cols += [torch.zeros_like(self.tstep)] * (self._packed.shape[1] - len(cols))
         return torch.stack(cols, dim=1).to(torch.int16).contiguous()
+
+
+class TronNet:
+    """A policy-value MLP packed for ``TronBatch.net_eval`` (made by ``TronBatch.net_pack``): the packed device tensor and the
+    (board size N, width H, layers L) it was packed for."""
+
+    def __init__(self, batch, N: int, H: int, L: int, packed: torch.Tensor):
+        self.batch, self.N, self.H, self.L, self.packed = batch, N, H, L, packed
+
+    def repack(self, hidden, policy, value):
+        """the same network shape with new weights, into the same buffer: one launch, no host synchronisation"""
+        return self.batch.net_pack(hidden, policy, value, into=self)
+
+    def evaluator(self):
+        """A callable for ``TronBatch.puct`` / ``puct_action`` and the searches of ``TronSinglePlayerVectorEnv``: the select
+        dict -> the integer (prior, value) of ``net_eval``, one launch per call, into one pair of buffers that calls on the same
+        number of leaves reuse.  It serves every batch of the packing batch's board, players and device."""
+        out = {}
+
+        def evaluate(leaves):
+            n = int(leaves["obs_board"].shape[0])
+            got = out[n] = self.batch.net_eval(self, leaves, out=out.get(n))
+            return got
+        return evaluate
 
 
 class TTTBatch(_RolloutStepper):

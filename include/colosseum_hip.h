@@ -99,7 +99,8 @@ const char *crl_last_error(void);
  *      crl_blokus_puct_tree_bytes / _begin / _select / _backup / _root (that search over sampled candidates in Blokus: five new
  *      entries, no new tag), and
  *      crl_ttt_net_bytes / _pack / _eval (the policy-value MLP of the TicTacToe search in one launch: three new entries, no new tag), and
- *      crl_ttt_puct_search (that search with that MLP, all simulations in one launch: one new entry, no new tag). */
+ *      crl_ttt_puct_search (that search with that MLP, all simulations in one launch: one new entry, no new tag), and
+ *      crl_tron_net_bytes / _pack / _eval (the policy-value MLP of the Tron search in one launch: three new entries, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -1315,6 +1316,66 @@ int crl_tron_puct_backup(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, c
 int crl_tron_puct_root(const crl_ctx *ctx, int64_t B, void *tree, int S_cap,
                        uint32_t *visits, uint32_t *value, uint32_t *prior, uint32_t *nodes, uint32_t *sims, int32_t *best,
                        void *stream);
+
+/* ------------------------------------------------------------------ the policy-value MLP of that search in one launch, Tron
+ * crl_tron_net_*: the evaluator between `crl_tron_puct_select` and `crl_tron_puct_backup` as ONE launch: the leaf observations
+ * -> four board planes and the facing -> a multi-layer perceptron (float32 MFMA) -> priors and values in the integer formats
+ * `crl_tron_puct_backup` reads.  crl_ttt_net_*'s contract for Tron.
+ * Added under revision 113: three new entries, no new Philox tag, no existing struct, argument list or RNG contract changed.
+ * A floating-point kernel, as crl_ttt_net_eval is: its results are NOT bit-exact against another summation order (the tests
+ * hold it to 4 output units of a float64 evaluation).  Its own order is fixed by (N, H, L) alone, so the results are the same
+ * from run to run, for every B and every grid.
+ *
+ * The network, for a context of N x N cells and P players
+ * - Inputs: `obs_board` int8 [B][N*N], `obs_heads` int16 [P][B], `obs_dirs` int8 [P][B], exactly as `crl_tron_puct_select` (or
+ *   `crl_tron_observe`) writes them. Only row 0 of `obs_heads` and `obs_dirs`, the seat's, is read.
+ * - They are expanded to F = 4*N*N + 4 features, 0 or 1:
+ *   - `cell` (0 <= cell < N*N) is 1 where `board[cell] == 0` (empty);
+ *   - `N*N + cell` is 1 where `board[cell] == 1` (the seat's own trail);
+ *   - `2*N*N + cell` is 1 where `board[cell] > 1` (anybody else's);
+ *   - `3*N*N + cell` is 1 where `cell == clamp(obs_heads[0][b], 0, N*N - 1)`;
+ *   - `4*N*N + d` is 1 where `(obs_dirs[0][b] & 3) == d`.
+ *   A negative board value sets none of the three class features. No input value, whatever it is, causes an access outside
+ *   the row.
+ * - L hidden layers (L in [1, 3]) of width H (a multiple of 16 in [16, 256]), each `relu(W x + b)`; the first is [H, F], the
+ *   others [H, H].
+ * - The policy head [3, H] + bias gives the logits l of forward, right, left; the value head [1, H] + bias gives v.
+ * - Every matrix is float32, row-major [out, in] (torch's `Linear.weight`), every bias float32 [out].
+ *
+ * `net_bytes` / `net_pack`
+ * - `crl_tron_net_bytes` returns the bytes of one packed network, a multiple of 16 that grows with H and L, or a negative code.
+ * - `net` is a caller-owned device buffer of that many bytes, 16-byte aligned. Its layout is the library's own business
+ *   (DESIGN.md 4.5o states it). `eval` takes the H, L and the context that `pack` took.
+ * - `weight` and `bias` are HOST arrays of L + 2 DEVICE pointers: the hidden layers in order, then the policy head, then the
+ *   value head. `pack` reads the arrays before it returns and the matrices on the stream.
+ * - One launch, no allocation, no host synchronisation: a trainer may re-pack after every optimiser step.
+ *
+ * `net_eval`, every word of rows < B overwritten, nothing outside them touched
+ * - `pending` uint8 [B], or NULL: a row with `pending[b] == 0` is written as zeros and is not computed. NULL evaluates every
+ *   row, which makes the call a plain policy outside a search.
+ * - `prior` uint16 [B][3]: `round(65535 * exp(l_a - max l))`, so that the action of the greatest logit holds exactly 65535.
+ *   (`crl_tron_puct_backup` normalises, so no softmax denominator is needed.)
+ * - `value` int32 [B]: `round(65536 * sigmoid(v))`, always inside [0, 65536].
+ * - Rounding is to nearest, ties to even. A NaN logit gives prior 0, a NaN value 0.
+ * - One launch, no allocation, no synchronisation: capturable into a graph.
+ *
+ * Refused with `CRL_EINVAL` and a `crl_last_error` message, before any device work
+ * - NULL pointers, other than `pending` (a NULL entry of `weight` or `bias` included).
+ * - A `net` pointer that is not 16-byte aligned.
+ * - H not a multiple of 16 in [16, 256], L outside [1, 3].
+ * - `flags != 0`.
+ * - B out of range, as the siblings define it.
+ * - A context that is not a Tron context.
+ * A board above 40x40 answers CRL_EUNSUPPORTED from all three entries: a workgroup keeps its 16 boards as bytes in LDS beside
+ * two activation buffers (the boards the rollout kernels keep in LDS are the ones supported).
+ * A workgroup of four waves per 16 leaves and trip, the output tiles of every layer dealt over the waves, 64-bit row offsets,
+ * a grid-stride loop over the 16-leaf tiles; nothing is shared between workgroups, so the results do not depend on their order. */
+int64_t crl_tron_net_bytes(const crl_ctx *ctx, int H, int L);
+int crl_tron_net_pack(const crl_ctx *ctx, int H, int L, const float *const *weight, const float *const *bias, void *net,
+                      void *stream);
+int crl_tron_net_eval(const crl_ctx *ctx, int64_t B, const void *net, int H, int L, const int8_t *obs_board,
+                      const int16_t *obs_heads, const int8_t *obs_dirs, const uint8_t *pending /* may be NULL */,
+                      uint16_t *prior, int32_t *value, uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ tree search valued by the caller's network (PUCT), Blokus
  * crl_blokus_puct_*: crl_ttt_puct_*'s design over SAMPLED actions (Hubert et al., "Learning and Planning in Complex Action

@@ -118,6 +118,7 @@ PROTOTYPES = {
     "crl_tron_net_bytes": (_I64, [_VP, _I, _I]),
     "crl_tron_net_pack": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP]),
     "crl_tron_net_eval": (_I, [_VP, _I64, _VP, _I, _I] + [_VP] * 6 + [_U32, _VP]),
+    "crl_tron_puct_search": (_I, [_VP, _I64, _VP, _I, _I, _VP, _I, _I, _U32, _U32, _U32, _VP]),
     "crl_tron_territory": (_I, [_VP, _I64] + [_VP] * 6 + [_I] + [_VP] * 2 + [_VP]),
     "crl_tron_sample_territory": (_I, [_VP, _I64, _U64, _U64, _VP, _I, C.c_double, _U32] + [_VP] * 5 + [_VP]),
     "crl_ttt_create": (_I, [_I, _I, _I, _I, _I, C.POINTER(_VP)]),

@@ -823,6 +823,42 @@ class TronBatch(_RolloutStepper):
             check(rc, "crl_tron_net_eval")
         return prior, value
 
+    # -- that search with that MLP, all simulations in one launch; the contract is with crl_tron_puct_search
+    def _puct_net_check(self, net):
+        if not isinstance(net, TronNet) or net.N != self.N or net.packed.device != self.device:
+            raise ValueError("net must be a handle of a net_pack on a batch of this board size and device")
+
+    def puct_search(self, net, simulations: int, exploration: float = 1.25, fpu: float = 0.5):
+        """``simulations`` (1 .. 4095) simulations of every open tree, valued by the packed ``net`` of a ``net_pack`` on this
+        board size, in ONE launch (``crl_tron_puct_search``): the trees are left exactly as that many rounds of
+        ``puct_select`` -> ``net_eval`` -> ``puct_backup`` leave them, so the two paths may be mixed on one search.  Trees
+        that reach the capacity of ``puct_begin`` stay as they are.  No host synchronisation; capturable into a graph."""
+        tree, cap = self._puct_open()
+        self._puct_net_check(net)
+        S = _int_in("simulations", simulations, 1, self.PUCT_MAX_CAPACITY)
+        cpuct = _exploration("exploration", exploration)
+        fpu16 = int(round(65536.0 * _unit("fpu", fpu)))
+        self._call("crl_tron_puct_search", _ptr(tree), cap, S, _ptr(net.packed), net.H, net.L, cpuct, fpu16, 0)
+
+    def puct_net(self, net, simulations: int, exploration: float = 1.25, fpu: float = 0.5, seed: int = 0, agent: str = "random",
+                 noise: float = 0.1, seat: Optional[torch.Tensor] = None, out: Optional[dict] = None):
+        """A whole search valued by the packed ``net``: ``puct_begin(simulations, seed, agent, noise, seat)``, ``puct_search``,
+        ``puct_root`` -- three launches where ``puct(net.evaluator(), ...)`` makes three per simulation, with the same root
+        dict."""
+        self._puct_net_check(net)
+        S = _int_in("simulations", simulations, 1, self.PUCT_MAX_CAPACITY)
+        _exploration("exploration", exploration), _unit("fpu", fpu)
+        self.puct_begin(S, seed, agent, noise, seat)
+        self.puct_search(net, S, exploration, fpu)
+        return self.puct_root(out)
+
+    def puct_net_action(self, net, simulations: int, exploration: float = 1.25, fpu: float = 0.5, seed: int = 0,
+                        agent: str = "random", noise: float = 0.1, seat: Optional[torch.Tensor] = None,
+                        out: Optional[dict] = None) -> torch.Tensor:
+        """``puct_net``'s most visited action as an int64 [B] action in {0, 1, 2} for ``step_single`` (-1 where the seat is dead
+        or the game is over)."""
+        return self.puct_net(net, simulations, exploration, fpu, seed, agent, noise, seat, out)["best"].to(torch.int64)
+
     # -- Voronoi territory of every game's position (the deterministic evaluator beside playout)
     def territory(self, candidates: Optional[torch.Tensor] = None, seat: Optional[torch.Tensor] = None,
                   out: Optional[dict] = None):

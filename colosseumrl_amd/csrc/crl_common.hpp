@@ -121,7 +121,7 @@ static inline unsigned crl_playout_blocks(const uint64_t n_lanes, const uint64_t
 // explicit range checks in a build of their own (tools/gpu_bounds.sh): a failing check does not fault, it counts itself
 // and keeps the first offender -- {failures, code, value, limit} per translation unit, read by crl_diag_bounds().  The
 // shipped build compiles none of it (the macros expand to nothing).  Codes: 1xx tron.hip (170..191: tron_mcts.hip, 165..167 and
-// 192..199: tron_puct.hip, whose counters crl_diag_bounds folds into tron's four words), 2xx ttt.hip (230..239: ttt_puct.hip, 240..249: ttt_puct_search.hip, both folded into ttt's), 3xx blokus.hip (350..359:
+// 192..199: tron_puct.hip, 124..129: tron_puct_search.hip, whose counters crl_diag_bounds folds into tron's four words), 2xx ttt.hip (230..239: ttt_puct.hip, 240..249: ttt_puct_search.hip, both folded into ttt's), 3xx blokus.hip (350..359:
 // blokus_mcts_search.hpp, the one search text of blokus_mcts.hip and blokus_mcts_agent.hip; each of the two units counts in
 // words of its own, what it includes of blokus.hip too, and both are folded into blokus's four words; 360..369 are retired;
 // 370..389: blokus_puct.hip, folded into blokus's words as well).
@@ -149,6 +149,7 @@ __device__ __forceinline__ void crl_bounds_fail(const unsigned code, const unsig
 int crl_tron_bounds(unsigned int *out4);
 int crl_tron_mcts_bounds(unsigned int *out4);
 int crl_tron_puct_bounds(unsigned int *out4);
+int crl_tron_puct_search_bounds(unsigned int *out4);
 int crl_ttt_bounds(unsigned int *out4);
 int crl_ttt_puct_bounds(unsigned int *out4);
 int crl_ttt_puct_search_bounds(unsigned int *out4);

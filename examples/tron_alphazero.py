@@ -5,11 +5,12 @@ the network values (two launches per simulation for the whole batch, the trees i
 agent inside the tree); the root's visit counts are the policy target and the episode's outcome (1 = the learner survived
 as the winner) the value target.  Prints the learner's first-episode win rate before and after the iterations.  --evaluator
 hip runs the same network between select and backup as one launch (``TronBatch.net_pack`` / ``net_eval``, packed once and
-re-packed after each training iteration) instead of torch's thirty-odd.  One run is one run: the figures it prints are what
+re-packed after each training iteration) instead of torch's thirty-odd; --evaluator fused runs the whole search of a move with
+that packed network as one launch (``TronBatch.puct_net``: begin, search, root).  One run is one run: the figures it prints are what
 that run measured, nothing more.
 
     python examples/tron_alphazero.py [--size 11] [--players 4] [--batch 512] [--iterations 4] [--simulations 24]
-                                      [--epochs 4] [--eval-games 512] [--max-steps 120] [--evaluator torch|hip]
+                                      [--epochs 4] [--eval-games 512] [--max-steps 120] [--evaluator torch|hip|fused]
 """
 import argparse
 import os
@@ -53,10 +54,11 @@ def layers(net):
     return [(m.weight, m.bias) for m in linear], (net.policy.weight, net.policy.bias), (net.value.weight, net.value.bias)
 
 
-def episodes(torch, net, args, games, seed, sample, evaluate=None):
+def episodes(torch, net, args, games, seed, sample, evaluate=None, fused=None):
     """every game's first episode with the search learner: (boards, heads, dirs, policy targets, value targets) of the
     learner's positions, and the share of episodes it won.  sample: draw the move from the visit counts (self-play) or take
-    the most visited (evaluation).  evaluate: the search's evaluator (by default the torch network's)."""
+    the most visited (evaluation).  evaluate: the search's evaluator (by default the torch network's).  fused: a packed
+    network; the search is then ``puct_net``'s one launch."""
     from colosseumrl_amd.vector import TronSinglePlayerVectorEnv
     env = TronSinglePlayerVectorEnv(args.size, args.players, games, noise=0.1, seed=seed, device="cuda")
     env.reset()
@@ -67,7 +69,10 @@ def episodes(torch, net, args, games, seed, sample, evaluate=None):
     evaluate = evaluate or evaluator(torch, net)
     for t in range(args.max_steps):
         b = env.batch
-        root = b.puct(evaluate, args.simulations, seed=1000 + t, agent="avoid", noise=env.noise, out=root)
+        if fused is not None:
+            root = b.puct_net(fused, args.simulations, seed=1000 + t, agent="avoid", noise=env.noise, out=root)
+        else:
+            root = b.puct(evaluate, args.simulations, seed=1000 + t, agent="avoid", noise=env.noise, out=root)
         visits = root["visits"].float()
         total = visits.sum(dim=1, keepdim=True)
         kept.append((b.board.clone(), b.heads.clone(), b.dirs.clone(), visits / total.clamp_min(1.0), (~over) & (total.view(-1) > 0)))
@@ -109,29 +114,30 @@ def main():
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--eval-games", type=int, default=512)
     ap.add_argument("--max-steps", type=int, default=120)
-    ap.add_argument("--evaluator", choices=("torch", "hip"), default="torch",
-                    help="what values the leaves: the torch network, or the same weights packed for TronBatch.net_eval (one launch)")
+    ap.add_argument("--evaluator", choices=("torch", "hip", "fused"), default="torch",
+                    help="what values the leaves: the torch network, the same weights packed for TronBatch.net_eval (one launch a "
+                         "simulation), or the packed network inside TronBatch.puct_net (one launch a search)")
     args = ap.parse_args()
     import torch
     torch.manual_seed(0)
     net = make_net(torch, args.size, args.players).to("cuda")
     opt = torch.optim.Adam(net.parameters(), lr=3e-3)
-    packed = evaluate = None
-    if args.evaluator == "hip":                      # one packed network serves every batch of this board, players and device
+    packed = evaluate = fused = None
+    if args.evaluator != "torch":                      # one packed network serves every batch of this board, players and device
         from colosseumrl_amd.batched import TronBatch
         packed = TronBatch(args.size, args.players, 1, device="cuda").net_pack(*layers(net))
-        evaluate = packed.evaluator()
-    _, rate = episodes(torch, net, args, args.eval_games, 3, sample=False, evaluate=evaluate)
+        evaluate, fused = packed.evaluator(), (packed if args.evaluator == "fused" else None)
+    _, rate = episodes(torch, net, args, args.eval_games, 3, sample=False, evaluate=evaluate, fused=fused)
     print("win rate against %d avoid opponents, before: %.3f (%d games, %d simulations a move)"
           % (args.players - 1, rate, args.eval_games, args.simulations))
     for it in range(args.iterations):
-        data, played = episodes(torch, net, args, args.batch, 100 + it, sample=True, evaluate=evaluate)
+        data, played = episodes(torch, net, args, args.batch, 100 + it, sample=True, evaluate=evaluate, fused=fused)
         loss = train(torch, net, opt, data, args.epochs)
         if packed is not None:
             packed.repack(*layers(net))
         print("iteration %d: boards %s policy targets %s values %s, self-play win rate %.3f, loss %.4f"
               % (it + 1, tuple(data[0].shape), tuple(data[3].shape), tuple(data[4].shape), played, loss))
-    _, rate = episodes(torch, net, args, args.eval_games, 3, sample=False, evaluate=evaluate)
+    _, rate = episodes(torch, net, args, args.eval_games, 3, sample=False, evaluate=evaluate, fused=fused)
     print("win rate against %d avoid opponents, after %d iterations: %.3f" % (args.players - 1, args.iterations, rate))
 
 

@@ -100,7 +100,8 @@ const char *crl_last_error(void);
  *      entries, no new tag), and
  *      crl_ttt_net_bytes / _pack / _eval (the policy-value MLP of the TicTacToe search in one launch: three new entries, no new tag), and
  *      crl_ttt_puct_search (that search with that MLP, all simulations in one launch: one new entry, no new tag), and
- *      crl_tron_net_bytes / _pack / _eval (the policy-value MLP of the Tron search in one launch: three new entries, no new tag). */
+ *      crl_tron_net_bytes / _pack / _eval (the policy-value MLP of the Tron search in one launch: three new entries, no new tag), and
+ *      crl_tron_puct_search (the Tron search with that MLP, all simulations in one launch: one new entry, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -1376,6 +1377,41 @@ int crl_tron_net_pack(const crl_ctx *ctx, int H, int L, const float *const *weig
 int crl_tron_net_eval(const crl_ctx *ctx, int64_t B, const void *net, int H, int L, const int8_t *obs_board,
                       const int16_t *obs_heads, const int8_t *obs_dirs, const uint8_t *pending /* may be NULL */,
                       uint16_t *prior, int32_t *value, uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------ that search and that MLP as one launch, Tron
+ * crl_tron_puct_search: `n_sims` simulations of every tree in ONE launch, valued by a network that `crl_tron_net_pack` packed.
+ * crl_ttt_puct_search's contract for Tron.
+ * Added under revision 113: one new entry, no new Philox tag, no existing struct, argument list or RNG contract changed.
+ *
+ * The contract
+ * - On trees made by `crl_tron_puct_begin`, the call leaves EVERY BYTE of every tree exactly as `n_sims` repetitions of
+ *   (`crl_tron_puct_select`, `crl_tron_net_eval` on its obs_board / obs_heads / obs_dirs outputs with its `pending`,
+ *   `crl_tron_puct_backup`) with the same S_cap, cpuct, fpu, H and L leave it: skipped trees, trees whose simulation count has
+ *   reached S_cap (they stay as they are however large `n_sims` is), terminal leaves, the path slots and the header's node /
+ *   sims / path / leaf words included.
+ * - The priors and values are `crl_tron_net_eval`'s bit for bit: the sums run in that kernel's order (the bias first, the k
+ *   tiles ascending), the epilogue is its `round(65535 * exp(l - max))` and `round(65536 * sigmoid(v))`.  The first layer's
+ *   planes are made from the position's own player ids against the seat's id; for every board with values in 0..P they are
+ *   the bits `crl_tron_net_eval` makes from `select`'s relative observation.
+ * - The tree layout and the packed-network layout are unchanged: `crl_tron_puct_root`, `_select` and `_backup` work on the same
+ *   trees before and after, and a search may be continued by either path.
+ * - `net` is read only; leaves, priors and values never reach device memory outside the trees.
+ * - One launch, no allocation, no host synchronisation: capturable into a graph.  Every loop is bounded: the descent by S_cap,
+ *   the simulations by `n_sims`.
+ *
+ * Refused with `CRL_EINVAL` and a `crl_last_error` message, before any device work
+ * - NULL `tree` or `net`, or one that is not 16-byte aligned.
+ * - B out of range, `S_cap` outside [1, 4095], a context that is not a Tron context, as `crl_tron_puct_select`.
+ * - `n_sims` outside [1, 4095].
+ * - H not a multiple of 16 in [16, 256], L outside [1, 3], as `crl_tron_net_eval`.
+ * - `cpuct` > 65535, `fpu` > 65536, `flags != 0`.
+ * A board above 40x40 answers CRL_EUNSUPPORTED, as `crl_tron_net_eval` does.
+ * A workgroup of 8 waves per 16 trees (one MFMA tile of leaves), two trees a wave in every phase, 64-bit tree offsets, a
+ * grid-stride loop over the groups of 16; a ragged last group computes its missing rows on padding and touches no tree.
+ * Nothing is shared between workgroups and no workgroup waits on another, so the results do not depend on their order.
+ * DESIGN.md 4.5p states the layout. */
+int crl_tron_puct_search(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, int n_sims, const void *net, int H, int L,
+                         uint32_t cpuct, uint32_t fpu, uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ tree search valued by the caller's network (PUCT), Blokus
  * crl_blokus_puct_*: crl_ttt_puct_*'s design over SAMPLED actions (Hubert et al., "Learning and Planning in Complex Action

@@ -159,6 +159,9 @@ PROTOTYPES = {
     "crl_blokus_puct_select": (_I, [_VP, _I64, _VP, _I, _I, _U32, _U32] + [_VP] * 14 + [_U32, _VP]),
     "crl_blokus_puct_backup": (_I, [_VP, _I64, _VP, _I, _I, _VP, _VP, _U32, _VP]),
     "crl_blokus_puct_root": (_I, [_VP, _I64, _VP, _I, _I] + [_VP] * 7 + [_VP]),
+    "crl_blokus_net_bytes": (_I64, [_VP, _I, _I]),
+    "crl_blokus_net_pack": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP]),
+    "crl_blokus_net_eval": (_I, [_VP, _I64, _VP, _I, _I, _I] + [_VP] * 8 + [_U32, _VP]),
     "crl_blokus_create": (_I, [C.POINTER(_VP)]),
     "crl_blokus_placement": (_I, [_I, _I, _I, _VP]),
     "crl_blokus_stamps": (_I, [_VP, _I]),

@@ -2016,6 +2016,95 @@ class BlokusBatch(_RolloutStepper):
         visit)."""
         return self.puct(evaluate, simulations, width, exploration, fpu, seed, out)["best"].to(torch.int64).clamp_(min=-1)
 
+    # -- the policy-value MLP of that search in one launch; the contract is with crl_blokus_net_eval in include/colosseum_hip.h
+    NET_FEATURES = 4 * 400 + 4 * 21
+
+    def _net_tensors(self, hidden, cells, pieces, value):
+        """the L + 3 (W, b) pairs checked against the network's shape -> (H, L, weights, biases)"""
+        pairs = list(hidden) if isinstance(hidden, (list, tuple)) else None
+        if not pairs or len(pairs) > 3:
+            raise ValueError("hidden must be a list of 1..3 (W, b) pairs, got %r" % (None if pairs is None else len(pairs),))
+        pairs += [cells, pieces, value]
+        if any(not isinstance(p, (list, tuple)) or len(p) != 2 or not all(isinstance(t, torch.Tensor) for t in p) for p in pairs):
+            raise ValueError("every layer must be a (W, b) pair of tensors")
+        H, L = int(pairs[0][0].shape[0]) if pairs[0][0].dim() == 2 else 0, len(pairs) - 3
+        if H % 16 or not 16 <= H <= 256:
+            raise ValueError("the hidden width must be a multiple of 16 in [16, 256], got %d" % H)
+        outs = [H] * L + [400, 21, 4]
+        ins = [self.NET_FEATURES] + [H] * (L + 2)
+        names = ["hidden[%d]" % i for i in range(L)] + ["cells", "pieces", "value"]
+        for (W, b), n_out, n_in, name in zip(pairs, outs, ins, names):
+            _want(W.detach(), torch.float32, (n_out, n_in), self.device, name + " weight")
+            _want(b.detach(), torch.float32, (n_out,), self.device, name + " bias")
+        return H, L, [W.detach() for W, _ in pairs], [b.detach() for _, b in pairs]
+
+    def net_pack(self, hidden, cells, pieces, value, into=None):
+        """Packs a policy-value MLP for ``net_eval`` (``crl_blokus_net_pack``): ``hidden`` a list of 1..3 (W, b) of width H (a
+        multiple of 16 in 16 .. 256; the first W is [H, 1684] over the four owner planes of the observed board and the 4 x 21
+        inventories, the others [H, H]), ``cells`` a (W [400, H], b): a map over the observation's cells, ``pieces`` a
+        (W [21, H], b) and ``value`` a (W [4, H], b): the mover, then the players after it; all float32 device tensors in
+        torch's ``Linear`` layout.  A candidate's logit is its piece's term plus the map over the cells it would cover.  Returns
+        a ``BlokusNet`` handle: ``repack(...)`` into the same buffer after an optimiser step, ``evaluator()`` for ``puct``.
+        One launch, no host synchronisation."""
+        H, L, ws, bs = self._net_tensors(hidden, cells, pieces, value)
+        if into is None:
+            nbytes = self._lib.crl_blokus_net_bytes(self._ctx.handle, H, L)
+            if nbytes < 0:
+                check(int(nbytes), "crl_blokus_net_bytes")
+            with torch.cuda.device(self.device):
+                into = BlokusNet(self, H, L, torch.empty((int(nbytes) // 16, 2), dtype=torch.int64, device=self.device))   # (16-byte units)
+        elif (into.H, into.L) != (H, L):
+            raise ValueError("repack: the network is (H, L) = %r, the handle holds %r" % ((H, L), (into.H, into.L)))
+        wp, bp = (C.c_void_p * (L + 3))(*[t.data_ptr() for t in ws]), (C.c_void_p * (L + 3))(*[t.data_ptr() for t in bs])
+        with _DevGuard(self.device):
+            check(self._lib.crl_blokus_net_pack(self._ctx.handle, H, L, wp, bp, _ptr(into.packed), _stream()), "crl_blokus_net_pack")
+        return into
+
+    def net_eval(self, net, leaves, pieces: Optional[torch.Tensor] = None, cand: Optional[torch.Tensor] = None,
+                 n_cand: Optional[torch.Tensor] = None, mover: Optional[torch.Tensor] = None,
+                 pending: Optional[torch.Tensor] = None, out=None):
+        """The packed network on a batch of leaves in one launch (``crl_blokus_net_eval``): ``leaves`` is the dict of
+        ``puct_select`` (its 'board', 'pieces', 'cand', 'n_cand', 'mover' and 'pending') or an observed board int8 [n, 20, 20]
+        with ``pieces`` uint8 [n, 4, 21], ``cand`` int32 [n, W], ``n_cand`` int32 [n], ``mover`` int8 [n] and ``pending`` uint8
+        [n] (by default every row).  Returns (prior int16 [n, W] holding uint16 bits, the greatest logit's slot 65535, slots
+        from 'n_cand' on 0; value int32 [n, 4] on 0 .. 65536), what ``puct_backup`` takes; rows that are not pending are
+        zeros.  ``out`` reuses such a pair."""
+        if not isinstance(net, BlokusNet) or net.packed.device != self.device:
+            raise ValueError("net must be a handle of a net_pack on a batch of this device")
+        if isinstance(leaves, dict):
+            board, pieces, cand, n_cand = leaves["board"], leaves["pieces"], leaves["cand"], leaves["n_cand"]
+            mover, pending = leaves["mover"], leaves["pending"]
+        else:
+            board = leaves
+        if not isinstance(board, torch.Tensor) or board.dim() != 3 or board.shape[0] < 1:
+            raise ValueError("board must be an int8 tensor of shape (n, 20, 20)")
+        n = int(board.shape[0])
+        _want(board, torch.int8, (n, 20, 20), self.device, "board")
+        if not all(isinstance(t, torch.Tensor) for t in (pieces, cand, n_cand, mover)) or cand.dim() != 2:
+            raise ValueError("pieces (uint8 [n, 4, 21]), cand (int32 [n, W]), n_cand (int32 [n]) and mover (int8 [n]) must be tensors")
+        W = int(cand.shape[1])
+        if not 1 <= W <= 64:
+            raise ValueError("cand must have 1..64 columns, got %d" % W)
+        _want(pieces, torch.uint8, (n, 4, 21), self.device, "pieces")
+        _want(cand, torch.int32, (n, W), self.device, "cand")
+        _want(n_cand, torch.int32, (n,), self.device, "n_cand")
+        _want(mover, torch.int8, (n,), self.device, "mover")
+        if pending is not None:
+            _want(pending, torch.uint8, (n,), self.device, "pending")
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = (torch.empty((n, W), dtype=torch.int16, device=self.device), torch.empty((n, 4), dtype=torch.int32, device=self.device))
+        prior, value = out
+        _want(prior, torch.int16, (n, W), self.device, "out[0]")
+        _want(value, torch.int32, (n, 4), self.device, "out[1]")
+        with _DevGuard(self.device):
+            rc = self._lib.crl_blokus_net_eval(self._ctx.handle, n, _ptr(net.packed), net.H, net.L, W, _ptr(board), _ptr(pieces),
+                                               _ptr(cand), _ptr(n_cand), _ptr(mover), _ptr(pending), _ptr(prior), _ptr(value), 0,
+                                               _stream())
+        if rc:
+            check(rc, "crl_blokus_net_eval")
+        return prior, value
+
     def board(self):
         out = torch.empty((self.B, 20, 20), dtype=torch.int8, device=self.device)
         self._call("crl_blokus_board", _ptr(self.occ), _ptr(out))
@@ -2032,3 +2121,27 @@ class BlokusBatch(_RolloutStepper):
     def results_from_columns(self):
         cols = [self.n_episodes, self.len_sum] + [self.win_count[p] for p in range(4)] + [self.score_sum[p] for p in range(4)]
         return torch.stack(cols, dim=1).contiguous()
+
+
+class BlokusNet:
+    """A policy-value MLP packed for ``BlokusBatch.net_eval`` (made by ``BlokusBatch.net_pack``): the packed device tensor and
+    the (width H, layers L) it was packed for."""
+
+    def __init__(self, batch, H: int, L: int, packed: torch.Tensor):
+        self.batch, self.H, self.L, self.packed = batch, H, L, packed
+
+    def repack(self, hidden, cells, pieces, value):
+        """the same network shape with new weights, into the same buffer: one launch, no host synchronisation"""
+        return self.batch.net_pack(hidden, cells, pieces, value, into=self)
+
+    def evaluator(self):
+        """A callable for ``BlokusBatch.puct`` / ``puct_action`` and ``BlokusSinglePlayerVectorEnv.puct_action``: the select
+        dict -> the integer (prior, value) of ``net_eval``, one launch per call, into one pair of buffers that calls on the same
+        number of leaves and width reuse.  It serves every batch of the packing batch's device."""
+        out = {}
+
+        def evaluate(leaves):
+            key = tuple(leaves["cand"].shape)
+            got = out[key] = self.batch.net_eval(self, leaves, out=out.get(key))
+            return got
+        return evaluate

@@ -124,7 +124,7 @@ static inline unsigned crl_playout_blocks(const uint64_t n_lanes, const uint64_t
 // 192..199: tron_puct.hip, 124..129: tron_puct_search.hip, whose counters crl_diag_bounds folds into tron's four words), 2xx ttt.hip (230..239: ttt_puct.hip, 240..249: ttt_puct_search.hip, both folded into ttt's), 3xx blokus.hip (350..359:
 // blokus_mcts_search.hpp, the one search text of blokus_mcts.hip and blokus_mcts_agent.hip; each of the two units counts in
 // words of its own, what it includes of blokus.hip too, and both are folded into blokus's four words; 360..369 are retired;
-// 370..389: blokus_puct.hip, folded into blokus's words as well).
+// 370..389: blokus_puct.hip and 390..399: blokus_net.hip, folded into blokus's words as well).
 #ifdef CRL_BOUNDS
 namespace {
 __device__ unsigned int g_crl_bounds[4];
@@ -157,6 +157,7 @@ int crl_blokus_bounds(unsigned int *out4);
 int crl_blokus_mcts_bounds(unsigned int *out4);
 int crl_blokus_mcts_agent_bounds(unsigned int *out4);
 int crl_blokus_puct_bounds(unsigned int *out4);
+int crl_blokus_net_bounds(unsigned int *out4);
 
 // host side of a completion flag in mapped memory (capi.hip): spin until *flag_host == seq, fall back to hipStreamSynchronize
 // after timeout_s; `who` names the caller in error messages

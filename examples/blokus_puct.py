@@ -2,11 +2,14 @@
 games: the tree search valued by the caller (``crl_blokus_puct_*``: at most ``--width`` sampled candidates per node, two
 launches per simulation, the trees in device memory).  No network is trained here: the priors are uniform over the candidates
 and the value of a leaf is the share of ``--playouts`` random playouts each player won from the leaf, run by ``playout`` on a
-second stepper loaded from the leaf's ``leaf_*`` state -- the place where a trained network would go.  Beside it, with the same
-opponents, a uniformly random learner.  Prints the share of games each learner won (alone or tied on top); each game's
+second stepper loaded from the leaf's ``leaf_*`` state.  ``--evaluator net`` puts a policy-value MLP there instead, in one launch
+per simulation (``BlokusBatch.net_pack`` / ``BlokusNet.evaluator()``, ``crl_blokus_net_eval``): ``--layers`` hidden layers of
+width ``--hidden``, randomly initialised -- the wiring a trained network would use, not a strong player.  Beside it, with the
+same opponents, a uniformly random learner.  Prints the share of games each learner won (alone or tied on top); each game's
 first finished episode counts.
 
     python examples/blokus_puct.py [--batch 128] [--seat 0] [--simulations 16] [--width 8] [--playouts 4] [--tiny]
+                                   [--evaluator playout|net] [--hidden 128] [--layers 2]
 """
 import argparse
 import itertools
@@ -36,6 +39,15 @@ def playout_evaluator(batch, width, playouts):
     return evaluate
 
 
+def net_evaluator(hidden, layers):
+    """the select dict -> the integer (prior, value) of a randomly initialised MLP packed for ``net_eval``"""
+    def linear(n_out, n_in):
+        m = torch.nn.Linear(n_in, n_out).to("cuda")
+        return m.weight.detach(), m.bias.detach()
+    trunk = [linear(hidden, BlokusBatch.NET_FEATURES if i == 0 else hidden) for i in range(layers)]
+    return BlokusBatch(1, device="cuda").net_pack(trunk, linear(400, hidden), linear(21, hidden), linear(4, hidden)).evaluator()
+
+
 def random_policy(env, t):
     """a uniformly drawn legal action of the learner (the pass where it has none)"""
     count = env.batch.valid()
@@ -63,13 +75,17 @@ def main():
     ap.add_argument("--simulations", type=int, default=16)
     ap.add_argument("--width", type=int, default=8)
     ap.add_argument("--playouts", type=int, default=4)
+    ap.add_argument("--evaluator", choices=("playout", "net"), default="playout")
+    ap.add_argument("--hidden", type=int, default=128, help="--evaluator net: the MLP's width, a multiple of 16 in 16 .. 256")
+    ap.add_argument("--layers", type=int, default=2, help="--evaluator net: its hidden layers, 1 .. 3")
     ap.add_argument("--tiny", action="store_true", help="a smoke run: 16 games, 4 simulations, width 4, 1 playout")
     args = ap.parse_args()
     B, S, W, R = (16, 4, 4, 1) if args.tiny else (args.batch, args.simulations, args.width, args.playouts)
     torch.manual_seed(1)
-    evaluate = playout_evaluator(B, W, R)
+    evaluate = net_evaluator(args.hidden, args.layers) if args.evaluator == "net" else playout_evaluator(B, W, R)
+    valued = "a random %d x %d MLP" % (args.hidden, args.layers) if args.evaluator == "net" else "%d playouts" % R
     learners = (("puct", lambda env, t: env.puct_action(evaluate, S, width=W, seed=1000 + t)), ("random", random_policy))
-    print("blokus, %d games at seat %d; puct: S = %d, W = %d, leaves valued by %d playouts" % (B, args.seat, S, W, R))
+    print("blokus, %d games at seat %d; puct: S = %d, W = %d, leaves valued by %s" % (B, args.seat, S, W, valued))
     for name, policy in learners:
         share, n = play(B, args.seat, policy)
         print("blokus, %-6s learner at seat %d: win share %.3f  (%d games)" % (name, args.seat, share, n))

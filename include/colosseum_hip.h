@@ -101,7 +101,8 @@ const char *crl_last_error(void);
  *      crl_ttt_net_bytes / _pack / _eval (the policy-value MLP of the TicTacToe search in one launch: three new entries, no new tag), and
  *      crl_ttt_puct_search (that search with that MLP, all simulations in one launch: one new entry, no new tag), and
  *      crl_tron_net_bytes / _pack / _eval (the policy-value MLP of the Tron search in one launch: three new entries, no new tag), and
- *      crl_tron_puct_search (the Tron search with that MLP, all simulations in one launch: one new entry, no new tag). */
+ *      crl_tron_puct_search (the Tron search with that MLP, all simulations in one launch: one new entry, no new tag), and
+ *      crl_blokus_net_bytes / _pack / _eval (the policy-value MLP of the Blokus search in one launch: three new entries, no new tag). */
 #define CRL_ABI_VERSION 113
 int crl_version(void);
 /* number of visible HIP devices, or a negative code */
@@ -1542,6 +1543,77 @@ int crl_blokus_puct_backup(const crl_ctx *ctx, int64_t B, void *tree, int S_cap,
 int crl_blokus_puct_root(const crl_ctx *ctx, int64_t B, void *tree, int S_cap, int W,
                          int32_t *ids, uint32_t *visits, uint32_t *value, uint32_t *prior, uint32_t *nodes, uint32_t *sims,
                          int32_t *best, void *stream);
+
+/* ------------------------------------------------------------------ the policy-value MLP of that search in one launch, Blokus
+ * crl_blokus_net_*: the evaluator between `crl_blokus_puct_select` and `crl_blokus_puct_backup` as ONE launch: the leaf
+ * observations -> four owner planes and the inventories -> a multi-layer perceptron (float32 MFMA) -> a map over the cells, a
+ * term per piece and four values -> the priors of the leaf's sampled candidates and the values in the integer formats
+ * `crl_blokus_puct_backup` reads.  crl_tron_net_*'s contract for Blokus, where the policy head scores a LIST of ids (at most
+ * W <= 64 of 336,000, different from leaf to leaf) and cannot emit a fixed vector.
+ * Added under revision 113: three new entries, no new Philox tag, no existing struct, argument list or RNG contract changed.
+ * A floating-point kernel, as crl_tron_net_eval is: its results are NOT bit-exact against another summation order (the tests
+ * hold it to 4 output units of a float64 evaluation).  Its own order is fixed by (H, L) alone, so the results are the same from
+ * run to run, for every B, every W and every grid.
+ *
+ * The network
+ * - Inputs, per leaf, exactly as `crl_blokus_puct_select` writes them: `obs_board` int8 [B][400] and `obs_pieces` uint8
+ *   [B][4][21] (which `crl_blokus_observe` may also supply), `cand` int32 [B][W], `n_cand` int32 [B], `mover` int8 [B].
+ *   `obs_score` is not an input: it is a function of the pieces up to the end-game bonuses, and it is unbounded.
+ * - They are expanded to F = 1684 features, 0 or 1:
+ *   - `400 j + c` is 1 where `obs_board[c] == j`, j = 0..3 (own, next, across, previous); -1 (empty) and any other board
+ *     value set none of these;
+ *   - `1600 + 21 r + i` is 1 where `obs_pieces[r][i] != 0`.
+ * - L hidden layers (L in [1, 3]) of width H (a multiple of 16 in [16, 256]), each `relu(W x + b)`; the first is [H, 1684], the
+ *   others [H, H].
+ * - Three heads on the last hidden vector: `cells` [400, H] + bias gives a map q[c] over the observation cells, `pieces`
+ *   [21, H] + bias gives r[piece], `value` [4, H] + bias gives v[j] for player (mover + j) & 3.
+ * - Every matrix is float32, row-major [out, in] (torch's `Linear.weight`), every bias float32 [out].
+ * - The logit l_k of candidate slot k < K = clamp(n_cand[b], 0, W), for the id a = cand[b][k]:
+ *   - a < 0, a >= 336,000, or a shift that is >= the piece's cell count: l_k = 0.  (This is the pass's logit; the pass is only
+ *     ever a leaf's sole candidate.)
+ *   - otherwise a is decoded as the step entries decode a dense id, into piece, orientation, shift and anchor (x, y); with
+ *     the piece's oriented cell offsets (dx_j, dy_j) in table order j = 0..n-1 the covered board cells are
+ *     (X_j, Y_j) = (x + dx_j - dx_shift, y + dy_j - dy_shift), WITHOUT the wrap-around of the step entries, and
+ *     `l_k = r[piece] + sum_j q[obs(X_j, Y_j)]`, r first, then the cells in order j ascending; a cell outside [0, 20)^2
+ *     contributes nothing.
+ *   - obs(X, Y) = 20 i + j is that board cell's index in the mover's observation, the inverse of the observation's rotation;
+ *     with m = mover[b] & 3: m = 0: (i, j) = (Y, X); m = 1: (X, 19 - Y); m = 2: (19 - Y, 19 - X); m = 3: (19 - X, Y).  For a
+ *     legal candidate these are exactly the cells in which `obs_board` for observer m differs before and after the ply.
+ *
+ * `net_bytes` / `net_pack`
+ * - `crl_blokus_net_bytes` returns the bytes of one packed network, a multiple of 16 that grows with H and L, or a negative code.
+ * - `net` is a caller-owned device buffer of that many bytes, 16-byte aligned. Its layout is the library's own business
+ *   (DESIGN.md 4.5q states it). `eval` takes the H, L and the context that `pack` took.
+ * - `weight` and `bias` are HOST arrays of L + 3 DEVICE pointers: the hidden layers in order, then cells, pieces, value.
+ *   `pack` reads the arrays before it returns and the matrices on the stream.
+ * - One launch, no allocation, no host synchronisation: a trainer may re-pack after every optimiser step.
+ *
+ * `net_eval`, every word of rows < B overwritten, nothing outside them touched
+ * - `pending` uint8 [B], or NULL: a row with `pending[b] == 0` is written as zeros and is not computed. NULL evaluates every row.
+ * - `prior` uint16 [B][W]: `round(65535 * exp(l_k - max_{k<K} l))` for k < K, so that the greatest slot holds exactly 65535;
+ *   0 for k >= K.  (`crl_blokus_puct_backup` normalises over the K slots, so no softmax denominator is needed.)
+ * - `value` int32 [B][4]: `round(65536 * sigmoid(v_j))`, always inside [0, 65536].
+ * - Rounding is to nearest, ties to even. A NaN gives 0.
+ * - No input value, whatever it is, causes an access outside its row or outside the tables.
+ * - One launch, no allocation, no synchronisation: capturable into a graph.
+ *
+ * Refused with `CRL_EINVAL` and a `crl_last_error` message, before any device work
+ * - NULL pointers, other than `pending` (a NULL entry of `weight` or `bias` included).
+ * - A `net` pointer that is not 16-byte aligned.
+ * - H not a multiple of 16 in [16, 256], L outside [1, 3].
+ * - `W` outside [1, 64].
+ * - `flags != 0`.
+ * - B out of range, as crl_tron_net_eval defines it.
+ * - A context that is not a Blokus one.
+ * A workgroup of four waves per 16 leaves and trip, the output tiles of every layer dealt over the waves, then one lane per
+ * candidate slot; 64-bit row offsets, a grid-stride loop over the 16-leaf tiles; nothing is shared between workgroups, so the
+ * results do not depend on their order. */
+int64_t crl_blokus_net_bytes(const crl_ctx *ctx, int H, int L);
+int crl_blokus_net_pack(const crl_ctx *ctx, int H, int L, const float *const *weight, const float *const *bias, void *net,
+                        void *stream);
+int crl_blokus_net_eval(const crl_ctx *ctx, int64_t B, const void *net, int H, int L, int W, const int8_t *obs_board,
+                        const uint8_t *obs_pieces, const int32_t *cand, const int32_t *n_cand, const int8_t *mover,
+                        const uint8_t *pending /* may be NULL */, uint16_t *prior, int32_t *value, uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------ batched tree search with progressive widening, Blokus
  * crl_blokus_mcts: from each of B positions build a search tree of its own by S simulations s = 0 .. S-1, in order, each

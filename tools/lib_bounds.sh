@@ -9,7 +9,7 @@ OUT=$ROOT/build/bounds
 mkdir -p "$OUT"
 rm -f "$OUT"/*.o "$OUT/libcolosseum_hip.so"        # a failed compile must not link against an object of an earlier run
 pids=()
-SRCS="capi tron tron_territory tron_mcts tron_puct ttt ttt_puct ttt_net ttt_puct_search blokus blokus_mcts blokus_mcts_agent blokus_puct tron_net tron_puct_search"
+SRCS="capi tron tron_territory tron_mcts tron_puct ttt ttt_puct ttt_net ttt_puct_search blokus blokus_mcts blokus_mcts_agent blokus_puct tron_net tron_puct_search blokus_net"
 for f in $SRCS; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -DCRL_BOUNDS \
       -c "$ROOT/colosseumrl_amd/csrc/$f.hip" -o "$OUT/$f.o" &
